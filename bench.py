@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- clips/s for AuM-Base (d_model=768, 24 Fo-Bi blocks, d_state=16) forward + backward + Adam step on
 synthetic 128-mel x 1024-frame spectrograms (BASELINE.json metric; configs[2] at N=1, configs[3] per-GPU batch 64 with
-DDP over RCCL at N>1), plus the live roofline of the dominant kernel and the CPU baseline (oracle on the host cores).
+DDP over RCCL at N>1).  With --full, also the per-kernel table, the live roofline of the dominant kernel, the step without
+the optimizer and the CPU baseline (oracle on the host cores).
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
   python bench.py --gpus N ...          (launches itself under torch.distributed.run, one rank per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one optimizer step on one per-GPU batch: fwd (bf16 autocast) -> BCE loss -> bwd (+ DDP bucketed all-reduce
 overlapped with backward) -> Adam.  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+--dump-outputs DIR writes what the last timed step computed (rank 0): loss.npy, logits.npy and params_sample.npy (a fixed,
+seeded sample of the updated fp32 parameters), all float32; inputs and initial weights are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -222,6 +228,20 @@ def step_alg_bytes(batch, length, d_model, depth, s=2):
     return depth * ((26 + 47) * H * s + (8 + 12) * H)
 
 
+def dump_outputs(out_dir, loss, logits, model, n_sample=1 << 22):
+    """--dump-outputs: what the last timed step hands its caller, as float32 .npy files -- the loss, the logits and the parameters
+    after the optimizer step.  The parameters (~90M floats at AuM-Base) are a fixed, seeded sample of n_sample elements of their
+    concatenation in named_parameters() order, so the files stay near 16 MB and two builds pick the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "logits.npy"), logits.detach().float().cpu().numpy())
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    idx = np.random.default_rng(0).choice(flat.numel(), size=min(n_sample, flat.numel()), replace=False)
+    idx.sort()
+    np.save(os.path.join(out_dir, "params_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -233,7 +253,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--grad-compress", default="no", choices=["no", "bf16", "fp16"], help="16-bit gradient exchange (N > 1)")
     ap.add_argument("--no-frontend", action="store_true", help="start from spectrograms instead of waveforms")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel table, the roofline figures, the step without the "
+                    "optimizer and the CPU baselines (runs of their own, outside the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, logits and a seeded sample of the "
+                    "updated parameters as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one process per GPU, RCCL over xGMI) the way the driver does
@@ -326,53 +352,58 @@ def main():
             homes.after_backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
-        return loss
+        return loss, logits
 
-    # Per-kernel table: every launch of the LAST warm-up step is bracketed with HIP events (~340 launches, ~3 ms of host
+    # --full: per-kernel table: every launch of the LAST warm-up step is bracketed with HIP events (~340 launches, ~3 ms of host
     # time per step -- kept out of the timed region).  Timed region: only the dominant kernel's launches are bracketed,
-    # which is what the roofline object needs.
+    # which is what the roofline object needs.  A plain run brackets nothing.
     table = None
     for i in range(args.warmup):
-        if i == args.warmup - 1:
+        if args.full and i == args.warmup - 1:
             aum_hip.timer.reset()
             aum_hip.timer.only, aum_hip.timer.enabled = None, True
         step()
-    if args.warmup > 0:
-        table = aum_hip.timer.summary()
-        tot_w = {k: v["avg_ms"] * v["launches"] for k, v in table.items()}
-        aum_hip.timer.only = {max(tot_w, key=tot_w.get)}
-    aum_hip.timer.reset()
-    aum_hip.timer.enabled = True
-    # ... every 5th of them (24 launches per step: 4 or 5 a step, every layer position over five steps): the two events of a bracket are two
-    # barrier packets on the stream, 2 x 5.8 us of idle GPU per bracketed launch -- 0.28 ms per step when all 24 are bracketed
-    # (profiles/r06_step_timeline.txt); `launches_timed` in the roofline object says how many the average is over
-    aum_hip.timer.every = int(os.environ.get("AUM_BENCH_TIMER_EVERY", "5"))
+    if args.full:
+        if args.warmup > 0:
+            table = aum_hip.timer.summary()
+            tot_w = {k: v["avg_ms"] * v["launches"] for k, v in table.items()}
+            aum_hip.timer.only = {max(tot_w, key=tot_w.get)}
+        aum_hip.timer.reset()
+        aum_hip.timer.enabled = True
+        # ... every 5th of them (24 launches per step: 4 or 5 a step, every layer position over five steps): the two events of a bracket are two
+        # barrier packets on the stream, 2 x 5.8 us of idle GPU per bracketed launch -- 0.28 ms per step when all 24 are bracketed
+        # (profiles/r06_step_timeline.txt); `launches_timed` in the roofline object says how many the average is over
+        aum_hip.timer.every = int(os.environ.get("AUM_BENCH_TIMER_EVERY", "5"))
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     aum_hip.timer.enabled = False
     aum_hip.timer.every = 1
-    # the same step without the optimizer (SURVEY 8d asks for both figures); a few extra steps, not part of `value`
-    def step_no_opt():
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            l_ = loss_fn(net(spec(), frontend=fe).float(), y)
-        l_.backward()
-        opt.zero_grad(set_to_none=True)
-    n_extra = max(2, min(5, args.steps))
-    step_no_opt()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(n_extra):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, logits, model)
+    ms_no_opt = None
+    if args.full:
+        # the same step without the optimizer (SURVEY 8d asks for both figures); a few extra steps, not part of `value`
+        def step_no_opt():
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                l_ = loss_fn(net(spec(), frontend=fe).float(), y)
+            l_.backward()
+            opt.zero_grad(set_to_none=True)
+        n_extra = max(2, min(5, args.steps))
         step_no_opt()
-    torch.cuda.synchronize()
-    ms_no_opt = (time.perf_counter() - t1) / n_extra * 1e3
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(n_extra):
+            step_no_opt()
+        torch.cuda.synchronize()
+        ms_no_opt = (time.perf_counter() - t1) / n_extra * 1e3
     rank_ms, n_buckets = None, None
     if dist is not None:
         # the slowest rank's time is the job's; every rank's own figure rides along so that a first multi-GPU run can be read from one line
@@ -392,8 +423,8 @@ def main():
     final_loss = float(loss.item())
     ktimes = aum_hip.timer.summary()
 
-    if rank == 0:
-        clips = world * args.batch * args.steps
+    full_figures = {}
+    if rank == 0 and args.full:
         # dominant kernel = largest share of summed launch time among the hand-written kernels
         tot = {k: v["avg_ms"] * v["launches"] for k, v in ktimes.items()}
         dom = max(tot, key=tot.get)
@@ -454,6 +485,11 @@ def main():
             if isinstance(fv, dict):
                 fwd_roof["valu_frac"] = fv.get("valu_busy_frac")
         gemm_roof = gemm_probe(dev, args.batch * 513, model.embed_dim, 2 * model.embed_dim) if world == 1 else None
+        full_figures = {"roofline": roof, "roofline_forward_kernel": fwd_roof, "roofline_gemm": gemm_roof,
+                        "ms_per_step_without_optimizer": round(ms_no_opt, 3),
+                        "kernel_ms_per_step": {k: round(v, 3) for k, v in sorted(per_step.items())}}
+    if rank == 0:
+        clips = world * args.batch * args.steps
         out = {
             "metric": "clips/sec/node AuM-Base 128x1024 fwd+bwd", "value": round(clips / elapsed, 2), "unit": "clips/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -465,24 +501,20 @@ def main():
                                    + ("" if args.no_frontend else ", input = 160000-sample waveforms through the one-launch HIP frontend (log-mel + 16x16 patch embedding + position rows)"),
                        "per_gpu_batch": args.batch, "global_batch": world * args.batch,
                        "parallelism": f"dp{world}" + (" (DDP, RCCL all-reduce overlapped with backward)" if dist is not None else "")},
-            "roofline": roof,
-            "roofline_forward_kernel": fwd_roof,
-            "roofline_gemm": gemm_roof,
             # whole step against the HBM roofline: SURVEY 8(d)'s algorithmic bytes of the 24 layers / measured step time
             "step_roofline": {"bound": "hbm", "alg_bytes_per_step": step_alg_bytes(args.batch, 513, model.embed_dim, args.depth),
                               "achieved": round(step_alg_bytes(args.batch, 513, model.embed_dim, args.depth) / (elapsed / args.steps) / 1e9, 1),
                               "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                               "frac": round(step_alg_bytes(args.batch, 513, model.embed_dim, args.depth) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, 4)},
-            "ms_per_step_without_optimizer": round(ms_no_opt, 3),
             "dist": {"world_size": world, "backend": (dist.get_backend() if dist is not None else None),
                      "rccl": bool(dist is not None and dist.get_backend() == "nccl"), "rank_ms_per_step": rank_ms,
                      "ddp_buckets": n_buckets, "bucket_cap_mb": (bucket_mb or 25) if dist is not None else None,
                      "grads_written_in_bucket": (ssi_mod.HOME_HITS[0] if dist is not None else None),
                      "grad_exchange_dtype": ("fp32" if args.grad_compress == "no" else args.grad_compress) if dist is not None else None},
-            "kernel_ms_per_step": {k: round(v, 3) for k, v in sorted(per_step.items())},
             "final_loss": round(final_loss, 5),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        out.update(full_figures)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # north_star's CPU baseline is the reference's pure-PyTorch selective_scan_ref loop; the C oracle (the checker of the parity
             # tests, all operators of a block, OpenMP on every core) is the faster CPU statement and is reported beside it
             out["cpu_baseline"] = cpu_baseline_torch_ref()

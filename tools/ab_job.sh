@@ -10,7 +10,7 @@
 #                                            tools/build_variant.sh); "-" = the default build and dispatch.
 #   tm_ab <fwd|bwd> <variant> [...]          tools/tm_ab.py: the time-serial scan kernels, default library against build variants
 #   variants <only>                          tools/variants_bench.py --only <only>   (bibi | long | ...), optionally after ENV=VALUE words
-#   profile [bench.py args]                  bench.py under rocprofv3 --kernel-trace --stats -> gpurun_out/prof/kernel_stats.txt
+#   profile [bench.py args]                  bench.py under rocprofv3 --kernel-trace --stats -> $JOB_OUT/prof/kernel_stats.txt
 #   probe <script.py> [args]                 any tools/*.py probe (gemm_probe.py, wgrad_probe.py, seg_time.py, skinny_probe.py ...)
 # Round-4 measurements and the invocation that repeats them (files under profiles/):
 #   r04_ab_msum.txt / r04_ab_tail2.txt       tm_ab bwd msum0   |  tm_ab bwd tail0          (+ bench_ab scan_tm_bwd_bidir -=- m=lib:msum0)
@@ -33,12 +33,13 @@
 #   r05_ab_conv_tc.txt       cv16 -DAUM_CONVT_NB16_BWD=16 -DAUM_CONVT_TC_BWD=64 (the round-4 backward) | cvb2 -DAUM_CONVT_BWD_BLOCKS=2:
 #                            bench_ab conv_tm_fwd,conv_tm_bwd d=- o=lib:cv16 b=lib:cvb2 x2
 #   r05_ab_bibi_ddp_streams.txt   variants bibi_ddp
-#   GEMM solutions (aum/tunableop_gfx950.csv)   tools/tune_job.sh, then tools/merge_tunable.py gpurun_out/tunable_*.csv
+#   GEMM solutions (aum/tunableop_gfx950.csv)   tools/tune_job.sh, then tools/merge_tunable.py $JOB_OUT/tunable_*.csv
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export PYTHONPATH=$PWD/audio-mamba-aum_amd:${PYTHONPATH:-}
 V=$PWD/audio-mamba-aum_amd/aum_hip/variants
-mkdir -p gpurun_out
+JOB_OUT=${JOB_OUT:-job_out}      # this job's logs and results, relative to the repository root
+mkdir -p $JOB_OUT
 
 apply_spec() {          # sets the environment of ONE run from a spec
     local spec=$1 item
@@ -64,7 +65,7 @@ run_recipe() {
             local rounds=1 specs=()
             for a in "$@"; do case $a in x[0-9]*) rounds=${a#x} ;; *) specs+=("$a") ;; esac; done
             for ((i = 0; i < rounds; ++i)); do for s in "${specs[@]}"; do
-                ( apply_spec "${s#*=}"; python bench.py --steps 12 --warmup 4 --no-cpu-baseline 2> gpurun_out/b.err | tail -1 | python -c "
+                ( apply_spec "${s#*=}"; python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline 2> $JOB_OUT/b.err | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = d['kernel_ms_per_step']
 print('${s%%=*}', d['ms_per_step'], d['value'], *[(n, k.get(n)) for n in '$keys'.split(',') if n])" )
@@ -75,10 +76,10 @@ print('${s%%=*}', d['ms_per_step'], d['value'], *[(n, k.get(n)) for n in '$keys'
               timeout 600 python tools/variants_bench.py --only "$1" 2>&1 | grep -v amdgpu.ids | tail -2 | cut -c1-300 ) ;;
         profile)
             cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
-            rm -rf /tmp/prof_run; mkdir -p gpurun_out/prof
-            timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_run -o bench -- python bench.py "$@" > gpurun_out/prof/bench.json 2> gpurun_out/prof/bench.err
-            tail -c 300 gpurun_out/prof/bench.json; echo
-            python tools/rocpd_stats.py "$(find /tmp/prof_run -name '*.db' | head -1)" gpurun_out/prof/kernel_stats.txt | head -40 | cut -c1-190 ;;
+            rm -rf /tmp/prof_run; mkdir -p $JOB_OUT/prof
+            timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_run -o bench -- python bench.py "$@" > $JOB_OUT/prof/bench.json 2> $JOB_OUT/prof/bench.err
+            tail -c 300 $JOB_OUT/prof/bench.json; echo
+            python tools/rocpd_stats.py "$(find /tmp/prof_run -name '*.db' | head -1)" $JOB_OUT/prof/kernel_stats.txt | head -40 | cut -c1-190 ;;
         probe) local script=$1; shift; timeout 900 python tools/$script "$@" 2>&1 | grep -v amdgpu.ids | tail -40 | cut -c1-300 ;;
         *) echo "unknown recipe $r"; return 2 ;;
     esac

@@ -19,6 +19,6 @@ for r in range(3):
     print("dtproj hip %.1f us   lib %.1f us" % (t(lambda: aum_hip.dtproj_tm_fwd(x, 48, w)), t(lambda: torch.matmul(x[:, :48], w.t()))))
 PY
 for i in 1 2; do
-  timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hip', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('dtproj_tm_fwd'))"
+  timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hip', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('dtproj_tm_fwd'))"
   AUM_DEBUG=1 AUM_DTPROJ_LIB=1 timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('lib', d['ms_per_step'], d['value'])"
 done

@@ -21,6 +21,6 @@ for r in range(3):
     print("xdt fused %.1f us   library x_proj + dtproj kernel %.1f us" % (t(lambda: aum_hip.xdt_tm_fwd(u, wx, w)), t(two)))
 PY
 for i in 1 2; do
-  timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('fused', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('xdt_tm_fwd'))"
-  AUM_DEBUG=1 AUM_XDT_LIB=1 timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('split', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('dtproj_tm_fwd'))"
+  timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('fused', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('xdt_tm_fwd'))"
+  AUM_DEBUG=1 AUM_XDT_LIB=1 timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('split', d['ms_per_step'], d['value'], d['kernel_ms_per_step'].get('dtproj_tm_fwd'))"
 done
