@@ -6,7 +6,8 @@ forward_features MM:509-667, Block.forward MM:58-99, defaults MM:191-242) and pr
 (patch_embed.proj.*, cls_token, pos_embed.pos_embed, layers.{i}.mixer.*, layers.{i}.norm.weight, norm_f.weight,
 head.*) so published checkpoints load.  Also mirrored: the cls-token placements of RUN's flags (middle / end / head,
 MM:528-535), `transpose_token_sequence` (time-major token order, MM:545-566) and `if_bidirectional` layer pairing
-(MM:623-638).  Options off that surface (rope, double cls, flexible patch sizes, drop-path > 0) are rejected.
+(MM:623-638), and ImageNet Vim initialisation (`imagenet_pretrain`, MM:348-395; aum.checkpoint.load_imagenet_checkpoint).
+Options off that surface (rope, double cls, flexible patch sizes, drop-path > 0) are rejected.
 """
 import math
 
@@ -114,11 +115,15 @@ class AudioMamba(nn.Module):
     def __init__(self, spectrogram_size=(128, 1024), patch_size=(16, 16), strides=(16, 16), depth=24, embed_dim=768,
                  channels=1, num_classes=527, norm_epsilon=1e-5, bimamba_type="v1", if_devide_out=True,
                  use_middle_cls_token=True, use_end_cls_token=False, transpose_token_sequence=False,
-                 if_bidirectional=False, ssm_cfg=None, device=None, dtype=None, **unsupported):
+                 if_bidirectional=False, ssm_cfg=None, device=None, dtype=None, imagenet_pretrain=False,
+                 imagenet_pretrain_path=None, imagenet_pretrain_modelkey="model", imagenet_load_middle_cls_token=True,
+                 imagenet_load_double_cls_token=False, **unsupported):
         super().__init__()
         on = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0.0, -1.0)
               and k not in ("if_cls_token", "rms_norm", "fused_add_norm", "residual_in_fp32", "if_abs_pos_embed", "final_pool_type",
-                            "imagenet_load_middle_cls_token", "use_PI_for_patch_embed", "imagenet_pretrain_modelkey")}
+                            "use_PI_for_patch_embed")}
+        if imagenet_load_double_cls_token:                        # needs a double-cls model
+            on["imagenet_load_double_cls_token"] = imagenet_load_double_cls_token
         if on:
             raise NotImplementedError(f"AudioMamba options outside the accelerated path: {sorted(on)}")
         if tuple(patch_size) != tuple(strides):
@@ -150,6 +155,10 @@ class AudioMamba(nn.Module):
         self.apply(lambda m: _init_weights(m, depth))              # MM:146-176
         self.patch_embed = PatchEmbed(tuple(patch_size), tuple(strides), channels, embed_dim)
         self.pos_embed = PosEmbed(self.num_patches + self.num_tokens, embed_dim)
+        if imagenet_pretrain:                                      # MM:348-395: after the model's own init, the loaded values win
+            from .checkpoint import load_imagenet_checkpoint
+            print(load_imagenet_checkpoint(self, imagenet_pretrain_path, imagenet_pretrain_modelkey,
+                                           imagenet_load_middle_cls_token, imagenet_load_double_cls_token))
         if device is not None or dtype is not None:
             self.to(device=device, dtype=dtype)
 

@@ -13,7 +13,8 @@ per-epoch validation with mAP/AUC/d' (TT:188-218), and every file an experiment 
 
 What is MI355X-first: DataLoader workers only decode waveforms; mel + SpecAug + normalisation + noise run on the
 GPU; bf16 autocast (no GradScaler needed) around the HIP mixer; DDP with a static graph and gradient-as-bucket-view.
-Out of scope here (rejected with an error): --model ast, epic_sounds, flexible patch training, ImageNet init.
+ImageNet init (--imagenet_pretrain, a Vim checkpoint as the backbone) is aum.checkpoint.load_imagenet_checkpoint.
+Out of scope here (rejected with an error): --model ast, epic_sounds, flexible patch training, double-cls ImageNet init.
 """
 import argparse
 import ast as _ast
@@ -64,6 +65,8 @@ def build_parser():
     a("--fstride", type=int, default=16)
     a("--tstride", type=int, default=16)
     a("--imagenet_pretrain", type=_lit, default="False")
+    a("--imagenet_pretrain_path", type=str, default=None)
+    a("--imagenet_pretrain_modelkey", type=str, default="model")
     a("--aum_pretrain", type=_lit, default="False")
     a("--aum_pretrain_path", type=str, default=None)
     a("--aum_pretrain_fstride", type=int, default=16)
@@ -71,6 +74,8 @@ def build_parser():
     a("--if_continue_inf", type=_lit, default="True")
     a("--if_nan2num", type=_lit, default="True")
     a("--aum_drop_path", type=float, default=0)
+    a("--imagenet_load_middle_cls_token", type=_lit, default="True")
+    a("--imagenet_load_double_cls_token", type=_lit, default="False")
     a("--if_cls_token", type=_lit, default="True")
     a("--use_middle_cls_token", type=_lit, default="True")
     a("--use_double_cls_token", type=_lit, default="False")
@@ -107,8 +112,13 @@ def build_parser():
 def check_scope(args):
     if args.model != "aum":
         raise NotImplementedError("--model ast (the transformer baseline) is outside the accelerated path")
-    if args.dataset == "epic_sounds" or args.flexible_training or args.imagenet_pretrain or args.aum_drop_path:
-        raise NotImplementedError("epic_sounds / flexible training / ImageNet init / drop-path are out of scope")
+    if args.dataset == "epic_sounds" or args.flexible_training or args.aum_drop_path:
+        raise NotImplementedError("epic_sounds / flexible training / drop-path are out of scope")
+    if args.imagenet_pretrain and args.imagenet_load_double_cls_token:
+        raise NotImplementedError("--imagenet_load_double_cls_token: a double-cls ImageNet checkpoint needs a double-cls model, "
+                                  "which is off the accelerated path")
+    if args.imagenet_pretrain and not args.imagenet_pretrain_path:
+        raise ValueError("--imagenet_pretrain True needs --imagenet_pretrain_path")
     if not args.if_cls_token or args.use_double_cls_token or args.if_random_cls_token_position or args.if_random_token_rank:
         raise NotImplementedError("no / double / randomly placed cls tokens are off the accelerated path")
 
@@ -180,6 +190,10 @@ def build_model(args):
                        strides=(args.fstride, args.tstride), depth=args.depth, embed_dim=AUM_SIZES[size], num_classes=args.n_class,
                        bimamba_type=bimamba, use_middle_cls_token=args.use_middle_cls_token,
                        use_end_cls_token=args.use_end_cls_token, transpose_token_sequence=args.transpose_token_sequence)
+    if args.imagenet_pretrain:                   # ImageNet first, AuM second: the AuM checkpoint's values win (MM:348-446)
+        from .checkpoint import load_imagenet_checkpoint
+        print(load_imagenet_checkpoint(model, args.imagenet_pretrain_path, args.imagenet_pretrain_modelkey,
+                                       args.imagenet_load_middle_cls_token, args.imagenet_load_double_cls_token))
     if args.aum_pretrain:
         from .checkpoint import load_aum_checkpoint
         print(load_aum_checkpoint(model, args.aum_pretrain_path, args.aum_pretrain_fstride, args.aum_pretrain_tstride))
