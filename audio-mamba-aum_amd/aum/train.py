@@ -14,7 +14,9 @@ per-epoch validation with mAP/AUC/d' (TT:188-218), and every file an experiment 
 What is MI355X-first: DataLoader workers only decode waveforms; mel + SpecAug + normalisation + noise run on the
 GPU; bf16 autocast (no GradScaler needed) around the HIP mixer; DDP with a static graph and gradient-as-bucket-view.
 ImageNet init (--imagenet_pretrain, a Vim checkpoint as the backbone) is aum.checkpoint.load_imagenet_checkpoint.
-Out of scope here (rejected with an error): --model ast, epic_sounds, flexible patch training, double-cls ImageNet init.
+EPIC-Sounds (--dataset epic_sounds, run.py:139-158) reads the reference's annotation pickles and audio; its log-mel and SpecAugment run on
+the GPU (aum.epic).
+Out of scope here (rejected with an error): --model ast, flexible patch training, drop path, double-cls ImageNet init.
 """
 import argparse
 import ast as _ast
@@ -106,14 +108,26 @@ def build_parser():
     a("--grad_compress", type=str, default="no", choices=["no", "bf16", "fp16"],
       help="(new) exchange the gradient buckets in 16 bits (DDP communication hook): 368 -> 184 MB per step for AuM-Base")
     a("--max-steps", type=int, default=0, help="(new) stop each epoch after this many steps (smoke runs)")
+    a("--epic_config", type=str, default=None,
+      help="(new) the reference's epic_sounds config yaml: ANNOTATIONS_DIR, AUDIO_DATA_FILE and the split lists are read from it")
+    a("--epic_annotations_dir", type=str, default=None,
+      help="(new) directory of EPIC_Sounds_{train,validation}.pkl (overrides the config's ANNOTATIONS_DIR)")
+    a("--epic_audio", type=str, default=None,
+      help="(new) EPIC audio: the HDF5 file of the reference (needs h5py) or a directory of <video_id>.npy float arrays "
+           "(overrides the config's AUDIO_DATA_FILE)")
     return p
 
 
 def check_scope(args):
     if args.model != "aum":
         raise NotImplementedError("--model ast (the transformer baseline) is outside the accelerated path")
-    if args.dataset == "epic_sounds" or args.flexible_training or args.aum_drop_path:
-        raise NotImplementedError("epic_sounds / flexible training / drop-path are out of scope")
+    if args.flexible_training or args.aum_drop_path:
+        raise NotImplementedError("flexible training / drop-path are out of scope")
+    if args.dataset == "epic_sounds" and not (args.epic_config or (args.epic_annotations_dir and args.epic_audio)):
+        # run.py:139-141 falls back to the config_default.yaml of its own source tree, whose paths name the authors' storage; that
+        # implicit configuration is not implemented here: the data source is always given
+        raise NotImplementedError("--dataset epic_sounds needs its data source: --epic_config (the reference's yaml), or "
+                                  "--epic_annotations_dir and --epic_audio; the reference's built-in default config is not implemented")
     if args.imagenet_pretrain and args.imagenet_load_double_cls_token:
         raise NotImplementedError("--imagenet_load_double_cls_token: a double-cls ImageNet checkpoint needs a double-cls model, "
                                   "which is off the accelerated path")
@@ -250,7 +264,62 @@ class Frontend:
         return (wave, fe) if fused else (fe.spectrogram(wave), None)
 
 
+EPIC_DEFAULTS = dict(SAMPLING_RATE=24000, TRAIN_LIST="EPIC_Sounds_train.pkl", VAL_LIST="EPIC_Sounds_validation.pkl",
+                     ANNOTATIONS_DIR=None, AUDIO_DATA_FILE=None)
+
+
+def epic_config(args):
+    """run.py:139-158: the reference's yaml (paths, split lists, sample rate) with the launcher's overrides"""
+    cfg = dict(EPIC_DEFAULTS)
+    if args.epic_config:
+        import yaml
+        with open(args.epic_config) as f:
+            y = yaml.safe_load(f)
+        cfg.update({k: v for k, v in y.get("EPICSOUNDS", {}).items() if k in cfg})
+        cfg["SAMPLING_RATE"] = y.get("AUDIO_DATA", {}).get("SAMPLING_RATE", cfg["SAMPLING_RATE"])
+    if args.epic_annotations_dir:
+        cfg["ANNOTATIONS_DIR"] = args.epic_annotations_dir
+    if args.epic_audio:
+        cfg["AUDIO_DATA_FILE"] = args.epic_audio
+    if not cfg["ANNOTATIONS_DIR"] or not cfg["AUDIO_DATA_FILE"]:
+        raise ValueError("--dataset epic_sounds needs --epic_annotations_dir and --epic_audio (or an --epic_config that names them)")
+    cfg["T_MASK"] = int(args.timem * args.audio_length / 1024)
+    cfg["F_MASK"] = args.freqm
+    cfg["CLIP_SECS"] = int(args.audio_length / 100)
+    cfg["NUM_FRAMES"] = args.audio_length
+    cfg["T_WARP"] = 5
+    return cfg
+
+
+def make_epic_loader(args, train, D):
+    """the reference's construct_loader(cfg, "train" / "val") (loader.py:75-120): train shuffles and drops the last partial batch; both
+    splits take TRAIN.BATCH_SIZE = -b (the val split reads TRAIN.BATCH_SIZE, not the TEST.BATCH_SIZE = 2b that run.py also sets)"""
+    from .epic import EpicSoundsDataset
+    cfg = epic_config(args)
+    ann = os.path.join(cfg["ANNOTATIONS_DIR"], cfg["TRAIN_LIST"] if train else cfg["VAL_LIST"])
+    ds = EpicSoundsDataset(ann, cfg["AUDIO_DATA_FILE"], cfg["CLIP_SECS"], cfg["NUM_FRAMES"], sample_rate=cfg["SAMPLING_RATE"])
+    sampler = None
+    if D.world > 1:
+        sampler = torch.utils.data.distributed.DistributedSampler(ds, D.world, D.rank, shuffle=train, drop_last=False)
+    g = torch.Generator().manual_seed(EXP_SEED + 1000 * D.rank + (1 if train else 0))
+    return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=(train and sampler is None), sampler=sampler,
+                                       num_workers=args.num_workers, pin_memory=D.cuda, drop_last=train,
+                                       generator=g, worker_init_fn=_seed_worker)
+
+
+def make_frontend(args, device, train, D=None):
+    """Frontend (Kaldi fbank, AudioSet-style datasets) or aum.epic.EpicFrontend (--dataset epic_sounds)"""
+    if args.dataset != "epic_sounds":
+        return Frontend(args, device, train)
+    from .epic import EpicFrontend
+    cfg = epic_config(args)
+    return EpicFrontend(device, args.audio_length, train, t_mask=cfg["T_MASK"], f_mask=cfg["F_MASK"], warp=cfg["T_WARP"],
+                        seed=EXP_SEED + (D.rank if D is not None else 0), sample_rate=cfg["SAMPLING_RATE"])
+
+
 def make_loader(args, path, train, D):
+    if args.dataset == "epic_sounds":
+        return make_epic_loader(args, train, D)
     from .data import WaveformDataset
     win = int(args.sample_rate * 0.025)
     shift = int(args.sample_rate * args.fshift * 0.001)
@@ -385,10 +454,16 @@ def train(model, train_loader, val_loader, args, D):
         # bucket and leaves every view behind it off a 16-byte boundary, which the in-bucket gradient writes of ssi.grad_home need)
         homes = compress_gradients(net, args.grad_compress)
     scaler = torch.amp.GradScaler("cuda", enabled=(args.mixed_precision == "fp16" and D.cuda))
-    scheduler = torch.optim.lr_scheduler.MultiStepLR(
-        optimizer, list(range(args.lrscheduler_start, 1000, args.lrscheduler_step)), gamma=args.lrscheduler_decay)
+    epic = args.dataset == "epic_sounds"
+    if epic:                                    # TT:63-72: LambdaLR per epoch, and the warm-up of 2 epochs' steps below
+        from .epic import epic_lr_factor, epic_warm_lr
+        scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=epic_lr_factor)
+        epic_warm_steps = 2 * len(train_loader)
+    else:
+        scheduler = torch.optim.lr_scheduler.MultiStepLR(
+            optimizer, list(range(args.lrscheduler_start, 1000, args.lrscheduler_step)), gamma=args.lrscheduler_decay)
     loss_fn = _loss_fn(args)
-    fe_train, fe_val = Frontend(args, D.device, True), Frontend(args, D.device, False)
+    fe_train, fe_val = make_frontend(args, D.device, True, D), make_frontend(args, D.device, False, D)
     D.print("now training with {:s}, main metrics: {:s}, loss function: {:s}, learning rate scheduler: {:s}".format(
         str(args.dataset), str(args.metrics), str(loss_fn), str(scheduler)))
 
@@ -409,7 +484,12 @@ def train(model, train_loader, val_loader, args, D):
             if args.max_steps and i >= args.max_steps:
                 break
             wave, labels = wave.to(D.device, non_blocking=True), labels.to(D.device, non_blocking=True)
-            if args.warmup and global_step <= warm_steps and global_step % warm_every == 0:
+            if epic and args.warmup:
+                # TT:99-112: linear from lr / 100 over the first 2 epochs' steps, then lr on EVERY step (which overrides the LambdaLR decay:
+                # the reference's behaviour, kept)
+                for g in optimizer.param_groups:
+                    g["lr"] = epic_warm_lr(global_step, args.lr, epic_warm_steps)
+            elif args.warmup and global_step <= warm_steps and global_step % warm_every == 0:
                 warm_lr = (global_step / warm_steps) * args.lr
                 for g in optimizer.param_groups:
                     g["lr"] = warm_lr
@@ -514,7 +594,7 @@ def _sync_loss(loss_acc, D):
 def evaluate(model, val_loader, args, D, tag):
     """RUN:283-324"""
     from .stats import summarize
-    stats, loss = validate(model.to(D.device), val_loader, Frontend(args, D.device, False), args, D, tag)
+    stats, loss = validate(model.to(D.device), val_loader, make_frontend(args, D.device, False, D), args, D, tag)
     if not D.main:
         return None
     s = summarize(stats, args.metrics)

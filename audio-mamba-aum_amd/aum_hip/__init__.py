@@ -127,6 +127,18 @@ class FbankArgs(C.Structure):
                 + [("aug", _vp), ("noise", _vp)])
 
 
+class StftArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("wave", "window", "twiddle", "mel_start_f", "mel_count_f", "mel_w", "n_valid", "out")]
+                + [(n, _i64) for n in ("wave_bs", "out_bs")]
+                + [(n, _i32) for n in ("batch", "n_samples", "win", "hop", "n_fft", "num_mel", "mel_wstride", "target_length")]
+                + [("eps", C.c_float), ("reserved", _i32)])
+
+
+class TimeWarpArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("in_", "table", "out")] + [(n, _i64) for n in ("in_bs", "out_bs")]
+                + [(n, _i32) for n in ("batch", "frames", "num_mel", "reserved")])
+
+
 class FrontendArgs(C.Structure):
     _fields_ = ([("fbank", FbankArgs)] + [(n, _vp) for n in ("weight", "bias", "pos", "cls_row", "tokens", "patches")]
                 + [("tokens_bs", _i64)] + [(n, _i32) for n in ("dim", "cls_pos", "dtype", "out_dtype")] + [("flags", _u32)])
@@ -189,7 +201,8 @@ EXPORTS = ["aum_gemm_tn", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_proj_fwd",
            "aum_rmsnorm_bwd", "aum_rmsnorm_bwd_partials", "aum_selftest_wave_scan", "aum_hbm_copy", "aum_sum_rows", "aum_sum_rows_multi",
            "aum_scan_tm_fwd", "aum_scan_tm_nck", "aum_scan_tm_ckpt_rows", "aum_scan_tm_bwd", "aum_scan_tm_workspace_bytes", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd",
            "aum_scan_tm_seg_carry_bytes", "aum_scan_tm_seg_workspace_bytes", "aum_selftest_wave_sum32",
-           "aum_conv1d_tm_fwd", "aum_conv1d_tm_bwd", "aum_conv1d_tm_nparts", "aum_gemm_wgrad", "aum_xdt_tm_bwd", "aum_causal_conv1d_update", "aum_selective_state_update", "aum_cast_bank", "aum_rmsnorm_bwd_partial_rows"]
+           "aum_conv1d_tm_fwd", "aum_conv1d_tm_bwd", "aum_conv1d_tm_nparts", "aum_gemm_wgrad", "aum_xdt_tm_bwd", "aum_causal_conv1d_update", "aum_selective_state_update", "aum_cast_bank", "aum_rmsnorm_bwd_partial_rows",
+           "aum_stft_logmel_fwd", "aum_spec_time_warp"]
 
 
 class Lib:
@@ -232,6 +245,8 @@ class Lib:
             fn.argtypes = [_i32] * 6
         self.c.aum_fbank_fwd.argtypes = [_vp, _vp]
         self.c.aum_frontend_tokens_fwd.argtypes = [_vp, _vp]
+        self.c.aum_stft_logmel_fwd.argtypes = [_vp, _vp]
+        self.c.aum_spec_time_warp.argtypes = [_vp, _vp]
         for n in ("aum_proj_fwd", "aum_proj_bwd_data", "aum_proj_bwd_weight"):
             getattr(self.c, n).argtypes = [_vp, _vp]
         self.c.aum_proj_bwd_weight_splits.argtypes = [_i32, _i64]
@@ -1162,6 +1177,49 @@ def _fill_fbank(a, lib, wave, tables, target_length, norm_mean, norm_std, preemp
         assert noise.shape == (batch, target_length, num_mel)
         lib.check_tensor(noise)
         a.noise = _ptr(noise)
+
+
+TIME_WARP_COLS = 8     # columns of the per-clip time-warp table (include/aum_hip.h AUM_TIME_WARP_COLS)
+
+
+def stft_logmel_fwd(wave, n_valid, tables, target_length, eps=1e-6, lib=None):
+    """EPIC-Sounds log-mel frontend (librosa stft -> |X| -> HTK mel -> log(x + eps) -> edge padding).  wave: (batch, n_samples) fp32;
+    n_valid: (batch,) int32 valid samples per clip; tables: dict(window, twiddle, mel_start_f, mel_count_f, mel_w [num_mel, stride], win,
+    hop, n_fft) of device tensors built by aum.epic.StftTables.  -> (batch, target_length, num_mel) fp32."""
+    lib = lib or get()
+    lib.check_tensor(wave)
+    lib.check_tensor(n_valid)
+    assert wave.dtype == torch.float32 and wave.dim() == 2 and wave.stride(1) == 1
+    assert n_valid.dtype == torch.int32 and n_valid.is_contiguous() and n_valid.shape == (wave.shape[0],)
+    batch, n = wave.shape
+    num_mel, stride = tables["mel_w"].shape
+    out = torch.empty((batch, target_length, num_mel), dtype=torch.float32, device=wave.device)
+    a = StftArgs()
+    a.wave, a.n_valid, a.out = _ptr(wave), _ptr(n_valid), _ptr(out)
+    a.window, a.twiddle = _ptr(tables["window"]), _ptr(tables["twiddle"])
+    a.mel_start_f, a.mel_count_f, a.mel_w = _ptr(tables["mel_start_f"]), _ptr(tables["mel_count_f"]), _ptr(tables["mel_w"])
+    a.wave_bs, a.out_bs = wave.stride(0), out.stride(0)
+    a.batch, a.n_samples, a.win, a.hop, a.n_fft = batch, n, tables["win"], tables["hop"], tables["n_fft"]
+    a.num_mel, a.mel_wstride, a.target_length, a.eps = num_mel, stride, target_length, eps
+    _launch(lib.c.aum_stft_logmel_fwd, a, wave, lib, "stft_logmel_fwd", (batch, target_length, num_mel))
+    return out
+
+
+def spec_time_warp(spec, table, lib=None):
+    """SpecAugment time warp of the EPIC-Sounds recipe, out of place.  spec: (batch, frames, num_mel) fp32; table: (batch, 8) fp32 per clip
+    [cy, cx, w, v0, v1, v2, xn, yn] (aum.epic.warp_table).  -> (batch, frames, num_mel) fp32."""
+    lib = lib or get()
+    lib.check_tensor(spec)
+    lib.check_tensor(table)
+    assert spec.dtype == torch.float32 and spec.dim() == 3 and spec.stride(2) == 1 and spec.stride(1) == spec.shape[2]
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape == (spec.shape[0], TIME_WARP_COLS)
+    out = torch.empty_like(spec, memory_format=torch.contiguous_format)
+    a = TimeWarpArgs()
+    a.in_, a.table, a.out = _ptr(spec), _ptr(table), _ptr(out)
+    a.in_bs, a.out_bs = spec.stride(0), out.stride(0)
+    a.batch, a.frames, a.num_mel = spec.shape
+    _launch(lib.c.aum_spec_time_warp, a, spec, lib, "spec_time_warp", tuple(spec.shape))
+    return out
 
 
 FRONTEND_TIME_MAJOR = 1

@@ -11,6 +11,7 @@
 #include "scan_half_kernels.h"
 #include "scan_row_kernels.h"
 #include "fbank_kernels.h"
+#include "stft_kernels.h"
 #include "proj_kernels.h"
 #include "frontend_kernels.h"
 #include "conv_rows_kernels.h"
@@ -884,6 +885,47 @@ AUM_API int aum_fbank_fwd(const AumFbankArgs* a, void* stream) {
 #else
     if (per_wave) hipLaunchKernelGGL(k_fbank_w, dim3((unsigned)grid_w), dim3(FBANK_THREADS), 0, (aum_stream_t)stream, *a);
     else hipLaunchKernelGGL(k_fbank, dim3((unsigned)grid), dim3(FBANK_THREADS), 0, (aum_stream_t)stream, *a);
+#endif
+    return launch_status();
+}
+
+// ---- EPIC-Sounds frontend: log-mel (librosa-style STFT) and the SpecAugment time warp ------------------------------
+#ifndef AUM_EMU
+__global__ __launch_bounds__(STFT_THREADS) void k_stft_logmel(AumStftArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[STFT_LDS_FLOATS];
+    stft_logmel_frame(a, (int)blockIdx.x, lds);
+}
+__global__ __launch_bounds__(STFT_THREADS) void k_spec_time_warp(AumTimeWarpArgs a) { spec_time_warp_wg(a, (int)blockIdx.x); }
+#endif
+AUM_API int aum_stft_logmel_fwd(const AumStftArgs* a, void* stream) {
+    if (!a || !a->wave || !a->n_valid || !a->out || !a->window || !a->twiddle || !a->mel_start_f || !a->mel_count_f || !a->mel_w) return AUM_E_NULL;
+    if (a->batch <= 0 || a->n_samples < 0 || a->win <= 0 || a->hop <= 0 || a->num_mel <= 0 || a->mel_wstride <= 0 || a->target_length <= 0)
+        return AUM_E_SHAPE;
+    if (a->n_fft < 256 || a->n_fft > AUM_STFT_MAX_FFT || (a->n_fft & (a->n_fft - 1)) || a->win > a->n_fft) return AUM_E_UNSUPPORTED;
+    if ((int64_t)a->batch * a->target_length > 0x7fffffff) return AUM_E_SHAPE;
+    const int grid = a->batch * a->target_length;
+#ifdef AUM_EMU
+    (void)stream;
+    std::vector<float> lds(STFT_LDS_FLOATS);
+    for (int wg = 0; wg < grid; ++wg) stft_logmel_frame(*a, wg, lds.data());
+#else
+    hipLaunchKernelGGL(k_stft_logmel, dim3((unsigned)grid), dim3(STFT_THREADS), 0, (aum_stream_t)stream, *a);
+#endif
+    return launch_status();
+}
+AUM_API int aum_spec_time_warp(const AumTimeWarpArgs* a, void* stream) {
+    if (!a || !a->in || !a->table || !a->out) return AUM_E_NULL;
+    if (a->in == a->out) return AUM_E_UNSUPPORTED;
+    if (a->batch <= 0 || a->frames < 2 || a->num_mel < 2 || (int64_t)a->frames * a->num_mel < WAVE) return AUM_E_SHAPE;
+    const int64_t per_clip = (int64_t)a->frames * a->num_mel;
+    if (per_clip + WAVE > 0x7fffffff || a->in_bs < per_clip || a->out_bs < per_clip) return AUM_E_SHAPE;
+    const int64_t grid = (per_clip * a->batch + STFT_THREADS - 1) / STFT_THREADS;
+    if (grid > 0x7fffffff) return AUM_E_SHAPE;
+#ifdef AUM_EMU
+    (void)stream;
+    for (int64_t wg = 0; wg < grid; ++wg) spec_time_warp_wg(*a, (int)wg);
+#else
+    hipLaunchKernelGGL(k_spec_time_warp, dim3((unsigned)grid), dim3(STFT_THREADS), 0, (aum_stream_t)stream, *a);
 #endif
     return launch_status();
 }

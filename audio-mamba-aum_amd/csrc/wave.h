@@ -118,6 +118,9 @@ AUM_DEV bool any_lane(vm m) { return __any(m); }
 AUM_DEV vi vcvt_i(vf x) { return (int)x; }
 AUM_DEV vi vmin_i(vi a, int b) { return a < b ? a : b; }
 AUM_DEV vi vmax_i(vi a, int b) { return a > b ? a : b; }
+AUM_DEV vf vmin(vf a, vf b) { return __builtin_fminf(a, b); }
+AUM_DEV vf vfloor(vf x) { return __builtin_floorf(x); }         // v_floor_f32
+AUM_DEV vf vcvt_f(vi x) { return (float)x; }
 
 // Packed pair of fp32 lanes-values: the VALU of gfx950 executes a wave64 fp32 instruction in 4 cycles (measured:
 // SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 4.2-4.5 on the scan kernels) and the packed forms v_pk_fma_f32 / v_pk_mul_f32 /
@@ -595,6 +598,9 @@ inline bool any_lane(const vm& m) { bool r = false; AUM_LANES r = r || m.v[l]; r
 inline vi vcvt_i(const vf& x) { vi r; AUM_LANES r.v[l] = (int)x.v[l]; return r; }
 inline vi vmin_i(const vi& a, int b) { vi r; AUM_LANES r.v[l] = a.v[l] < b ? a.v[l] : b; return r; }
 inline vi vmax_i(const vi& a, int b) { vi r; AUM_LANES r.v[l] = a.v[l] > b ? a.v[l] : b; return r; }
+inline vf vmin(const vf& a, const vf& b) { vf r; AUM_LANES r.v[l] = std::fmin(a.v[l], b.v[l]); return r; }
+inline vf vfloor(const vf& x) { vf r; AUM_LANES r.v[l] = std::floor(x.v[l]); return r; }
+inline vf vcvt_f(const vi& x) { vf r; AUM_LANES r.v[l] = (float)x.v[l]; return r; }
 // scalar (wave-uniform) overloads so kernel code can mix uniform floats freely
 inline float vfma(float a, float b, float c) { return std::fmaf(a, b, c); }
 inline float vexp2(float x) { return std::exp2(x); }

@@ -43,7 +43,9 @@ extern "C" {
                                    _NO_PREFETCH / _W4 / _RING, aum_gemm_tn_sk, aum_gemm_tn_sk_workspace_bytes, aum_scan_tm_bwd_matrix_sums); AUM_GEMM_PACED;
                                    aum_sum_rows / aum_sum_rows_multi take any float address as destination;
                                13: aum_cast_bank (the 16-bit copies -- and transposes -- of a group of fp32 master weights in one launch);
-                                   aum_rmsnorm_bwd_partial_rows (the vectorised norm backward leaves an eighth of the partial rows) */
+                                   aum_rmsnorm_bwd_partial_rows (the vectorised norm backward leaves an eighth of the partial rows);
+                                   additions without a version step (no existing struct or entry point changes): aum_stft_logmel_fwd, aum_spec_time_warp
+                                   (the EPIC-Sounds frontend) */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -599,6 +601,51 @@ int aum_sum_rows_multi(const AumSumJob* jobs, int32_t njobs, void* stream);
  *   bank_t  (n, cols, rows): the transposes, or NULL
  * rows % 8 == 0, cols % 4 == 0; bank / bank_t 16-byte aligned. */
 int aum_cast_bank(const uint64_t* src, int32_t n, int32_t rows, int32_t cols, void* bank, void* bank_t, int32_t dtype, void* stream);
+
+/*
+ * EPIC-Sounds log-mel frontend (an addition to ABI 13; replaces librosa.stft + filters.mel + log on the CPU DataLoader workers of the reference,
+ * src/epic_sounds/epic_data/audio_loader_epicsounds.py:94-156).  Per clip b and output frame t < target_length:
+ *   frames  = 1 + n_valid[b] / hop   (librosa center=True: the clip is zero-padded by n_fft / 2 on both sides);  frame t >= frames is a copy of
+ *             frame frames - 1 (np.pad 'edge'), frames past target_length are dropped
+ *   frame f = samples f * hop - n_fft / 2 + (n_fft - win) / 2 + j, j < win, times window[j] (zero outside [0, n_valid[b]))
+ *   out[b][t][m] = log(sum_c mel_w[m][c] * |X[mel_start[m] + c]| + eps),   X = the n_fft-point DFT of the frame (magnitude, not power)
+ *   wave        (batch, n_samples) fp32, batch stride wave_bs elements;  n_valid (batch) int32, 0 <= n_valid[b] <= n_samples
+ *   window      (win) fp32;  twiddle (n_fft / 2 complex pairs exp(-2 pi i k / n_fft));  mel_start_f / mel_count_f (num_mel, small integers
+ *               stored as fp32), mel_w (num_mel, mel_wstride): the sparse HTK filterbank built by the host (aum/epic.py)
+ *   out         (batch, target_length, num_mel) fp32, batch stride out_bs elements
+ * n_fft a power of two, 256 <= n_fft <= AUM_STFT_MAX_FFT; 0 < win <= n_fft; hop > 0.
+ */
+#define AUM_STFT_MAX_FFT 2048
+typedef struct AumStftArgs {
+    const float *wave, *window, *twiddle, *mel_start_f, *mel_count_f, *mel_w;
+    const int32_t* n_valid;
+    float* out;
+    int64_t wave_bs, out_bs;
+    int32_t batch, n_samples, win, hop, n_fft, num_mel, mel_wstride, target_length;
+    float eps;
+    int32_t reserved;
+} AumStftArgs;
+int aum_stft_logmel_fwd(const AumStftArgs* args, void* stream);
+
+/*
+ * SpecAugment time warp of the EPIC-Sounds recipe (an addition to ABI 13; spec_augment.py:346-360 -> sparse_image_warp / dense_image_warp,
+ * :6-42, 199-345), out of place.  The reference warps the (num_mel, frames) image with a one-centre polyharmonic spline (order 2) whose
+ * frequency flow is exactly 0; per clip its time flow is
+ *   r(y, x)    = (xn - 2 (y cy + x cx)) + yn                      (the reference's squared distance: xn sums the squares of EVERY grid point)
+ *   flow(y, x) = 0.5 r log(max(r, 1e-10)) w + ((y v0 + x v1) + v2),   y = mel bin, x = frame
+ * and out[y][x] is the bilinear sample of in at (y, x - flow) with dense_image_warp's clamping (floor in [0, size - 2], weight in [0, 1]).
+ *   in / out (batch, frames, num_mel) fp32 (frame-major, the layout of aum_stft_logmel_fwd), batch strides in_bs / out_bs; in != out
+ *   table    (batch, AUM_TIME_WARP_COLS) fp32 per clip: [cy, cx, w, v0, v1, v2, xn, yn], solved on the host (aum/epic.py)
+ * frames >= 2, num_mel >= 2, frames * num_mel >= 64.
+ */
+#define AUM_TIME_WARP_COLS 8
+typedef struct AumTimeWarpArgs {
+    const float *in, *table;
+    float* out;
+    int64_t in_bs, out_bs;
+    int32_t batch, frames, num_mel, reserved;
+} AumTimeWarpArgs;
+int aum_spec_time_warp(const AumTimeWarpArgs* args, void* stream);
 
 #ifdef __cplusplus
 }
