@@ -20,6 +20,8 @@ _SO = os.path.join(_HERE, "libaum_hip.so")
 
 AUM_F32, AUM_BF16, AUM_F16 = 0, 1, 2
 SCAN_SOFTPLUS, SCAN_REVERSE, SCAN_GENERIC, SCAN_ROWPAIR, SCAN_ACCUMULATE = 1, 2, 4, 8, 16
+SCAN_DELTA_ACTIVATED = 32       # token-major scans: delta already holds softplus(raw + delta_bias) (xdt_tm_fwd(..., delta_softplus=True))
+XDT_DELTA_SOFTPLUS = 1
 CONV_SILU, CONV_REVERSE = 1, 2
 _DT = {torch.float32: AUM_F32, torch.bfloat16: AUM_BF16, torch.float16: AUM_F16}
 _ERR = {-1: "AUM_E_NULL", -2: "AUM_E_SHAPE", -3: "AUM_E_DTYPE", -4: "AUM_E_UNSUPPORTED", -5: "AUM_E_WORKSPACE",
@@ -193,7 +195,8 @@ class DtProjArgs(C.Structure):
 
 class XdtArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("u", "wx", "wdt", "x_dbl", "delta")] + [("ntok", _i64)]
-                + [(n, _i32) for n in ("dim", "rank", "ncols", "ldu", "ldwx", "ldwdt", "ldx", "ldd", "dtype")])
+                + [(n, _i32) for n in ("dim", "rank", "ncols", "ldu", "ldwx", "ldwdt", "ldx", "ldd", "dtype")]
+                + [("delta_bias", _vp), ("flags", _u32)])
 
 
 EXPORTS = ["aum_gemm_tn", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_proj_fwd", "aum_proj_bwd_data", "aum_proj_bwd_weight", "aum_proj_bwd_weight_splits", "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_abi_version", "aum_selective_scan_fwd", "aum_selective_scan_bwd", "aum_scan_max_single_pass_len",
@@ -587,10 +590,11 @@ def scan_tm_segments(batch, dim, length, bidir, training=False, nsimd=None, devi
 
 
 def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, reverse=False, A_b=None,
-                want_out_pre=False, ckpt=None, out=None, lib=None, segments=1):
+                want_out_pre=False, ckpt=None, out=None, lib=None, segments=1, delta_activated=False):
     """Selective scan forward on token-major tensors: u, delta, z (batch, len, dim) with channels contiguous (row strides free: z
     may be a slice of an xz tensor); B, C (batch, len, dstate) in u's dtype.  A_b != None: both directions (Fo-Bi).
     segments > 1: the rows are cut into that many time ranges that run as waves of their own (aum_scan_tm_seg_fwd).
+    delta_activated: delta already holds softplus(raw + delta_bias) (AUM_SCAN_DELTA_ACTIVATED; 16-bit with z only): used as it is.
     Returns (out, out_pre|None), both (batch, len, dim) contiguous."""
     lib = lib or get()
     batch, length, dim = u.shape
@@ -625,7 +629,7 @@ def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softpl
         lib.check_tensor(ckpt)
         a.ckpt = _ptr(ckpt)
     a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0)
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
     if segments > 1:
         sa = ScanTmSegFwdArgs()
         sa.base = a
@@ -644,9 +648,11 @@ def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softpl
 
 
 def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_softplus=False, reverse=False, A_b=None, dz_out=None,
-                lib=None, segments=1, want_dA_xA=False, param_out=None):
+                lib=None, segments=1, want_dA_xA=False, param_out=None, delta_activated=False):
     """Backward of scan_tm_fwd (same tensor conventions; ckpt: the tensor scan_tm_fwd filled).  Returns dict(du, ddelta, dz (batch, len,
-    dim) in u's dtype, dBC (batch, len, 2 * dstate) fp32 = dB | dC, dA, dA_b (dim, dstate), dD, ddelta_bias (dim) fp32)."""
+    dim) in u's dtype, dBC (batch, len, 2 * dstate) fp32 = dB | dC, dA, dA_b (dim, dstate), dD, ddelta_bias (dim) fp32).
+    delta_activated: delta holds softplus(raw + delta_bias); ddelta and ddelta_bias are still the gradients with respect to raw and the
+    bias (ddelta_bias whenever delta_bias is given)."""
     lib = lib or get()
     batch, length, dim = u.shape
     dstate = A.shape[1]
@@ -714,7 +720,7 @@ def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_
         a.pre_bs, a.pre_ts = _tm3(out_pre, "out_pre", dim)
         a.dz_bs, a.dz_ts = _tm3(dz, "dz", dim)
     a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0)
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
     if segments > 1:
         sa = ScanTmSegBwdArgs()
         sa.base = a
@@ -942,13 +948,25 @@ def xdt_tm_bwd(ddelta, dbc, wdt_t, wx_t, du, lib=None):
     return dx_dbl
 
 
-def xdt_tm_fwd(u, wx, wdt, lib=None):
-    """(x_dbl (ntok, 80), delta (ntok, dim)) = (u @ wx^T, x_dbl[:, :rank] @ wdt^T) in one pass over u (SSI:467-468 on token-major rows)"""
+def xdt_tm_fwd(u, wx, wdt, lib=None, delta_bias=None, delta_softplus=False):
+    """(x_dbl (ntok, 80), delta (ntok, dim)) = (u @ wx^T, x_dbl[:, :rank] @ wdt^T) in one pass over u (SSI:467-468 on token-major rows).
+    delta_softplus: delta = softplus(x_dbl[:, :rank] @ wdt^T + delta_bias) instead, rounded once -- the activated delta a token-major scan
+    takes with delta_activated=True (delta_bias: (dim) fp32 or None)."""
     lib = lib or get()
     for t in (u, wx, wdt):
         lib.check_tensor(t)
     if not xdt_tm_supported(u, wx, wdt):
         raise RuntimeError(f"xdt_tm_fwd: unsupported operands {tuple(u.shape)} {u.dtype}, {tuple(wx.shape)}, {tuple(wdt.shape)}")
+    if delta_bias is not None and not delta_softplus:
+        raise RuntimeError("xdt_tm_fwd: delta_bias is only added together with the softplus (delta_softplus=True)")
+    if delta_softplus and lib.host:
+        # the lane-array build's aum_xdt_tm_fwd is a plain loop that ignores the activation fields: it would hand back the raw product
+        raise RuntimeError("xdt_tm_fwd: delta_softplus needs the device library")
+    if delta_bias is not None:
+        delta_bias = _f32c(delta_bias)
+        lib.check_tensor(delta_bias)
+        if delta_bias.shape != (u.shape[1],) or delta_bias.data_ptr() % 16:
+            raise RuntimeError(f"xdt_tm_fwd: delta_bias must be a 16-byte aligned ({u.shape[1]},) fp32 tensor")
     ntok, dim = u.shape
     rank = wdt.shape[1]
     ncols = wx.shape[0]
@@ -958,6 +976,7 @@ def xdt_tm_fwd(u, wx, wdt, lib=None):
     a.u, a.wx, a.wdt, a.x_dbl, a.delta = _ptr(u), _ptr(wx), _ptr(wdt), _ptr(x_dbl), _ptr(delta)
     a.ntok, a.dim, a.rank, a.ncols = ntok, dim, rank, ncols
     a.ldu, a.ldwx, a.ldwdt, a.ldx, a.ldd, a.dtype = u.stride(0), wx.stride(0), wdt.stride(0), ncols, dim, _DT[u.dtype]
+    a.delta_bias, a.flags = _ptr(delta_bias), (XDT_DELTA_SOFTPLUS if delta_softplus else 0)
     _launch(lib.c.aum_xdt_tm_fwd, a, u, lib, "xdt_tm_fwd", (ntok, dim, rank))
     return x_dbl, delta
 

@@ -145,7 +145,7 @@ int scan_tm_seg_fwd_f16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase
 #endif
 #if AUM_API_PART == 6 || AUM_API_PART == 0
 #ifndef AUM_EMU
-template <class T, bool SP, bool HAS_Z, bool BIDIR>
+template <class T, int SP, bool HAS_Z, bool BIDIR>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_bwd(AumScanTmBwdArgs a, ScanTBwdOut wo) {
     __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_bwd_lds_wave_floats<T>()];
 #ifdef AUM_SCANT_TRACE      // tools/tm_trace.py builds only: 16 x uint64 per wave behind the partials of the workspace
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_bwd
 #endif
 }
 #endif
-template <class T, bool SP, bool HAS_Z, bool BIDIR> static int launch_scant_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) {
+template <class T, int SP, bool HAS_Z, bool BIDIR> static int launch_scant_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) {
     const int grid = scant_bwd_wgs<BIDIR>(a.batch * (a.dim / WAVE));
 #ifdef AUM_EMU
     (void)s;
@@ -177,22 +177,27 @@ template <class T, bool SP, bool HAS_Z, bool BIDIR> static int launch_scant_bwd(
     return launch_status();
 }
 template <class T> static int scan_tm_bwd_t(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) {
+    if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {       // built for the product path only: 16-bit activations with z (scan_tm_bwd_any checks)
+        if constexpr (sizeof(T) == 2)
+            return a.A_b ? launch_scant_bwd<T, SCANT_SP_ACT, true, true>(a, wo, s) : launch_scant_bwd<T, SCANT_SP_ACT, true, false>(a, wo, s);
+        return AUM_E_UNSUPPORTED;
+    }
     const int key = ((a.flags & AUM_SCAN_SOFTPLUS) ? 4 : 0) | (a.z ? 2 : 0) | (a.A_b ? 1 : 0);
     switch (key) {
-#define AUM_TMB(K) case K: return launch_scant_bwd<T, ((K) & 4) != 0, ((K) & 2) != 0, ((K) & 1) != 0>(a, wo, s);
+#define AUM_TMB(K) case K: return launch_scant_bwd<T, ((K) & 4) ? SCANT_SP_IN : SCANT_SP_NONE, ((K) & 2) != 0, ((K) & 1) != 0>(a, wo, s);
         AUM_TMB(0) AUM_TMB(1) AUM_TMB(2) AUM_TMB(3) AUM_TMB(4) AUM_TMB(5) AUM_TMB(6) AUM_TMB(7)
 #undef AUM_TMB
     }
     return AUM_E_UNSUPPORTED;
 }
 #ifndef AUM_EMU
-template <class T, int PHASE, bool SP, bool HAS_Z>
+template <class T, int PHASE, int SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_seg_bwd(AumScanTmBwdArgs a, ScanTBwdOut wo, ScanTSeg sg) {
     __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_bwd_lds_wave_floats<T>()];
     scant_seg_bwd<T, PHASE, SP, HAS_Z>(a, wo, sg, (int)blockIdx.x, lds);
 }
 #endif
-template <class T, int PHASE, bool SP, bool HAS_Z>
+template <class T, int PHASE, int SP, bool HAS_Z>
 static int launch_scant_seg_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, aum_stream_t s) {
     const int grid = (a.batch * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
 #ifdef AUM_EMU
@@ -205,9 +210,19 @@ static int launch_scant_seg_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo
     return launch_status();
 }
 template <class T> static int scan_tm_seg_bwd_t(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s) {
+    if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {
+        if constexpr (sizeof(T) == 2) {
+            switch (phase) {
+                case 0: return launch_scant_seg_bwd<T, 0, SCANT_SP_ACT, true>(a, wo, sg, s);
+                case 1: return launch_scant_seg_bwd<T, 1, SCANT_SP_ACT, true>(a, wo, sg, s);
+                case 2: return launch_scant_seg_bwd<T, 2, SCANT_SP_ACT, true>(a, wo, sg, s);
+            }
+        }
+        return AUM_E_UNSUPPORTED;
+    }
     const int key = ((a.flags & AUM_SCAN_SOFTPLUS) ? 2 : 0) | (a.z ? 1 : 0);
     switch (phase * 4 + key) {
-#define AUM_TMS(P, K) case (P) * 4 + (K): return launch_scant_seg_bwd<T, P, ((K) & 2) != 0, ((K) & 1) != 0>(a, wo, sg, s);
+#define AUM_TMS(P, K) case (P) * 4 + (K): return launch_scant_seg_bwd<T, P, ((K) & 2) ? SCANT_SP_IN : SCANT_SP_NONE, ((K) & 1) != 0>(a, wo, sg, s);
 #define AUM_TMS4(P) AUM_TMS(P, 0) AUM_TMS(P, 1) AUM_TMS(P, 2) AUM_TMS(P, 3)
         AUM_TMS4(0) AUM_TMS4(1) AUM_TMS4(2)
 #undef AUM_TMS4
@@ -237,12 +252,24 @@ AUM_API int32_t aum_scan_tm_ckpt_rows(int32_t dtype) {
     return dtype == AUM_F32 ? scant_ck_rows<float>() : (dtype == AUM_BF16 || dtype == AUM_F16) ? scant_ck_rows<bf16_t>() : 0;
 }
 
+// AUM_SCAN_DELTA_ACTIVATED (16-bit activations with z): delta already holds softplus(raw + delta_bias).  The forward reads it as it is -- the
+// kernels without bias and softplus; the backward keeps the softplus derivative (SCANT_SP_ACT) and still writes ddelta_bias.
+static bool scan_tm_act_ok(uint32_t flags, int32_t dtype, const void* z) { return !(flags & AUM_SCAN_DELTA_ACTIVATED) || (dtype != AUM_F32 && z); }
+static AumScanTmFwdArgs scan_tm_fwd_resolve(const AumScanTmFwdArgs& a) {
+    AumScanTmFwdArgs r = a;
+    if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {
+        r.delta_bias = nullptr;
+        r.flags &= ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED);
+    }
+    return r;
+}
 static int scan_tm_fwd_check(const AumScanTmFwdArgs* a) {
     if (!a) return AUM_E_NULL;
     if (!a->u || !a->delta || !a->B || !a->C || !a->A || !a->out) return AUM_E_NULL;
     if (a->batch <= 0 || a->dim <= 0 || a->len <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
     if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
     if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
+    if (!scan_tm_act_ok(a->flags, a->dtype, a->z)) return AUM_E_UNSUPPORTED;
     if (a->A_b && (a->flags & AUM_SCAN_REVERSE)) return AUM_E_UNSUPPORTED;
     if (a->dtype != AUM_F32) {      // 16-bit B / C rows are read as dwords through the scalar cache
         if ((a->B_bs | a->B_ts | a->C_bs | a->C_ts) & 1) return AUM_E_UNSUPPORTED;
@@ -266,10 +293,11 @@ AUM_API int aum_scan_tm_fwd(const AumScanTmFwdArgs* a, void* stream) {
     const int rc = scan_tm_fwd_check(a);
     if (rc != AUM_OK) return rc;
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return scan_tm_fwd_f32(*a, s);
-        case AUM_BF16: return scan_tm_fwd_bf16(*a, s);
-        default: return scan_tm_fwd_f16(*a, s);
+    const AumScanTmFwdArgs k = scan_tm_fwd_resolve(*a);
+    switch (k.dtype) {
+        case AUM_F32: return scan_tm_fwd_f32(k, s);
+        case AUM_BF16: return scan_tm_fwd_bf16(k, s);
+        default: return scan_tm_fwd_f16(k, s);
     }
 }
 static int scan_tm_seg_fwd_any(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) {
@@ -299,14 +327,15 @@ AUM_API int aum_scan_tm_seg_fwd(const AumScanTmSegFwdArgs* sa, void* stream) {
     sg.seg_len = scant_seg_len(a->len, sa->segments);
     sg.dir0 = 0;
     sg.ndl = bidir ? 2 : 1;
-    int r = scan_tm_seg_fwd_any(*a, sg, 3, s);
+    const AumScanTmFwdArgs k = scan_tm_fwd_resolve(*a);
+    int r = scan_tm_seg_fwd_any(k, sg, 3, s);
     if (r != AUM_OK) return r;
     sg.ndl = 1;
-    if (!bidir) return scan_tm_seg_fwd_any(*a, sg, 0, s);
-    r = scan_tm_seg_fwd_any(*a, sg, 1, s);
+    if (!bidir) return scan_tm_seg_fwd_any(k, sg, 0, s);
+    r = scan_tm_seg_fwd_any(k, sg, 1, s);
     if (r != AUM_OK) return r;
     sg.dir0 = 1;
-    return scan_tm_seg_fwd_any(*a, sg, 2, s);
+    return scan_tm_seg_fwd_any(k, sg, 2, s);
 }
 AUM_API int64_t aum_scan_tm_workspace_bytes(int32_t batch, int32_t dim, int32_t len, int32_t dstate, int32_t bidirectional) {
     if (batch <= 0 || dim <= 0 || len <= 0 || dstate <= 0 || !scant_supported(dim, dstate)) return 0;
@@ -417,6 +446,7 @@ static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
     if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
     if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
     if (a->A_b && (a->flags & AUM_SCAN_REVERSE)) return AUM_E_UNSUPPORTED;
+    if (!scan_tm_act_ok(a->flags, a->dtype, a->z)) return AUM_E_UNSUPPORTED;
     const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
     if (a->dtype != AUM_F32) {
         if ((a->B_bs | a->B_ts | a->C_bs | a->C_ts) & 1) return AUM_E_UNSUPPORTED;
@@ -451,12 +481,15 @@ static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
     wo.trace = reinterpret_cast<unsigned long long*>(ws + L.trace);
 #endif
     aum_stream_t s = (aum_stream_t)stream;
+    const bool act = (a->flags & AUM_SCAN_DELTA_ACTIVATED) != 0;
+    AumScanTmBwdArgs k = *a;            // the kernels' view: an activated delta carries its bias already
+    if (act) k.delta_bias = nullptr;
     int rc = AUM_OK;
     if (nseg == 1) {
-        switch (a->dtype) {
-            case AUM_F32: rc = scan_tm_bwd_f32(*a, wo, s); break;
-            case AUM_BF16: rc = scan_tm_bwd_bf16(*a, wo, s); break;
-            default: rc = scan_tm_bwd_f16(*a, wo, s); break;
+        switch (k.dtype) {
+            case AUM_F32: rc = scan_tm_bwd_f32(k, wo, s); break;
+            case AUM_BF16: rc = scan_tm_bwd_bf16(k, wo, s); break;
+            default: rc = scan_tm_bwd_f16(k, wo, s); break;
         }
     } else {
         ScanTSeg sg;
@@ -475,24 +508,24 @@ static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
             f.A = a->A; f.A_b = a->A_b; f.delta_bias = a->delta_bias;
             f.out = a->du; f.out_bs = a->du_bs; f.out_ts = a->du_ts;       // never written by a carry pass
             f.batch = a->batch; f.dim = a->dim; f.len = a->len; f.dstate = a->dstate; f.dtype = a->dtype; f.flags = a->flags;
-            rc = scan_tm_seg_fwd_any(f, sg, 4, s);
+            rc = scan_tm_seg_fwd_any(scan_tm_fwd_resolve(f), sg, 4, s);
             if (rc != AUM_OK) return rc;
         }
         sg.ndl = 1;
         for (int d = 0; d < (bidir ? 2 : 1) && rc == AUM_OK; ++d) {
             sg.dir0 = d;
             const int phase = bidir ? 1 + d : 0;
-            switch (a->dtype) {
-                case AUM_F32: rc = scan_tm_seg_bwd_f32(*a, wo, sg, phase, s); break;
-                case AUM_BF16: rc = scan_tm_seg_bwd_bf16(*a, wo, sg, phase, s); break;
-                default: rc = scan_tm_seg_bwd_f16(*a, wo, sg, phase, s); break;
+            switch (k.dtype) {
+                case AUM_F32: rc = scan_tm_seg_bwd_f32(k, wo, sg, phase, s); break;
+                case AUM_BF16: rc = scan_tm_seg_bwd_bf16(k, wo, sg, phase, s); break;
+                default: rc = scan_tm_seg_bwd_f16(k, wo, sg, phase, s); break;
             }
         }
     }
     if (rc != AUM_OK) return rc;
     ScanTReduceArgs r;
     r.ws = ws;
-    r.dBC = a->dBC; r.dA = a->dA; r.dA_b = a->dA_b; r.dD = a->D ? a->dD : nullptr; r.dbias = a->delta_bias ? a->ddelta_bias : nullptr;
+    r.dBC = a->dBC; r.dA = a->dA; r.dA_b = a->dA_b; r.dD = a->D ? a->dD : nullptr; r.dbias = a->delta_bias || act ? a->ddelta_bias : nullptr;
     r.o_dA = L.dA; r.o_dD = L.dD; r.o_dbias = L.dbias;
     r.A = a->A; r.A_b = a->A_b; r.dAx = a->dA_xA; r.dAx_b = a->A_b ? a->dA_b_xA : nullptr;
     r.batch = a->batch; r.pbatch = a->batch * nseg; r.dim = a->dim; r.len = a->len; r.dstate = a->dstate; r.nparts = L.nparts; r.ndir = L.ndir; r.nsum = scant_dbc_rows_to_sum(L.nparts, bidir);

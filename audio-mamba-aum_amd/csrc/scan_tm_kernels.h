@@ -728,13 +728,17 @@ struct ScanTBwdOut {
     unsigned long long* trace;      // -DAUM_SCANT_TRACE builds (tools/tm_trace.py): 16 x uint64 per wave behind the partials; else unused
 };
 
+// SP of the backward: where delta's activation happens.  NONE: delta as it is (delta_softplus=False).  IN: the kernel forms softplus(raw + bias)
+// and multiplies ddelta by its derivative.  ACT (AUM_SCAN_DELTA_ACTIVATED): delta arrives as softplus(raw + bias) (aum_xdt_tm_fwd formed
+// it; the caller passes no bias), only the derivative is applied -- ddelta and ddelta_bias stay gradients with respect to raw and the bias.
+constexpr int SCANT_SP_NONE = 0, SCANT_SP_IN = 1, SCANT_SP_ACT = 2;
 #ifndef AUM_SCANT_TAIL2
 #define AUM_SCANT_TAIL2 1     // 0 (A/B builds): each butterfly complete where its terms exist, as in round 3
 #endif
 #ifndef AUM_SCANT_BABL
 #define AUM_SCANT_BABL 0      // timing experiments only (wrong results): 1 no butterflies, 2 no exponentials, 4 carries at a fixed register index,
 #endif                        // 8 no loads of the next block, 16 no entry-state loads, 32 no B/C reads from LDS
-template <class T, int N, int PHASE, bool SP, bool HAS_Z>
+template <class T, int N, int PHASE, int SP, bool HAS_Z>
 AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int b, int e0, int dir, int part, int t0, int tstep, int it0,
                            int it1, const float* Aptr, float dmul, vf16& hh, vf16& dAacc, vf& dDacc, vf& dbacc, float* lds,
                            unsigned long long* tacc = nullptr) {
@@ -960,7 +964,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
                 const int s0 = 2 * i, s1 = 2 * i + 1;
                 const vf2 us = mk2(raw_to_f32<T>(ru[s0]), raw_to_f32<T>(ru[s1]));
                 vf2 d = mk2(raw_to_f32<T>(rd[s0]), raw_to_f32<T>(rd[s1])) + bias2;
-                if (SP) d = vsoftplus2(d);
+                if (SP == SCANT_SP_IN) d = vsoftplus2(d);
                 Pd[i] = d;
                 Pu[i] = d * us;
                 const vf2 go = mk2(raw_to_f32<T>(rg[s0]), raw_to_f32<T>(rg[s1]));
@@ -1165,7 +1169,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
                         du = du + mk2(raw_to_f32<T>(rpu[s0]), raw_to_f32<T>(rpu[s1]));
                         dd = dd + mk2(raw_to_f32<T>(rpd[s0]), raw_to_f32<T>(rpd[s1]));
                     }
-                    if (SP) dd = dd * (one2 - vexp2_2(dls * spl2(splat(-LOG2E))));      // sigmoid(raw) = 1 - exp(-softplus(raw))
+                    if (SP != SCANT_SP_NONE) dd = dd * (one2 - vexp2_2(dls * spl2(splat(-LOG2E))));      // sigmoid(raw) = 1 - exp(-softplus(raw))
                     dbacc = dbacc + lo2(dd);
                     dbacc = dbacc + hi2(dd);
                 }
@@ -1191,7 +1195,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
                             du = du + raw_to_f32<T>(rpu[s]);
                             dd = dd + raw_to_f32<T>(rpd[s]);
                         }
-                        if (SP) dd = dd * (splat(1.f) - vexp2(dls * (-LOG2E)));      // sigmoid(raw) = 1 - exp(-softplus(raw))
+                        if (SP != SCANT_SP_NONE) dd = dd * (splat(1.f) - vexp2(dls * (-LOG2E)));      // sigmoid(raw) = 1 - exp(-softplus(raw))
                         dbacc = dbacc + dd;
                     }
                     lds_write_elem<T>(t_du, off, du);
@@ -1225,7 +1229,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
 }
 
 // workgroup = four waves as in the forward.  Workspace partials are summed by scant_bwd_reduce.
-template <class T, bool SP, bool HAS_Z, bool BIDIR>
+template <class T, int SP, bool HAS_Z, bool BIDIR>
 AUM_DEV void scant_bwd(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int wg, float* lds, unsigned long long* tacc = nullptr) {
     constexpr int N = SCANT_N;
     constexpr int NW = SCANT_NW;
@@ -1326,7 +1330,7 @@ AUM_DEV void scant_bwd(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int wg,
 // first step from zero behind its last), and leaves its partial sums of dA / dD / ddelta_bias in rows of their own: the reduce
 // kernel sums batch * nseg rows per direction.  PHASE 0: one direction alone; 1 / 2: direction 0 / direction 1 of a Fo-Bi pair, each
 // over the whole row, in two launches.
-template <class T, int PHASE, bool SP, bool HAS_Z>
+template <class T, int PHASE, int SP, bool HAS_Z>
 AUM_DEV void scant_seg_bwd(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, const ScanTSeg& sg, int wg, float* lds) {
     constexpr int N = SCANT_N;
     constexpr int NW = SCANT_NW;

@@ -1,4 +1,4 @@
-// xdt_args.h -- argument rules of aum_xdt_tm_fwd (include/aum_hip.h, ABI 9), shared by the device library (gemm.hip) and the tests-only
+// xdt_args.h -- argument rules of aum_xdt_tm_fwd (include/aum_hip.h, ABI 9; delta_bias / flags: ABI 13), shared by the device library (gemm.hip) and the tests-only
 // host build (tests/emu/aum_emu.cpp): no HIP dependency.
 #pragma once
 #include <stdint.h>
@@ -25,6 +25,9 @@ inline int xdt_check(const AumXdtArgs* p) {
     if ((g.ncols != XDT_COLS && g.ncols != XDT_COLS_SMALL) || g.rank % 8 || g.rank > 64 || g.rank > g.ncols || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
     if (g.ldu % 8 || g.ldwx % 8 || g.ldwdt % 8 || g.ldx % 8 || g.ldd % 8) return AUM_E_UNSUPPORTED;
     if (((uintptr_t)g.u | (uintptr_t)g.wx | (uintptr_t)g.wdt | (uintptr_t)g.x_dbl | (uintptr_t)g.delta) & 15u) return AUM_E_UNSUPPORTED;
+    // the bias is staged 16 bytes at a time and only ever added together with the softplus
+    if ((g.flags & ~AUM_XDT_DELTA_SOFTPLUS) || (g.delta_bias && !(g.flags & AUM_XDT_DELTA_SOFTPLUS)) || ((uintptr_t)g.delta_bias & 15u))
+        return AUM_E_UNSUPPORTED;
     return AUM_OK;
 }
 inline int xdt_bwd_check(const AumXdtBwdArgs* p) {

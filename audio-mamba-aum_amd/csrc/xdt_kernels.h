@@ -12,10 +12,14 @@
 // halves, storing delta 64 contiguous bytes per token row and instruction (the store layout of dtproj_kernels.h).
 // u is fetched 32 contiguous bytes per lane (a full 128-byte line per token row and K-step of 64) four K-steps ahead of its use; the k
 // order inside a step is permuted the same way on both operands (lane group kg holds k0 + 16 kg .. + 15), which the product does not see.
+// SOFTPLUS (AUM_XDT_DELTA_SOFTPLUS): delta = softplus(product + delta_bias) on the fp32 accumulators, rounded once -- the per-element work both
+// token-major scans did twice per direction pair (forward and backward: four softplus evaluations per element), done once here, in a kernel
+// that waits on its stores; the half's bias rides behind its W_dt rows in the slab.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave.h"
 #include "xdt_args.h"
 
 namespace aumx {
@@ -92,7 +96,7 @@ __device__ __forceinline__ void stage_rows(char* dst, int dst_pitch, const char*
 // NC = columns of x_dbl: 80 (AuM-Base: dt_rank 48 + 2 x 16) or 56 (AuM-Small: 24 + 32).  56 is three and a half column fragments: the
 // fourth fragment multiplies eight weight rows that do not exist (whatever the slab holds behind row 55) -- their products are columns 56..63
 // of the wave's tile, inside the row's padding, which nothing reads.
-template <bool BF16, int KS, int NW, int NC>
+template <bool BF16, int KS, int NW, int NC, bool SOFTPLUS>
 __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_fwd(AumXdtArgs g) {
     constexpr int NCF = (NC + 15) / 16;
     constexpr int XP = NC == 80 ? 176 : 144;             // bytes per tile row: an odd number of 16-byte chunks (conflict-free fragment reads)
@@ -196,9 +200,16 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_fwd(AumXdtArgs g) {
     // fragment j of a channel pair reads weight rows c0 + 8 (rho >> 2) + 4 j + (rho & 3): accumulator rows 4 kg + r of fragments 0, 1 are
     // channels c0 + 8 kg + 0..7
     const char* wdr = slab + ((rho >> 2) * 8 + (rho & 3)) * WDP + kg * 16;
+    // SOFTPLUS: the half's CH bias values behind its W_dt rows (CH * WDP + 4 CH <= slab_bytes(E)), one 16-byte piece per thread; this lane's
+    // eight channels of pair p at floats p * 32 + 8 kg
+    static_assert((XDT_MAX_DIM / 2) / 4 <= XDT_WAVES_MIN * 64 && (XDT_MAX_DIM / 2) * (WDP + 4) <= slab_bytes(XDT_MAX_DIM), "bias staging");
+    const float* bl = reinterpret_cast<const float*>(slab + CH * WDP) + kg * 8;
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
+        f4v bv = {0.f, 0.f, 0.f, 0.f};
+        if (SOFTPLUS && tid < CH / 4 && g.delta_bias) bv = *reinterpret_cast<const f4v*>(g.delta_bias + half * CH + tid * 4);
         stage_rows<NW * 64>(slab, WDP, static_cast<const char*>(g.wdt) + (int64_t)half * CH * g.ldwdt * 2, (int64_t)g.ldwdt * 2, CH, wchunks, tid);
+        if (SOFTPLUS && tid < CH / 4) *reinterpret_cast<f4v*>(slab + CH * WDP + tid * 16) = bv;
         __syncthreads();
         const int npairs = CH / 32;
 #pragma unroll 2
@@ -218,10 +229,22 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_fwd(AumXdtArgs g) {
                     for (int ks = 0; ks < KS; ++ks) a2[j] = mfma<BF16>(wf[j][ks], xf[tf][ks], a2[j]);
                 if (tok_ok[tf]) {
                     u4v o;
-                    o.x = pack2<BF16>(a2[0][0], a2[0][1]);
-                    o.y = pack2<BF16>(a2[0][2], a2[0][3]);
-                    o.z = pack2<BF16>(a2[1][0], a2[1][1]);
-                    o.w = pack2<BF16>(a2[1][2], a2[1][3]);
+                    if constexpr (SOFTPLUS) {       // the scans' softplus (SSI:106-107) on pairs: x > 20 passes, d == 0 keeps exp(x)
+                        const f4v b0 = *reinterpret_cast<const f4v*>(bl + p * 32), b1 = *reinterpret_cast<const f4v*>(bl + p * 32 + 4);
+                        const aum::vf2 d0 = aum::vsoftplus2(aum::vf2{a2[0][0], a2[0][1]} + aum::vf2{b0[0], b0[1]});
+                        const aum::vf2 d1 = aum::vsoftplus2(aum::vf2{a2[0][2], a2[0][3]} + aum::vf2{b0[2], b0[3]});
+                        const aum::vf2 d2 = aum::vsoftplus2(aum::vf2{a2[1][0], a2[1][1]} + aum::vf2{b1[0], b1[1]});
+                        const aum::vf2 d3 = aum::vsoftplus2(aum::vf2{a2[1][2], a2[1][3]} + aum::vf2{b1[2], b1[3]});
+                        o.x = pack2<BF16>(d0[0], d0[1]);
+                        o.y = pack2<BF16>(d1[0], d1[1]);
+                        o.z = pack2<BF16>(d2[0], d2[1]);
+                        o.w = pack2<BF16>(d3[0], d3[1]);
+                    } else {
+                        o.x = pack2<BF16>(a2[0][0], a2[0][1]);
+                        o.y = pack2<BF16>(a2[0][2], a2[0][3]);
+                        o.z = pack2<BF16>(a2[1][0], a2[1][1]);
+                        o.w = pack2<BF16>(a2[1][2], a2[1][3]);
+                    }
                     *reinterpret_cast<u4v*>(ob + tf * otf + ((int64_t)half * CH + p * 32) * 2) = o;
                 }
             }

@@ -554,6 +554,9 @@ def register_ddp_join_streams(ddp, state=None, hook=None):
 _XDT_BWD_HIP = _dbg_env("AUM_XDT_BWD_LIB", "0") != "1"      # AUM_DEBUG=1 AUM_XDT_BWD_LIB=1: the x_proj / dt_proj gradients as five library calls (A/B)
 _XDT_HIP = _dbg_env("AUM_XDT_LIB", "0") != "1"              # AUM_DEBUG=1 AUM_XDT_LIB=1: x_proj as a library GEMM + the dt projection kernel (A/B)
 _DTPROJ_HIP = _dbg_env("AUM_DTPROJ_LIB", "0") != "1"        # AUM_DEBUG=1 AUM_DTPROJ_LIB=1: the dt projection back on the library GEMM (A/B)
+# AUM_DEBUG=1 AUM_DELTA_IN_XDT=0: dt_bias and the softplus back inside both token-major scans (A/B).  By default the fused x/dt kernel writes
+# delta = softplus(raw + dt_bias) once and the scans read it as it is (AUM_SCAN_DELTA_ACTIVATED).
+_DELTA_IN_XDT = _dbg_env("AUM_DELTA_IN_XDT", "1") != "0"
 _GEMM_MODE = _dbg_env("AUM_GEMM", "auto")
 if _GEMM_MODE not in ("auto", "hip", "lib"):
     raise ValueError("AUM_GEMM takes auto, hip or lib")
@@ -715,8 +718,11 @@ def _inner_forward_tm(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_
     conv_out = aum_hip.conv1d_tm_fwd(x, conv_w, conv1d_bias, True, reverse)                 # SSI:463  (B, L, E)
     conv2d = conv_out.view(Bsz * L, E)
     w_x, w_dt = x_proj_weight.to(conv2d.dtype), delta_proj_weight.to(conv2d.dtype)
+    act_delta = False           # delta leaves the x/dt kernel as softplus(raw + dt_bias): the scans read it as it is
     if _XDT_HIP and conv2d.is_cuda and aum_hip.xdt_tm_supported(conv2d, w_x, w_dt):
-        x_dbl, delta = aum_hip.xdt_tm_fwd(conv2d, w_x, w_dt)                                 # SSI:467-468 in one pass over conv_out
+        act_delta = _DELTA_IN_XDT and bool(delta_softplus)
+        x_dbl, delta = aum_hip.xdt_tm_fwd(conv2d, w_x, w_dt, delta_bias=delta_bias if act_delta else None,
+                                          delta_softplus=act_delta)                           # SSI:467-468 in one pass over conv_out (+ SSI:106-107)
     else:
         x_dbl = torch.matmul(conv2d, w_x.t())                                                # SSI:467  (BL, R+2N)
         delta = None
@@ -740,8 +746,9 @@ def _inner_forward_tm(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_
     cut = waves < (-(-_TM_MIN_WAVES * 4 // 3) if need_bwd and A_b is not None else _TM_MIN_WAVES)
     out_z, out_pre = aum_hip.scan_tm_fwd(conv_out, delta.view(Bsz, L, E), A, Bm, Cm, D, z, delta_bias, delta_softplus,
                                          reverse if A_b is None else False, A_b=A_b, want_out_pre=need_bwd, ckpt=ckpt,
-                                         segments=tm_segments(Bsz, E, L, A_b is not None, False, device=xz.device) if cut else 1)
-    ctx.tm_cut = cut
+                                         segments=tm_segments(Bsz, E, L, A_b is not None, False, device=xz.device) if cut else 1,
+                                         delta_activated=act_delta)
+    ctx.tm_cut, ctx.act_delta = cut, act_delta
     # the scan backward forms d A .* A only for an A that neg_exp took out of THIS forward's cache (its _NegExpFn node is the consumer)
     ctx.A_cached = (need_bwd and A.dtype == torch.float32 and A.is_contiguous() and A.data_ptr() in _A_CACHE_PTRS
                     and (A_b is None or (A_b.is_contiguous() and A_b.data_ptr() in _A_CACHE_PTRS)))
@@ -789,7 +796,7 @@ def _inner_backward_tm(ctx, dout):
     g = aum_hip.scan_tm_bwd(conv_out, delta.view(Bsz, L, E), A, x3[:, :, R:R + N], x3[:, :, R + N:], D, z, delta_bias, dout_z, out_pre,
                             ckpt, ctx.delta_softplus, ctx.reverse if A_b is None else False, A_b=A_b, dz_out=dz,
                             segments=tm_segments(Bsz, E, L, A_b is not None, True, device=conv_out.device) if ctx.tm_cut else 1,
-                            want_dA_xA=ctx.A_cached,
+                            want_dA_xA=ctx.A_cached, delta_activated=ctx.act_delta,
                             param_out=dict(dD=H["D"], ddelta_bias=H["dt_bias"], dA_xA=H["A_log"], dA_b_xA=H["A_b_log"]))        # SSI:541-561
     if ctx.A_cached:            # A came out of the forward's cache (neg_exp): its d A_log is ready (see _NegExpFn)
         _da_xa_put(g["dA"], g["dA_xA"], A)

@@ -45,7 +45,8 @@ extern "C" {
                                13: aum_cast_bank (the 16-bit copies -- and transposes -- of a group of fp32 master weights in one launch);
                                    aum_rmsnorm_bwd_partial_rows (the vectorised norm backward leaves an eighth of the partial rows);
                                    additions without a version step (no existing struct or entry point changes): aum_stft_logmel_fwd, aum_spec_time_warp
-                                   (the EPIC-Sounds frontend) */
+                                   (the EPIC-Sounds frontend); AUM_SCAN_DELTA_ACTIVATED (token-major scans) and, appended to AumXdtArgs, delta_bias /
+                                   flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -70,6 +71,12 @@ enum {
 #define AUM_SCAN_ACCUMULATE 16u /* long rows (the chunked kernels; anything else: AUM_E_UNSUPPORTED): add to out (forward) / du, ddelta, dz
                                   (backward) instead of overwriting them -- the second direction of a bidirectional layer lands on
                                   the first one's tensors, replacing the element-wise sums of selective_scan_interface.py:507,554-559 */
+#define AUM_SCAN_DELTA_ACTIVATED 32u /* token-major scans (aum_scan_tm_* and their time-segment forms), 16-bit activations with z only (else
+                                  AUM_E_UNSUPPORTED): delta already holds softplus(raw + delta_bias) (aum_xdt_tm_fwd with AUM_XDT_DELTA_SOFTPLUS).
+                                  Replaces AUM_SCAN_SOFTPLUS (either may be set with it).  Forward: delta is used as it is; delta_bias is not read.
+                                  Backward: delta_bias is not read; ddelta and ddelta_bias remain the gradients with respect to RAW and the bias
+                                  (ddelta = d delta * sigmoid(raw + delta_bias), sigmoid formed as 1 - exp(-delta)), and ddelta_bias is written
+                                  whenever the pointer is not NULL */
 #define AUM_CONV_SILU 1u
 #define AUM_CONV_REVERSE 2u  /* anti-causal: y[l] = act(b + sum_w W[w] x[l+(W-1)-w])                            */
 #define AUM_CONV_GENERIC 4u  /* force the any-width kernel (default: the vectorised width-4 kernel when width == 4)  */
@@ -483,7 +490,10 @@ int aum_dtproj_tm_fwd(const AumDtProjArgs* args, void* stream);
 
 /*
  * x_proj and dt_proj of the token-major block in one pass over conv_out (ABI 9; selective_scan_interface.py:467-468 without their
- * transposes): x_dbl = u . x_proj.weight^T, delta = x_dbl[:, :rank] . dt_proj.weight^T (bias and softplus stay in the scan).
+ * transposes): x_dbl = u . x_proj.weight^T, delta = x_dbl[:, :rank] . dt_proj.weight^T.  flags = 0 (delta_bias NULL): delta is that
+ * product and the scan adds the bias and applies the softplus, as in the reference.  flags = AUM_XDT_DELTA_SOFTPLUS: delta =
+ * softplus(product + delta_bias) formed on the fp32 accumulators (the scans' softplus, SSI:106-107) and rounded once -- what a token-major
+ * scan with AUM_SCAN_DELTA_ACTIVATED reads; delta_bias: (dim) fp32, 16-byte aligned, or NULL (no bias).
  *   u: (ntok, dim) rows of pitch ldu (conv_out);  wx: (ncols, dim) pitch ldwx;  wdt: (dim, rank) pitch ldwdt;
  *   x_dbl (out): (ntok, ncols) pitch ldx;  delta (out): (ntok, dim) pitch ldd.  Pitches in ELEMENTS, all tensors `dtype` (AUM_BF16 / AUM_F16).
  *   Built for ncols == 80 or 56 (dt_rank + 2 d_state of AuM-Base / AuM-Small), dim % 256 == 0, dim <= 1536, rank % 8 == 0, rank <= 64, pitches % 8 == 0,
@@ -497,7 +507,10 @@ typedef struct AumXdtArgs {
     int32_t dim, rank, ncols;
     int32_t ldu, ldwx, ldwdt, ldx, ldd;
     int32_t dtype;
+    const float* delta_bias;    /* AUM_XDT_DELTA_SOFTPLUS only (else NULL) */
+    uint32_t flags;
 } AumXdtArgs;
+#define AUM_XDT_DELTA_SOFTPLUS 1u
 int aum_xdt_tm_fwd(const AumXdtArgs* args, void* stream);
 
 /*
