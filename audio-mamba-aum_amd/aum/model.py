@@ -218,6 +218,75 @@ class AudioMamba(nn.Module):
                 hidden, residual = hf + hb, rf + rb
         return hidden, residual
 
+    # ---- streaming inference (causal models): feed a clip hop by hop -----------------------------
+    def _check_streamable(self):
+        """Streaming needs every token to depend on earlier tokens only and the cls token to come last: causal blocks, one direction,
+        time-major token order, cls at the end."""
+        bt = self.layers[0].mixer.bimamba_type if len(self.layers) else "none"
+        if bt != "none":
+            raise ValueError(f"streaming inference needs bimamba_type='none' (causal blocks), not {bt!r}")
+        if self.if_bidirectional:
+            raise ValueError("streaming inference needs if_bidirectional=False")
+        if self.use_middle_cls_token:
+            raise ValueError("streaming inference needs use_middle_cls_token=False (the cls token must close the sequence)")
+        if not self.use_end_cls_token:
+            raise ValueError("streaming inference needs use_end_cls_token=True (the cls token must close the sequence)")
+        if not self.transpose_token_sequence:
+            raise ValueError("streaming inference needs transpose_token_sequence=True (time-major token order)")
+
+    def allocate_inference_cache(self, batch_size, max_seqlen=0, dtype=None, **kwargs):
+        """Caches of a streaming session (MM:496-503): per layer the block's (conv_state, ssm_state), fp32 whatever the parameters' dtype
+        (what the chunk kernels advance in place), plus the number of time columns pushed so far."""
+        self._check_streamable()
+        dtype = torch.float32 if dtype is None else dtype
+        return {"layers": {i: layer.mixer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
+                           for i, layer in enumerate(self.layers)},
+                "columns": 0, "batch": batch_size}
+
+    def _stream_layers(self, hidden, layer_caches):
+        """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place"""
+        residual = None
+        for i, layer in enumerate(self.layers):
+            hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
+                                           residual_in_fp32=True, eps=layer.norm.eps)
+            conv_state, ssm_state = layer_caches[i]
+            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state)
+        return hidden, residual
+
+    @torch.no_grad()
+    def stream_push(self, spec, cache):
+        """spec: (batch, 16 k, n_mels) -- the next k time columns of the clip's normalised log-mel spectrogram.  Embeds their
+        k x n_f tokens (time-major, each with the position row of its (f, t) cell), runs them through all blocks from the carried caches
+        and advances the caches.  Returns the number of columns pushed so far."""
+        self._check_streamable()
+        ph, pw = self.patch_embed.proj.kernel_size
+        nf, nt = self.patch_grid_size
+        if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
+            raise ValueError(f"stream_push takes (batch={cache['batch']}, a positive multiple of {pw} frames, {nf * ph} mel bins), got {tuple(spec.shape)}")
+        k, c0 = spec.shape[1] // pw, cache["columns"]
+        if c0 + k > nt:
+            raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
+        x = self.patch_embed(spec.unsqueeze(1).transpose(2, 3))                  # (B, nf * k, Dm), token index f * k + t
+        Bsz = x.shape[0]
+        pe = self.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1)[:, :, c0:c0 + k]
+        x = (x.reshape(Bsz, nf, k, -1) + pe).transpose(1, 2).reshape(Bsz, k * nf, -1)
+        self._stream_layers(x, cache["layers"])
+        cache["columns"] = c0 + k
+        return cache["columns"]
+
+    @torch.no_grad()
+    def stream_read(self, cache, return_features=False):
+        """Logits if the clip ended now: the cls row run through the blocks from a COPY of the caches (the session is not advanced),
+        then the final norm and the head.  After all columns of a clip have been pushed this is model(spec)."""
+        self._check_streamable()
+        copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
+        pe = self.pos_embed.pos_embed
+        cls = (self.cls_token + pe[:, :1]).expand(cache["batch"], -1, -1)
+        hidden, residual = self._stream_layers(cls, copies)
+        f = rms_norm_fn(hidden[:, 0], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual[:, 0],
+                        prenorm=False, residual_in_fp32=True)
+        return f if return_features else self.head(f)
+
     def forward(self, x, return_features=False, frontend=None):
         """x: (B, T, F) normalised log-mel spectrogram, or -- with frontend=aum.frontend.WaveInput -- (B, n_samples) waveform"""
         f = self.forward_features(x, frontend)

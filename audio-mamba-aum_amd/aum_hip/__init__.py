@@ -189,6 +189,17 @@ class StateUpdateArgs(C.Structure):
                 ("batch", C.c_int32), ("dim", C.c_int32), ("dstate", C.c_int32), ("dtype", C.c_int32), ("flags", C.c_uint32)]
 
 
+class ConvTmChunkArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("x", "conv_state", "weight", "bias", "y")] + [(n, _i64) for n in ("x_bs", "x_ts", "y_bs", "y_ts")]
+                + [(n, _i32) for n in ("batch", "dim", "len", "width", "dtype")] + [("flags", _u32)])
+
+
+class ScanTmChunkArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("u", "delta", "z", "B", "C", "A", "D", "delta_bias", "state", "out")]
+                + [(n, _i64) for n in ("u_bs", "u_ts", "delta_bs", "delta_ts", "z_bs", "z_ts", "B_bs", "B_ts", "C_bs", "C_ts", "out_bs", "out_ts")]
+                + [(n, _i32) for n in ("batch", "dim", "len", "dstate", "dtype")] + [("flags", _u32)])
+
+
 class DtProjArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "w", "out")] + [("ntok", _i64)] + [(n, _i32) for n in ("dim", "rank", "ldx", "ldw", "ldo", "dtype")])
 
@@ -205,7 +216,7 @@ EXPORTS = ["aum_gemm_tn", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_proj_fwd",
            "aum_scan_tm_fwd", "aum_scan_tm_nck", "aum_scan_tm_ckpt_rows", "aum_scan_tm_bwd", "aum_scan_tm_workspace_bytes", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd",
            "aum_scan_tm_seg_carry_bytes", "aum_scan_tm_seg_workspace_bytes", "aum_selftest_wave_sum32",
            "aum_conv1d_tm_fwd", "aum_conv1d_tm_bwd", "aum_conv1d_tm_nparts", "aum_gemm_wgrad", "aum_xdt_tm_bwd", "aum_causal_conv1d_update", "aum_selective_state_update", "aum_cast_bank", "aum_rmsnorm_bwd_partial_rows",
-           "aum_stft_logmel_fwd", "aum_spec_time_warp"]
+           "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk"]
 
 
 class Lib:
@@ -238,6 +249,8 @@ class Lib:
         self.c.aum_gemm_wgrad.argtypes = [_vp, _vp]
         self.c.aum_causal_conv1d_update.argtypes = [_vp, _vp]
         self.c.aum_selective_state_update.argtypes = [_vp, _vp]
+        self.c.aum_conv1d_tm_chunk.argtypes = [_vp, _vp]
+        self.c.aum_scan_tm_chunk.argtypes = [_vp, _vp]
         self.c.aum_dtproj_tm_fwd.argtypes = [_vp, _vp]
         self.c.aum_xdt_tm_fwd.argtypes = [_vp, _vp]
         self.c.aum_xdt_tm_bwd.argtypes = [_vp, _vp]
@@ -874,6 +887,87 @@ def state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplu
     a.A, a.D, a.dt_bias, a.out = _ptr(A), _ptr(D), _ptr(dt_bias), _ptr(out)
     a.batch, a.dim, a.dstate, a.dtype, a.flags = x.shape[0], x.shape[1], state.shape[2], _DT[dty], (SCAN_SOFTPLUS if dt_softplus else 0)
     _launch(lib.c.aum_selective_state_update, a, x, lib, "state_update")
+    return out
+
+
+def conv1d_tm_chunk_supported(x, conv_state):
+    """the limits of aum_conv1d_tm_chunk (include/aum_hip.h): a token-major (batch, T, dim) view as conv1d_tm_fwd takes it, an fp32
+    contiguous (batch, dim, width <= 4) cache; outside them callers use conv1d_update token by token"""
+    return (conv_state.dim() == 3 and conv_state.dtype == torch.float32 and conv_state.is_contiguous() and x.dim() == 3 and x.shape[1] >= 1
+            and conv_state.shape[:2] == (x.shape[0], x.shape[2]) and conv1d_tm_supported(x, conv_state.shape[2]))
+
+
+def conv1d_tm_chunk(x, conv_state, weight, bias=None, silu=True, lib=None):
+    """T tokens of the causal conv in one launch (aum_conv1d_tm_chunk) = T conv1d_update calls: x (batch, T, dim) token-major view (may be
+    the first half of in_proj output rows); conv_state (batch, dim, width) fp32 contiguous, advanced IN PLACE; weight (dim, width);
+    returns y (batch, T, dim) contiguous in x's dtype.  The result does not depend on how a stream is cut into calls (bitwise)."""
+    lib = lib or get()
+    for t in (x, conv_state):
+        lib.check_tensor(t)
+    if not conv1d_tm_chunk_supported(x, conv_state):
+        raise RuntimeError(f"conv1d_tm_chunk: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (batch, T, dim) token-major, 16-byte rows; fp32 contiguous (batch, dim, width <= 4))")
+    batch, length, dim = x.shape
+    weight = _al16(_f32c(weight.reshape(dim, -1)))
+    bias = _al16(_f32c(bias))
+    if weight.shape[1] != conv_state.shape[2]:
+        raise RuntimeError("conv1d_tm_chunk: weight (dim, width) and conv_state (batch, dim, width) disagree on the width")
+    for t in (weight, bias):
+        lib.check_tensor(t)
+    y = torch.empty((batch, length, dim), dtype=x.dtype, device=x.device)
+    a = ConvTmChunkArgs()
+    a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
+    a.x_bs, a.x_ts = _tm3(x, "x", dim)
+    a.y_bs, a.y_ts = _tm3(y, "y", dim)
+    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
+    a.flags = CONV_SILU if silu else 0
+    _launch(lib.c.aum_conv1d_tm_chunk, a, x, lib, "conv_tm_chunk", (batch, dim, length, x.element_size()))
+    return y
+
+
+def scan_tm_chunk_supported(state, u):
+    """the limits of aum_scan_tm_chunk (include/aum_hip.h): fp32 contiguous (batch, dim, 16) state, dim % 64 == 0, (batch, T, dim)
+    activations; outside them callers use state_update token by token"""
+    return (state.dim() == 3 and state.dtype == torch.float32 and state.is_contiguous() and state.data_ptr() % 16 == 0 and u.dim() == 3
+            and u.dtype in _DT and u.shape[1] >= 1 and state.shape[:2] == (u.shape[0], u.shape[2]) and scan_tm_supported(u.shape[2], state.shape[2]))
+
+
+def scan_tm_chunk(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, out=None, lib=None):
+    """T tokens of the selective scan in one launch (aum_scan_tm_chunk) = T state_update calls: state (batch, dim, dstate) fp32 contiguous,
+    advanced IN PLACE; u, delta, z (batch, T, dim) token-major views (row strides free: u / z may be the halves of xz rows), B, C
+    (batch, T, dstate) views (column blocks of the x_dbl rows) in u's dtype.  delta_activated: delta already holds
+    softplus(raw + delta_bias) (xdt_tm_fwd(..., delta_softplus=True)).  Returns (batch, T, dim) contiguous in u's dtype.  The result does
+    not depend on how a stream is cut into calls (bitwise)."""
+    lib = lib or get()
+    for t in (state, u, delta, z, B, C):
+        lib.check_tensor(t)
+    if not scan_tm_chunk_supported(state, u):
+        raise RuntimeError(f"scan_tm_chunk: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
+                           "(need fp32 contiguous (batch, dim, 16), dim % 64 == 0, u (batch, T, dim))")
+    batch, length, dim = u.shape
+    dstate = state.shape[2]
+    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
+        raise RuntimeError("scan_tm_chunk: u, delta, z, B, C must share one dtype")
+    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
+    for t in (A, D, delta_bias):
+        lib.check_tensor(t)
+    if A.shape != (dim, dstate):
+        raise RuntimeError("scan_tm_chunk: A must be (dim, dstate)")
+    a = ScanTmChunkArgs()
+    a.u_bs, a.u_ts = _tm3(u, "u", dim)
+    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
+    if z is not None:
+        a.z_bs, a.z_ts = _tm3(z, "z", dim)
+    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
+    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
+    if out is None:
+        out = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device)
+    a.out_bs, a.out_ts = _tm3(out, "out", dim)
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
+    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    _launch(lib.c.aum_scan_tm_chunk, a, u, lib, "scan_tm_chunk", (batch, dim, length, dstate, u.element_size()))
     return out
 
 

@@ -33,13 +33,26 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
 
 
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
-    """One token of streaming inference (the wheel's function of the same name, call site MS:328-334): x (batch, dim); conv_state (batch, dim,
+    """Streaming inference (the wheel's function of the same name, call site MS:328-334).  x (batch, dim): one token; conv_state (batch, dim,
     width) is shifted left and extended by x IN PLACE; returns act(sum(conv_state * weight, -1) + bias) in x's dtype (aum_causal_conv1d_update;
-    a cache that is not fp32 goes through an fp32 copy and is written back)."""
+    a cache that is not fp32 goes through an fp32 copy and is written back).  x (batch, dim, seqlen), as the wheel takes from 1.4 on:
+    `seqlen` successive updates, returned as (batch, dim, seqlen) -- one launch (aum_conv1d_tm_chunk: the token-major (batch, seqlen, dim)
+    storage is read in place when x is its transposed view, e.g. the x half of in_proj output rows) where that kernel takes the shape,
+    token by token otherwise."""
     if activation not in (None, "silu", "swish"):
         raise NotImplementedError("activation must be None, silu, or swish")
+    silu = activation in ("silu", "swish")
     st = conv_state if conv_state.dtype == torch.float32 and conv_state.is_contiguous() else conv_state.float().contiguous()
-    out = aum_hip.conv1d_update(x, st, weight, bias, activation in ("silu", "swish"))
+    if x.dim() == 3:
+        xt = x.transpose(1, 2)                                   # (batch, seqlen, dim)
+        if not aum_hip.conv1d_tm_chunk_supported(xt, st):        # channel-major storage or a misaligned view: token-major copy
+            xt = xt.contiguous()
+        if aum_hip.conv1d_tm_chunk_supported(xt, st):
+            out = aum_hip.conv1d_tm_chunk(xt, st, weight, bias, silu).transpose(1, 2)
+        else:
+            out = torch.stack([aum_hip.conv1d_update(x[:, :, t], st, weight, bias, silu) for t in range(x.shape[2])], dim=2)
+    else:
+        out = aum_hip.conv1d_update(x, st, weight, bias, silu)
     if st is not conv_state:
         conv_state.copy_(st)
     return out

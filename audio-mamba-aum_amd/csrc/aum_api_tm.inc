@@ -3,6 +3,7 @@
 // device library; part 3 holds the extern "C" surface; part 0 (the lane-array test build) holds everything.
 #include "scan_tm_kernels.h"
 #include "conv_tm_kernels.h"
+#include "stream_tm_kernels.h"
 
 namespace aum {
 
@@ -588,4 +589,85 @@ AUM_API int aum_conv1d_tm_fwd(const AumConvTmArgs* a, void* stream) { return con
 AUM_API int aum_conv1d_tm_bwd(const AumConvTmArgs* a, void* stream) { return convt_dispatch(a, true, stream); }
 /* 1 when this build sums the dB / dC terms of 16-bit activations on the matrix pipe (terms rounded to bf16): tests bound them accordingly */
 AUM_API int32_t aum_conv1d_tm_nparts(int32_t batch, int32_t len) { return batch > 0 && len > 0 ? convt_nparts(batch, len) : 0; }
+
+// ---- chunked streaming inference (stream_tm_kernels.h): T tokens per call from carried caches ------
+#ifndef AUM_EMU
+template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk(AumConvTmChunkArgs a) { convc_wave<T, SILU>(a, (int)blockIdx.x); }
+template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk(AumScanTmChunkArgs a) { scanc_wave<T, SP, HAS_Z>(a, (int)blockIdx.x); }
+#endif
+template <class T, bool SILU> static int convc_launch(const AumConvTmChunkArgs& a, aum_stream_t s) {
+    const int grid = a.batch * convt_cblocks<T, false>(a.dim);
+#ifdef AUM_EMU
+    (void)s;
+    for (int wg = 0; wg < grid; ++wg) convc_wave<T, SILU>(a, wg);
+#else
+    AUM_LAUNCH((k_convt_chunk<T, SILU>), grid, 0, s, a);
+#endif
+    return launch_status();
+}
+template <class T> static int convc_dispatch_t(const AumConvTmChunkArgs& a, aum_stream_t s) {
+    return (a.flags & AUM_CONV_SILU) ? convc_launch<T, true>(a, s) : convc_launch<T, false>(a, s);
+}
+AUM_API int aum_conv1d_tm_chunk(const AumConvTmChunkArgs* a, void* stream) {
+    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
+    if (a->batch <= 0 || a->dim <= 0 || a->len <= 0 || a->width <= 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (a->width > CONVT_W) return AUM_E_UNSUPPORTED;
+    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
+    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
+    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
+    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
+    const int64_t strides = a->x_bs | a->x_ts | a->y_bs | a->y_ts;
+    if ((ptrs & 15) || ((strides * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
+    if (a->x == a->y) return AUM_E_UNSUPPORTED;      // rows are fetched ahead of the steps that write them
+    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit: one batch entry's rows must fit
+    if ((int64_t)a->len * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
+    aum_stream_t s = (aum_stream_t)stream;
+    switch (a->dtype) {
+        case AUM_F32: return convc_dispatch_t<float>(*a, s);
+        case AUM_BF16: return convc_dispatch_t<bf16_t>(*a, s);
+        default: return convc_dispatch_t<f16_t>(*a, s);
+    }
+}
+template <class T, bool SP, bool HAS_Z> static int scanc_launch(const AumScanTmChunkArgs& a, aum_stream_t s) {
+    const int grid = a.batch * (a.dim / WAVE);
+#ifdef AUM_EMU
+    (void)s;
+    for (int wg = 0; wg < grid; ++wg) scanc_wave<T, SP, HAS_Z>(a, wg);
+#else
+    AUM_LAUNCH((k_stream_scan_chunk<T, SP, HAS_Z>), grid, 0, s, a);
+#endif
+    return launch_status();
+}
+template <class T> static int scanc_dispatch_t(const AumScanTmChunkArgs& a, aum_stream_t s) {
+    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scanc_launch<T, true, true>(a, s) : scanc_launch<T, true, false>(a, s);
+    return a.z ? scanc_launch<T, false, true>(a, s) : scanc_launch<T, false, false>(a, s);
+}
+AUM_API int aum_scan_tm_chunk(const AumScanTmChunkArgs* a, void* stream) {
+    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
+    if (a->batch <= 0 || a->dim <= 0 || a->len <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
+    {       // row offsets inside a batch entry are 32-bit byte cursors
+        const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
+        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
+        for (int64_t t : ts)
+            if (t < 0 || (t + a->dim) * es * a->len > lim) return AUM_E_UNSUPPORTED;
+        if ((int64_t)a->dim * a->dstate * 4 > lim) return AUM_E_UNSUPPORTED;
+        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->B | (uintptr_t)a->C;
+        if ((ptrs & (uintptr_t)(es - 1)) || ((uintptr_t)a->state & 15)) return AUM_E_UNSUPPORTED;       // elements aligned; a channel's states move as 16-byte chunks
+    }
+    AumScanTmChunkArgs k = *a;          // the kernels' view: an activated delta carries its bias and softplus already
+    if (a->flags & AUM_SCAN_DELTA_ACTIVATED) {
+        k.delta_bias = nullptr;
+        k.flags = 0;
+    }
+    aum_stream_t s = (aum_stream_t)stream;
+    switch (k.dtype) {
+        case AUM_F32: return scanc_dispatch_t<float>(k, s);
+        case AUM_BF16: return scanc_dispatch_t<bf16_t>(k, s);
+        default: return scanc_dispatch_t<f16_t>(k, s);
+    }
+}
 #endif

@@ -1,0 +1,241 @@
+// stream_tm_kernels.h -- chunked streaming inference of the causal block: the conv window and the SSM state advanced by T >= 1 tokens per
+// launch FROM CARRIED STATE (include/aum_hip.h: aum_conv1d_tm_chunk, aum_scan_tm_chunk).  Token-major activations (batch, T, dim), the
+// caches fp32, contiguous and updated in place in the layouts Mamba.allocate_inference_cache returns: conv_state (batch, dim, width),
+// state (batch, dim, dstate).  Results = T successive calls of the per-token kernels of decode_kernels.h.
+//
+// These are latency kernels (B = 1..8, E = 1536: 24..192 waves on 1024 SIMDs): one launch and one serial chain of T steps per wave, no LDS,
+// no workgroup barriers, no atomics, waits left to the compiler.
+//   * conv: the division of conv_tm_kernels.h -- a lane owns 16 bytes of consecutive channels, the window is four register rows -- seeded
+//     from conv_state instead of from zero and written back to it behind the last step.
+//   * scan: the division of scan_tm_kernels.h -- a wavefront owns 64 channels of one batch entry (lane = channel), the 16 states of a
+//     channel live in registers for the whole call.  B_t / C_t are wave-uniform: lane n (mod 16) fetches element n of the step's rows and a
+//     step takes its 32 values out of the two registers with v_readlane_b32, so they enter the arithmetic as scalar operands.
+//   * two blocks of 8 steps of operands are in flight (requests past the chunk are clamped to its last row: no conditions around loads).
+//
+// PARTITION PROPERTY: advancing by T1 + T2 tokens in one call and by T1, then T2 gives bit-identical outputs and caches.  The carried
+// state crosses calls as exact fp32 (the conv window holds the inputs themselves), and every step is the same instruction sequence on
+// the same values wherever it falls in a call or in a block: one `step` body, no first / last step special cases, no re-association that
+// depends on the block phase (the library is built with -ffp-contract=off).
+#pragma once
+#include "conv_tm_kernels.h"
+#include "scan_tm_kernels.h"
+
+namespace aum {
+
+constexpr int STREAM_UB = 8;       // steps fetched together; two such blocks in flight
+
+// ---- conv ---------------------------------------------------------------------------------------
+// unit = (batch entry, block of 64 * V channels), channel block fastest
+template <class T, bool SILU>
+AUM_DEV void convc_wave(const AumConvTmChunkArgs& a, int wg) {
+    constexpr int V = convt_vec<T, false>(), NP = V / 2, ES = (int)sizeof(T), W = CONVT_W;
+    const int ncb = convt_cblocks<T, false>(a.dim), L = a.len;
+    const int cb = wg % ncb, b = wg / ncb;
+    AumConvTmArgs s = {};
+    s.weight = a.weight;
+    s.bias = a.bias;
+    s.dim = a.dim;
+    s.width = a.width;
+    ConvtLane<T, false> ln;
+    convt_lane_setup<T, false>(s, cb, ln);
+    const gbuf<T> xb = make_gbuf(row_ptr<T>(a.x, (int64_t)b * a.x_bs));
+    const gbuf<T> yb = make_gbuf(row_ptr<T>(a.y, (int64_t)b * a.y_bs));
+    const vi coff = ln.c0 * ES;
+    const int x_tb = (int)a.x_ts * ES, y_tb = (int)a.y_ts * ES;
+    float* win = a.conv_state + (int64_t)b * a.dim * a.width;
+    vf2 w2[W][NP], bias2[NP];
+    AUM_UNROLL
+    for (int p = 0; p < NP; ++p) {
+        bias2[p] = mk2(ln.bias[2 * p], ln.bias[2 * p + 1]);
+        AUM_UNROLL
+        for (int k = 0; k < W; ++k) w2[k][p] = mk2(ln.w[k][2 * p], ln.w[k][2 * p + 1]);
+    }
+    // xr[i]: the input of step t - 4 + i before step t.  Entry: conv_state[j] is input j - width, so row i is conv_state[width - 4 + i]
+    // (rows older than the cache are zero: they meet zero taps and are never written back).
+    vf2 xr[W][NP];
+    AUM_UNROLL
+    for (int i = 0; i < W; ++i) {
+        const int j = a.width - W + i;
+        AUM_UNROLL
+        for (int p = 0; p < NP; ++p) {
+            if (j >= 0) xr[i][p] = mk2(gload_u(win, (ln.c0 + 2 * p) * a.width + j), gload_u(win, (ln.c0 + 2 * p + 1) * a.width + j));
+            else xr[i][p] = spl2(splat(0.f));
+        }
+    }
+    auto unpack2 = [&](const convt_raw<T, false>& q, vf2 (&o)[NP]) {
+        vf t[V];
+        convt_unpack<T, false>(q, t);
+        AUM_UNROLL
+        for (int p = 0; p < NP; ++p) o[p] = mk2(t[2 * p], t[2 * p + 1]);
+    };
+    const bool all_live = a.dim % (WAVE * V) == 0;
+    auto load_blk = [&](int itb, convt_raw<T, false> (&raw)[STREAM_UB]) {
+        AUM_UNROLL
+        for (int j = 0; j < STREAM_UB; ++j) {
+            const int it = itb + j < L ? itb + j : L - 1;
+            raw[j] = convt_load<T, false>(xb, coff, it * x_tb);
+        }
+    };
+    // one step: y = act(bias + w0 x[t-3] + w1 x[t-2] + w2 x[t-1] + w3 x[t]) in that order, then the window moves by one row
+    auto step = [&](int it, const convt_raw<T, false>& raw) {
+        vf2 xn[NP];
+        unpack2(raw, xn);
+        vf y[V];
+        AUM_UNROLL
+        for (int p = 0; p < NP; ++p) {
+            vf2 acc = bias2[p];
+            AUM_UNROLL
+            for (int k = 0; k < W - 1; ++k) acc = vfma2(w2[k][p], xr[k + 1][p], acc);
+            acc = vfma2(w2[W - 1][p], xn[p], acc);
+            if (SILU) acc = acc * vsigmoid2(acc);
+            y[2 * p] = lo2(acc);
+            y[2 * p + 1] = hi2(acc);
+            AUM_UNROLL
+            for (int k = 0; k < W - 1; ++k) xr[k][p] = xr[k + 1][p];
+            xr[W - 1][p] = xn[p];
+        }
+        if (all_live) convt_store<T, false>(yb, coff, it * y_tb, y);
+        else convt_store_m<T, false>(yb, coff, it * y_tb, y, ln.live);
+    };
+    auto comp_blk = [&](int itb, const convt_raw<T, false> (&raw)[STREAM_UB]) {
+        AUM_UNROLL
+        for (int j = 0; j < STREAM_UB; ++j) {
+            if (itb + j < L) step(itb + j, raw[j]);
+        }
+    };
+    convt_raw<T, false> ra[STREAM_UB], rb[STREAM_UB];
+    load_blk(0, ra);
+    for (int itb = 0; itb < L; itb += 2 * STREAM_UB) {
+        load_blk(itb + STREAM_UB, rb);
+        comp_blk(itb, ra);
+        load_blk(itb + 2 * STREAM_UB, ra);
+        comp_blk(itb + STREAM_UB, rb);
+    }
+    // exit: conv_state[j] = input L - width + j = row 4 - width + j
+    AUM_UNROLL
+    for (int i = 0; i < W; ++i) {
+        const int j = a.width - W + i;
+        if (j >= 0) {
+            AUM_UNROLL
+            for (int p = 0; p < NP; ++p) {
+                gstore(win, (ln.c0 + 2 * p) * a.width + j, lo2(xr[i][p]), ln.live);
+                gstore(win, (ln.c0 + 2 * p + 1) * a.width + j, hi2(xr[i][p]), ln.live);
+            }
+        }
+    }
+}
+
+// ---- scan ---------------------------------------------------------------------------------------
+struct ScancRaw { vi u, d, z, b, c; };      // one step's operands as loaded (widened where they are used)
+
+// unit = (batch entry, group of 64 channels), channel group fastest.  SP: delta = softplus(delta + bias); otherwise delta + bias (an
+// activated delta comes with bias == NULL: the launcher drops it).
+template <class T, bool SP, bool HAS_Z>
+AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
+    constexpr int N = SCANT_N, ES = (int)sizeof(T);
+    const int ngrp = p.dim / WAVE, L = p.len;
+    const int e0 = (wg % ngrp) * WAVE, b = wg / ngrp;
+    const vi lane = lane_id();
+    const vi ec = lane + e0;                     // dim % 64 == 0: every lane is a channel
+    vf2 A2[N / 2];                               // A * log2(e), states (2j, 2j+1)
+    AUM_UNROLL
+    for (int j = 0; j < N / 2; ++j) A2[j] = mk2(gload_u(p.A, ec * N + 2 * j) * LOG2E, gload_u(p.A, ec * N + 2 * j + 1) * LOG2E);
+    const vf biasv = p.delta_bias ? gload_u(p.delta_bias, ec) : splat(0.f);
+    const vf Dv = p.D ? gload_u(p.D, ec) : splat(0.f);
+    const gbuf<T> ubuf = make_gbuf(row_ptr<T>(p.u, (int64_t)b * p.u_bs));
+    const gbuf<T> dbuf = make_gbuf(row_ptr<T>(p.delta, (int64_t)b * p.delta_bs));
+    const gbuf<T> zbuf = make_gbuf(HAS_Z ? row_ptr<T>(p.z, (int64_t)b * p.z_bs) : row_ptr<T>(p.u, 0));
+    const gbuf<T> obuf = make_gbuf(row_ptr<T>(p.out, (int64_t)b * p.out_bs));
+    const gbuf<T> Bbuf = make_gbuf(row_ptr<T>(p.B, (int64_t)b * p.B_bs));
+    const gbuf<T> Cbuf = make_gbuf(row_ptr<T>(p.C, (int64_t)b * p.C_bs));
+    const gbuf<float> sbuf = make_gbuf(p.state + (int64_t)b * p.dim * N);
+    const int u_tb = (int)p.u_ts * ES, d_tb = (int)p.delta_ts * ES, z_tb = HAS_Z ? (int)p.z_ts * ES : 0, o_tb = (int)p.out_ts * ES,
+              B_tb = (int)p.B_ts * ES, C_tb = (int)p.C_ts * ES;
+    const vi el_off = ec * ES;                   // this lane's channel inside a token row
+    const vi bc_off = (lane & (N - 1)) * ES;     // the element of a B / C row this lane fetches
+    const vi st_off = ec * (N * 4);              // this lane's 16 states: 64 contiguous bytes
+    // entry state
+    vf2 x[N / 2];
+    AUM_UNROLL
+    for (int i = 0; i < N / 4; ++i) {
+        vf t[4];
+        vq_unpack<float>(gbuf_load16(sbuf, st_off + 16 * i, 0), t);
+        x[2 * i] = mk2(t[0], t[1]);
+        x[2 * i + 1] = mk2(t[2], t[3]);
+    }
+    auto load_blk = [&](int itb, ScancRaw (&raw)[STREAM_UB]) {
+        AUM_UNROLL
+        for (int j = 0; j < STREAM_UB; ++j) {
+            const int it = itb + j < L ? itb + j : L - 1;
+            raw[j].u = gbuf_load_raw(ubuf, el_off, it * u_tb);
+            raw[j].d = gbuf_load_raw(dbuf, el_off, it * d_tb);
+            if (HAS_Z) raw[j].z = gbuf_load_raw(zbuf, el_off, it * z_tb);
+            raw[j].b = gbuf_load_raw(Bbuf, bc_off, it * B_tb);
+            raw[j].c = gbuf_load_raw(Cbuf, bc_off, it * C_tb);
+        }
+    };
+    // one step (the arithmetic of scant_fwd_run's `step`, stage by stage over the eight state pairs):
+    //   dl = softplus?(delta + bias);  a = exp2(dl A log2e);  x = a x + (dl u) B;  y = <x, C> + D u;  out = y z sigmoid(z)
+    auto step = [&](int it, const ScancRaw& r) {
+        vf dl = raw_to_f32<T>(r.d) + biasv;
+        if (SP) dl = vsoftplus(dl);
+        const vf uu = raw_to_f32<T>(r.u);
+        const vf du = dl * uu;
+        const vf bv = raw_to_f32<T>(r.b), cv = raw_to_f32<T>(r.c);
+        const vf2 dl2 = spl2(dl), du2 = spl2(du);
+        vf2 a[N / 2], Bp[N / 2], Cp[N / 2];
+        AUM_UNROLL
+        for (int j = 0; j < N / 2; ++j) {
+            Bp[j] = mk2(splat(readlane(bv, 2 * j)), splat(readlane(bv, 2 * j + 1)));
+            Cp[j] = mk2(splat(readlane(cv, 2 * j)), splat(readlane(cv, 2 * j + 1)));
+        }
+        AUM_UNROLL
+        for (int j = 0; j < N / 2; ++j) a[j] = dl2 * A2[j];
+        vf zz = splat(0.f), ez = splat(0.f);
+        if (HAS_Z) {
+            zz = raw_to_f32<T>(r.z);
+            ez = zz * (-LOG2E);
+        }
+        AUM_UNROLL
+        for (int j = 0; j < N / 2; ++j) Bp[j] = du2 * Bp[j];
+        AUM_UNROLL
+        for (int j = 0; j < N / 2; ++j) a[j] = vexp2_2(a[j]);
+        if (HAS_Z) ez = vexp2(ez);
+        AUM_UNROLL
+        for (int j = 0; j < N / 2; ++j) x[j] = vfma2(a[j], x[j], Bp[j]);
+        vf sg = splat(1.f);
+        if (HAS_Z) sg = vrcp(ez + 1.0f);
+        vf2 y2[4];
+        AUM_UNROLL
+        for (int j = 0; j < 4; ++j) y2[j] = x[j] * Cp[j];
+        AUM_UNROLL
+        for (int j = 4; j < N / 2; ++j) y2[j & 3] = vfma2(x[j], Cp[j], y2[j & 3]);
+        const vf2 ysum = (y2[0] + y2[1]) + (y2[2] + y2[3]);
+        const vf ys = lo2(ysum) + hi2(ysum);
+        vf tot = vfma(uu, Dv, ys);
+        if (HAS_Z) tot = tot * (zz * sg);
+        gbuf_store(obuf, el_off, it * o_tb, tot);
+    };
+    auto comp_blk = [&](int itb, const ScancRaw (&raw)[STREAM_UB]) {
+        AUM_UNROLL
+        for (int j = 0; j < STREAM_UB; ++j) {
+            if (itb + j < L) step(itb + j, raw[j]);
+        }
+    };
+    ScancRaw ra[STREAM_UB], rb[STREAM_UB];
+    load_blk(0, ra);
+    for (int itb = 0; itb < L; itb += 2 * STREAM_UB) {
+        load_blk(itb + STREAM_UB, rb);
+        comp_blk(itb, ra);
+        load_blk(itb + 2 * STREAM_UB, ra);
+        comp_blk(itb + STREAM_UB, rb);
+    }
+    // exit state
+    AUM_UNROLL
+    for (int i = 0; i < N / 4; ++i) {
+        const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
+        gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
+    }
+}
+
+}  // namespace aum

@@ -19,6 +19,7 @@ from mamba_ssm.ops.selective_scan_interface import (InProjFn, bimamba_inner_fn, 
                                                     neg_exp, selective_scan_fn)
 import mamba_ssm.ops.selective_scan_interface as ssi
 from causal_conv1d import causal_conv1d_fn, causal_conv1d_update
+from mamba_ssm.ops.selective_scan_interface import selective_scan_update
 from mamba_ssm.ops.triton.selective_state_update import selective_state_update
 
 
@@ -95,8 +96,11 @@ class Mamba(nn.Module):
             if self.bimamba_type != "none":
                 raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
             conv_state, ssm_state = self._get_states_from_cache(inference_params, hidden_states.shape[0])
-            if inference_params.seqlen_offset > 0:
-                out, _, _ = self.step(hidden_states, conv_state, ssm_state)    # states updated in place
+            if inference_params.seqlen_offset > 0:                         # states updated in place
+                if hidden_states.dim() == 3 and hidden_states.shape[1] > 1:
+                    out, _, _ = self.step_chunk(hidden_states, conv_state, ssm_state)
+                else:
+                    out, _, _ = self.step(hidden_states, conv_state, ssm_state)
                 return out
         batch, seqlen, _ = hidden_states.shape
         tm = (ssi.TOKEN_MAJOR and self.use_fast_path and inference_params is None
@@ -210,6 +214,47 @@ class Mamba(nn.Module):
         y = selective_state_update(ssm_state, xc, dt, -torch.exp(self.A_log.float()), B_t, C_t, self.D, z=z, dt_bias=self.dt_proj.bias,
                                    dt_softplus=True)
         return self.out_proj(y).unsqueeze(1), conv_state, ssm_state
+
+    def step_chunk(self, hidden_states, conv_state, ssm_state):
+        """T >= 1 tokens of streaming inference for the causal block in one pass: (batch, T, d_model) in, (batch, T, d_model) out, the
+        caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the two
+        recurrent stages as one launch each (aum_conv1d_tm_chunk, aum_scan_tm_chunk; the result does not depend on how a stream is cut
+        into chunks):
+            xz = in_proj(h)                                                      (batch, T, 2E) token-major rows [x | z]
+            xc = causal_conv1d_update(x half in place, conv_state, w, b, silu)   T window updates
+            (dt, B, C) = x_proj(xc);  delta = dt W_dt^T                          (one fused launch where aum_xdt_tm_fwd takes the shape)
+            y = selective_scan_update(ssm_state, xc, delta, A, B, C, D, z half, dt_bias, softplus)
+            out = out_proj(y)"""
+        import aum_hip
+        if self.bimamba_type != "none":
+            raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
+        if hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
+            raise ValueError("step_chunk() takes hidden_states of shape (batch, T >= 1, d_model)")
+        batch, T, _ = hidden_states.shape
+        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
+        x, z = xz[..., :E], xz[..., E:]
+        xc = causal_conv1d_update(x.transpose(1, 2), conv_state, self.conv1d.weight.view(E, self.d_conv), self.conv1d.bias,
+                                  self.activation).transpose(1, 2)                 # (batch, T, E) rows again
+        if not xc.is_contiguous():
+            xc = xc.contiguous()
+        xc2 = xc.reshape(batch * T, E)
+        A = -torch.exp(self.A_log.float())
+        activated = False
+        w_x, w_dt = self.x_proj.weight.to(xc2.dtype), self.dt_proj.weight.to(xc2.dtype)
+        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, w_x, w_dt):
+            proj, delta = aum_hip.xdt_tm_fwd(xc2, w_x, w_dt, delta_bias=self.dt_proj.bias.float(), delta_softplus=True)
+            activated = True
+        else:
+            proj = self.x_proj(xc2)
+            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
+            proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
+        proj = proj.view(batch, T, -1)
+        y = selective_scan_update(ssm_state, xc, delta.view(batch, T, E), A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], self.D, z=z,
+                                  delta_bias=None if activated else self.dt_proj.bias, delta_softplus=not activated,
+                                  delta_activated=activated)
+        out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
+        return out, conv_state, ssm_state
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         """MS:360-373"""

@@ -1158,3 +1158,29 @@ def bimamba_inner_ref(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_
     fl = lambda t: t.flip([-1])
     y_b = selective_scan_ref(fl(xc), fl(delta), A_b, fl(Bm), fl(Cm), D, fl(z), delta_bias, delta_softplus=True)
     return F.linear((y + fl(y_b)).transpose(1, 2), out_proj_weight, out_proj_bias)
+
+
+def selective_scan_update(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False):
+    """Streaming inference, `seqlen` tokens from a carried state: the selective scan of selective_scan_fn started from `state` instead of from
+    zero = `seqlen` successive selective_state_update calls.  state (batch, dim, dstate) is advanced IN PLACE (a cache that is not fp32
+    goes through an fp32 copy and is written back); u, delta, z (batch, seqlen, dim) and B, C (batch, seqlen, dstate) are token-major (row
+    strides free: views into xz / x_dbl rows are read in place); returns (batch, seqlen, dim) in u's dtype.  delta_activated (extension):
+    delta already holds softplus(raw + delta_bias).  One launch (aum_scan_tm_chunk) where that kernel takes the shape (dstate == 16,
+    dim % 64 == 0), the per-token kernel otherwise."""
+    st = state if state.dtype == torch.float32 and state.is_contiguous() else state.float().contiguous()
+    dty = u.dtype
+    delta, B, C = delta.to(dty), B.to(dty), C.to(dty)
+    z = None if z is None else z.to(dty)
+    if u.dim() != 3 or delta.shape != u.shape or B.dim() != 3 or B.shape != C.shape or B.shape[:2] != u.shape[:2] or (z is not None and z.shape != u.shape):
+        raise RuntimeError("selective_scan_update: u, delta, z (batch, seqlen, dim); B, C (batch, seqlen, dstate)")
+    if aum_hip.scan_tm_chunk_supported(st, u):
+        fix = lambda t: t if t is None or t.stride(2) == 1 or t.shape[2] == 1 else t.contiguous()
+        out = aum_hip.scan_tm_chunk(st, fix(u), fix(delta), A, fix(B), fix(C), D, fix(z), None if delta_activated else delta_bias,
+                                    delta_softplus and not delta_activated, delta_activated)
+    else:
+        bias, sp = (None, False) if delta_activated else (delta_bias, delta_softplus)
+        out = torch.stack([aum_hip.state_update(st, u[:, t], delta[:, t], A, B[:, t], C[:, t], D, None if z is None else z[:, t], bias, sp)
+                           for t in range(u.shape[1])], dim=1)
+    if st is not state:
+        state.copy_(st)
+    return out

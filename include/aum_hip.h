@@ -567,6 +567,49 @@ typedef struct AumStateUpdateArgs {
 } AumStateUpdateArgs;
 int aum_selective_state_update(const AumStateUpdateArgs* args, void* stream);
 
+/*
+ * Streaming inference, T >= 1 tokens per call from carried caches (additive to ABI 13; `Mamba.step_chunk`).  Token-major activations:
+ * element (b, t, e) at  b * X_bs + t * X_ts + e  (strides in ELEMENTS, channel stride 1 -- x / u and z may be the two halves of an in_proj
+ * output row with X_ts = 2 * dim), `dtype` fp32 / bf16 / fp16.  The caches are fp32, contiguous, updated in place, in the layouts of
+ * aum_causal_conv1d_update / aum_selective_state_update; the arithmetic is fp32.  Inference only (no backward).
+ * Both results are independent of how a token stream is cut into calls: advancing by T1 + T2 tokens in one call or by T1, then T2 gives
+ * bit-identical outputs and caches.
+ *
+ * aum_conv1d_tm_chunk -- `len` successive aum_causal_conv1d_update calls in one launch: y[t] = act(bias + sum_k weight[k] * win_t[k]) with the
+ *   window sliding over (conv_state, x[0..t]); on exit conv_state (batch, dim, width) holds the last `width` inputs (for len < width old
+ *   entries survive, shifted).  x, y (batch, len, dim), y != x; weight (dim, width) fp32, width <= 4; bias (dim) fp32 or NULL; flags:
+ *   AUM_CONV_SILU.  Limits as aum_conv1d_tm_fwd: dim % (16 / sizeof(dtype)) == 0, 16-byte aligned x, y, weight, bias and row strides.
+ * aum_scan_tm_chunk -- `len` successive aum_selective_state_update calls in one launch: d = softplus?(delta + delta_bias);
+ *   state (batch, dim, dstate) <- exp(d A) state + d u B_t;  out_t = (<state, C_t> + D u) * silu(z).  u, delta, z, out (batch, len, dim);
+ *   B, C (batch, len, dstate) in `dtype` (column blocks of the x_dbl rows, read in place); A (dim, dstate), D, delta_bias (dim) fp32
+ *   (D, delta_bias, z may be NULL).  flags: AUM_SCAN_SOFTPLUS, or AUM_SCAN_DELTA_ACTIVATED when delta already holds
+ *   softplus(raw + delta_bias) (what aum_xdt_tm_fwd writes with AUM_XDT_DELTA_SOFTPLUS; delta_bias is then ignored) -- either form for
+ *   every dtype, with or without z.  Limits as aum_scan_tm_fwd: dstate == 16, dim % 64 == 0, 16-byte aligned state; otherwise
+ *   AUM_E_UNSUPPORTED (callers use the per-token kernels).
+ */
+typedef struct AumConvTmChunkArgs {
+    const void* x;
+    float* conv_state;
+    const float *weight, *bias;
+    void* y;
+    int64_t x_bs, x_ts, y_bs, y_ts;
+    int32_t batch, dim, len, width;
+    int32_t dtype;
+    uint32_t flags;
+} AumConvTmChunkArgs;
+int aum_conv1d_tm_chunk(const AumConvTmChunkArgs* args, void* stream);
+typedef struct AumScanTmChunkArgs {
+    const void *u, *delta, *z, *B, *C;
+    const float *A, *D, *delta_bias;
+    float* state;
+    void* out;
+    int64_t u_bs, u_ts, delta_bs, delta_ts, z_bs, z_ts, B_bs, B_ts, C_bs, C_ts, out_bs, out_ts;
+    int32_t batch, dim, len, dstate;
+    int32_t dtype;
+    uint32_t flags;
+} AumScanTmChunkArgs;
+int aum_scan_tm_chunk(const AumScanTmChunkArgs* args, void* stream);
+
 /* Self-tests and calibration (used by tests/ and bench.py; not part of the reference's surface). */
 int aum_abi_version(void);
 /* runs wave_scan_affine<rev> on 64 (P,S) pairs: in/out are device arrays of 128 floats (P[0..63], S[0..63]) */

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Wall time of ONE 8-token hop (one time column of 16 x 16 patches on 128 mel bins) through a causal AuM, two ways, alternating in one
+process: (a) eight rounds of the per-token Mamba.step through all blocks, (b) one AudioMamba.stream_push (Mamba.step_chunk).  HIP events
+around each call, warm hops discarded, medians; the spread of (a) is the range of the medians of its repeat groups.
+
+    python tools/stream_hop_bench.py [--size base] [--depth 24] [--batch 1 8] [--warm 20] [--hops 120] [--groups 4]
+    python tools/stream_hop_bench.py --count-only a|b     (a few hops of one path only: for a kernel trace that counts launches per hop)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "audio-mamba-aum_amd"))
+
+from aum.model import AUM_SIZES, AudioMamba  # noqa: E402
+from mamba_ssm.ops.triton.layernorm import rms_norm_fn  # noqa: E402
+
+
+def make(size, depth, dev):
+    torch.manual_seed(0)
+    m = AudioMamba(spectrogram_size=(128, 1024), depth=depth, embed_dim=AUM_SIZES[size], num_classes=527, bimamba_type="none",
+                   use_middle_cls_token=False, use_end_cls_token=True, transpose_token_sequence=True)
+    return m.eval().to(dev).to(torch.bfloat16)
+
+
+def embed(model, spec, c0):
+    """the 8 tokens of time column c0 (what stream_push builds before the blocks)"""
+    nf, nt = model.patch_grid_size
+    x = model.patch_embed(spec.unsqueeze(1).transpose(2, 3))
+    pe = model.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1)[:, :, c0:c0 + 1]
+    return (x.reshape(x.shape[0], nf, 1, -1) + pe).transpose(1, 2).reshape(x.shape[0], nf, -1)
+
+
+def hop_steps(model, spec, cache):
+    """path (a): the hop's tokens one at a time through every block's step()"""
+    x = embed(model, spec, cache["columns"])
+    for t in range(x.shape[1]):
+        hidden, residual = x[:, t:t + 1], None
+        for i, layer in enumerate(model.layers):
+            hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True, residual_in_fp32=True,
+                                           eps=layer.norm.eps)
+            hidden, _, _ = layer.mixer.step(hidden, *cache["layers"][i])
+    cache["columns"] += 1
+
+
+def hop_push(model, spec, cache):
+    model.stream_push(spec, cache)
+
+
+def timed(fn, model, spec, cache):
+    if cache["columns"] >= model.patch_grid_size[1]:
+        cache["columns"] = 0                      # a new clip: the caches' values do not matter for timing
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn(model, spec, cache)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="base")
+    ap.add_argument("--depth", type=int, default=24)
+    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--warm", type=int, default=20)
+    ap.add_argument("--hops", type=int, default=120)
+    ap.add_argument("--groups", type=int, default=4)
+    ap.add_argument("--count-only", choices=["a", "b"])
+    ap.add_argument("--count-hops", type=int, default=4)
+    args = ap.parse_args()
+    dev = "cuda:0"
+    model = make(args.size, args.depth, dev)
+    with torch.no_grad():
+        for B in args.batch:
+            spec = torch.randn(B, 16, 128, device=dev, dtype=torch.bfloat16)
+            ca, cb = model.allocate_inference_cache(B), model.allocate_inference_cache(B)
+            if args.count_only:
+                fn, c = (hop_steps, ca) if args.count_only == "a" else (hop_push, cb)
+                for _ in range(args.count_hops):
+                    fn(model, spec, c)
+                torch.cuda.synchronize()
+                print(json.dumps({"path": args.count_only, "batch": B, "hops": args.count_hops}))
+                continue
+            for _ in range(args.warm):
+                timed(hop_steps, model, spec, ca)
+                timed(hop_push, model, spec, cb)
+            ta, tb = [], []
+            for _ in range(args.hops):
+                ta.append(timed(hop_steps, model, spec, ca))
+                tb.append(timed(hop_push, model, spec, cb))
+            g = max(len(ta) // args.groups, 1)
+            meds_a = [statistics.median(ta[i:i + g]) for i in range(0, g * args.groups, g)]
+            meds_b = [statistics.median(tb[i:i + g]) for i in range(0, g * args.groups, g)]
+            ma, mb = statistics.median(ta), statistics.median(tb)
+            print(json.dumps({"model": f"aum-{args.size} causal depth {args.depth} bf16", "batch": B, "hop_tokens": 8, "hops": args.hops, "warm": args.warm,
+                              "steps_ms_median": round(ma, 4), "steps_ms_group_medians": [round(v, 4) for v in meds_a],
+                              "push_ms_median": round(mb, 4), "push_ms_group_medians": [round(v, 4) for v in meds_b],
+                              "ratio_steps_over_push": round(ma / mb, 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
