@@ -243,15 +243,93 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches):
-        """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place"""
+    def _stream_layers(self, hidden, layer_caches, seq_map=None):
+        """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
+        (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk)"""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
                                            residual_in_fp32=True, eps=layer.norm.eps)
             conv_state, ssm_state = layer_caches[i]
-            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state)
+            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map)
         return hidden, residual
+
+    # ---- many sessions at different positions: a pool of caches, one pass per push -----------------
+    def allocate_stream_pool(self, sessions, dtype=None):
+        """Caches for `sessions` independent streaming sessions: per layer (conv_state, ssm_state) with one row per session, and one
+        column count per session.  Rows are advanced by stream_push_many, read by stream_read(..., sessions=) and emptied for the
+        next clip by stream_reset."""
+        if int(sessions) < 1:
+            raise ValueError("allocate_stream_pool: at least one session")
+        pool = self.allocate_inference_cache(int(sessions), dtype=dtype)
+        pool["columns"] = [0] * int(sessions)
+        return pool
+
+    @staticmethod
+    def _is_pool(cache):
+        return isinstance(cache["columns"], list)
+
+    def _check_sessions(self, what, pool, sessions):
+        if not self._is_pool(pool):
+            raise ValueError(f"{what} takes a pool from allocate_stream_pool")
+        rows = [int(r) for r in sessions]
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"{what}: the sessions {rows} are not distinct")
+        if rows and (min(rows) < 0 or max(rows) >= pool["batch"]):
+            raise ValueError(f"{what}: the sessions {rows} are not all rows of a pool of {pool['batch']}")
+        return rows
+
+    @torch.no_grad()
+    def stream_push_many(self, specs, pool, sessions):
+        """specs[i]: (16 k_i, n_mels), k_i >= 1 -- the next k_i time columns of the clip of session sessions[i] (distinct rows of a pool from
+        allocate_stream_pool), every session at its own column offset and with its own hop size.  One patch-embed GEMM over the frames
+        concatenated in time, each session's position rows gathered from its own offset, tokens time-major within a session, then ONE pass
+        through all blocks on the packed tokens (Mamba.step_chunk(seq_map=): only the conv and the scan see the session boundaries).
+        Returns the per-session column counts.  Every argument is checked before any cache is touched: a refused call changes nothing."""
+        import aum_hip
+        self._check_streamable()
+        rows = self._check_sessions("stream_push_many", pool, sessions)
+        ph, pw = self.patch_embed.proj.kernel_size
+        nf, nt = self.patch_grid_size
+        specs = list(specs)
+        if not rows or len(specs) != len(rows):
+            raise ValueError(f"stream_push_many: one spectrogram piece per session, got {len(specs)} for the sessions {rows}")
+        ks = []
+        for sp, r in zip(specs, rows):
+            if sp.dim() != 2 or sp.shape[0] == 0 or sp.shape[0] % pw or sp.shape[1] // ph != nf:
+                raise ValueError(f"stream_push_many takes (a positive multiple of {pw} frames, {nf * ph} mel bins) per session, got "
+                                 f"{tuple(sp.shape)} for session {r}")
+            k = sp.shape[0] // pw
+            if pool["columns"][r] + k > nt:
+                raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
+            ks.append(k)
+        dev = specs[0].device
+        smap = aum_hip.seq_map([k * nf for k in ks], rows, device=dev)
+        K = sum(ks)
+        # the position row of every new column: one host-built index vector, uploaded like the sequence map
+        cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
+        if dev.type == "cuda":
+            cols = cols.pin_memory()
+        cols = cols.to(dev, non_blocking=True)
+        x = self.patch_embed(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3))     # (1, nf * K, Dm), token index f * K + t
+        pe = self.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1).index_select(2, cols)
+        x = (x.reshape(1, nf, K, -1) + pe).transpose(1, 2).reshape(1, K * nf, -1)                 # column-major: a session's tokens are contiguous
+        self._stream_layers(x, pool["layers"], smap)
+        for r, k in zip(rows, ks):
+            pool["columns"][r] += k
+        return [pool["columns"][r] for r in rows]
+
+    def stream_reset(self, pool, sessions):
+        """Empty the caches and the column counts of those rows of a pool: the slots are free for new clips."""
+        rows = self._check_sessions("stream_reset", pool, sessions)
+        if rows:
+            idx = torch.tensor(rows, dtype=torch.int64)
+            for c, s in pool["layers"].values():
+                ix = idx.to(c.device)
+                c.index_fill_(0, ix, 0)
+                s.index_fill_(0, ix, 0)
+            for r in rows:
+                pool["columns"][r] = 0
 
     @torch.no_grad()
     def stream_push(self, spec, cache):
@@ -259,6 +337,9 @@ class AudioMamba(nn.Module):
         k x n_f tokens (time-major, each with the position row of its (f, t) cell), runs them through all blocks from the carried caches
         and advances the caches.  Returns the number of columns pushed so far."""
         self._check_streamable()
+        if self._is_pool(cache):
+            raise ValueError("stream_push advances all rows of a cache from allocate_inference_cache together; a pool from "
+                             "allocate_stream_pool is advanced by stream_push_many(specs, pool, sessions)")
         ph, pw = self.patch_embed.proj.kernel_size
         nf, nt = self.patch_grid_size
         if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
@@ -275,13 +356,23 @@ class AudioMamba(nn.Module):
         return cache["columns"]
 
     @torch.no_grad()
-    def stream_read(self, cache, return_features=False):
+    def stream_read(self, cache, return_features=False, sessions=None):
         """Logits if the clip ended now: the cls row run through the blocks from a COPY of the caches (the session is not advanced),
-        then the final norm and the head.  After all columns of a clip have been pushed this is model(spec)."""
+        then the final norm and the head.  After all columns of a clip have been pushed this is model(spec).  sessions: read those rows
+        only (gathered copies), (len(sessions), ...) in that order; None: every row (of a pool too)."""
         self._check_streamable()
-        copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
+        if sessions is None:
+            copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
+            n = cache["batch"]
+        else:
+            rows = [int(r) for r in sessions]
+            if not rows or min(rows) < 0 or max(rows) >= cache["batch"]:
+                raise ValueError(f"stream_read: the sessions {rows} are not all rows of a cache of {cache['batch']}")
+            idx = torch.tensor(rows, dtype=torch.int64)
+            copies = {i: (c.index_select(0, idx.to(c.device)), s.index_select(0, idx.to(s.device))) for i, (c, s) in cache["layers"].items()}
+            n = len(rows)
         pe = self.pos_embed.pos_embed
-        cls = (self.cls_token + pe[:, :1]).expand(cache["batch"], -1, -1)
+        cls = (self.cls_token + pe[:, :1]).expand(n, -1, -1)
         hidden, residual = self._stream_layers(cls, copies)
         f = rms_norm_fn(hidden[:, 0], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual[:, 0],
                         prenorm=False, residual_in_fp32=True)

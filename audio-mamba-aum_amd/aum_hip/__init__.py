@@ -12,6 +12,7 @@ The functions mirror the reference's extension modules:
 import ctypes as C
 import math
 import os
+import typing
 
 import torch
 
@@ -200,6 +201,17 @@ class ScanTmChunkArgs(C.Structure):
                 + [(n, _i32) for n in ("batch", "dim", "len", "dstate", "dtype")] + [("flags", _u32)])
 
 
+class ConvTmChunkVarArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("x", "conv_state", "weight", "bias", "y", "cu_seqlens", "state_indices")] + [(n, _i64) for n in ("x_ts", "y_ts")]
+                + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "width", "dtype")] + [("flags", _u32)])
+
+
+class ScanTmChunkVarArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("u", "delta", "z", "B", "C", "A", "D", "delta_bias", "state", "out", "cu_seqlens", "state_indices")]
+                + [(n, _i64) for n in ("u_ts", "delta_ts", "z_ts", "B_ts", "C_ts", "out_ts")]
+                + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "dstate", "dtype")] + [("flags", _u32)])
+
+
 class DtProjArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "w", "out")] + [("ntok", _i64)] + [(n, _i32) for n in ("dim", "rank", "ldx", "ldw", "ldo", "dtype")])
 
@@ -216,7 +228,8 @@ EXPORTS = ["aum_gemm_tn", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_proj_fwd",
            "aum_scan_tm_fwd", "aum_scan_tm_nck", "aum_scan_tm_ckpt_rows", "aum_scan_tm_bwd", "aum_scan_tm_workspace_bytes", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd",
            "aum_scan_tm_seg_carry_bytes", "aum_scan_tm_seg_workspace_bytes", "aum_selftest_wave_sum32",
            "aum_conv1d_tm_fwd", "aum_conv1d_tm_bwd", "aum_conv1d_tm_nparts", "aum_gemm_wgrad", "aum_xdt_tm_bwd", "aum_causal_conv1d_update", "aum_selective_state_update", "aum_cast_bank", "aum_rmsnorm_bwd_partial_rows",
-           "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk"]
+           "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk",
+           "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var"]
 
 
 class Lib:
@@ -251,6 +264,8 @@ class Lib:
         self.c.aum_selective_state_update.argtypes = [_vp, _vp]
         self.c.aum_conv1d_tm_chunk.argtypes = [_vp, _vp]
         self.c.aum_scan_tm_chunk.argtypes = [_vp, _vp]
+        self.c.aum_conv1d_tm_chunk_var.argtypes = [_vp, _vp]
+        self.c.aum_scan_tm_chunk_var.argtypes = [_vp, _vp]
         self.c.aum_dtproj_tm_fwd.argtypes = [_vp, _vp]
         self.c.aum_xdt_tm_fwd.argtypes = [_vp, _vp]
         self.c.aum_xdt_tm_bwd.argtypes = [_vp, _vp]
@@ -968,6 +983,150 @@ def scan_tm_chunk(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, del
     a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
     a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
     _launch(lib.c.aum_scan_tm_chunk, a, u, lib, "scan_tm_chunk", (batch, dim, length, dstate, u.element_size()))
+    return out
+
+
+class SeqMap(typing.NamedTuple):
+    """Where the sessions of one packed call are (seq_map builds it): session i owns rows [sum(lens[:i]), sum(lens[:i + 1])) of the
+    (total, dim) token stream and row rows[i] of the pool of caches.  lens, rows: host tuples; cu (nseq + 1) / idx (nseq, or None: session
+    i owns row i) the same as int32 device tensors, what the kernels read."""
+    lens: tuple
+    rows: tuple
+    total: int
+    cu: torch.Tensor
+    idx: typing.Optional[torch.Tensor]
+
+
+def seq_map(seq_lens, state_indices=None, *, device):
+    """Built once per push and handed to every layer: the per-session row counts (>= 0) and the cache row of each session (distinct, >= 0;
+    None: session i owns row i) -- checked here, on the host, and sent to `device` in ONE pinned, non-blocking upload.  That the rows exist
+    is checked where a cache is known (conv1d_tm_chunk_var, scan_tm_chunk_var)."""
+    lens = tuple(int(n) for n in seq_lens)
+    if not lens or min(lens) < 0:
+        raise ValueError(f"seq_map: one length >= 0 per session, got {lens}")
+    rows = tuple(range(len(lens))) if state_indices is None else tuple(int(r) for r in state_indices)
+    if len(rows) != len(lens) or min(rows) < 0 or len(set(rows)) != len(rows):
+        raise ValueError(f"seq_map: one cache row per session, distinct and >= 0, got {rows} for {len(lens)} sessions")
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    if cu[-1] >= 1 << 31:
+        raise ValueError("seq_map: too many rows")
+    host = torch.tensor(cu + (list(rows) if state_indices is not None else []), dtype=torch.int32)
+    device = torch.device(device)
+    if device.type == "cuda":
+        host = host.pin_memory()
+    buf = host.to(device, non_blocking=True)
+    n1 = len(lens) + 1
+    return SeqMap(lens, rows, cu[-1], buf[:n1], buf[n1:] if state_indices is not None else None)
+
+
+def _var_common(name, m, rows2d, cache):
+    """the checks a packed call makes where the cache is known: the map is of this stream and of this device, its rows are in the pool"""
+    if not isinstance(m, SeqMap):
+        raise TypeError(f"{name}: seq_map must come from aum_hip.seq_map()")
+    if m.total != rows2d.shape[0]:
+        raise ValueError(f"{name}: seq_map describes {m.total} rows, the packed stream has {rows2d.shape[0]}")
+    if max(m.rows) >= cache.shape[0]:
+        raise ValueError(f"{name}: seq_map names cache row {max(m.rows)}, the pool has {cache.shape[0]} rows")
+    if m.cu.device != rows2d.device or m.cu.dtype != torch.int32 or (m.idx is not None and (m.idx.device != rows2d.device or m.idx.dtype != torch.int32)):
+        raise RuntimeError(f"{name}: seq_map lives on {m.cu.device}, the packed stream on {rows2d.device}")
+
+
+def _tm2(t, name, last):
+    """(total, X) packed rows with unit stride along X -> row stride in elements"""
+    if t.dim() != 2 or t.shape[1] != last or (t.stride(1) != 1 and last != 1):
+        raise RuntimeError(f"{name}: expected (total, {last}) with the last axis contiguous (packed token-major rows)")
+    return t.stride(0) if t.shape[0] > 1 else last
+
+
+def conv1d_tm_chunk_var_supported(x, conv_state):
+    """the limits of aum_conv1d_tm_chunk_var (include/aum_hip.h): packed (total >= 1, dim) rows as conv1d_tm_chunk takes them at batch 1, an
+    fp32 contiguous (nrows, dim, width <= 4) pool; outside them callers loop over the sessions through conv1d_tm_chunk / conv1d_update"""
+    return (conv_state.dim() == 3 and conv_state.dtype == torch.float32 and conv_state.is_contiguous() and conv_state.shape[0] >= 1
+            and x.dim() == 2 and x.shape[0] >= 1 and conv_state.shape[1] == x.shape[1] and conv1d_tm_supported(x.unsqueeze(0), conv_state.shape[2]))
+
+
+def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None):
+    """The causal conv on packed sessions in one launch (aum_conv1d_tm_chunk_var): x (total, dim) packed rows (row stride free: may be the
+    first half of in_proj output rows), conv_state (nrows, dim, width) the pool of fp32 caches -- the rows seq_map names are advanced IN
+    PLACE, the others are not touched.  Per session bit for bit conv1d_tm_chunk at batch 1.  Returns y (total, dim) in x's dtype.  No
+    device synchronisation."""
+    lib = lib or get()
+    for t in (x, conv_state, out):
+        lib.check_tensor(t)
+    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return x.new_empty(x.shape) if out is None else out
+    if not conv1d_tm_chunk_var_supported(x, conv_state):
+        raise RuntimeError(f"conv1d_tm_chunk_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
+    _var_common("conv1d_tm_chunk_var", seq_map, x, conv_state)
+    total, dim = x.shape
+    weight = _al16(_f32c(weight.reshape(dim, -1)))
+    bias = _al16(_f32c(bias))
+    if weight.shape[1] != conv_state.shape[2]:
+        raise RuntimeError("conv1d_tm_chunk_var: weight (dim, width) and conv_state (nrows, dim, width) disagree on the width")
+    for t in (weight, bias):
+        lib.check_tensor(t)
+    y = torch.empty((total, dim), dtype=x.dtype, device=x.device) if out is None else out
+    if y.dtype != x.dtype or y.shape != x.shape:
+        raise RuntimeError("conv1d_tm_chunk_var: out must have x's shape and dtype")
+    a = ConvTmChunkVarArgs()
+    a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
+    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
+    a.x_ts, a.y_ts = _tm2(x, "x", dim), _tm2(y, "out", dim)
+    a.total, a.nseq, a.nrows, a.dim, a.width, a.dtype = total, len(seq_map.lens), conv_state.shape[0], dim, weight.shape[1], _DT[x.dtype]
+    a.flags = CONV_SILU if silu else 0
+    _launch(lib.c.aum_conv1d_tm_chunk_var, a, x, lib, "conv_tm_chunk_var", (len(seq_map.lens), dim, total, x.element_size()))
+    return y
+
+
+def scan_tm_chunk_var_supported(state, u):
+    """the limits of aum_scan_tm_chunk_var (include/aum_hip.h): an fp32 contiguous (nrows, dim, 16) pool, dim % 64 == 0, packed
+    (total >= 1, dim) activations; outside them callers loop over the sessions through scan_tm_chunk / state_update"""
+    return (state.dim() == 3 and state.dtype == torch.float32 and state.is_contiguous() and state.data_ptr() % 16 == 0 and state.shape[0] >= 1
+            and u.dim() == 2 and u.dtype in _DT and u.shape[0] >= 1 and state.shape[1] == u.shape[1] and scan_tm_supported(u.shape[1], state.shape[2]))
+
+
+def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
+                      out=None, lib=None):
+    """The selective scan on packed sessions in one launch (aum_scan_tm_chunk_var): state (nrows, dim, dstate) the pool of fp32 caches --
+    the rows seq_map names are advanced IN PLACE, the others are not touched; u, delta, z (total, dim) and B, C (total, dstate) packed
+    rows in one dtype (row strides free).  Per session bit for bit scan_tm_chunk at batch 1.  Returns (total, dim) in u's dtype.  No
+    device synchronisation."""
+    lib = lib or get()
+    for t in (state, u, delta, z, B, C, out):
+        lib.check_tensor(t)
+    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return u.new_empty(u.shape) if out is None else out
+    if not scan_tm_chunk_var_supported(state, u):
+        raise RuntimeError(f"scan_tm_chunk_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
+                           "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
+    _var_common("scan_tm_chunk_var", seq_map, u, state)
+    total, dim = u.shape
+    dstate = state.shape[2]
+    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
+        raise RuntimeError("scan_tm_chunk_var: u, delta, z, B, C must share one dtype")
+    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
+    for t in (A, D, delta_bias):
+        lib.check_tensor(t)
+    if A.shape != (dim, dstate):
+        raise RuntimeError("scan_tm_chunk_var: A must be (dim, dstate)")
+    if out is None:
+        out = torch.empty((total, dim), dtype=u.dtype, device=u.device)
+    if out.dtype != u.dtype or out.shape != u.shape:
+        raise RuntimeError("scan_tm_chunk_var: out must have u's shape and dtype")
+    a = ScanTmChunkVarArgs()
+    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
+    if z is not None:
+        a.z_ts = _tm2(z, "z", dim)
+    a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
+    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
+    a.total, a.nseq, a.nrows, a.dim, a.dstate, a.dtype = total, len(seq_map.lens), state.shape[0], dim, dstate, _DT[u.dtype]
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(seq_map.lens), dim, total, dstate, u.element_size()))
     return out
 
 

@@ -594,6 +594,8 @@ AUM_API int32_t aum_conv1d_tm_nparts(int32_t batch, int32_t len) { return batch 
 #ifndef AUM_EMU
 template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk(AumConvTmChunkArgs a) { convc_wave<T, SILU>(a, (int)blockIdx.x); }
 template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk(AumScanTmChunkArgs a) { scanc_wave<T, SP, HAS_Z>(a, (int)blockIdx.x); }
+template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk_var(AumConvTmChunkVarArgs a) { convc_var_wave<T, SILU>(a, (int)blockIdx.x); }
+template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk_var(AumScanTmChunkVarArgs a) { scanc_var_wave<T, SP, HAS_Z>(a, (int)blockIdx.x); }
 #endif
 template <class T, bool SILU> static int convc_launch(const AumConvTmChunkArgs& a, aum_stream_t s) {
     const int grid = a.batch * convt_cblocks<T, false>(a.dim);
@@ -668,6 +670,93 @@ AUM_API int aum_scan_tm_chunk(const AumScanTmChunkArgs* a, void* stream) {
         case AUM_F32: return scanc_dispatch_t<float>(k, s);
         case AUM_BF16: return scanc_dispatch_t<bf16_t>(k, s);
         default: return scanc_dispatch_t<f16_t>(k, s);
+    }
+}
+
+// ---- the same on packed sessions: (sequence, channel block) units, rows and cache row from cu_seqlens / state_indices ----
+static bool stream_var_ok(const int32_t* cu_seqlens, const int32_t* state_indices, int total, int nseq, int nrows, int& err) {
+    if (!cu_seqlens) { err = AUM_E_NULL; return false; }
+    if (total <= 0 || nseq <= 0 || nrows <= 0) { err = AUM_E_SHAPE; return false; }
+    if (((uintptr_t)cu_seqlens | (uintptr_t)state_indices) & 3) { err = AUM_E_UNSUPPORTED; return false; }
+    return true;
+}
+template <class T, bool SILU> static int convcv_launch(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
+    const int grid = a.nseq * convt_cblocks<T, false>(a.dim);
+#ifdef AUM_EMU
+    (void)s;
+    for (int wg = 0; wg < grid; ++wg) convc_var_wave<T, SILU>(a, wg);
+#else
+    AUM_LAUNCH((k_convt_chunk_var<T, SILU>), grid, 0, s, a);
+#endif
+    return launch_status();
+}
+template <class T> static int convcv_dispatch_t(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
+    return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true>(a, s) : convcv_launch<T, false>(a, s);
+}
+AUM_API int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* a, void* stream) {
+    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
+    int err = 0;
+    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    if (a->dim <= 0 || a->width <= 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (a->width > CONVT_W) return AUM_E_UNSUPPORTED;
+    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
+    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
+    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
+    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
+    if ((ptrs & 15) || (((a->x_ts | a->y_ts) * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
+    if (a->x == a->y) return AUM_E_UNSUPPORTED;
+    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit; a sequence has at most `total` rows
+    if ((int64_t)a->total * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
+    if ((int64_t)a->nseq * convt_cblocks<float, false>(a->dim) >= lim) return AUM_E_UNSUPPORTED;
+    aum_stream_t s = (aum_stream_t)stream;
+    switch (a->dtype) {
+        case AUM_F32: return convcv_dispatch_t<float>(*a, s);
+        case AUM_BF16: return convcv_dispatch_t<bf16_t>(*a, s);
+        default: return convcv_dispatch_t<f16_t>(*a, s);
+    }
+}
+template <class T, bool SP, bool HAS_Z> static int scancv_launch(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
+    const int grid = a.nseq * (a.dim / WAVE);
+#ifdef AUM_EMU
+    (void)s;
+    for (int wg = 0; wg < grid; ++wg) scanc_var_wave<T, SP, HAS_Z>(a, wg);
+#else
+    AUM_LAUNCH((k_stream_scan_chunk_var<T, SP, HAS_Z>), grid, 0, s, a);
+#endif
+    return launch_status();
+}
+template <class T> static int scancv_dispatch_t(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
+    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scancv_launch<T, true, true>(a, s) : scancv_launch<T, true, false>(a, s);
+    return a.z ? scancv_launch<T, false, true>(a, s) : scancv_launch<T, false, false>(a, s);
+}
+AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) {
+    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
+    int err = 0;
+    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    if (a->dim <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
+    {       // row offsets inside a sequence are 32-bit byte cursors; a sequence has at most `total` rows
+        const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
+        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
+        for (int64_t t : ts)
+            if (t < 0 || (t + a->dim) * es * a->total > lim) return AUM_E_UNSUPPORTED;
+        if ((int64_t)a->dim * a->dstate * 4 > lim || (int64_t)a->nseq * (a->dim / WAVE) > lim) return AUM_E_UNSUPPORTED;
+        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->B | (uintptr_t)a->C;
+        if ((ptrs & (uintptr_t)(es - 1)) || ((uintptr_t)a->state & 15)) return AUM_E_UNSUPPORTED;
+    }
+    AumScanTmChunkVarArgs k = *a;       // the kernels' view: an activated delta carries its bias and softplus already
+    if (a->flags & AUM_SCAN_DELTA_ACTIVATED) {
+        k.delta_bias = nullptr;
+        k.flags = 0;
+    }
+    aum_stream_t s = (aum_stream_t)stream;
+    switch (k.dtype) {
+        case AUM_F32: return scancv_dispatch_t<float>(k, s);
+        case AUM_BF16: return scancv_dispatch_t<bf16_t>(k, s);
+        default: return scancv_dispatch_t<f16_t>(k, s);
     }
 }
 #endif

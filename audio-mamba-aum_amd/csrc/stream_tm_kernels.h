@@ -16,6 +16,15 @@
 // state crosses calls as exact fp32 (the conv window holds the inputs themselves), and every step is the same instruction sequence on
 // the same values wherever it falls in a call or in a block: one `step` body, no first / last step special cases, no re-association that
 // depends on the block phase (the library is built with -ffp-contract=off).
+//
+// PACKED SESSIONS (aum_conv1d_tm_chunk_var, aum_scan_tm_chunk_var): the rows of several sessions behind one another in one (total, dim)
+// stream, cu_seqlens saying where each session's rows are and state_indices which row of a pool of caches it owns.  The partition
+// property extends to packing: a session's outputs and cache row are bit for bit what the fixed-batch kernel gives at batch 1 on those rows,
+// whichever other sessions share the call, wherever it sits in the pack, whichever cache row it owns.  That holds by construction: ONE
+// per-unit routine per operator (convc_unit, scanc_unit: a sequence's base pointers, its length, its cache row) holds the step; the
+// fixed-batch kernel and the packed kernel differ only in where those arguments come from (b * X_bs / b-th cache row; cu_seqlens[i] * X_ts
+// / cache row state_indices[i], wave-uniform values read with plain loads).  An empty sequence, an index outside the pool or a
+// cu_seqlens pair outside [0, total] returns before anything is fetched.
 #pragma once
 #include "conv_tm_kernels.h"
 #include "scan_tm_kernels.h"
@@ -25,12 +34,17 @@ namespace aum {
 constexpr int STREAM_UB = 8;       // steps fetched together; two such blocks in flight
 
 // ---- conv ---------------------------------------------------------------------------------------
-// unit = (batch entry, block of 64 * V channels), channel block fastest
+// what the units of one launch share
+struct ConvcOps {
+    const float *weight, *bias;
+    int64_t x_ts, y_ts;
+    int dim, width;
+};
+
+// unit = (sequence, block of 64 * V channels): L >= 1 rows at x / y (row stride x_ts / y_ts elements), the sequence's cache row `win`
 template <class T, bool SILU>
-AUM_DEV void convc_wave(const AumConvTmChunkArgs& a, int wg) {
+AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb) {
     constexpr int V = convt_vec<T, false>(), NP = V / 2, ES = (int)sizeof(T), W = CONVT_W;
-    const int ncb = convt_cblocks<T, false>(a.dim), L = a.len;
-    const int cb = wg % ncb, b = wg / ncb;
     AumConvTmArgs s = {};
     s.weight = a.weight;
     s.bias = a.bias;
@@ -38,11 +52,10 @@ AUM_DEV void convc_wave(const AumConvTmChunkArgs& a, int wg) {
     s.width = a.width;
     ConvtLane<T, false> ln;
     convt_lane_setup<T, false>(s, cb, ln);
-    const gbuf<T> xb = make_gbuf(row_ptr<T>(a.x, (int64_t)b * a.x_bs));
-    const gbuf<T> yb = make_gbuf(row_ptr<T>(a.y, (int64_t)b * a.y_bs));
+    const gbuf<T> xb = make_gbuf(x);
+    const gbuf<T> yb = make_gbuf(y);
     const vi coff = ln.c0 * ES;
     const int x_tb = (int)a.x_ts * ES, y_tb = (int)a.y_ts * ES;
-    float* win = a.conv_state + (int64_t)b * a.dim * a.width;
     vf2 w2[W][NP], bias2[NP];
     AUM_UNROLL
     for (int p = 0; p < NP; ++p) {
@@ -125,16 +138,59 @@ AUM_DEV void convc_wave(const AumConvTmChunkArgs& a, int wg) {
     }
 }
 
+// fixed batch: unit = (batch entry, channel block), channel block fastest
+template <class T, bool SILU>
+AUM_DEV void convc_wave(const AumConvTmChunkArgs& a, int wg) {
+    const int ncb = convt_cblocks<T, false>(a.dim);
+    const int cb = wg % ncb, b = wg / ncb;
+    const ConvcOps o = {a.weight, a.bias, a.x_ts, a.y_ts, a.dim, a.width};
+    convc_unit<T, SILU>(o, row_ptr<T>(a.x, (int64_t)b * a.x_bs), row_ptr<T>(a.y, (int64_t)b * a.y_bs), a.conv_state + (int64_t)b * a.dim * a.width,
+                        a.len, cb);
+}
+
+// rows [r0, r1) and the cache row of sequence i of a packed call; false: the sequence is a no-op (empty, a cache row outside the pool, or
+// a cu_seqlens pair that is not inside [0, total]) and nothing of it may be touched
+AUM_DEV bool stream_seq(const int32_t* cu_seqlens, const int32_t* state_indices, int i, int total, int nrows, int& r0, int& len, int& row) {
+    r0 = cu_seqlens[i];
+    const int r1 = cu_seqlens[i + 1];
+    row = state_indices ? state_indices[i] : i;
+    len = r1 - r0;
+    return r0 >= 0 && r1 <= total && len > 0 && row >= 0 && row < nrows;
+}
+
+// packed sessions: unit = (sequence, channel block), channel block fastest
+template <class T, bool SILU>
+AUM_DEV void convc_var_wave(const AumConvTmChunkVarArgs& a, int wg) {
+    const int ncb = convt_cblocks<T, false>(a.dim);
+    const int cb = wg % ncb, i = wg / ncb;
+    int r0, len, row;
+    if (!stream_seq(a.cu_seqlens, a.state_indices, i, a.total, a.nrows, r0, len, row)) return;
+    const ConvcOps o = {a.weight, a.bias, a.x_ts, a.y_ts, a.dim, a.width};
+    convc_unit<T, SILU>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), row_ptr<T>(a.y, (int64_t)r0 * a.y_ts), a.conv_state + (int64_t)row * a.dim * a.width,
+                        len, cb);
+}
+
 // ---- scan ---------------------------------------------------------------------------------------
 struct ScancRaw { vi u, d, z, b, c; };      // one step's operands as loaded (widened where they are used)
 
-// unit = (batch entry, group of 64 channels), channel group fastest.  SP: delta = softplus(delta + bias); otherwise delta + bias (an
-// activated delta comes with bias == NULL: the launcher drops it).
+// what the units of one launch share (row strides in elements)
+struct ScancOps {
+    const float *A, *D, *delta_bias;
+    int64_t u_ts, delta_ts, z_ts, B_ts, C_ts, out_ts;
+};
+// one sequence: its first row in every operand, its cache row, its length
+template <class T> struct ScancSeq {
+    const T *u, *delta, *z, *B, *C, *out;
+    const float* state;
+    int len;
+};
+
+// unit = (sequence, group of 64 channels from e0).  SP: delta = softplus(delta + bias); otherwise delta + bias (an activated delta comes
+// with bias == NULL: the launcher drops it).
 template <class T, bool SP, bool HAS_Z>
-AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
+AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0) {
     constexpr int N = SCANT_N, ES = (int)sizeof(T);
-    const int ngrp = p.dim / WAVE, L = p.len;
-    const int e0 = (wg % ngrp) * WAVE, b = wg / ngrp;
+    const int L = q.len;
     const vi lane = lane_id();
     const vi ec = lane + e0;                     // dim % 64 == 0: every lane is a channel
     vf2 A2[N / 2];                               // A * log2(e), states (2j, 2j+1)
@@ -142,13 +198,13 @@ AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
     for (int j = 0; j < N / 2; ++j) A2[j] = mk2(gload_u(p.A, ec * N + 2 * j) * LOG2E, gload_u(p.A, ec * N + 2 * j + 1) * LOG2E);
     const vf biasv = p.delta_bias ? gload_u(p.delta_bias, ec) : splat(0.f);
     const vf Dv = p.D ? gload_u(p.D, ec) : splat(0.f);
-    const gbuf<T> ubuf = make_gbuf(row_ptr<T>(p.u, (int64_t)b * p.u_bs));
-    const gbuf<T> dbuf = make_gbuf(row_ptr<T>(p.delta, (int64_t)b * p.delta_bs));
-    const gbuf<T> zbuf = make_gbuf(HAS_Z ? row_ptr<T>(p.z, (int64_t)b * p.z_bs) : row_ptr<T>(p.u, 0));
-    const gbuf<T> obuf = make_gbuf(row_ptr<T>(p.out, (int64_t)b * p.out_bs));
-    const gbuf<T> Bbuf = make_gbuf(row_ptr<T>(p.B, (int64_t)b * p.B_bs));
-    const gbuf<T> Cbuf = make_gbuf(row_ptr<T>(p.C, (int64_t)b * p.C_bs));
-    const gbuf<float> sbuf = make_gbuf(p.state + (int64_t)b * p.dim * N);
+    const gbuf<T> ubuf = make_gbuf(q.u);
+    const gbuf<T> dbuf = make_gbuf(q.delta);
+    const gbuf<T> zbuf = make_gbuf(HAS_Z ? q.z : q.u);
+    const gbuf<T> obuf = make_gbuf(q.out);
+    const gbuf<T> Bbuf = make_gbuf(q.B);
+    const gbuf<T> Cbuf = make_gbuf(q.C);
+    const gbuf<float> sbuf = make_gbuf(q.state);
     const int u_tb = (int)p.u_ts * ES, d_tb = (int)p.delta_ts * ES, z_tb = HAS_Z ? (int)p.z_ts * ES : 0, o_tb = (int)p.out_ts * ES,
               B_tb = (int)p.B_ts * ES, C_tb = (int)p.C_ts * ES;
     const vi el_off = ec * ES;                   // this lane's channel inside a token row
@@ -236,6 +292,34 @@ AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
         const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
         gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
     }
+}
+
+// fixed batch: unit = (batch entry, group of 64 channels), channel group fastest
+template <class T, bool SP, bool HAS_Z>
+AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
+    const int ngrp = p.dim / WAVE;
+    const int e0 = (wg % ngrp) * WAVE, b = wg / ngrp;
+    const ScancOps o = {p.A, p.D, p.delta_bias, p.u_ts, p.delta_ts, p.z_ts, p.B_ts, p.C_ts, p.out_ts};
+    const ScancSeq<T> q = {row_ptr<T>(p.u, (int64_t)b * p.u_bs), row_ptr<T>(p.delta, (int64_t)b * p.delta_bs),
+                           HAS_Z ? row_ptr<T>(p.z, (int64_t)b * p.z_bs) : nullptr, row_ptr<T>(p.B, (int64_t)b * p.B_bs),
+                           row_ptr<T>(p.C, (int64_t)b * p.C_bs), row_ptr<T>(p.out, (int64_t)b * p.out_bs),
+                           p.state + (int64_t)b * p.dim * SCANT_N, p.len};
+    scanc_unit<T, SP, HAS_Z>(o, q, e0);
+}
+
+// packed sessions: unit = (sequence, group of 64 channels), channel group fastest
+template <class T, bool SP, bool HAS_Z>
+AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg) {
+    const int ngrp = p.dim / WAVE;
+    const int e0 = (wg % ngrp) * WAVE, i = wg / ngrp;
+    int r0, len, row;
+    if (!stream_seq(p.cu_seqlens, p.state_indices, i, p.total, p.nrows, r0, len, row)) return;
+    const ScancOps o = {p.A, p.D, p.delta_bias, p.u_ts, p.delta_ts, p.z_ts, p.B_ts, p.C_ts, p.out_ts};
+    const ScancSeq<T> q = {row_ptr<T>(p.u, (int64_t)r0 * p.u_ts), row_ptr<T>(p.delta, (int64_t)r0 * p.delta_ts),
+                           HAS_Z ? row_ptr<T>(p.z, (int64_t)r0 * p.z_ts) : nullptr, row_ptr<T>(p.B, (int64_t)r0 * p.B_ts),
+                           row_ptr<T>(p.C, (int64_t)r0 * p.C_ts), row_ptr<T>(p.out, (int64_t)r0 * p.out_ts),
+                           p.state + (int64_t)row * p.dim * SCANT_N, len};
+    scanc_unit<T, SP, HAS_Z>(o, q, e0);
 }
 
 }  // namespace aum

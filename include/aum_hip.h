@@ -610,6 +610,48 @@ typedef struct AumScanTmChunkArgs {
 } AumScanTmChunkArgs;
 int aum_scan_tm_chunk(const AumScanTmChunkArgs* args, void* stream);
 
+/*
+ * The same two operators on PACKED SESSIONS (additive to ABI 13; `Mamba.step_chunk(..., seq_map=)`): the new rows of `nseq` streaming
+ * sessions, each at its own position and with its own number of rows, behind one another in one token stream, and a pool of `nrows`
+ * cache rows of which every session owns one.  Activations are packed: element (row, e) at  row * X_ts + e  (no batch stride), `total`
+ * rows in all.  cu_seqlens: device int32[nseq + 1], cu_seqlens[0] == 0, non-decreasing, cu_seqlens[nseq] <= total -- sequence i owns rows
+ * [cu_seqlens[i], cu_seqlens[i + 1]).  state_indices: device int32[nseq], the cache row of sequence i, or NULL (sequence i uses row i).
+ * conv_state (nrows, dim, width) / state (nrows, dim, dstate): the pool, fp32 contiguous; rows that no sequence names are not touched.
+ *
+ * For every sequence i with cache row r = state_indices[i] the outputs and cache row r are BIT FOR BIT what aum_conv1d_tm_chunk /
+ * aum_scan_tm_chunk give at batch 1 on those rows and that cache row (the kernels share one step routine).  So the partition property
+ * extends to packing: a session's results depend neither on which other sessions share the call, nor on its place in the pack, nor on
+ * its cache row.  An empty sequence is a no-op.  A sequence whose index is outside [0, nrows), or whose cu_seqlens pair is not inside
+ * [0, total], is a no-op too: nothing is read or written for it, and nothing is reported (no device-side assert).  Two sequences naming
+ * one cache row in one call: undefined results for that row (callers refuse it on the host).  Every other field, flag and limit is that of the fixed-batch
+ * entry point; the 32-bit byte-cursor limit applies to `total` rows (the launcher cannot see the per-sequence lengths).
+ * nseq >= 1, nrows >= 1, total >= 1; cu_seqlens non-NULL; cu_seqlens and state_indices 4-byte aligned.
+ */
+typedef struct AumConvTmChunkVarArgs {
+    const void* x;
+    float* conv_state;
+    const float *weight, *bias;
+    void* y;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t x_ts, y_ts;
+    int32_t total, nseq, nrows, dim, width;
+    int32_t dtype;
+    uint32_t flags;
+} AumConvTmChunkVarArgs;
+int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* args, void* stream);
+typedef struct AumScanTmChunkVarArgs {
+    const void *u, *delta, *z, *B, *C;
+    const float *A, *D, *delta_bias;
+    float* state;
+    void* out;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t u_ts, delta_ts, z_ts, B_ts, C_ts, out_ts;
+    int32_t total, nseq, nrows, dim, dstate;
+    int32_t dtype;
+    uint32_t flags;
+} AumScanTmChunkVarArgs;
+int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
+
 /* Self-tests and calibration (used by tests/ and bench.py; not part of the reference's surface). */
 int aum_abi_version(void);
 /* runs wave_scan_affine<rev> on 64 (P,S) pairs: in/out are device arrays of 128 floats (P[0..63], S[0..63]) */

@@ -5,6 +5,16 @@ around each call, warm hops discarded, medians; the spread of (a) is the range o
 
     python tools/stream_hop_bench.py [--size base] [--depth 24] [--batch 1 8] [--warm 20] [--hops 120] [--groups 4]
     python tools/stream_hop_bench.py --count-only a|b     (a few hops of one path only: for a kernel trace that counts launches per hop)
+
+--pool S: S sessions at DIFFERENT positions, one hop each, three ways alternating in one process (same method):
+  (a) S stream_push calls on S batch-1 caches -- the only way to serve staggered sessions without stream_push_many;
+  (b) one stream_push_many for the S sessions at staggered offsets, one column each;
+  (c) the same with ragged hops, k_i cycling through 1, 2, 1, 4 columns;
+  and for reference the lockstep batch-S stream_push (all sessions at one position).
+Arms (b) and (c) are skipped on a tree without stream_push_many, so the file also measures (a) on an older commit.
+
+    python tools/stream_hop_bench.py --pool 8
+    python tools/stream_hop_bench.py --pool 8 --count-only pa|pb|pc|lock
 """
 import argparse
 import json
@@ -63,6 +73,92 @@ def timed(fn, model, spec, cache):
     return a.elapsed_time(b)
 
 
+RAGGED = (1, 2, 1, 4)
+
+
+def pool_arms(model, S, dev):
+    """-> {arm: (callable doing one hop of all S sessions, columns served per hop)}"""
+    nt = model.patch_grid_size[1]
+    piece = lambda k: torch.randn(16 * k, 128, device=dev, dtype=torch.bfloat16)
+    start = [(7 * i) % (nt - 8) for i in range(S)]                  # staggered offsets into the clips
+    solo = [model.allocate_inference_cache(1) for _ in range(S)]
+    for c, c0 in zip(solo, start):
+        c["columns"] = c0
+    one = [piece(1) for _ in range(S)]
+
+    def wrap(columns, i, k):
+        if columns[i] + k > nt:
+            columns[i] = 0                                          # a new clip: the caches' values do not matter for timing
+
+    def arm_a():
+        for c, sp in zip(solo, one):
+            if c["columns"] + 1 > nt:
+                c["columns"] = 0
+            model.stream_push(sp.unsqueeze(0), c)
+
+    lock_cache = model.allocate_inference_cache(S)
+    lock_spec = torch.randn(S, 16, 128, device=dev, dtype=torch.bfloat16)
+
+    def arm_lock():
+        if lock_cache["columns"] + 1 > nt:
+            lock_cache["columns"] = 0
+        model.stream_push(lock_spec, lock_cache)
+
+    arms = {"a_solo_pushes": (arm_a, S), "lockstep_batch_push": (arm_lock, S)}
+    if hasattr(model, "stream_push_many"):
+        pools = {}
+        for name, ks in (("b_push_many", [1] * S), ("c_push_many_ragged", [RAGGED[i % len(RAGGED)] for i in range(S)])):
+            pool = model.allocate_stream_pool(S)
+            pool["columns"] = list(start)
+            pools[name] = (pool, ks, [piece(k) for k in ks])
+
+        def many(name):
+            pool, ks, specs = pools[name]
+            for i, k in enumerate(ks):
+                wrap(pool["columns"], i, k)
+            model.stream_push_many(specs, pool, range(S))
+
+        arms["b_push_many"] = (lambda: many("b_push_many"), S)
+        arms["c_push_many_ragged"] = (lambda: many("c_push_many_ragged"), sum(pools["c_push_many_ragged"][1]))
+    return arms
+
+
+def timed_call(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def pool_main(model, args, dev):
+    S = args.pool
+    arms = pool_arms(model, S, dev)
+    if args.count_only:
+        name = {"pa": "a_solo_pushes", "pb": "b_push_many", "pc": "c_push_many_ragged", "lock": "lockstep_batch_push"}[args.count_only]
+        for _ in range(args.count_hops):
+            arms[name][0]()
+        torch.cuda.synchronize()
+        print(json.dumps({"path": name, "sessions": S, "hops": args.count_hops}))
+        return
+    for _ in range(args.warm):
+        for fn, _ in arms.values():
+            timed_call(fn)
+    times = {k: [] for k in arms}
+    for _ in range(args.hops):
+        for k, (fn, _) in arms.items():
+            times[k].append(timed_call(fn))
+    g = max(args.hops // args.groups, 1)
+    out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "sessions": S, "hops": args.hops, "warm": args.warm}
+    for k, v in times.items():
+        out[k] = {"ms_median": round(statistics.median(v), 4), "columns_per_hop": arms[k][1],
+                  "ms_group_medians": [round(statistics.median(v[i:i + g]), 4) for i in range(0, g * args.groups, g)]}
+    if "b_push_many" in out:
+        out["ratio_a_over_b"] = round(out["a_solo_pushes"]["ms_median"] / out["b_push_many"]["ms_median"], 3)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="base")
@@ -71,11 +167,16 @@ def main():
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--hops", type=int, default=120)
     ap.add_argument("--groups", type=int, default=4)
-    ap.add_argument("--count-only", choices=["a", "b"])
+    ap.add_argument("--pool", type=int, default=0, help="S sessions at different positions: S stream_push calls vs one stream_push_many")
+    ap.add_argument("--count-only", choices=["a", "b", "pa", "pb", "pc", "lock"])
     ap.add_argument("--count-hops", type=int, default=4)
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev)
+    if args.pool:
+        with torch.no_grad():
+            pool_main(model, args, dev)
+        return
     with torch.no_grad():
         for B in args.batch:
             spec = torch.randn(B, 16, 128, device=dev, dtype=torch.bfloat16)
