@@ -269,15 +269,26 @@ class AudioMamba(nn.Module):
     def _is_pool(cache):
         return isinstance(cache["columns"], list)
 
-    def _check_sessions(self, what, pool, sessions):
-        if not self._is_pool(pool):
+    def _check_sessions(self, what, cache, sessions, writes=True):
+        """the rows `sessions` names; writes: of a pool, and distinct (stream_read takes any cache and may read a row twice)"""
+        if writes and not self._is_pool(cache):
             raise ValueError(f"{what} takes a pool from allocate_stream_pool")
         rows = [int(r) for r in sessions]
-        if len(set(rows)) != len(rows):
+        if writes and len(set(rows)) != len(rows):
             raise ValueError(f"{what}: the sessions {rows} are not distinct")
-        if rows and (min(rows) < 0 or max(rows) >= pool["batch"]):
-            raise ValueError(f"{what}: the sessions {rows} are not all rows of a pool of {pool['batch']}")
+        if rows and (min(rows) < 0 or max(rows) >= cache["batch"]):
+            raise ValueError(f"{what}: the sessions {rows} are not all rows of a cache of {cache['batch']}")
         return rows
+
+    def _embed_columns(self, spec4d, cols):
+        """(B, 1, n_mels, 16 k) frames of k time columns -> their (B, k * nf, Dm) tokens, time-major, each with the position row of its
+        (f, t) cell.  cols: where the k columns sit in the clip -- a slice, or an int64 index vector on the frames' device."""
+        nf, nt = self.patch_grid_size
+        x = self.patch_embed(spec4d)                                             # (B, nf * k, Dm), token index f * k + t
+        Bsz, k = x.shape[0], x.shape[1] // nf
+        pe = self.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1)
+        pe = pe[:, :, cols] if isinstance(cols, slice) else pe.index_select(2, cols)
+        return (x.reshape(Bsz, nf, k, -1) + pe).transpose(1, 2).reshape(Bsz, k * nf, -1)
 
     @torch.no_grad()
     def stream_push_many(self, specs, pool, sessions):
@@ -305,15 +316,12 @@ class AudioMamba(nn.Module):
             ks.append(k)
         dev = specs[0].device
         smap = aum_hip.seq_map([k * nf for k in ks], rows, device=dev)
-        K = sum(ks)
         # the position row of every new column: one host-built index vector, uploaded like the sequence map
         cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
         if dev.type == "cuda":
             cols = cols.pin_memory()
         cols = cols.to(dev, non_blocking=True)
-        x = self.patch_embed(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3))     # (1, nf * K, Dm), token index f * K + t
-        pe = self.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1).index_select(2, cols)
-        x = (x.reshape(1, nf, K, -1) + pe).transpose(1, 2).reshape(1, K * nf, -1)                 # column-major: a session's tokens are contiguous
+        x = self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)   # a session's tokens are contiguous
         self._stream_layers(x, pool["layers"], smap)
         for r, k in zip(rows, ks):
             pool["columns"][r] += k
@@ -347,11 +355,7 @@ class AudioMamba(nn.Module):
         k, c0 = spec.shape[1] // pw, cache["columns"]
         if c0 + k > nt:
             raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
-        x = self.patch_embed(spec.unsqueeze(1).transpose(2, 3))                  # (B, nf * k, Dm), token index f * k + t
-        Bsz = x.shape[0]
-        pe = self.pos_embed.pos_embed[:, 1:].reshape(1, nf, nt, -1)[:, :, c0:c0 + k]
-        x = (x.reshape(Bsz, nf, k, -1) + pe).transpose(1, 2).reshape(Bsz, k * nf, -1)
-        self._stream_layers(x, cache["layers"])
+        self._stream_layers(self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k)), cache["layers"])
         cache["columns"] = c0 + k
         return cache["columns"]
 
@@ -365,9 +369,9 @@ class AudioMamba(nn.Module):
             copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
             n = cache["batch"]
         else:
-            rows = [int(r) for r in sessions]
-            if not rows or min(rows) < 0 or max(rows) >= cache["batch"]:
-                raise ValueError(f"stream_read: the sessions {rows} are not all rows of a cache of {cache['batch']}")
+            rows = self._check_sessions("stream_read", cache, sessions, writes=False)
+            if not rows:
+                raise ValueError("stream_read: at least one session")
             idx = torch.tensor(rows, dtype=torch.int64)
             copies = {i: (c.index_select(0, idx.to(c.device)), s.index_select(0, idx.to(s.device))) for i, (c, s) in cache["layers"].items()}
             n = len(rows)

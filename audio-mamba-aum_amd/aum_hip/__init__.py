@@ -222,14 +222,27 @@ class XdtArgs(C.Structure):
                 + [("delta_bias", _vp), ("flags", _u32)])
 
 
-EXPORTS = ["aum_gemm_tn", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_proj_fwd", "aum_proj_bwd_data", "aum_proj_bwd_weight", "aum_proj_bwd_weight_splits", "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_abi_version", "aum_selective_scan_fwd", "aum_selective_scan_bwd", "aum_scan_max_single_pass_len",
-           "aum_selective_scan_workspace_bytes", "aum_selective_scan_ckpt_bytes", "aum_selective_scan_lane_ckpt_bytes", "aum_causal_conv1d_fwd", "aum_causal_conv1d_bwd", "aum_rmsnorm_fwd",
-           "aum_rmsnorm_bwd", "aum_rmsnorm_bwd_partials", "aum_selftest_wave_scan", "aum_hbm_copy", "aum_sum_rows", "aum_sum_rows_multi",
-           "aum_scan_tm_fwd", "aum_scan_tm_nck", "aum_scan_tm_ckpt_rows", "aum_scan_tm_bwd", "aum_scan_tm_workspace_bytes", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd",
-           "aum_scan_tm_seg_carry_bytes", "aum_scan_tm_seg_workspace_bytes", "aum_selftest_wave_sum32",
-           "aum_conv1d_tm_fwd", "aum_conv1d_tm_bwd", "aum_conv1d_tm_nparts", "aum_gemm_wgrad", "aum_xdt_tm_bwd", "aum_causal_conv1d_update", "aum_selective_state_update", "aum_cast_bank", "aum_rmsnorm_bwd_partial_rows",
-           "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk",
-           "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var"]
+# Every entry point of include/aum_hip.h: name -> (argtypes, restype).  The launches take (const Args*, void* stream) and return an AUM_E_*
+# code; only the other forms are spelled out.  Lib sets these on load; EXPORTS (what tests/test_abi.py holds against the header) is the keys.
+_SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
+    "aum_selective_scan_fwd", "aum_selective_scan_bwd", "aum_causal_conv1d_fwd", "aum_causal_conv1d_bwd", "aum_rmsnorm_fwd", "aum_rmsnorm_bwd",
+    "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_proj_fwd", "aum_proj_bwd_data",
+    "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
+    "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
+    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var")}
+_SIGNATURES.update({
+    "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
+    "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
+    "aum_selective_scan_lane_ckpt_bytes": ([_i32] * 5, _i64), "aum_scan_tm_workspace_bytes": ([_i32] * 5, _i64),
+    "aum_scan_tm_seg_carry_bytes": ([_i32] * 6, _i64), "aum_scan_tm_seg_workspace_bytes": ([_i32] * 6, _i64),
+    "aum_rmsnorm_bwd_partials": ([_i32], C.c_int), "aum_rmsnorm_bwd_partial_rows": ([_i32, _i32, _u32], C.c_int),
+    "aum_scan_tm_nck": ([_i32], _i32), "aum_scan_tm_ckpt_rows": ([_i32], _i32), "aum_conv1d_tm_nparts": ([_i32, _i32], _i32),
+    "aum_proj_bwd_weight_splits": ([_i32, _i64], C.c_int), "aum_hbm_copy": ([_vp, _vp, _i64, _vp], C.c_int),
+    "aum_selftest_wave_scan": ([_vp, _vp, C.c_int, _vp], C.c_int), "aum_selftest_wave_sum32": ([_vp, _vp, _vp], C.c_int),
+    "aum_sum_rows": ([_vp, _vp, _i64, _i64, _i64, _i32, _vp], C.c_int), "aum_sum_rows_multi": ([_vp, _i32, _vp], C.c_int),
+    "aum_cast_bank": ([_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp], C.c_int),
+})
+EXPORTS = list(_SIGNATURES)
 
 
 class Lib:
@@ -242,55 +255,9 @@ class Lib:
                 "(hipcc, gfx950).  There is no CPU fallback on the product path.")
         self.path, self.host = path, host
         self.c = C.CDLL(path)
-        for name in EXPORTS:
-            getattr(self.c, name)   # AttributeError if a declared symbol is missing
-        self.c.aum_selective_scan_workspace_bytes.restype = _i64
-        self.c.aum_selective_scan_workspace_bytes.argtypes = [_i32] * 6
-        for n in ("aum_selective_scan_fwd", "aum_selective_scan_bwd", "aum_causal_conv1d_fwd", "aum_causal_conv1d_bwd",
-                  "aum_rmsnorm_fwd", "aum_rmsnorm_bwd"):
-            getattr(self.c, n).argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_fwd.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_bwd.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_seg_fwd.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_seg_bwd.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_nck.argtypes = [_i32]
-        self.c.aum_scan_tm_ckpt_rows.argtypes = [_i32]
-        self.c.aum_conv1d_tm_fwd.argtypes = [_vp, _vp]
-        self.c.aum_conv1d_tm_bwd.argtypes = [_vp, _vp]
-        self.c.aum_conv1d_tm_nparts.argtypes = [_i32, _i32]
-        self.c.aum_gemm_tn.argtypes = [_vp, _vp]
-        self.c.aum_gemm_wgrad.argtypes = [_vp, _vp]
-        self.c.aum_causal_conv1d_update.argtypes = [_vp, _vp]
-        self.c.aum_selective_state_update.argtypes = [_vp, _vp]
-        self.c.aum_conv1d_tm_chunk.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_chunk.argtypes = [_vp, _vp]
-        self.c.aum_conv1d_tm_chunk_var.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_chunk_var.argtypes = [_vp, _vp]
-        self.c.aum_dtproj_tm_fwd.argtypes = [_vp, _vp]
-        self.c.aum_xdt_tm_fwd.argtypes = [_vp, _vp]
-        self.c.aum_xdt_tm_bwd.argtypes = [_vp, _vp]
-        self.c.aum_scan_tm_workspace_bytes.restype = _i64
-        self.c.aum_scan_tm_workspace_bytes.argtypes = [_i32] * 5
-        for fn in (self.c.aum_scan_tm_seg_carry_bytes, self.c.aum_scan_tm_seg_workspace_bytes):
-            fn.restype = _i64
-            fn.argtypes = [_i32] * 6
-        self.c.aum_fbank_fwd.argtypes = [_vp, _vp]
-        self.c.aum_frontend_tokens_fwd.argtypes = [_vp, _vp]
-        self.c.aum_stft_logmel_fwd.argtypes = [_vp, _vp]
-        self.c.aum_spec_time_warp.argtypes = [_vp, _vp]
-        for n in ("aum_proj_fwd", "aum_proj_bwd_data", "aum_proj_bwd_weight"):
-            getattr(self.c, n).argtypes = [_vp, _vp]
-        self.c.aum_proj_bwd_weight_splits.argtypes = [_i32, _i64]
-        self.c.aum_selftest_wave_scan.argtypes = [_vp, _vp, C.c_int, _vp]
-        self.c.aum_hbm_copy.argtypes = [_vp, _vp, _i64, _vp]
-        self.c.aum_cast_bank.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]
-        self.c.aum_selftest_wave_sum32.argtypes = [_vp, _vp, _vp]
-        self.c.aum_sum_rows.argtypes = [_vp, _vp, _i64, _i64, _i64, _i32, _vp]
-        self.c.aum_sum_rows_multi.argtypes = [_vp, _i32, _vp]
-        self.c.aum_selective_scan_ckpt_bytes.restype = _i64
-        self.c.aum_selective_scan_ckpt_bytes.argtypes = [_i32] * 4
-        self.c.aum_selective_scan_lane_ckpt_bytes.restype = _i64
-        self.c.aum_selective_scan_lane_ckpt_bytes.argtypes = [_i32] * 5
+        for name, (argtypes, restype) in _SIGNATURES.items():
+            fn = getattr(self.c, name)   # AttributeError if a declared symbol is missing
+            fn.argtypes, fn.restype = argtypes, restype
         if self.c.aum_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {self.c.aum_abi_version()}, this binding speaks {ABI_VERSION} -- rebuild the library "
                                "(python audio-mamba-aum_amd/csrc/build.py)")
@@ -361,6 +328,10 @@ class LaunchTimer:
 
 
 timer = LaunchTimer()
+
+
+def C_byref(s):
+    return C.cast(C.byref(s), C.c_void_p)
 
 
 def _launch(fn, args, stream_tensor, lib, name, meta=None):
@@ -489,10 +460,6 @@ def scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
     _launch(lib.c.aum_selective_scan_fwd, a, u, lib, "scan_fwd_bidir" if A_b is not None else "scan_fwd",
             (batch, dim, length, dstate, u.element_size(), want_out_pre))
     return out, out_pre, last
-
-
-def C_byref(s):
-    return C.cast(C.byref(s), C.c_void_p)
 
 
 def scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, delta_softplus=False, reverse=False, A_b=None,
@@ -905,11 +872,77 @@ def state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplu
     return out
 
 
+# ---- streaming inference, T tokens per launch: fixed batch (aum_*_tm_chunk) or packed sessions (aum_*_tm_chunk_var), which differ in addressing only
+def _stream_ok(cache, x, scan):
+    """x a token-major (batch, T >= 1, dim) view, cache fp32 contiguous (., dim, .), of a dim / dstate / width the operator's kernels take"""
+    if not (cache.dim() == 3 and cache.dtype == torch.float32 and cache.is_contiguous() and x.dim() == 3 and x.shape[1] >= 1
+            and cache.shape[1] == x.shape[2]):
+        return False
+    if scan:            # the state is read with 16-byte accesses
+        return cache.data_ptr() % 16 == 0 and x.dtype in _DT and scan_tm_supported(x.shape[2], cache.shape[2])
+    return conv1d_tm_supported(x, cache.shape[2])
+
+
 def conv1d_tm_chunk_supported(x, conv_state):
     """the limits of aum_conv1d_tm_chunk (include/aum_hip.h): a token-major (batch, T, dim) view as conv1d_tm_fwd takes it, an fp32
     contiguous (batch, dim, width <= 4) cache; outside them callers use conv1d_update token by token"""
-    return (conv_state.dim() == 3 and conv_state.dtype == torch.float32 and conv_state.is_contiguous() and x.dim() == 3 and x.shape[1] >= 1
-            and conv_state.shape[:2] == (x.shape[0], x.shape[2]) and conv1d_tm_supported(x, conv_state.shape[2]))
+    return _stream_ok(conv_state, x, False) and conv_state.shape[0] == x.shape[0]
+
+
+def scan_tm_chunk_supported(state, u):
+    """the limits of aum_scan_tm_chunk (include/aum_hip.h): fp32 contiguous (batch, dim, 16) state, dim % 64 == 0, (batch, T, dim)
+    activations; outside them callers use state_update token by token"""
+    return _stream_ok(state, u, True) and state.shape[0] == u.shape[0]
+
+
+def conv1d_tm_chunk_var_supported(x, conv_state):
+    """the limits of aum_conv1d_tm_chunk_var (include/aum_hip.h): packed (total >= 1, dim) rows as conv1d_tm_chunk takes them at batch 1, an
+    fp32 contiguous (nrows, dim, width <= 4) pool; outside them callers loop over the sessions through conv1d_tm_chunk / conv1d_update"""
+    return x.dim() == 2 and _stream_ok(conv_state, x.unsqueeze(0), False) and conv_state.shape[0] >= 1
+
+
+def scan_tm_chunk_var_supported(state, u):
+    """the limits of aum_scan_tm_chunk_var (include/aum_hip.h): an fp32 contiguous (nrows, dim, 16) pool, dim % 64 == 0, packed
+    (total >= 1, dim) activations; outside them callers loop over the sessions through scan_tm_chunk / state_update"""
+    return u.dim() == 2 and _stream_ok(state, u.unsqueeze(0), True) and state.shape[0] >= 1
+
+
+def _conv_chunk_operands(a, name, lib, x, conv_state, weight, bias, silu, out):
+    """Fills what ConvTmChunkArgs and ConvTmChunkVarArgs share (operand pointers, dim, width, dtype, flags); returns y (out, or allocated)."""
+    dim = x.shape[-1]
+    weight = _al16(_f32c(weight.reshape(dim, -1)))
+    bias = _al16(_f32c(bias))
+    if weight.shape[1] != conv_state.shape[2]:
+        raise RuntimeError(f"{name}: weight (dim, width) and conv_state (rows, dim, width) disagree on the width")
+    for t in (weight, bias):
+        lib.check_tensor(t)
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    if y.dtype != x.dtype or y.shape != x.shape:
+        raise RuntimeError(f"{name}: out must have x's shape and dtype")
+    a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
+    a.dim, a.width, a.dtype, a.flags = dim, weight.shape[1], _DT[x.dtype], (CONV_SILU if silu else 0)
+    return y, (weight, bias)             # the converted operands: the caller holds them until its launch is enqueued
+
+
+def _scan_chunk_operands(a, name, lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out):
+    """Fills what ScanTmChunkArgs and ScanTmChunkVarArgs share (operand pointers, dim, dstate, dtype, flags); returns out (given, or allocated)."""
+    dim, dstate = u.shape[-1], state.shape[2]
+    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
+        raise RuntimeError(f"{name}: u, delta, z, B, C must share one dtype")
+    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
+    for t in (A, D, delta_bias):
+        lib.check_tensor(t)
+    if A.shape != (dim, dstate):
+        raise RuntimeError(f"{name}: A must be (dim, dstate)")
+    if out is None:
+        out = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    if out.dtype != u.dtype or out.shape != u.shape:
+        raise RuntimeError(f"{name}: out must have u's shape and dtype")
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
+    a.dim, a.dstate, a.dtype = dim, dstate, _DT[u.dtype]
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    return out, (A, D, delta_bias)       # the converted operands: the caller holds them until its launch is enqueued
 
 
 def conv1d_tm_chunk(x, conv_state, weight, bias=None, silu=True, lib=None):
@@ -923,28 +956,13 @@ def conv1d_tm_chunk(x, conv_state, weight, bias=None, silu=True, lib=None):
         raise RuntimeError(f"conv1d_tm_chunk: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
                            f"{tuple(conv_state.shape)} {conv_state.dtype} (need (batch, T, dim) token-major, 16-byte rows; fp32 contiguous (batch, dim, width <= 4))")
     batch, length, dim = x.shape
-    weight = _al16(_f32c(weight.reshape(dim, -1)))
-    bias = _al16(_f32c(bias))
-    if weight.shape[1] != conv_state.shape[2]:
-        raise RuntimeError("conv1d_tm_chunk: weight (dim, width) and conv_state (batch, dim, width) disagree on the width")
-    for t in (weight, bias):
-        lib.check_tensor(t)
-    y = torch.empty((batch, length, dim), dtype=x.dtype, device=x.device)
     a = ConvTmChunkArgs()
-    a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
+    y, _held = _conv_chunk_operands(a, "conv1d_tm_chunk", lib, x, conv_state, weight, bias, silu, None)
     a.x_bs, a.x_ts = _tm3(x, "x", dim)
     a.y_bs, a.y_ts = _tm3(y, "y", dim)
-    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
-    a.flags = CONV_SILU if silu else 0
+    a.batch, a.len = batch, length
     _launch(lib.c.aum_conv1d_tm_chunk, a, x, lib, "conv_tm_chunk", (batch, dim, length, x.element_size()))
     return y
-
-
-def scan_tm_chunk_supported(state, u):
-    """the limits of aum_scan_tm_chunk (include/aum_hip.h): fp32 contiguous (batch, dim, 16) state, dim % 64 == 0, (batch, T, dim)
-    activations; outside them callers use state_update token by token"""
-    return (state.dim() == 3 and state.dtype == torch.float32 and state.is_contiguous() and state.data_ptr() % 16 == 0 and u.dim() == 3
-            and u.dtype in _DT and u.shape[1] >= 1 and state.shape[:2] == (u.shape[0], u.shape[2]) and scan_tm_supported(u.shape[2], state.shape[2]))
 
 
 def scan_tm_chunk(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, out=None, lib=None):
@@ -954,34 +972,22 @@ def scan_tm_chunk(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, del
     softplus(raw + delta_bias) (xdt_tm_fwd(..., delta_softplus=True)).  Returns (batch, T, dim) contiguous in u's dtype.  The result does
     not depend on how a stream is cut into calls (bitwise)."""
     lib = lib or get()
-    for t in (state, u, delta, z, B, C):
+    for t in (state, u, delta, z, B, C, out):
         lib.check_tensor(t)
     if not scan_tm_chunk_supported(state, u):
         raise RuntimeError(f"scan_tm_chunk: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
                            "(need fp32 contiguous (batch, dim, 16), dim % 64 == 0, u (batch, T, dim))")
     batch, length, dim = u.shape
     dstate = state.shape[2]
-    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
-        raise RuntimeError("scan_tm_chunk: u, delta, z, B, C must share one dtype")
-    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
-    for t in (A, D, delta_bias):
-        lib.check_tensor(t)
-    if A.shape != (dim, dstate):
-        raise RuntimeError("scan_tm_chunk: A must be (dim, dstate)")
     a = ScanTmChunkArgs()
+    out, _held = _scan_chunk_operands(a, "scan_tm_chunk", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
     a.u_bs, a.u_ts = _tm3(u, "u", dim)
     a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
-    if z is not None:
-        a.z_bs, a.z_ts = _tm3(z, "z", dim)
+    a.z_bs, a.z_ts = (0, 0) if z is None else _tm3(z, "z", dim)
     a.B_bs, a.B_ts = _tm3(B, "B", dstate)
     a.C_bs, a.C_ts = _tm3(C, "C", dstate)
-    if out is None:
-        out = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device)
     a.out_bs, a.out_ts = _tm3(out, "out", dim)
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    a.batch, a.len = batch, length
     _launch(lib.c.aum_scan_tm_chunk, a, u, lib, "scan_tm_chunk", (batch, dim, length, dstate, u.element_size()))
     return out
 
@@ -1000,7 +1006,7 @@ class SeqMap(typing.NamedTuple):
 def seq_map(seq_lens, state_indices=None, *, device):
     """Built once per push and handed to every layer: the per-session row counts (>= 0) and the cache row of each session (distinct, >= 0;
     None: session i owns row i) -- checked here, on the host, and sent to `device` in ONE pinned, non-blocking upload.  That the rows exist
-    is checked where a cache is known (conv1d_tm_chunk_var, scan_tm_chunk_var)."""
+    is checked where a cache is known (check_seq_map)."""
     lens = tuple(int(n) for n in seq_lens)
     if not lens or min(lens) < 0:
         raise ValueError(f"seq_map: one length >= 0 per session, got {lens}")
@@ -1021,16 +1027,18 @@ def seq_map(seq_lens, state_indices=None, *, device):
     return SeqMap(lens, rows, cu[-1], buf[:n1], buf[n1:] if state_indices is not None else None)
 
 
-def _var_common(name, m, rows2d, cache):
-    """the checks a packed call makes where the cache is known: the map is of this stream and of this device, its rows are in the pool"""
+def check_seq_map(name, m, total, nrows, device):
+    """The one check of a SeqMap against a call: it is of this stream (`total` packed rows) and of this device, its rows are in the pool
+    (`nrows` cache rows).  Made ONCE per call, by the outermost public function the caller used (conv1d_tm_chunk_var / scan_tm_chunk_var,
+    causal_conv1d_update / selective_scan_update, Mamba.step_chunk); what those call underneath trusts the map."""
     if not isinstance(m, SeqMap):
         raise TypeError(f"{name}: seq_map must come from aum_hip.seq_map()")
-    if m.total != rows2d.shape[0]:
-        raise ValueError(f"{name}: seq_map describes {m.total} rows, the packed stream has {rows2d.shape[0]}")
-    if max(m.rows) >= cache.shape[0]:
-        raise ValueError(f"{name}: seq_map names cache row {max(m.rows)}, the pool has {cache.shape[0]} rows")
-    if m.cu.device != rows2d.device or m.cu.dtype != torch.int32 or (m.idx is not None and (m.idx.device != rows2d.device or m.idx.dtype != torch.int32)):
-        raise RuntimeError(f"{name}: seq_map lives on {m.cu.device}, the packed stream on {rows2d.device}")
+    if m.total != total:
+        raise ValueError(f"{name}: seq_map describes {m.total} rows, the packed stream has {total}")
+    if max(m.rows) >= nrows:
+        raise ValueError(f"{name}: seq_map names cache row {max(m.rows)}, the pool has {nrows} rows")
+    if m.cu.device != device or m.cu.dtype != torch.int32 or (m.idx is not None and (m.idx.device != device or m.idx.dtype != torch.int32)):
+        raise RuntimeError(f"{name}: seq_map lives on {m.cu.device}, the packed stream on {device}")
 
 
 def _tm2(t, name, last):
@@ -1038,13 +1046,6 @@ def _tm2(t, name, last):
     if t.dim() != 2 or t.shape[1] != last or (t.stride(1) != 1 and last != 1):
         raise RuntimeError(f"{name}: expected (total, {last}) with the last axis contiguous (packed token-major rows)")
     return t.stride(0) if t.shape[0] > 1 else last
-
-
-def conv1d_tm_chunk_var_supported(x, conv_state):
-    """the limits of aum_conv1d_tm_chunk_var (include/aum_hip.h): packed (total >= 1, dim) rows as conv1d_tm_chunk takes them at batch 1, an
-    fp32 contiguous (nrows, dim, width <= 4) pool; outside them callers loop over the sessions through conv1d_tm_chunk / conv1d_update"""
-    return (conv_state.dim() == 3 and conv_state.dtype == torch.float32 and conv_state.is_contiguous() and conv_state.shape[0] >= 1
-            and x.dim() == 2 and x.shape[0] >= 1 and conv_state.shape[1] == x.shape[1] and conv1d_tm_supported(x.unsqueeze(0), conv_state.shape[2]))
 
 
 def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None):
@@ -1060,32 +1061,20 @@ def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=Non
     if not conv1d_tm_chunk_var_supported(x, conv_state):
         raise RuntimeError(f"conv1d_tm_chunk_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
                            f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
-    _var_common("conv1d_tm_chunk_var", seq_map, x, conv_state)
+    check_seq_map("conv1d_tm_chunk_var", seq_map, x.shape[0], conv_state.shape[0], x.device)
+    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib)
+
+
+def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib):
+    """conv1d_tm_chunk_var behind its checks: operands conv1d_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
     total, dim = x.shape
-    weight = _al16(_f32c(weight.reshape(dim, -1)))
-    bias = _al16(_f32c(bias))
-    if weight.shape[1] != conv_state.shape[2]:
-        raise RuntimeError("conv1d_tm_chunk_var: weight (dim, width) and conv_state (nrows, dim, width) disagree on the width")
-    for t in (weight, bias):
-        lib.check_tensor(t)
-    y = torch.empty((total, dim), dtype=x.dtype, device=x.device) if out is None else out
-    if y.dtype != x.dtype or y.shape != x.shape:
-        raise RuntimeError("conv1d_tm_chunk_var: out must have x's shape and dtype")
     a = ConvTmChunkVarArgs()
-    a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
-    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
+    y, _held = _conv_chunk_operands(a, "conv1d_tm_chunk_var", lib, x, conv_state, weight, bias, silu, out)
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
     a.x_ts, a.y_ts = _tm2(x, "x", dim), _tm2(y, "out", dim)
-    a.total, a.nseq, a.nrows, a.dim, a.width, a.dtype = total, len(seq_map.lens), conv_state.shape[0], dim, weight.shape[1], _DT[x.dtype]
-    a.flags = CONV_SILU if silu else 0
-    _launch(lib.c.aum_conv1d_tm_chunk_var, a, x, lib, "conv_tm_chunk_var", (len(seq_map.lens), dim, total, x.element_size()))
+    a.total, a.nseq, a.nrows = total, len(m.lens), conv_state.shape[0]
+    _launch(lib.c.aum_conv1d_tm_chunk_var, a, x, lib, "conv_tm_chunk_var", (len(m.lens), dim, total, x.element_size()))
     return y
-
-
-def scan_tm_chunk_var_supported(state, u):
-    """the limits of aum_scan_tm_chunk_var (include/aum_hip.h): an fp32 contiguous (nrows, dim, 16) pool, dim % 64 == 0, packed
-    (total >= 1, dim) activations; outside them callers loop over the sessions through scan_tm_chunk / state_update"""
-    return (state.dim() == 3 and state.dtype == torch.float32 and state.is_contiguous() and state.data_ptr() % 16 == 0 and state.shape[0] >= 1
-            and u.dim() == 2 and u.dtype in _DT and u.shape[0] >= 1 and state.shape[1] == u.shape[1] and scan_tm_supported(u.shape[1], state.shape[2]))
 
 
 def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
@@ -1102,32 +1091,100 @@ def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None,
     if not scan_tm_chunk_var_supported(state, u):
         raise RuntimeError(f"scan_tm_chunk_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
                            "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
-    _var_common("scan_tm_chunk_var", seq_map, u, state)
+    check_seq_map("scan_tm_chunk_var", seq_map, u.shape[0], state.shape[0], u.device)
+    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib)
+
+
+def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib):
+    """scan_tm_chunk_var behind its checks: operands scan_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
     total, dim = u.shape
     dstate = state.shape[2]
-    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
-        raise RuntimeError("scan_tm_chunk_var: u, delta, z, B, C must share one dtype")
-    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
-    for t in (A, D, delta_bias):
-        lib.check_tensor(t)
-    if A.shape != (dim, dstate):
-        raise RuntimeError("scan_tm_chunk_var: A must be (dim, dstate)")
-    if out is None:
-        out = torch.empty((total, dim), dtype=u.dtype, device=u.device)
-    if out.dtype != u.dtype or out.shape != u.shape:
-        raise RuntimeError("scan_tm_chunk_var: out must have u's shape and dtype")
     a = ScanTmChunkVarArgs()
+    out, _held = _scan_chunk_operands(a, "scan_tm_chunk_var", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
     a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
-    if z is not None:
-        a.z_ts = _tm2(z, "z", dim)
+    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
     a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
-    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
-    a.total, a.nseq, a.nrows, a.dim, a.dstate, a.dtype = total, len(seq_map.lens), state.shape[0], dim, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
-    _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(seq_map.lens), dim, total, dstate, u.element_size()))
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
+    a.total, a.nseq, a.nrows = total, len(m.lens), state.shape[0]
+    _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(m.lens), dim, total, dstate, u.element_size()))
     return out
+
+
+def _unit_last(t):
+    return t if t is None or t.stride(-1) == 1 or t.shape[-1] == 1 else t.contiguous()
+
+
+def _settled(ok, st, lead):
+    """the leading operand as a launch takes it -- itself, or a contiguous copy where that is what turns ok() true -- or None"""
+    lead = _unit_last(lead)
+    if ok(st, lead):
+        return lead
+    c = lead.contiguous()
+    return c if c is not lead and ok(st, c) else None
+
+
+def _advance_batch(st, rows, chunk_ok, chunk, token):
+    lead = _settled(chunk_ok, st, rows[0])
+    if lead is not None:
+        return chunk(st, lead, *[_unit_last(t) for t in rows[1:]])
+    return torch.stack([token(st, *[None if t is None else t[:, i] for t in rows]) for i in range(rows[0].shape[1])], dim=1)
+
+
+def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token):
+    """The one ladder under conv1d_stream and scan_stream: advance `cache` IN PLACE (through an fp32 copy, written back, if it is not fp32
+    contiguous) by the token-major operands `rows` ((batch, T, .) views or None; rows[0] is what the *_ok predicates look at) with the
+    first launch that takes them.  m (a SeqMap its caller checked; rows (1, total, .), cache a pool): var() on the packed rows, else a host
+    loop over the sessions (host lengths: no synchronisation), each on its pool row as without m: chunk(), else token() token by token
+    (a (batch, .) rows[0] is one token).  An operand is copied to contiguous rows only where that makes a launch take it."""
+    for t in (cache, *rows):
+        lib.check_tensor(t)
+    st = cache if cache.dtype == torch.float32 and cache.is_contiguous() else cache.float().contiguous()
+    if m is None:
+        out = token(st, *rows) if rows[0].dim() == 2 else _advance_batch(st, rows, chunk_ok, chunk, token)
+    elif m.total == 0:
+        out = rows[0].new_empty(rows[0].shape)
+    else:
+        rows2d = [None if t is None else t[0] for t in rows]
+        lead = _settled(var_ok, st, rows2d[0])
+        if lead is not None:
+            out = var(st, lead, *[_unit_last(t) for t in rows2d[1:]]).unsqueeze(0)
+        else:
+            outs, o = [], 0
+            for n, r in zip(m.lens, m.rows):
+                if n:
+                    outs.append(_advance_batch(st[r:r + 1], [None if t is None else t[:, o:o + n] for t in rows], chunk_ok, chunk, token))
+                o += n
+            out = torch.cat(outs, dim=1)
+    if st is not cache:
+        cache.copy_(st)
+    return out
+
+
+def conv1d_stream(x, conv_state, weight, bias=None, silu=True, seq_map=None, lib=None):
+    """causal_conv1d.causal_conv1d_update on token-major rows, as Mamba.step_chunk has them: x (batch, T, dim) (a view is read in place),
+    (batch, dim) one token, or with seq_map (trusted: check_seq_map is the caller's) (1, total, dim) over a pool; returns x's shape."""
+    lib = lib or get()
+    return _stream_advance(lib, conv_state, (x,), seq_map,
+                           lambda st, x: conv1d_tm_chunk_var_supported(x, st),
+                           lambda st, x: _conv1d_tm_chunk_var(x, st, weight, bias, silu, seq_map, None, lib),
+                           lambda st, x: conv1d_tm_chunk_supported(x, st),
+                           lambda st, x: conv1d_tm_chunk(x, st, weight, bias, silu, lib),
+                           lambda st, x: conv1d_update(x, st, weight, bias, silu, lib))
+
+
+def scan_stream(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None, lib=None):
+    """selective_scan_update behind its argument normalisation (operands of one dtype), what Mamba.step_chunk calls: seq_map is trusted
+    (check_seq_map is the caller's)."""
+    lib = lib or get()
+    if delta_activated:                 # delta holds softplus(raw + delta_bias) already
+        delta_bias, delta_softplus = None, False
+    return _stream_advance(lib, state, (u, delta, z, B, C), seq_map,
+                           scan_tm_chunk_var_supported,
+                           lambda st, u, dl, z, B, C: _scan_tm_chunk_var(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated,
+                                                                         seq_map, None, lib),
+                           scan_tm_chunk_supported,
+                           lambda st, u, dl, z, B, C: scan_tm_chunk(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, lib=lib),
+                           lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib))
 
 
 def dtproj_tm_supported(x_dbl, rank, w):

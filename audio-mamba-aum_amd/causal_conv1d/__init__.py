@@ -32,15 +32,6 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
     return CausalConv1dFn.apply(x, weight, bias, activation)
 
 
-def _check_seq_map(name, seq_map, total, cache):
-    if not isinstance(seq_map, aum_hip.SeqMap):
-        raise TypeError(f"{name}: seq_map must come from aum_hip.seq_map()")
-    if seq_map.total != total:
-        raise ValueError(f"{name}: seq_map describes {seq_map.total} packed tokens, got {total}")
-    if max(seq_map.rows) >= cache.shape[0]:
-        raise ValueError(f"{name}: seq_map names cache row {max(seq_map.rows)}, the pool has {cache.shape[0]} rows")
-
-
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, *, seq_map=None):
     """Streaming inference (the wheel's function of the same name, call site MS:328-334).  x (batch, dim): one token; conv_state (batch, dim,
     width) is shifted left and extended by x IN PLACE; returns act(sum(conv_state * weight, -1) + bias) in x's dtype (aum_causal_conv1d_update;
@@ -50,41 +41,15 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, *, s
     token by token otherwise.
     seq_map (extension, keyword only; aum_hip.seq_map): PACKED SESSIONS -- x (1, dim, total) holds the new tokens of several sessions behind
     one another, conv_state (nrows, dim, width) is a pool of caches and session i advances row seq_map.rows[i] by seq_map.lens[i] tokens;
-    the other rows are not touched.  One launch (aum_conv1d_tm_chunk_var) where that kernel takes the shape; otherwise a host loop over
-    the sessions through this function (the lengths are host values: no synchronisation).  Returns (1, dim, total)."""
+    the other rows are not touched.  One launch (aum_conv1d_tm_chunk_var) where that kernel takes the shape, a host loop over the sessions
+    otherwise; returns (1, dim, total).  The wheel's layout over aum_hip.conv1d_stream, which picks the launch."""
     if activation not in (None, "silu", "swish"):
         raise NotImplementedError("activation must be None, silu, or swish")
     silu = activation in ("silu", "swish")
     if seq_map is not None:
         if x.dim() != 3 or x.shape[0] != 1 or conv_state.dim() != 3:
             raise ValueError("causal_conv1d_update: with seq_map x is (1, dim, total) and conv_state the pool (nrows, dim, width)")
-        _check_seq_map("causal_conv1d_update", seq_map, x.shape[2], conv_state)
-    st = conv_state if conv_state.dtype == torch.float32 and conv_state.is_contiguous() else conv_state.float().contiguous()
-    if seq_map is not None:
-        xt = x[0].t()                                            # (total, dim) packed rows
-        if seq_map.total and not aum_hip.conv1d_tm_chunk_var_supported(xt, st):
-            xt = xt.contiguous()
-        if seq_map.total == 0:
-            out = x.new_empty(x.shape)
-        elif aum_hip.conv1d_tm_chunk_var_supported(xt, st):
-            out = aum_hip.conv1d_tm_chunk_var(xt, st, weight, bias, silu, seq_map).t().unsqueeze(0)
-        else:
-            outs, o = [], 0
-            for n, r in zip(seq_map.lens, seq_map.rows):
-                if n:
-                    outs.append(causal_conv1d_update(x[:, :, o:o + n], st[r:r + 1], weight, bias, activation))
-                o += n
-            out = torch.cat(outs, dim=2)
-    elif x.dim() == 3:
-        xt = x.transpose(1, 2)                                   # (batch, seqlen, dim)
-        if not aum_hip.conv1d_tm_chunk_supported(xt, st):        # channel-major storage or a misaligned view: token-major copy
-            xt = xt.contiguous()
-        if aum_hip.conv1d_tm_chunk_supported(xt, st):
-            out = aum_hip.conv1d_tm_chunk(xt, st, weight, bias, silu).transpose(1, 2)
-        else:
-            out = torch.stack([aum_hip.conv1d_update(x[:, :, t], st, weight, bias, silu) for t in range(x.shape[2])], dim=2)
-    else:
-        out = aum_hip.conv1d_update(x, st, weight, bias, silu)
-    if st is not conv_state:
-        conv_state.copy_(st)
-    return out
+        aum_hip.check_seq_map("causal_conv1d_update", seq_map, x.shape[2], conv_state.shape[0], x.device)
+    if x.dim() != 3:
+        return aum_hip.conv1d_stream(x, conv_state, weight, bias, silu)
+    return aum_hip.conv1d_stream(x.transpose(1, 2), conv_state, weight, bias, silu, seq_map).transpose(1, 2)

@@ -19,7 +19,6 @@ from mamba_ssm.ops.selective_scan_interface import (InProjFn, bimamba_inner_fn, 
                                                     neg_exp, selective_scan_fn)
 import mamba_ssm.ops.selective_scan_interface as ssi
 from causal_conv1d import causal_conv1d_fn, causal_conv1d_update
-from mamba_ssm.ops.selective_scan_interface import selective_scan_update
 from mamba_ssm.ops.triton.selective_state_update import selective_state_update
 
 
@@ -221,23 +220,21 @@ class Mamba(nn.Module):
         recurrent stages as one launch each (aum_conv1d_tm_chunk, aum_scan_tm_chunk; the result does not depend on how a stream is cut
         into chunks):
             xz = in_proj(h)                                                      (batch, T, 2E) token-major rows [x | z]
-            xc = causal_conv1d_update(x half in place, conv_state, w, b, silu)   T window updates
+            xc = aum_hip.conv1d_stream(x half in place, conv_state, w, b, silu)  T window updates (causal_conv1d_update, token-major)
             (dt, B, C) = x_proj(xc);  delta = dt W_dt^T                          (one fused launch where aum_xdt_tm_fwd takes the shape)
-            y = selective_scan_update(ssm_state, xc, delta, A, B, C, D, z half, dt_bias, softplus)
+            y = aum_hip.scan_stream(ssm_state, xc, delta, A, B, C, D, z half, dt_bias, softplus)        (selective_scan_update)
             out = out_proj(y)
         seq_map (aum_hip.seq_map): PACKED SESSIONS at different positions in one pass -- hidden_states (1, total, d_model) holds the new
         tokens of several sessions behind one another, the caches are pools of nrows rows, session i advances row seq_map.rows[i] by
         seq_map.lens[i] tokens (the other rows are not touched).  Only the two recurrent stages see the session boundaries
-        (aum_conv1d_tm_chunk_var, aum_scan_tm_chunk_var); the projections take the packed rows as they are."""
+        (aum_conv1d_tm_chunk_var, aum_scan_tm_chunk_var, the map checked here for both); the projections take the packed rows as they are."""
         import aum_hip
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
         if seq_map is not None:
-            if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or hidden_states.shape[1] != seq_map.total:
-                raise ValueError(f"step_chunk(seq_map=) takes hidden_states of shape (1, total = {seq_map.total}, d_model)")
-            if conv_state.shape[0] != ssm_state.shape[0] or max(seq_map.rows) >= conv_state.shape[0]:
-                raise ValueError(f"step_chunk(seq_map=): cache pools of {conv_state.shape[0]} / {ssm_state.shape[0]} rows, seq_map names row "
-                                 f"{max(seq_map.rows)}")
+            if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or conv_state.shape[0] != ssm_state.shape[0]:
+                raise ValueError(f"step_chunk(seq_map=): hidden_states (1, total, d_model), pools of one size, not {conv_state.shape[0]} / {ssm_state.shape[0]} rows")
+            aum_hip.check_seq_map("step_chunk", seq_map, hidden_states.shape[1], conv_state.shape[0], hidden_states.device)
             if seq_map.total == 0:
                 return hidden_states.new_empty(hidden_states.shape), conv_state, ssm_state
         elif hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
@@ -246,8 +243,8 @@ class Mamba(nn.Module):
         E, N, R = self.d_inner, self.d_state, self.dt_rank
         xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
         x, z = xz[..., :E], xz[..., E:]
-        xc = causal_conv1d_update(x.transpose(1, 2), conv_state, self.conv1d.weight.view(E, self.d_conv), self.conv1d.bias,
-                                  self.activation, seq_map=seq_map).transpose(1, 2)     # (batch, T, E) rows again
+        xc = aum_hip.conv1d_stream(x, conv_state, self.conv1d.weight.view(E, self.d_conv), self.conv1d.bias,
+                                   self.activation in ("silu", "swish"), seq_map)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         xc2 = xc.reshape(batch * T, E)
@@ -262,9 +259,8 @@ class Mamba(nn.Module):
             delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
             proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
         proj = proj.view(batch, T, -1)
-        y = selective_scan_update(ssm_state, xc, delta.view(batch, T, E), A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], self.D, z=z,
-                                  delta_bias=None if activated else self.dt_proj.bias, delta_softplus=not activated,
-                                  delta_activated=activated, seq_map=seq_map)
+        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], self.D, z,
+                                self.dt_proj.bias, True, activated, seq_map)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
 

@@ -1170,40 +1170,14 @@ def selective_scan_update(state, u, delta, A, B, C, D=None, z=None, delta_bias=N
     seq_map (extension, keyword only; aum_hip.seq_map): PACKED SESSIONS -- the operands are (1, total, .) with the new tokens of several
     sessions behind one another, state (nrows, dim, dstate) is a pool of caches and session i advances row seq_map.rows[i] by
     seq_map.lens[i] tokens; the other rows are not touched.  One launch (aum_scan_tm_chunk_var) where that kernel takes the shape;
-    otherwise a host loop over the sessions through this function (the lengths are host values: no synchronisation)."""
+    otherwise a host loop over the sessions.  Argument normalisation over aum_hip.scan_stream, which picks the launch."""
     if seq_map is not None:
         if u.dim() != 3 or u.shape[0] != 1 or state.dim() != 3:
             raise ValueError("selective_scan_update: with seq_map the operands are (1, total, .) and state the pool (nrows, dim, dstate)")
-        from causal_conv1d import _check_seq_map
-        _check_seq_map("selective_scan_update", seq_map, u.shape[1], state)
-    st = state if state.dtype == torch.float32 and state.is_contiguous() else state.float().contiguous()
+        aum_hip.check_seq_map("selective_scan_update", seq_map, u.shape[1], state.shape[0], u.device)
     dty = u.dtype
     delta, B, C = delta.to(dty), B.to(dty), C.to(dty)
     z = None if z is None else z.to(dty)
     if u.dim() != 3 or delta.shape != u.shape or B.dim() != 3 or B.shape != C.shape or B.shape[:2] != u.shape[:2] or (z is not None and z.shape != u.shape):
         raise RuntimeError("selective_scan_update: u, delta, z (batch, seqlen, dim); B, C (batch, seqlen, dstate)")
-    fix = lambda t: t if t is None or t.stride(2) == 1 or t.shape[2] == 1 else t.contiguous()
-    if seq_map is not None and seq_map.total == 0:
-        out = u.new_empty(u.shape)
-    elif seq_map is not None and aum_hip.scan_tm_chunk_var_supported(st, u[0]):
-        r0 = lambda t: None if t is None else fix(t)[0]
-        out = aum_hip.scan_tm_chunk_var(st, r0(u), r0(delta), A, r0(B), r0(C), D, r0(z), None if delta_activated else delta_bias,
-                                        delta_softplus and not delta_activated, delta_activated, seq_map).unsqueeze(0)
-    elif seq_map is not None:
-        outs, o = [], 0
-        for n, r in zip(seq_map.lens, seq_map.rows):
-            if n:
-                sl = lambda t: None if t is None else t[:, o:o + n]
-                outs.append(selective_scan_update(st[r:r + 1], sl(u), sl(delta), A, sl(B), sl(C), D, sl(z), delta_bias, delta_softplus, delta_activated))
-            o += n
-        out = torch.cat(outs, dim=1)
-    elif aum_hip.scan_tm_chunk_supported(st, u):
-        out = aum_hip.scan_tm_chunk(st, fix(u), fix(delta), A, fix(B), fix(C), D, fix(z), None if delta_activated else delta_bias,
-                                    delta_softplus and not delta_activated, delta_activated)
-    else:
-        bias, sp = (None, False) if delta_activated else (delta_bias, delta_softplus)
-        out = torch.stack([aum_hip.state_update(st, u[:, t], delta[:, t], A, B[:, t], C[:, t], D, None if z is None else z[:, t], bias, sp)
-                           for t in range(u.shape[1])], dim=1)
-    if st is not state:
-        state.copy_(st)
-    return out
+    return aum_hip.scan_stream(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map)

@@ -130,6 +130,31 @@ def test_shims_take_packed_sessions_and_fall_back_per_session(emu_as_product):
         causal_conv1d_update(torch.zeros(1, 64, 6), torch.zeros(5, 64, 4), torch.zeros(64, 4), seq_map=aum_hip.seq_map(lens, (0, 1, 2, 5), device="cpu"))
 
 
+def test_bad_map_raises_at_every_entry_and_is_checked_once(lib, emu_as_product, monkeypatch):
+    """a direct aum_hip.*_var call with a map that is no SeqMap, of another stream or naming a row outside the pool raises what it always
+    raised and leaves the pool alone; Mamba.step_chunk(seq_map=) checks its map once for both recurrent stages"""
+    from mamba_ssm.modules.mamba_simple import Mamba
+    dim = 64
+    u, bc, A, w = torch.randn(3, dim), torch.randn(3, 16), -torch.rand(dim, 16), torch.randn(dim, 4)
+    for bad, exc in (((1, 2), TypeError), (aum_hip.seq_map([1, 3], None, device="cpu"), ValueError),
+                     (aum_hip.seq_map([1, 2], [0, 2], device="cpu"), ValueError)):
+        st, cs = torch.randn(2, dim, 16), torch.randn(2, dim, 4)
+        st0, cs0 = st.clone(), cs.clone()
+        with pytest.raises(exc):
+            aum_hip.scan_tm_chunk_var(st, u, u, A, bc, bc, seq_map=bad, lib=lib)
+        with pytest.raises(exc):
+            aum_hip.conv1d_tm_chunk_var(u, cs, w, seq_map=bad, lib=lib)
+        assert torch.equal(st, st0) and torch.equal(cs, cs0)
+    calls = []
+    real = aum_hip.check_seq_map
+    monkeypatch.setattr(aum_hip, "check_seq_map", lambda *a: (calls.append(a[0]), real(*a))[1])
+    m = Mamba(32, layer_idx=0, bimamba_type="none").eval()
+    conv_pool, ssm_pool = m.allocate_inference_cache(3, 0, dtype=torch.float32)
+    with torch.no_grad():
+        m.step_chunk(torch.randn(1, 5, 32), conv_pool, ssm_pool, seq_map=aum_hip.seq_map([2, 3], [2, 0], device="cpu"))
+    assert calls == ["step_chunk"]
+
+
 def test_mamba_step_chunk_takes_packed_sessions(emu_as_product):
     pc.check_mamba_pool(32, "cpu")          # d_inner = 64: the var kernels
 
