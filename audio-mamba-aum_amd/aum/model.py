@@ -243,16 +243,32 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches, seq_map=None):
+    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
-        (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk)"""
+        (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
+        are read and not written"""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
                                            residual_in_fp32=True, eps=layer.norm.eps)
             conv_state, ssm_state = layer_caches[i]
-            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map)
+            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit)
         return hidden, residual
+
+    def _read_in_place(self, cls, cache, rows):
+        """stream_read without copies: the cls row of each session through the blocks ON the caches themselves, as one-token sessions on
+        the rows read with nothing written back.  None where a block does not take the one-launch path (Mamba.step_chunk(commit=False)
+        says so before it touches anything, and an uncommitted pass leaves no trace: the caller reads from copies instead)."""
+        import aum_hip
+        n = cls.shape[0]
+        if cls.device.type != "cuda" or not aum_hip.debug.stream_fused:
+            return None
+        smap = aum_hip.fixed_seq_map(n, 1, cls.device) if rows is None else aum_hip.seq_map((1,) * n, rows, device=cls.device)
+        try:
+            hidden, residual = self._stream_layers(cls.reshape(1, n, -1), cache["layers"], smap, commit=False)
+        except NotImplementedError:
+            return None
+        return hidden.reshape(n, 1, -1), residual.reshape(n, 1, -1)
 
     # ---- many sessions at different positions: a pool of caches, one pass per push -----------------
     def allocate_stream_pool(self, sessions, dtype=None):
@@ -361,23 +377,30 @@ class AudioMamba(nn.Module):
 
     @torch.no_grad()
     def stream_read(self, cache, return_features=False, sessions=None):
-        """Logits if the clip ended now: the cls row run through the blocks from a COPY of the caches (the session is not advanced),
-        then the final norm and the head.  After all columns of a clip have been pushed this is model(spec).  sessions: read those rows
-        only (gathered copies), (len(sessions), ...) in that order; None: every row (of a pool too)."""
+        """Logits if the clip ended now: the cls row run through the blocks from the caches, which are NOT advanced (read in place where
+        every block takes the one-launch path, Mamba.step_chunk(commit=False); otherwise from a copy -- also where a row is named
+        twice), then the final norm and the head.  After all columns of a clip have been pushed this is model(spec).  sessions: read
+        those rows only, (len(sessions), ...) in that order; None: every row (of a pool too)."""
+        import aum_hip
         self._check_streamable()
-        if sessions is None:
-            copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
-            n = cache["batch"]
-        else:
+        rows = None
+        if sessions is not None:
             rows = self._check_sessions("stream_read", cache, sessions, writes=False)
             if not rows:
                 raise ValueError("stream_read: at least one session")
-            idx = torch.tensor(rows, dtype=torch.int64)
-            copies = {i: (c.index_select(0, idx.to(c.device)), s.index_select(0, idx.to(s.device))) for i, (c, s) in cache["layers"].items()}
-            n = len(rows)
+        n = cache["batch"] if rows is None else len(rows)
         pe = self.pos_embed.pos_embed
         cls = (self.cls_token + pe[:, :1]).expand(n, -1, -1)
-        hidden, residual = self._stream_layers(cls, copies)
+        done = self._read_in_place(cls, cache, rows) if rows is None or len(set(rows)) == len(rows) else None
+        if done is not None:
+            hidden, residual = done
+        else:
+            if rows is None:
+                copies = {i: (c.clone(), s.clone()) for i, (c, s) in cache["layers"].items()}
+            else:
+                idx = torch.tensor(rows, dtype=torch.int64)
+                copies = {i: (c.index_select(0, idx.to(c.device)), s.index_select(0, idx.to(s.device))) for i, (c, s) in cache["layers"].items()}
+            hidden, residual = self._stream_layers(cls, copies)
         f = rms_norm_fn(hidden[:, 0], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual[:, 0],
                         prenorm=False, residual_in_fp32=True)
         return f if return_features else self.head(f)

@@ -46,6 +46,7 @@ class _Debug:
         self.proj_splits = 0       # token splits of the projection weight-gradient kernel (0: aum_proj_bwd_weight_splits)
         self.torch_sums = False    # partial results summed by torch.sum instead of aum_sum_rows
         self.sums_one_by_one = False   # sum_rows_multi: one aum_sum_rows launch per partial set (the launches of rounds 2-4; A/B)
+        self.stream_fused = True   # Mamba.step_chunk: conv + x/dt + scan in one launch (stream_block) where it takes the shapes
         if os.environ.get("AUM_DEBUG") == "1":
             self.ablate = int(os.environ.get("AUM_ABLATE", "0"))
             self.rowpair = os.environ.get("AUM_SCAN_ROWPAIR") == "1"
@@ -54,6 +55,7 @@ class _Debug:
             self.no_lane_ckpt = os.environ.get("AUM_SCAN_NO_LANE_CKPT") == "1"
             self.torch_sums = os.environ.get("AUM_TORCH_SUMS") == "1"
             self.sums_one_by_one = os.environ.get("AUM_SUMS_ONE_BY_ONE") == "1"
+            self.stream_fused = os.environ.get("AUM_STREAM_FUSED", "1") != "0"
 
 
 debug = _Debug()
@@ -212,6 +214,14 @@ class ScanTmChunkVarArgs(C.Structure):
                 + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "dstate", "dtype")] + [("flags", _u32)])
 
 
+class StreamBlockArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("x", "z", "conv_state", "state", "conv_weight", "conv_bias", "wx", "wdt", "A", "D", "delta_bias", "y", "scratch",
+                                    "cu_seqlens", "state_indices")]
+                + [(n, _i64) for n in ("x_ts", "z_ts", "y_ts", "scratch_bytes")]
+                + [(n, _i32) for n in ("total", "nseq", "nrows", "max_len", "dim", "width", "dstate", "rank", "ncols", "ldwx", "ldwdt", "dtype")]
+                + [("flags", _u32)])
+
+
 class DtProjArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "w", "out")] + [("ntok", _i64)] + [(n, _i32) for n in ("dim", "rank", "ldx", "ldw", "ldo", "dtype")])
 
@@ -229,7 +239,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_proj_fwd", "aum_proj_bwd_data",
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
-    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var")}
+    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -241,6 +251,7 @@ _SIGNATURES.update({
     "aum_selftest_wave_scan": ([_vp, _vp, C.c_int, _vp], C.c_int), "aum_selftest_wave_sum32": ([_vp, _vp, _vp], C.c_int),
     "aum_sum_rows": ([_vp, _vp, _i64, _i64, _i64, _i32, _vp], C.c_int), "aum_sum_rows_multi": ([_vp, _i32, _vp], C.c_int),
     "aum_cast_bank": ([_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp], C.c_int),
+    "aum_stream_block_scratch_bytes": ([_i32] * 3, _i64), "aum_stream_block_max_len": ([], _i32),
 })
 EXPORTS = list(_SIGNATURES)
 
@@ -1185,6 +1196,89 @@ def scan_stream(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
                            scan_tm_chunk_supported,
                            lambda st, u, dl, z, B, C: scan_tm_chunk(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, lib=lib),
                            lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib))
+
+
+# ---- the block's recurrent middle in one launch (aum_stream_block_tm): conv -> x/dt projections -> scan on packed sessions
+STREAM_NO_COMMIT = 1
+STREAM_BLOCK_MAX_T = 128        # tokens per session and call (aum_stream_block_max_len)
+_fixed_maps = {}
+
+
+def fixed_seq_map(batch, length, device):
+    """The SeqMap of a fixed batch -- `batch` sessions of `length` rows on cache rows 0 .. batch - 1 -- uploaded once per (batch, length, device)"""
+    key = (int(batch), int(length), torch.device(device))
+    m = _fixed_maps.get(key)
+    if m is None:
+        if len(_fixed_maps) > 64:
+            _fixed_maps.clear()
+        m = _fixed_maps[key] = seq_map([length] * batch, device=device)
+    return m
+
+
+def stream_block_supported(x, z, conv_state, state, plan, max_len=1):
+    """the limits of aum_stream_block_tm (include/aum_hip.h): x, z (total >= 1, dim) packed 16-bit rows (the halves of the in_proj rows),
+    fp32 contiguous pools (nrows, dim, 4) / (nrows, dim, 16), the shapes xdt_tm_supported takes, sessions of at most STREAM_BLOCK_MAX_T rows,
+    a plan (Mamba.stream_params) in x's dtype; outside them callers use the three launches"""
+    if not (x.dim() == 2 and z.dim() == 2 and x.shape == z.shape and x.shape[0] >= 1 and x.dtype == z.dtype and x.dtype in (torch.bfloat16, torch.float16)):
+        return False
+    dim = x.shape[1]
+    if not (plan.w_x.dtype == x.dtype and plan.w_dt.dtype == x.dtype and 1 <= max_len <= STREAM_BLOCK_MAX_T):
+        return False
+    ok_t = lambda t: t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
+    rank = plan.w_dt.shape[1]
+    return (ok_t(x) and ok_t(z) and xdt_tm_supported(x, plan.w_x, plan.w_dt) and rank + 32 <= plan.w_x.shape[0]
+            and conv_state.dim() == 3 and conv_state.dtype == torch.float32 and conv_state.is_contiguous() and conv_state.shape[1:] == (dim, 4)
+            and state.dim() == 3 and state.dtype == torch.float32 and state.is_contiguous() and state.shape[1:] == (dim, 16)
+            and state.shape[0] == conv_state.shape[0] >= 1 and state.data_ptr() % 16 == 0 and conv_state.data_ptr() % 16 == 0
+            and plan.conv_w.shape == (dim, 4) and plan.A.shape == (dim, 16))
+
+
+def stream_block(xz_x, z, conv_state, state, plan, seq_map=None, commit=True, out=None, lib=None):
+    """Conv (SiLU) from the carried window -> x_proj, dt_proj (dt_bias and softplus once) -> selective scan (D, z gate) from the carried
+    state, in ONE launch (aum_stream_block_tm): xz_x, z the two halves of the in_proj rows -- (total, dim) packed rows with seq_map
+    (trusted: check_seq_map is the caller's), or (batch, T, dim) views of one (batch, T, 2 dim) tensor, session b on cache row b.
+    conv_state (nrows, dim, 4) / state (nrows, dim, 16): fp32 pools advanced IN PLACE; commit=False: read and not written.  plan:
+    Mamba.stream_params().  Bit for bit conv1d_tm_chunk_var -> xdt_tm_fwd(delta_softplus) -> scan_tm_chunk_var(delta_activated).
+    Returns y in xz_x's shape and dtype.  No device synchronisation."""
+    lib = lib or get()
+    shape = xz_x.shape
+    if xz_x.dim() == 3:
+        batch, T, dim = shape
+        if seq_map is None:
+            seq_map = fixed_seq_map(batch, T, xz_x.device)
+        x2 = xz_x.as_strided((batch * T, dim), (xz_x.stride(1), 1)) if batch == 1 or xz_x.stride(0) == T * xz_x.stride(1) else None
+        z2 = z.as_strided((batch * T, dim), (z.stride(1), 1)) if batch == 1 or z.stride(0) == T * z.stride(1) else None
+        if x2 is None or z2 is None:
+            raise RuntimeError("stream_block: (batch, T, dim) operands must be uniformly strided over (batch, T)")
+    else:
+        x2, z2 = xz_x, z
+        if seq_map is None:
+            seq_map = fixed_seq_map(1, x2.shape[0], x2.device)
+    for t in (x2, z2, conv_state, state, out, plan.conv_w, plan.w_x):
+        lib.check_tensor(t)
+    max_len = max(seq_map.lens)
+    if not stream_block_supported(x2, z2, conv_state, state, plan, max_len):
+        raise RuntimeError(f"stream_block: unsupported operands x {tuple(x2.shape)} {x2.dtype} strides {x2.stride()}, pools "
+                           f"{tuple(conv_state.shape)} / {tuple(state.shape)}, longest session {max_len}")
+    total, dim = x2.shape
+    y = torch.empty((total, dim), dtype=x2.dtype, device=x2.device) if out is None else out.reshape(total, dim)
+    if y.dtype != x2.dtype or y.stride(1) != 1 or (out is not None and y.data_ptr() != out.data_ptr()):
+        raise RuntimeError("stream_block: out must have x's shape and dtype, rows contiguous")
+    ncols = plan.w_x.shape[0]
+    nbytes = int(lib.c.aum_stream_block_scratch_bytes(total, dim, ncols))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+    a = StreamBlockArgs()
+    a.x, a.z, a.conv_state, a.state, a.y, a.scratch = _ptr(x2), _ptr(z2), _ptr(conv_state), _ptr(state), _ptr(y), _ptr(scratch)
+    a.conv_weight, a.conv_bias, a.wx, a.wdt = _ptr(plan.conv_w), _ptr(plan.conv_b), _ptr(plan.w_x), _ptr(plan.w_dt)
+    a.A, a.D, a.delta_bias = _ptr(plan.A), _ptr(plan.D), _ptr(plan.dt_bias)
+    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
+    a.x_ts, a.z_ts, a.y_ts, a.scratch_bytes = x2.stride(0), z2.stride(0), y.stride(0), nbytes
+    a.total, a.nseq, a.nrows, a.max_len = total, len(seq_map.lens), conv_state.shape[0], max_len
+    a.dim, a.width, a.dstate, a.rank, a.ncols = dim, 4, 16, plan.w_dt.shape[1], ncols
+    a.ldwx, a.ldwdt, a.dtype = plan.w_x.stride(0), plan.w_dt.stride(0), _DT[x2.dtype]
+    a.flags = 0 if commit else STREAM_NO_COMMIT
+    _launch(lib.c.aum_stream_block_tm, a, x2, lib, "stream_block", (len(seq_map.lens), dim, total))
+    return y.view(shape)
 
 
 def dtproj_tm_supported(x_dbl, rank, w):

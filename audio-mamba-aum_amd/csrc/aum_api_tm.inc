@@ -4,6 +4,7 @@
 #include "scan_tm_kernels.h"
 #include "conv_tm_kernels.h"
 #include "stream_tm_kernels.h"
+#include "stream_block_kernels.h"
 
 namespace aum {
 
@@ -758,5 +759,98 @@ AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) 
         case AUM_BF16: return scancv_dispatch_t<bf16_t>(k, s);
         default: return scancv_dispatch_t<f16_t>(k, s);
     }
+}
+
+// ---- conv -> x/dt projections -> scan of packed sessions in one launch (stream_block_kernels.h) ----
+#ifdef AUM_EMU
+// the operands as the lane-array build's three entry points take them: its aum_xdt_tm_fwd is a plain loop that writes the raw product, so
+// the bias and the softplus are the scan's here (the same function of the same values, rounded in another place than on the device)
+static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumXdtArgs& g, AumScanTmChunkVarArgs& k) {
+    const SbScratch so = sb_scratch(a.total, a.dim, a.ncols);
+    char* sc = static_cast<char*>(a.scratch);
+    void *xc = sc + so.xc * 2, *delta = sc + so.delta * 2, *x_dbl = sc + so.x_dbl * 2;
+    c = {};
+    c.x = a.x; c.conv_state = a.conv_state; c.weight = a.conv_weight; c.bias = a.conv_bias; c.y = xc;
+    c.cu_seqlens = a.cu_seqlens; c.state_indices = a.state_indices;
+    c.x_ts = a.x_ts; c.y_ts = a.dim;
+    c.total = a.total; c.nseq = a.nseq; c.nrows = a.nrows; c.dim = a.dim; c.width = a.width; c.dtype = a.dtype; c.flags = AUM_CONV_SILU;
+    g = {};
+    g.u = xc; g.wx = a.wx; g.wdt = a.wdt; g.x_dbl = x_dbl; g.delta = delta;
+    g.ntok = a.total; g.dim = a.dim; g.rank = a.rank; g.ncols = a.ncols;
+    g.ldu = a.dim; g.ldwx = a.ldwx; g.ldwdt = a.ldwdt; g.ldx = a.ncols; g.ldd = a.dim; g.dtype = a.dtype;
+    g.delta_bias = nullptr; g.flags = 0;
+    k = {};
+    k.u = xc; k.delta = delta; k.z = a.z;
+    k.B = static_cast<char*>(x_dbl) + (int64_t)a.rank * 2; k.C = static_cast<char*>(x_dbl) + (int64_t)(a.rank + SCANT_N) * 2;
+    k.A = a.A; k.D = a.D; k.delta_bias = a.delta_bias; k.state = a.state; k.out = a.y;
+    k.cu_seqlens = a.cu_seqlens; k.state_indices = a.state_indices;
+    k.u_ts = a.dim; k.delta_ts = a.dim; k.z_ts = a.z_ts; k.B_ts = a.ncols; k.C_ts = a.ncols; k.out_ts = a.y_ts;
+    k.total = a.total; k.nseq = a.nseq; k.nrows = a.nrows; k.dim = a.dim; k.dstate = a.dstate; k.dtype = a.dtype;
+    k.flags = AUM_SCAN_SOFTPLUS;
+}
+#else
+template <class T, bool BF16> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
+    const dim3 grid((unsigned)a.nseq), block(SB_NW * 64);
+    const bool one = a.rank <= 32, base = a.ncols == XDT_COLS;
+    if (base && one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS>), grid, block, 0, s, a);
+    else if (base) hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS>), grid, block, 0, s, a);
+    else if (one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS_SMALL>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS_SMALL>), grid, block, 0, s, a);
+    return launch_status();
+}
+#endif
+AUM_API int32_t aum_stream_block_max_len(void) { return SB_MAX_T; }
+AUM_API int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32_t ncols) {
+    if (total <= 0 || dim <= 0 || ncols <= 0) return 0;
+    return sb_scratch(total, dim, ncols).total * 2;
+}
+AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
+    if (!a || !a->x || !a->z || !a->conv_state || !a->state || !a->conv_weight || !a->wx || !a->wdt || !a->A || !a->y || !a->scratch) return AUM_E_NULL;
+    int err = 0;
+    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    if (a->dim <= 0 || a->width <= 0 || a->dstate <= 0 || a->rank <= 0 || a->ncols <= 0 || a->max_len <= 0 || a->ldwx < a->dim || a->ldwdt < a->rank)
+        return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (a->dtype == AUM_F32) return AUM_E_DTYPE;                  // the projections run on the 16-bit matrix pipe only
+    if (a->flags & ~AUM_STREAM_NO_COMMIT) return AUM_E_UNSUPPORTED;
+    if (a->max_len > SB_MAX_T) return AUM_E_UNSUPPORTED;
+    if (a->width != CONVT_W || a->dstate != SCANT_N || !scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
+    if ((a->ncols != XDT_COLS && a->ncols != XDT_COLS_SMALL) || a->rank % 8 || a->rank > 64 || a->rank + 2 * SCANT_N > a->ncols || a->dim % 256 ||
+        a->dim > XDT_MAX_DIM || a->ldwx % 8 || a->ldwdt % 8)
+        return AUM_E_UNSUPPORTED;
+    if (a->x_ts < a->dim || a->z_ts < a->dim || a->y_ts < a->dim || ((a->x_ts | a->z_ts | a->y_ts) & 7)) return AUM_E_UNSUPPORTED;
+    {
+        const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->z | (uintptr_t)a->y | (uintptr_t)a->scratch | (uintptr_t)a->conv_weight | (uintptr_t)a->conv_bias |
+                               (uintptr_t)a->wx | (uintptr_t)a->wdt | (uintptr_t)a->A | (uintptr_t)a->D | (uintptr_t)a->delta_bias | (uintptr_t)a->state |
+                               (uintptr_t)a->conv_state;
+        if (ptrs & 15) return AUM_E_UNSUPPORTED;
+        if (a->x == a->y) return AUM_E_UNSUPPORTED;
+        const int64_t lim = ((int64_t)1 << 31) - 1;               // row offsets inside a sequence are 32-bit byte cursors
+        const int64_t ts = a->x_ts > a->z_ts ? (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) : (a->z_ts > a->y_ts ? a->z_ts : a->y_ts);
+        if ((ts + a->dim) * 2 * a->total > lim || (int64_t)a->nseq > lim) return AUM_E_UNSUPPORTED;
+    }
+    if (a->scratch_bytes < aum_stream_block_scratch_bytes(a->total, a->dim, a->ncols)) return AUM_E_WORKSPACE;
+#ifdef AUM_EMU
+    // the lane-array build has no matrix pipe: the three host entry points behind one another on the same operands.
+    // AUM_STREAM_NO_COMMIT: the pools are advanced in copies.
+    AumConvTmChunkVarArgs c;
+    AumXdtArgs g;
+    AumScanTmChunkVarArgs k;
+    sb_split(*a, c, g, k);
+    std::vector<float> cw, sw;
+    if (a->flags & AUM_STREAM_NO_COMMIT) {
+        cw.assign(a->conv_state, a->conv_state + (int64_t)a->nrows * a->dim * a->width);
+        sw.assign(a->state, a->state + (int64_t)a->nrows * a->dim * a->dstate);
+        c.conv_state = cw.data();
+        k.state = sw.data();
+    }
+    int rc = aum_conv1d_tm_chunk_var(&c, stream);
+    if (rc == AUM_OK) rc = aum_xdt_tm_fwd(&g, stream);
+    if (rc == AUM_OK) rc = aum_scan_tm_chunk_var(&k, stream);
+    return rc;
+#else
+    aum_stream_t s = (aum_stream_t)stream;
+    return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true>(*a, s) : sb_launch<f16_t, false>(*a, s);
+#endif
 }
 #endif

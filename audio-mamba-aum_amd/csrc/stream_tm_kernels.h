@@ -41,9 +41,10 @@ struct ConvcOps {
     int dim, width;
 };
 
-// unit = (sequence, block of 64 * V channels): L >= 1 rows at x / y (row stride x_ts / y_ts elements), the sequence's cache row `win`
+// unit = (sequence, block of 64 * V channels): L >= 1 rows at x / y (row stride x_ts / y_ts elements), the sequence's cache row `win`.
+// commit == false (aum_stream_block_tm with AUM_STREAM_NO_COMMIT): the cache row is read and not written -- the exit stores are skipped
 template <class T, bool SILU>
-AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb) {
+AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb, bool commit = true) {
     constexpr int V = convt_vec<T, false>(), NP = V / 2, ES = (int)sizeof(T), W = CONVT_W;
     AumConvTmArgs s = {};
     s.weight = a.weight;
@@ -125,6 +126,7 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
         comp_blk(itb + STREAM_UB, rb);
     }
     // exit: conv_state[j] = input L - width + j = row 4 - width + j
+    if (!commit) return;
     AUM_UNROLL
     for (int i = 0; i < W; ++i) {
         const int j = a.width - W + i;
@@ -186,9 +188,9 @@ template <class T> struct ScancSeq {
 };
 
 // unit = (sequence, group of 64 channels from e0).  SP: delta = softplus(delta + bias); otherwise delta + bias (an activated delta comes
-// with bias == NULL: the launcher drops it).
+// with bias == NULL: the launcher drops it).  commit == false: the state row is read and not written (the exit stores are skipped).
 template <class T, bool SP, bool HAS_Z>
-AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0) {
+AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true) {
     constexpr int N = SCANT_N, ES = (int)sizeof(T);
     const int L = q.len;
     const vi lane = lane_id();
@@ -287,6 +289,7 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0) {
         comp_blk(itb + STREAM_UB, rb);
     }
     // exit state
+    if (!commit) return;
     AUM_UNROLL
     for (int i = 0; i < N / 4; ++i) {
         const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};

@@ -8,6 +8,7 @@ result (MS:229-246); single-token decoding (`step`, inference caches, MS:313-400
 (bimamba_type="none") as the reference's element-wise composition -- AuM itself never passes inference_params
 (MM:620-622).
 """
+import collections
 import contextlib
 import math
 
@@ -20,6 +21,11 @@ from mamba_ssm.ops.selective_scan_interface import (InProjFn, bimamba_inner_fn, 
 import mamba_ssm.ops.selective_scan_interface as ssi
 from causal_conv1d import causal_conv1d_fn, causal_conv1d_update
 from mamba_ssm.ops.triton.selective_state_update import selective_state_update
+
+
+# What streaming inference reads of a block's parameters, converted ONCE (Mamba.stream_params): conv_w (E, width) / conv_b fp32 contiguous and
+# 16-byte aligned, A = -exp(A_log) (E, N), D, dt_bias fp32, w_x = x_proj.weight and w_dt = dt_proj.weight in the working 16-bit (or fp32) dtype.
+StreamParams = collections.namedtuple("StreamParams", "conv_w conv_b A D dt_bias w_x w_dt dtype")
 
 
 class Mamba(nn.Module):
@@ -214,20 +220,50 @@ class Mamba(nn.Module):
                                    dt_softplus=True)
         return self.out_proj(y).unsqueeze(1), conv_state, ssm_state
 
-    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None):
+    def _stream_sources(self):
+        return (self.conv1d.weight, self.conv1d.bias, self.A_log, self.D, self.dt_proj.bias, self.x_proj.weight, self.dt_proj.weight)
+
+    @torch.no_grad()
+    def stream_params(self, dtype=None):
+        """The parameters as step_chunk reads them (StreamParams), converted once and cached: a hop through 24 blocks otherwise spends
+        144 launches on fp32 copies and 48 on rebuilding A = -exp(A_log) (profiles/r07_stream_hop.txt).  dtype: the working dtype of the
+        activations (default: in_proj.weight's).  The cache is keyed on every source parameter's identity, _version, dtype and device and
+        on dtype: an optimizer step, load_state_dict, .to() or .half() rebuild it, nothing else does.  A write through `p.data` does not
+        move `_version`: write under torch.no_grad() instead, as the optimizers do, or call invalidate_stream_params() behind such a
+        write.  The tensors are shared between calls: do not write to them."""
+        import aum_hip
+        dtype = self.in_proj.weight.dtype if dtype is None else dtype
+        key = (dtype,) + tuple(None if p is None else (id(p), p._version, p.dtype, p.device) for p in self._stream_sources())
+        hit = self.__dict__.get("_stream_params")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        E = self.d_inner
+        plan = StreamParams(aum_hip._al16(aum_hip._f32c(self.conv1d.weight.reshape(E, -1))), aum_hip._al16(aum_hip._f32c(self.conv1d.bias)),
+                            -torch.exp(self.A_log.float()), aum_hip._f32c(self.D), aum_hip._f32c(self.dt_proj.bias),
+                            self.x_proj.weight.detach().to(dtype), self.dt_proj.weight.detach().to(dtype), dtype)
+        self.__dict__["_stream_params"] = (key, plan)
+        return plan
+
+    def invalidate_stream_params(self):
+        """drop the cached stream_params(): the next call converts the parameters again (behind a write the key cannot see: `p.data`)"""
+        self.__dict__.pop("_stream_params", None)
+
+    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True):
         """T >= 1 tokens of streaming inference for the causal block in one pass: (batch, T, d_model) in, (batch, T, d_model) out, the
-        caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the two
-        recurrent stages as one launch each (aum_conv1d_tm_chunk, aum_scan_tm_chunk; the result does not depend on how a stream is cut
-        into chunks):
+        caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the
+        recurrent middle as ONE launch where aum_hip.stream_block takes the shapes (16-bit activations, fp32 caches, the widths of
+        aum_xdt_tm_fwd, at most 128 tokens per session), else as the ladder (the result does not depend on how a stream is cut into chunks):
             xz = in_proj(h)                                                      (batch, T, 2E) token-major rows [x | z]
             xc = aum_hip.conv1d_stream(x half in place, conv_state, w, b, silu)  T window updates (causal_conv1d_update, token-major)
             (dt, B, C) = x_proj(xc);  delta = dt W_dt^T                          (one fused launch where aum_xdt_tm_fwd takes the shape)
             y = aum_hip.scan_stream(ssm_state, xc, delta, A, B, C, D, z half, dt_bias, softplus)        (selective_scan_update)
             out = out_proj(y)
+        Both give the same bits.  The per-call parameter conversions come from stream_params() on every path.
         seq_map (aum_hip.seq_map): PACKED SESSIONS at different positions in one pass -- hidden_states (1, total, d_model) holds the new
         tokens of several sessions behind one another, the caches are pools of nrows rows, session i advances row seq_map.rows[i] by
-        seq_map.lens[i] tokens (the other rows are not touched).  Only the two recurrent stages see the session boundaries
-        (aum_conv1d_tm_chunk_var, aum_scan_tm_chunk_var, the map checked here for both); the projections take the packed rows as they are."""
+        seq_map.lens[i] tokens (the other rows are not touched).  Only the recurrent stages see the session boundaries (the map checked
+        here, once); the projections take the packed rows as they are.
+        commit=False: the caches are read and not written (the one-launch path only: NotImplementedError elsewhere)."""
         import aum_hip
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
@@ -243,26 +279,43 @@ class Mamba(nn.Module):
         E, N, R = self.d_inner, self.d_state, self.dt_rank
         xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
         x, z = xz[..., :E], xz[..., E:]
-        xc = aum_hip.conv1d_stream(x, conv_state, self.conv1d.weight.view(E, self.d_conv), self.conv1d.bias,
-                                   self.activation in ("silu", "swish"), seq_map)
+        plan = self.stream_params(xz.dtype)
+        if self.stream_block_ok(xz, conv_state, ssm_state, plan, seq_map):
+            y = aum_hip.stream_block(x if seq_map is None else x[0], z if seq_map is None else z[0], conv_state, ssm_state, plan,
+                                     seq_map=seq_map, commit=commit)
+            return self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1), conv_state, ssm_state
+        if not commit:
+            raise NotImplementedError("step_chunk(commit=False) needs the one-launch path (aum_hip.stream_block_supported)")
+        xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         xc2 = xc.reshape(batch * T, E)
-        A = -torch.exp(self.A_log.float())
         activated = False
-        w_x, w_dt = self.x_proj.weight.to(xc2.dtype), self.dt_proj.weight.to(xc2.dtype)
-        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, w_x, w_dt):
-            proj, delta = aum_hip.xdt_tm_fwd(xc2, w_x, w_dt, delta_bias=self.dt_proj.bias.float(), delta_softplus=True)
+        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, plan.w_x, plan.w_dt):
+            proj, delta = aum_hip.xdt_tm_fwd(xc2, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
             activated = True
         else:
             proj = self.x_proj(xc2)
             delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
             proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
         proj = proj.view(batch, T, -1)
-        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], self.D, z,
-                                self.dt_proj.bias, True, activated, seq_map)
+        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], plan.D, z,
+                                plan.dt_bias, True, activated, seq_map)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
+
+    def stream_block_ok(self, xz, conv_state, ssm_state, plan, seq_map=None):
+        """step_chunk's dispatch: the one-launch middle for these (batch, T, 2E) in_proj rows and caches?  (aum_hip.debug.stream_fused
+        = False: never -- the three-launch path, for A/B runs.)"""
+        import aum_hip
+        if not (aum_hip.debug.stream_fused and xz.is_cuda and self.activation in ("silu", "swish") and self.d_conv == 4 and self.conv1d.bias is not None):
+            return False
+        batch, T, E2 = xz.shape
+        rows = xz.view(batch * T, E2)
+        lens = (T,) if seq_map is None else seq_map.lens
+        if seq_map is None and conv_state.shape[0] != batch:
+            return False
+        return aum_hip.stream_block_supported(rows[:, :E2 // 2], rows[:, E2 // 2:], conv_state, ssm_state, plan, max(lens))
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         """MS:360-373"""

@@ -652,6 +652,48 @@ typedef struct AumScanTmChunkVarArgs {
 } AumScanTmChunkVarArgs;
 int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
 
+/*
+ * The recurrent middle of the causal block on packed sessions in ONE launch (additive to ABI 13; `Mamba.step_chunk` through
+ * aum_hip.stream_block): from the x half of the in_proj rows to the gated scan output,
+ *     xc = silu(conv(x) from conv_state);  x_dbl = xc . wx^T;  delta = softplus(x_dbl[:, :rank] . wdt^T + delta_bias);
+ *     y  = scan(xc, delta, A, B = x_dbl[:, rank : rank + 16], C = x_dbl[:, rank + 16 : rank + 32], D, z) from state
+ * with y, conv_state and state BIT FOR BIT what the three launches  aum_conv1d_tm_chunk_var (AUM_CONV_SILU)  ->  aum_xdt_tm_fwd
+ * (AUM_XDT_DELTA_SOFTPLUS)  ->  aum_scan_tm_chunk_var (AUM_SCAN_DELTA_ACTIVATED)  give on the same operands (the kernels share the step
+ * routines), so the partition and packing properties above carry over.  One workgroup per session takes its rows through the three
+ * phases; no workgroup waits for another.
+ *   x, z: (total, dim) packed rows of pitch x_ts / z_ts ELEMENTS (the halves of the in_proj rows), `dtype` AUM_BF16 / AUM_F16;  y (out):
+ *   (total, dim) pitch y_ts, y != x.  conv_state (nrows, dim, width) / state (nrows, dim, dstate): the fp32 pools, the named rows advanced
+ *   in place.  conv_weight (dim, width), conv_bias (dim) or NULL, A (dim, dstate), D (dim) or NULL, delta_bias (dim) or NULL: fp32, 16-byte
+ *   aligned;  wx (ncols, dim) pitch ldwx, wdt (dim, rank) pitch ldwdt in `dtype`.  cu_seqlens, state_indices, total, nseq, nrows: as for
+ *   aum_*_tm_chunk_var, with the same no-op rule (an empty sequence, a row outside the pool, a pair outside [0, total]).  max_len: the
+ *   longest session of the call as the host knows it, <= aum_stream_block_max_len() (128); a session longer than max_len is a no-op.
+ *   scratch: aum_stream_block_scratch_bytes(total, dim, ncols) bytes, 16-byte aligned -- xc, delta and x_dbl of the call; a session's
+ *   workgroup touches the rows of its own session only.
+ *   Built for width == 4, dstate == 16 and the shapes of aum_xdt_tm_fwd (dim % 256 == 0, dim <= 1536, ncols 80 or 56, rank % 8 == 0,
+ *   rank <= 64, rank + 32 <= ncols, pitches % 8 == 0, 16-byte aligned pointers); anything else returns the error the three entry points
+ *   would (AUM_E_DTYPE for fp32 activations, AUM_E_UNSUPPORTED, ...) and callers use the three launches.
+ *   flags: AUM_STREAM_NO_COMMIT -- the caches are read and not written (the stores that close the conv and the scan are skipped, nothing
+ *   else changes): the logits of a session "if the clip ended now" without copying its caches.
+ */
+typedef struct AumStreamBlockArgs {
+    const void *x, *z;
+    float *conv_state, *state;
+    const float *conv_weight, *conv_bias;
+    const void *wx, *wdt;
+    const float *A, *D, *delta_bias;
+    void *y, *scratch;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t x_ts, z_ts, y_ts, scratch_bytes;
+    int32_t total, nseq, nrows, max_len;
+    int32_t dim, width, dstate, rank, ncols, ldwx, ldwdt;
+    int32_t dtype;
+    uint32_t flags;
+} AumStreamBlockArgs;
+#define AUM_STREAM_NO_COMMIT 1u
+int aum_stream_block_tm(const AumStreamBlockArgs* args, void* stream);
+int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32_t ncols);
+int32_t aum_stream_block_max_len(void);
+
 /* Self-tests and calibration (used by tests/ and bench.py; not part of the reference's surface). */
 int aum_abi_version(void);
 /* runs wave_scan_affine<rev> on 64 (P,S) pairs: in/out are device arrays of 128 floats (P[0..63], S[0..63]) */

@@ -15,8 +15,15 @@ Arms (b) and (c) are skipped on a tree without stream_push_many, so the file als
 
     python tools/stream_hop_bench.py --pool 8
     python tools/stream_hop_bench.py --pool 8 --count-only pa|pb|pc|lock
+
+--fused-ab: stream_push (with --pool S: stream_push_many, staggered and ragged) with every block's conv, x/dt projections and scan as
+three launches (aum_hip.debug.stream_fused off: the path before aum_stream_block_tm) against the one launch, alternating in one process.
+
+    python tools/stream_hop_bench.py --fused-ab [--batch 1 8]        (--count-only a: three launches, b: one)
+    python tools/stream_hop_bench.py --fused-ab --pool 8             (--count-only pb0|pc0: three launches, pb|pc: one)
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -60,6 +67,56 @@ def hop_steps(model, spec, cache):
 
 def hop_push(model, spec, cache):
     model.stream_push(spec, cache)
+
+
+@contextlib.contextmanager
+def stream_fused(on):
+    """aum_hip.debug.stream_fused set for the block and put back to what it was (what AUM_DEBUG=1 AUM_STREAM_FUSED=0 sets for a process)"""
+    import aum_hip
+    was = aum_hip.debug.stream_fused
+    aum_hip.debug.stream_fused = on
+    try:
+        yield
+    finally:
+        aum_hip.debug.stream_fused = was
+
+
+def hop_push_unfused(model, spec, cache):
+    """the path before aum_stream_block_tm: conv, x/dt projections and scan as three launches per block"""
+    with stream_fused(False):
+        model.stream_push(spec, cache)
+
+
+def hop_push_fused(model, spec, cache):
+    with stream_fused(True):
+        model.stream_push(spec, cache)
+
+
+def fused_ab(model, args, dev):
+    """--fused-ab: one 8-token hop with the block's middle as three launches (a) against one launch (b), the arms alternating"""
+    for B in args.batch:
+        spec = torch.randn(B, 16, 128, device=dev, dtype=torch.bfloat16)
+        ca, cb = model.allocate_inference_cache(B), model.allocate_inference_cache(B)
+        if args.count_only:
+            fn, c = (hop_push_unfused, ca) if args.count_only == "a" else (hop_push_fused, cb)
+            for _ in range(args.count_hops):
+                fn(model, spec, c)
+            torch.cuda.synchronize()
+            print(json.dumps({"path": "fused-ab " + args.count_only, "batch": B, "hops": args.count_hops}))
+            continue
+        for _ in range(args.warm):
+            timed(hop_push_unfused, model, spec, ca)
+            timed(hop_push_fused, model, spec, cb)
+        ta, tb = [], []
+        for _ in range(args.hops):
+            ta.append(timed(hop_push_unfused, model, spec, ca))
+            tb.append(timed(hop_push_fused, model, spec, cb))
+        g = max(len(ta) // args.groups, 1)
+        med = lambda t: [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+        print(json.dumps({"model": f"aum-{args.size} causal depth {args.depth} bf16", "batch": B, "hop_tokens": 8, "hops": args.hops, "warm": args.warm,
+                          "three_launch_ms_median": round(statistics.median(ta), 4), "three_launch_ms_group_medians": med(ta),
+                          "fused_ms_median": round(statistics.median(tb), 4), "fused_ms_group_medians": med(tb),
+                          "ratio_three_over_fused": round(statistics.median(ta) / statistics.median(tb), 3)}), flush=True)
 
 
 def timed(fn, model, spec, cache):
@@ -132,11 +189,34 @@ def timed_call(fn):
     return a.elapsed_time(b)
 
 
+def pool_fused_arms(model, S, dev):
+    """--fused-ab --pool S: stream_push_many, staggered and ragged, with the block's middle as three launches against one launch; every
+    arm advances a pool of its own"""
+    sets = {"three_launch": (False, pool_arms(model, S, dev)), "fused": (True, pool_arms(model, S, dev))}
+
+    def under(on, fn):
+        def run():
+            with stream_fused(on):
+                fn()
+        return run
+
+    arms = {}
+    for k in ("b_push_many", "c_push_many_ragged"):
+        for tag, (on, base) in sets.items():
+            arms[f"{k}_{tag}"] = (under(on, base[k][0]), base[k][1])
+    return arms
+
+
+COUNT_ARMS = {"pa": "a_solo_pushes", "pb": "b_push_many", "pc": "c_push_many_ragged", "lock": "lockstep_batch_push"}
+COUNT_ARMS_FUSED_AB = {"pb0": "b_push_many_three_launch", "pb": "b_push_many_fused", "pc0": "c_push_many_ragged_three_launch",
+                       "pc": "c_push_many_ragged_fused"}
+
+
 def pool_main(model, args, dev):
     S = args.pool
-    arms = pool_arms(model, S, dev)
+    arms = pool_fused_arms(model, S, dev) if args.fused_ab else pool_arms(model, S, dev)
     if args.count_only:
-        name = {"pa": "a_solo_pushes", "pb": "b_push_many", "pc": "c_push_many_ragged", "lock": "lockstep_batch_push"}[args.count_only]
+        name = (COUNT_ARMS_FUSED_AB if args.fused_ab else COUNT_ARMS)[args.count_only]
         for _ in range(args.count_hops):
             arms[name][0]()
         torch.cuda.synchronize()
@@ -154,6 +234,9 @@ def pool_main(model, args, dev):
     for k, v in times.items():
         out[k] = {"ms_median": round(statistics.median(v), 4), "columns_per_hop": arms[k][1],
                   "ms_group_medians": [round(statistics.median(v[i:i + g]), 4) for i in range(0, g * args.groups, g)]}
+    for k in ("b_push_many", "c_push_many_ragged"):
+        if k + "_fused" in out:
+            out[f"ratio_{k}_three_over_fused"] = round(out[k + "_three_launch"]["ms_median"] / out[k + "_fused"]["ms_median"], 3)
     if "b_push_many" in out:
         out["ratio_a_over_b"] = round(out["a_solo_pushes"]["ms_median"] / out["b_push_many"]["ms_median"], 3)
     print(json.dumps(out), flush=True)
@@ -168,14 +251,19 @@ def main():
     ap.add_argument("--hops", type=int, default=120)
     ap.add_argument("--groups", type=int, default=4)
     ap.add_argument("--pool", type=int, default=0, help="S sessions at different positions: S stream_push calls vs one stream_push_many")
-    ap.add_argument("--count-only", choices=["a", "b", "pa", "pb", "pc", "lock"])
+    ap.add_argument("--count-only", choices=["a", "b", "pa", "pb", "pc", "lock", "pb0", "pc0"])
     ap.add_argument("--count-hops", type=int, default=4)
+    ap.add_argument("--fused-ab", action="store_true", help="stream_push with the block's middle as three launches vs aum_stream_block_tm")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev)
     if args.pool:
         with torch.no_grad():
             pool_main(model, args, dev)
+        return
+    if args.fused_ab:
+        with torch.no_grad():
+            fused_ab(model, args, dev)
         return
     with torch.no_grad():
         for B in args.batch:
