@@ -760,16 +760,19 @@ def cu_count(device=None):
 def gemm_wgrad_splits(n, k, ncu=None, device=None):
     """token splits that give every CU one workgroup: (n / 256) (k / 256) output tiles x splits ~ the CU count"""
     ncu = cu_count(device) if ncu is None else ncu
-    tiles = (n // 256) * max(1, k // 256)          # a skinny operand (k = 48 / 80) is one column tile
+    tiles = (n // 256) * max(1, k // 256)          # a skinny operand (k = 48 / 80, 24 / 56) is one column tile
     return max(1, min(64, ncu // max(tiles, 1)))
+
+
+WGRAD_SKINNY_K = (48, 80, 24, 56)        # dt_rank and dt_rank + 2 d_state of AuM-Base and AuM-Small
 
 
 def gemm_wgrad_supported(y, x, splits=None):
     """shapes aum_gemm_wgrad takes (include/aum_hip.h, ABI 10; the C side's gemm_wgrad_check, rule for rule): 16-bit 2-D token-major
-    operands (rows = tokens, unit column stride), y's width a multiple of 256, x's a multiple of 256 or one of the skinny widths 48 / 80,
-    at most 64 token splits, and a split's rows within 32-bit byte offsets of both operands"""
+    operands (rows = tokens, unit column stride), y's width a multiple of 256, x's a multiple of 256 or one of the skinny widths 48 / 80 (AuM-Base) and
+    24 / 56 (AuM-Small), at most 64 token splits, and a split's rows within 32-bit byte offsets of both operands"""
     if not (y.dim() == 2 and x.dim() == 2 and y.dtype == x.dtype and y.dtype in (torch.bfloat16, torch.float16) and y.shape[0] == x.shape[0]
-            and y.stride(1) == 1 and x.stride(1) == 1 and y.shape[1] % 256 == 0 and (x.shape[1] % 256 == 0 or x.shape[1] in (48, 80))
+            and y.stride(1) == 1 and x.stride(1) == 1 and y.shape[1] % 256 == 0 and (x.shape[1] % 256 == 0 or x.shape[1] in WGRAD_SKINNY_K)
             and y.stride(0) % 8 == 0 and y.stride(0) >= y.shape[1] and x.stride(0) >= x.shape[1]
             and x.stride(0) % 8 == 0 and y.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and y.shape[0] > 0):
         return False
@@ -1307,6 +1310,7 @@ def dtproj_tm_fwd(x_dbl, rank, w, lib=None):
 
 XDT_COLS, XDT_MAX_DIM = 80, 1536
 XDT_COLS_FWD = (80, 56)        # x_dbl widths aum_xdt_tm_fwd is built for (AuM-Base, AuM-Small)
+XDT_COLS_BWD = (80, 56)        # ... and aum_xdt_tm_bwd, each with its own dt_rank = width - 32 (48, 24) only
 
 
 def xdt_tm_supported(u, wx, wdt):
@@ -1323,30 +1327,35 @@ def xdt_tm_supported(u, wx, wdt):
 
 def xdt_tm_bwd_supported(ddelta, dbc, wdt_t, wx_t, du):
     """shapes aum_xdt_tm_bwd takes (include/aum_hip.h, ABI 10): 16-bit row-major ddelta / du (ntok, dim), fp32 dB | dC rows (ntok, 32),
-    dt_proj.weight^T (48, dim), x_proj.weight^T (dim, 80)"""
+    x_proj.weight^T (dim, ncols) and dt_proj.weight^T (ncols - 32, dim) with ncols = 80 (AuM-Base: rank 48) or 56 (AuM-Small: rank 24)"""
     if not (ddelta.dim() == 2 and du.shape == ddelta.shape and ddelta.dtype == du.dtype == wdt_t.dtype == wx_t.dtype
             and ddelta.dtype in (torch.bfloat16, torch.float16) and dbc.dtype == torch.float32 and dbc.dim() == 2):
         return False
+    if wx_t.dim() != 2 or wdt_t.dim() != 2:
+        return False
     ntok, dim = ddelta.shape
+    ncols = wx_t.shape[1]
     ok_t = lambda t, m=8: t.stride(1) == 1 and t.stride(0) % m == 0 and t.data_ptr() % 16 == 0
-    return (wx_t.shape == (dim, XDT_COLS) and wdt_t.shape == (XDT_COLS - 32, dim) and dbc.shape == (ntok, 32) and dim % 256 == 0
+    return (ncols in XDT_COLS_BWD and wx_t.shape == (dim, ncols) and wdt_t.shape == (ncols - 32, dim) and dbc.shape == (ntok, 32) and dim % 256 == 0
             and dim <= XDT_MAX_DIM and ok_t(ddelta) and ok_t(du) and ok_t(wdt_t) and ok_t(wx_t) and ok_t(dbc, 4))
 
 
 def xdt_tm_bwd(ddelta, dbc, wdt_t, wx_t, du, lib=None):
-    """dx_dbl (ntok, 80) = [ddelta @ wdt_t^T | dbc] in ddelta's dtype, and du += dx_dbl @ wx_t^T IN PLACE (SSI:570-574, 587, 590 on
-    token-major rows: one pass over ddelta and du).  Returns dx_dbl."""
+    """dx_dbl (ntok, ncols) = [ddelta @ wdt_t^T | dbc] in ddelta's dtype, and du += dx_dbl @ wx_t^T IN PLACE (SSI:570-574, 587, 590 on
+    token-major rows: one pass over ddelta and du).  ncols = wx_t.shape[1]: 80 or 56, the dt block its first ncols - 32 columns.
+    Returns dx_dbl."""
     lib = lib or get()
     for t in (ddelta, dbc, wdt_t, wx_t, du):
         lib.check_tensor(t)
     if not xdt_tm_bwd_supported(ddelta, dbc, wdt_t, wx_t, du):
         raise RuntimeError(f"xdt_tm_bwd: unsupported operands {tuple(ddelta.shape)} {ddelta.dtype}, {tuple(dbc.shape)}, {tuple(wdt_t.shape)}, {tuple(wx_t.shape)}")
     ntok, dim = ddelta.shape
-    dx_dbl = torch.empty((ntok, XDT_COLS), dtype=ddelta.dtype, device=ddelta.device)
+    ncols = wx_t.shape[1]
+    dx_dbl = torch.empty((ntok, ncols), dtype=ddelta.dtype, device=ddelta.device)
     a = XdtBwdArgs()
     a.ddelta, a.dbc, a.wdt_t, a.wx_t, a.du, a.dx_dbl = _ptr(ddelta), _ptr(dbc), _ptr(wdt_t), _ptr(wx_t), _ptr(du), _ptr(dx_dbl)
-    a.ntok, a.dim, a.rank, a.ncols = ntok, dim, XDT_COLS - 32, XDT_COLS
-    a.ldd, a.lddbc, a.ldwdt, a.ldwx, a.ldu, a.ldx = ddelta.stride(0), dbc.stride(0), wdt_t.stride(0), wx_t.stride(0), du.stride(0), XDT_COLS
+    a.ntok, a.dim, a.rank, a.ncols = ntok, dim, ncols - 32, ncols
+    a.ldd, a.lddbc, a.ldwdt, a.ldwx, a.ldu, a.ldx = ddelta.stride(0), dbc.stride(0), wdt_t.stride(0), wx_t.stride(0), du.stride(0), ncols
     a.dtype = _DT[ddelta.dtype]
     _launch(lib.c.aum_xdt_tm_bwd, a, ddelta, lib, "xdt_tm_bwd", (ntok, dim))
     return dx_dbl

@@ -57,6 +57,11 @@ extern "C" int aum_gemm_tn(const AumGemmArgs* p, void* stream) {
     return hipGetLastError() == hipSuccess ? AUM_OK : AUM_E_LAUNCH;
 }
 
+template <int K> static void wgrad_skinny_launch(const AumGemmWArgs& g, int grid, hipStream_t s) {
+    if (g.dtype == AUM_BF16) hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<true, K>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
+    else hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<false, K>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
+}
+
 extern "C" int aum_gemm_wgrad(const AumGemmWArgs* p, void* stream) {
     const int rc = aumg::gemm_wgrad_check(p);
     if (rc != AUM_OK) return rc;
@@ -67,12 +72,13 @@ extern "C" int aum_gemm_wgrad(const AumGemmWArgs* p, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     (void)hipGetLastError();
     const bool bf = g.dtype == AUM_BF16;
-    if (skinny && g.k == 48) {
-        if (bf) hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<true, 3>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
-        else hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<false, 3>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
-    } else if (skinny) {
-        if (bf) hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<true, 5>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
-        else hipLaunchKernelGGL((aumg::k_gemm_wgrad_skinny<false, 5>), dim3(grid), dim3(aumg::THREADS), 0, s, g);
+    if (skinny) {          // k: 48 / 80 (AuM-Base) or 24 / 56 (AuM-Small), gemm_wgrad_check
+        switch (g.k) {
+            case 24: wgrad_skinny_launch<24>(g, grid, s); break;
+            case 48: wgrad_skinny_launch<48>(g, grid, s); break;
+            case 56: wgrad_skinny_launch<56>(g, grid, s); break;
+            default: wgrad_skinny_launch<80>(g, grid, s); break;
+        }
     } else if (bf) hipLaunchKernelGGL(aumg::k_gemm_wgrad<true>, dim3(grid), dim3(aumg::THREADS), 0, s, g);
     else hipLaunchKernelGGL(aumg::k_gemm_wgrad<false>, dim3(grid), dim3(aumg::THREADS), 0, s, g);
     return hipGetLastError() == hipSuccess ? AUM_OK : AUM_E_LAUNCH;
@@ -126,13 +132,17 @@ extern "C" int aum_xdt_tm_fwd(const AumXdtArgs* p, void* stream) {
     return hipGetLastError() == hipSuccess ? AUM_OK : AUM_E_LAUNCH;
 }
 
-template <int NW> static void xdt_bwd_launch(const AumXdtBwdArgs& g, hipStream_t s) {
+template <int NW, int NC> static void xdt_bwd_launch_nc(const AumXdtBwdArgs& g, hipStream_t s) {
     const dim3 grid((unsigned)((g.ntok + NW * XDT_TOK_W - 1) / (NW * XDT_TOK_W))), block(NW * 64);
     const bool bf = g.dtype == AUM_BF16, deep = g.dim % 512 == 0;          // du read-ahead of four channel pairs where a quarter of the channels holds a multiple of four
-    if (bf && deep) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<true, 3, NW, 4>), grid, block, 0, s, g);
-    else if (bf) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<true, 3, NW, 2>), grid, block, 0, s, g);
-    else if (deep) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<false, 3, NW, 4>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<false, 3, NW, 2>), grid, block, 0, s, g);
+    if (bf && deep) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<true, NC, NW, 4>), grid, block, 0, s, g);
+    else if (bf) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<true, NC, NW, 2>), grid, block, 0, s, g);
+    else if (deep) hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<false, NC, NW, 4>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((aumx::k_xdt_tm_bwd<false, NC, NW, 2>), grid, block, 0, s, g);
+}
+template <int NW> static void xdt_bwd_launch(const AumXdtBwdArgs& g, hipStream_t s) {          // (ncols, rank): (80, 48) or (56, 24), xdt_bwd_check
+    if (g.ncols == XDT_COLS) xdt_bwd_launch_nc<NW, XDT_COLS>(g, s);
+    else xdt_bwd_launch_nc<NW, XDT_COLS_SMALL>(g, s);
 }
 
 extern "C" int aum_xdt_tm_bwd(const AumXdtBwdArgs* p, void* stream) {

@@ -431,11 +431,17 @@ __global__ __launch_bounds__(THREADS, 1) void k_gemm_wgrad(AumGemmWArgs g) {
 // kernel's ([32 tokens][256 columns], swizzled 512-byte rows), the x stage is [32 tokens][16 chunks] with the same swizzle in 256-byte rows
 // (6 / 10 chunks are real, the DMA lanes of the others fetch chunk 0 again: 3 % of the traffic); a wave multiplies its 32 channels (two
 // fragments) by all XC = 3 / 5 column fragments of x.  Three DMA pieces per wave and K-step, four stages in flight.
+// AuM-Small's widths, K = 24 / 56 (d W_dt [E][24], d W_x^T [E][56]), are one and a half / three and a half column fragments: KC = K / 8 = 3 / 7
+// chunks of a row are real (the descriptor ends behind the last row's K columns), the padded fragment's upper eight rows multiply the chunk-0
+// copies, and since the columns of x are OUTPUT rows here (the contraction runs over tokens) those products stay in accumulators that are
+// not stored: lanes gq >= 2 of the last fragment skip it.  The partial tile keeps its (n, K) layout, a row pitch of 96 / 224 bytes.
 // ------------------------------------------------------------------------------------------------------------------------------------
 constexpr int W_XSTAGE_S = 32 * 256;          // bytes of one skinny x stage
 
-template <bool BF16, int XC>
+template <bool BF16, int K>
 __global__ __launch_bounds__(THREADS, 1) void k_gemm_wgrad_skinny(AumGemmWArgs g) {
+    static_assert(K % 8 == 0 && K <= 128, "an x stage row holds 16 chunks of 8 columns");
+    constexpr int XC = (K + 15) / 16, KC = K / 8;          // column fragments, real 16-byte chunks of an x row
     __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
     const int lane = (int)(threadIdx.x & 63u);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -453,7 +459,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_gemm_wgrad_skinny(AumGemmWArgs g
     const char* y_base = static_cast<const char*>(g.y) + (t0 * g.ldy + n0) * 2;
     const char* x_base = static_cast<const char*>(g.x) + (t0 * g.ldx) * 2;
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(y_base), 0, rows > 0 ? (int)((int64_t)(rows - 1) * g.ldy * 2 + 512) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x_base), 0, rows > 0 ? (int)((int64_t)(rows - 1) * g.ldx * 2 + XC * 32) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(x_base), 0, rows > 0 ? (int)((int64_t)(rows - 1) * g.ldx * 2 + K * 2) : 0, 0x00020000);
 
     // y: piece c = jj * 8 + w is tokens 2 c, 2 c + 1 of the K-step (as in k_gemm_wgrad); x: piece w is tokens 4 w .. 4 w + 3, lane l fills
     // physical chunk l & 15 of token 4 w + (l >> 4) with logical chunk (l & 15) ^ swizzle(token), or with chunk 0 where that is past the row
@@ -463,7 +469,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_gemm_wgrad_skinny(AumGemmWArgs g
     const int step_y = 16 * (int)g.ldy * 2;
     const int xrow = 4 * w + (lane >> 4);
     const int xc_l = (lane & 15) ^ (2 * ((xrow & 3) + 4 * ((xrow >> 3) & 1)));
-    const int voff_x = xrow * (int)g.ldx * 2 + (xc_l < 2 * XC ? xc_l : 0) * 16;
+    const int voff_x = xrow * (int)g.ldx * 2 + (xc_l < KC ? xc_l : 0) * 16;
     const int step_x = 32 * (int)g.ldx * 2;
     auto stage_w = [&](int kstep, int st) {
 #pragma unroll
@@ -517,7 +523,8 @@ __global__ __launch_bounds__(THREADS, 1) void k_gemm_wgrad_skinny(AumGemmWArgs g
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int f = 0; f < XC; ++f) *reinterpret_cast<f4v*>(c_base + (int64_t)m * 16 * g.k + f * 16) = acc[m][f];
+        for (int f = 0; f < XC; ++f)
+            if (f * 16 + 4 * gq < K) *reinterpret_cast<f4v*>(c_base + (int64_t)m * 16 * g.k + f * 16) = acc[m][f];      // (not the dead rows of a half fragment)
 }
 
 }  // namespace aumg

@@ -6,7 +6,7 @@
 #include "../../include/aum_hip.h"
 
 #define XDT_COLS 80          // columns of x_dbl = dt_rank + 2 d_state the kernels are built for (AuM-Base: 48 + 32)
-#define XDT_COLS_SMALL 56    // ... and the forward kernel also for AuM-Small's 24 + 32
+#define XDT_COLS_SMALL 56    // ... and for AuM-Small's 24 + 32 (forward: any rank % 8 == 0; backward: the pairs (80, 48) and (56, 24) only)
 #ifndef XDT_TOK_W
 #define XDT_TOK_W 16         // tokens per wave
 #endif
@@ -37,7 +37,7 @@ inline int xdt_bwd_check(const AumXdtBwdArgs* p) {
         g.ldx < g.ncols || g.lddbc < g.ncols - g.rank)
         return AUM_E_SHAPE;
     if (g.dtype != AUM_BF16 && g.dtype != AUM_F16) return AUM_E_DTYPE;
-    if (g.ncols != XDT_COLS || g.rank != XDT_COLS - 32 || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
+    if ((g.ncols != XDT_COLS && g.ncols != XDT_COLS_SMALL) || g.rank != g.ncols - 32 || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
     if (g.ldd % 8 || g.ldu % 8 || g.ldwdt % 8 || g.ldwx % 8 || g.ldx % 8 || g.lddbc % 4) return AUM_E_UNSUPPORTED;
     if (((uintptr_t)g.ddelta | (uintptr_t)g.dbc | (uintptr_t)g.wdt_t | (uintptr_t)g.wx_t | (uintptr_t)g.du | (uintptr_t)g.dx_dbl) & 15u)
         return AUM_E_UNSUPPORTED;

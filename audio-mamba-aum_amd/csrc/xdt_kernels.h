@@ -116,13 +116,22 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_fwd(AumXdtArgs g) {
 // channel quarters through LDS) against the tile and adds each lane's eight channels of a token into du with one 16-byte load and store.
 // W_x^T rows sit at a 256-byte pitch with their 16-byte chunks XOR-ed by the row's position in its fragment (s = 4 (row / 8 % 4) + row % 4):
 // the 16 rows a fragment read touches share their first bank, the XOR spreads them over all 64.
+// NC = columns of dx_dbl, R = NC - 32 its dt block: (80, 48) for AuM-Base, (56, 24) for AuM-Small.  Small's widths end in HALF a fragment on
+// both sides, and unlike the forward's the halves do not fall into padding nobody reads:
+//   stage A: 24 rows of W_dt^T are one and a half row fragments.  Exactly R rows are staged (wdt_t has no row 24); the second fragment's
+//     rows 24..31 are whatever the slab held, and their products would be tile columns 24..31 -- the first eight of dB | dC.  The lanes
+//     that hold them (kg >= 2 of the last fragment) do not store.  MFMA rows do not mix: rows 16..23 of that fragment are clean.
+//   stage B: 56 columns are one and three quarter K-steps of 32, and columns 56..63 are in the CONTRACTION.  Neither side of it is read:
+//     the tile fragment of k >= NC and the W_x^T chunk q >= NC / 8 are zero REGISTERS (stale LDS may hold a NaN pattern, and NaN x 0 is
+//     NaN), and the staging copies NC / 8 chunks per row, never the chunk behind a row's end.
 // ------------------------------------------------------------------------------------------------------------------------------------
 constexpr int WXP = 256;                                  // bytes per W_x^T row in LDS (80 columns = 10 chunks, swizzled inside 16)
 
-template <bool BF16, int RF, int NW, int PD>
+template <bool BF16, int NC, int NW, int PD>
 __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_bwd(AumXdtBwdArgs g) {
     __shared__ __attribute__((aligned(16))) char lds[lds_bytes(XDT_MAX_DIM, NW)];
-    constexpr int R = RF * 16, KS = 3;
+    static_assert(NC % 8 == 0 && NC > 32 && NC <= XDT_COLS, "the tile row (XP) and the W_x^T row (WXP) hold at most XDT_COLS columns");
+    constexpr int R = NC - 32, RF = (R + 15) / 16, KS = (NC + 31) / 32;
     const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int rho = lane & 15, kg = lane >> 4;
     const int E = g.dim, KH = E / 2, SP = slab_pitch(KH);
@@ -173,7 +182,8 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_bwd(AumXdtBwdArgs g) {
         u2v v;
         v.x = pack2<BF16>(acc[f][0], acc[f][1]);
         v.y = pack2<BF16>(acc[f][2], acc[f][3]);
-        *reinterpret_cast<u2v*>(xt + rho * XP + (f * 16 + kg * 4) * 2) = v;
+        if (f * 16 + kg * 4 < R)                                      // (a half fragment's dead rows: columns R.. belong to dB | dC)
+            *reinterpret_cast<u2v*>(xt + rho * XP + (f * 16 + kg * 4) * 2) = v;
     }
     {       // 16 tokens x (C - R) fp32 columns: C - R = 32 -> lane = (token lane / 4, eight columns (lane % 4) * 8)
         const int tk = lane >> 2, c8 = (lane & 3) * 8;
@@ -191,7 +201,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_bwd(AumXdtBwdArgs g) {
     __builtin_amdgcn_s_waitcnt(0xc07f);                              // lgkmcnt(0): the wave's own tile is complete (nobody else reads it)
     {
         char* xo = static_cast<char*>(g.dx_dbl);
-        constexpr int PIECES = XDT_COLS * 2 / 16;
+        constexpr int PIECES = NC * 2 / 16;
         for (int idx = lane; idx < XDT_TOK_W * PIECES; idx += 64) {
             const int tk = idx / PIECES, pc = idx - tk * PIECES;
             if (t0 + tk < g.ntok)
@@ -203,7 +213,7 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_bwd(AumXdtBwdArgs g) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const int k = ks * 32 + kg * 8;
-        xf[ks] = k < XDT_COLS ? *reinterpret_cast<const s8v*>(xt + rho * XP + k * 2) : zero;
+        xf[ks] = k < NC ? *reinterpret_cast<const s8v*>(xt + rho * XP + k * 2) : zero;
     }
     const int CH = E / 4;
     char* ob = static_cast<char*>(g.du) + ((t0 + rho) * g.ldu + kg * 8) * 2;
@@ -213,14 +223,14 @@ __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_bwd(AumXdtBwdArgs g) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const int q = ks * 4 + kg;
-        q_ok[ks] = q < XDT_COLS / 8;
+        q_ok[ks] = q < NC / 8;
         qoff[ks] = ((q ^ rho) & 15) * 16;
     }
     for (int quarter = 0; quarter < 4; ++quarter) {
         __syncthreads();
-        {       // CH rows x 10 chunks of W_x^T -> swizzled rows of 256 bytes; eight loads in flight per thread
+        {       // CH rows x NC / 8 (10 or 7) chunks of W_x^T -> swizzled rows of 256 bytes; eight loads in flight per thread
             const char* src = static_cast<const char*>(g.wx_t) + (int64_t)quarter * CH * g.ldwx * 2;
-            constexpr int CHK = XDT_COLS / 8;
+            constexpr int CHK = NC / 8;
             const int totalc = CH * CHK;
             for (int base = tid; base < totalc; base += NW * 64 * 8) {
                 u4v r[8];

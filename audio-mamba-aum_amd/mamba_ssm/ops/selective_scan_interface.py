@@ -738,7 +738,7 @@ def _inner_forward_tm(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_
     # the backward's row pass (aum_xdt_tm_bwd) multiplies by the two small weights the other way round: their transposes, from the
     # step cache when the model filled it
     w_x_t = w_dt_t = None
-    if need_bwd and _XDT_BWD_HIP and conv2d.is_cuda and R + 2 * N == aum_hip.XDT_COLS and R == aum_hip.XDT_COLS - 32 and E % 256 == 0 \
+    if need_bwd and _XDT_BWD_HIP and conv2d.is_cuda and R + 2 * N in aum_hip.XDT_COLS_BWD and N == 16 and E % 256 == 0 \
             and E <= aum_hip.XDT_MAX_DIM and conv2d.dtype in (torch.bfloat16, torch.float16):
         w_x_t, w_dt_t = _cast_t(x_proj_param, conv2d.dtype), _cast_t(delta_proj_param, conv2d.dtype)
     ckpt = aum_hip.scan_tm_ckpt(Bsz, L, E, N, A_b is not None, xz.device, dtype=conv_out.dtype) if need_bwd else None
@@ -807,7 +807,7 @@ def _inner_backward_tm(ctx, dout):
     conv2d = conv_out.view(Bsz * L, E)
     if w_x_t is not None and aum_hip.xdt_tm_bwd_supported(ddelta2, dbc2, w_dt_t, w_x_t, du2):
         # SSI:570-574, 587, 590 in one pass over ddelta and du (aum_xdt_tm_bwd); the two weight gradients on the skinny form of the
-        # weight-gradient kernel (aum_gemm_wgrad, k = 48 / 80): every activation tensor is read once per product
+        # weight-gradient kernel (aum_gemm_wgrad, k = 48 / 80 at AuM-Base, 24 / 56 at AuM-Small): every activation tensor is read once per product
         dx_dbl = aum_hip.xdt_tm_bwd(ddelta2, dbc2, w_dt_t, w_x_t, du2)
         # (a shape the kernel's own argument check would refuse -- e.g. a token split beyond 32-bit byte offsets -- takes the library's
         # split-K products instead of raising inside backward)

@@ -46,7 +46,8 @@ extern "C" {
                                    aum_rmsnorm_bwd_partial_rows (the vectorised norm backward leaves an eighth of the partial rows);
                                    additions without a version step (no existing struct or entry point changes): aum_stft_logmel_fwd, aum_spec_time_warp
                                    (the EPIC-Sounds frontend); AUM_SCAN_DELTA_ACTIVATED (token-major scans) and, appended to AumXdtArgs, delta_bias /
-                                   flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour */
+                                   flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour; aum_xdt_tm_bwd also takes
+                                   (ncols, rank) = (56, 24) and aum_gemm_wgrad k in {24, 56} (AuM-Small: shapes that were AUM_E_UNSUPPORTED) */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -457,7 +458,7 @@ int aum_gemm_tn(const AumGemmArgs* args, void* stream);
  *   y: (t, n) rows of pitch ldy (the output gradient);  x: (t, k) rows of pitch ldx (the layer's input) -- pitches in ELEMENTS, both `dtype`
  *   (AUM_BF16 / AUM_F16; else AUM_E_DTYPE);  part: (splits, n, k) fp32, contiguous: the caller sums the splits in a fixed order (aum_sum_rows).
  *   Split s takes tokens [s c, min(t, (s + 1) c)) with c = ceil(ceil(t / splits) / 64) * 64 (a split may be empty: its tile is zero).
- *   n % 256 == 0, k % 256 == 0 or k in {48, 80} (the skinny operands of the dt_proj / x_proj weight gradients, SSI:586, 589), splits <= 64, pitches % 8 == 0, 16-byte aligned pointers, c * pitch * 2 < 2 GiB (else AUM_E_UNSUPPORTED: callers
+ *   n % 256 == 0, k % 256 == 0 or k in {48, 80, 24, 56} (the skinny operands of the dt_proj / x_proj weight gradients, SSI:586, 589, of AuM-Base and AuM-Small), splits <= 64, pitches % 8 == 0, 16-byte aligned pointers, c * pitch * 2 < 2 GiB (else AUM_E_UNSUPPORTED: callers
  *   use a library GEMM).  fp32 accumulation; no atomics: the result is bitwise repeatable.
  */
 typedef struct AumGemmWArgs {
@@ -519,7 +520,7 @@ int aum_xdt_tm_fwd(const AumXdtArgs* args, void* stream);
  *   du += dx_dbl . x_proj.weight  (in place).
  *   ddelta: (ntok, dim) pitch ldd;  dbc: (ntok, ncols - rank) fp32 pitch lddbc;  wdt_t: dt_proj.weight TRANSPOSED, (rank, dim) pitch ldwdt;
  *   wx_t: x_proj.weight TRANSPOSED, (dim, ncols) pitch ldwx;  du (in / out): (ntok, dim) pitch ldu;  dx_dbl (out): (ntok, ncols) pitch ldx.
- *   Built for ncols == 80, rank == 48 (AuM-Base), dim % 256 == 0, dim <= 1536, pitches % 8 == 0 (lddbc % 4 == 0), 16-byte aligned pointers;
+ *   Built for (ncols, rank) == (80, 48) (AuM-Base) or (56, 24) (AuM-Small) -- no other pair, not (80, 24) or (56, 48) --, dim % 256 == 0, dim <= 1536, pitches % 8 == 0 (lddbc % 4 == 0), 16-byte aligned pointers;
  *   anything else AUM_E_UNSUPPORTED (callers use the three library calls).
  */
 typedef struct AumXdtBwdArgs {
