@@ -243,16 +243,16 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True):
+    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
         (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
-        are read and not written"""
+        are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it"""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
                                            residual_in_fp32=True, eps=layer.norm.eps)
             conv_state, ssm_state = layer_caches[i]
-            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit)
+            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek)
         return hidden, residual
 
     def _read_in_place(self, cls, cache, rows):
@@ -306,13 +306,25 @@ class AudioMamba(nn.Module):
         pe = pe[:, :, cols] if isinstance(cols, slice) else pe.index_select(2, cols)
         return (x.reshape(Bsz, nf, k, -1) + pe).transpose(1, 2).reshape(Bsz, k * nf, -1)
 
+    def _cls_row(self):
+        return self.cls_token + self.pos_embed.pos_embed[:, :1]                  # (1, 1, Dm)
+
+    def _head_rows(self, hidden, residual, return_features):
+        """final norm and head on (n, Dm) rows of the last block's output and residual"""
+        f = rms_norm_fn(hidden, self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual, prenorm=False,
+                        residual_in_fp32=True)
+        return f if return_features else self.head(f)
+
     @torch.no_grad()
-    def stream_push_many(self, specs, pool, sessions):
+    def stream_push_many(self, specs, pool, sessions, read=False, return_features=False):
         """specs[i]: (16 k_i, n_mels), k_i >= 1 -- the next k_i time columns of the clip of session sessions[i] (distinct rows of a pool from
         allocate_stream_pool), every session at its own column offset and with its own hop size.  One patch-embed GEMM over the frames
         concatenated in time, each session's position rows gathered from its own offset, tokens time-major within a session, then ONE pass
         through all blocks on the packed tokens (Mamba.step_chunk(seq_map=): only the conv and the scan see the session boundaries).
-        Returns the per-session column counts.  Every argument is checked before any cache is touched: a refused call changes nothing."""
+        Returns the per-session column counts.  Every argument is checked before any cache is touched: a refused call changes nothing.
+        read=True: the logits "if the clip ended now" of every session with the same pass -- the cls row rides behind each session's new
+        tokens as a peek row (Mamba.step_chunk(peek=True): it sees the state the tokens produced, the caches do not take it in).
+        Returns (column counts, logits (len(sessions), classes) in the order of `sessions`; features with return_features)."""
         import aum_hip
         self._check_streamable()
         rows = self._check_sessions("stream_push_many", pool, sessions)
@@ -331,17 +343,32 @@ class AudioMamba(nn.Module):
                 raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
             ks.append(k)
         dev = specs[0].device
-        smap = aum_hip.seq_map([k * nf for k in ks], rows, device=dev)
+        smap = aum_hip.seq_map([k * nf + (1 if read else 0) for k in ks], rows, device=dev)
         # the position row of every new column: one host-built index vector, uploaded like the sequence map
         cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
         if dev.type == "cuda":
             cols = cols.pin_memory()
         cols = cols.to(dev, non_blocking=True)
         x = self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)   # a session's tokens are contiguous
-        self._stream_layers(x, pool["layers"], smap)
+        out = None
+        if read:                # a session's tokens, then its cls row; the last row of session i is row cu[i + 1] - 1 of the pack
+            cls = self._cls_row()[0].to(x.dtype)
+            pieces, at = [], 0
+            for k in ks:
+                pieces += [x[0, at:at + k * nf], cls]
+                at += k * nf
+            last = torch.tensor([sum(smap.lens[:i + 1]) - 1 for i in range(len(ks))], dtype=torch.int64)
+            if dev.type == "cuda":
+                last = last.pin_memory()
+            last = last.to(dev, non_blocking=True)
+            hidden, residual = self._stream_layers(torch.cat(pieces, dim=0).unsqueeze(0), pool["layers"], smap, peek=True)
+            out = self._head_rows(hidden[0].index_select(0, last), residual[0].index_select(0, last), return_features)
+        else:
+            self._stream_layers(x, pool["layers"], smap)
         for r, k in zip(rows, ks):
             pool["columns"][r] += k
-        return [pool["columns"][r] for r in rows]
+        counts = [pool["columns"][r] for r in rows]
+        return (counts, out) if read else counts
 
     def stream_reset(self, pool, sessions):
         """Empty the caches and the column counts of those rows of a pool: the slots are free for new clips."""
@@ -356,10 +383,13 @@ class AudioMamba(nn.Module):
                 pool["columns"][r] = 0
 
     @torch.no_grad()
-    def stream_push(self, spec, cache):
+    def stream_push(self, spec, cache, read=False, return_features=False):
         """spec: (batch, 16 k, n_mels) -- the next k time columns of the clip's normalised log-mel spectrogram.  Embeds their
         k x n_f tokens (time-major, each with the position row of its (f, t) cell), runs them through all blocks from the carried caches
-        and advances the caches.  Returns the number of columns pushed so far."""
+        and advances the caches.  Returns the number of columns pushed so far.
+        read=True: what stream_read would say behind this push, from the same pass -- the cls row rides behind the new tokens as a peek
+        row (Mamba.step_chunk(peek=True)), goes through the final norm and the head, and the caches advance by the tokens only.
+        Returns (columns, logits (batch, classes); features with return_features)."""
         self._check_streamable()
         if self._is_pool(cache):
             raise ValueError("stream_push advances all rows of a cache from allocate_inference_cache together; a pool from "
@@ -371,9 +401,15 @@ class AudioMamba(nn.Module):
         k, c0 = spec.shape[1] // pw, cache["columns"]
         if c0 + k > nt:
             raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
-        self._stream_layers(self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k)), cache["layers"])
+        x = self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
+        if not read:
+            self._stream_layers(x, cache["layers"])
+            cache["columns"] = c0 + k
+            return cache["columns"]
+        x = torch.cat((x, self._cls_row().to(x.dtype).expand(x.shape[0], -1, -1)), dim=1)
+        hidden, residual = self._stream_layers(x, cache["layers"], peek=True)
         cache["columns"] = c0 + k
-        return cache["columns"]
+        return cache["columns"], self._head_rows(hidden[:, -1], residual[:, -1], return_features)
 
     @torch.no_grad()
     def stream_read(self, cache, return_features=False, sessions=None):

@@ -1062,11 +1062,11 @@ def _tm2(t, name, last):
     return t.stride(0) if t.shape[0] > 1 else last
 
 
-def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None):
+def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None, peek=False):
     """The causal conv on packed sessions in one launch (aum_conv1d_tm_chunk_var): x (total, dim) packed rows (row stride free: may be the
     first half of in_proj output rows), conv_state (nrows, dim, width) the pool of fp32 caches -- the rows seq_map names are advanced IN
     PLACE, the others are not touched.  Per session bit for bit conv1d_tm_chunk at batch 1.  Returns y (total, dim) in x's dtype.  No
-    device synchronisation."""
+    device synchronisation.  peek (AUM_CONV_PEEK_LAST): every session's last row is computed and the caches close one row early."""
     lib = lib or get()
     for t in (x, conv_state, out):
         lib.check_tensor(t)
@@ -1076,10 +1076,10 @@ def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=Non
         raise RuntimeError(f"conv1d_tm_chunk_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
                            f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
     check_seq_map("conv1d_tm_chunk_var", seq_map, x.shape[0], conv_state.shape[0], x.device)
-    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib)
+    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, peek)
 
 
-def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib):
+def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib, peek=False):
     """conv1d_tm_chunk_var behind its checks: operands conv1d_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
     total, dim = x.shape
     a = ConvTmChunkVarArgs()
@@ -1087,16 +1087,18 @@ def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib):
     a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
     a.x_ts, a.y_ts = _tm2(x, "x", dim), _tm2(y, "out", dim)
     a.total, a.nseq, a.nrows = total, len(m.lens), conv_state.shape[0]
+    if peek:
+        a.flags |= CONV_PEEK_LAST
     _launch(lib.c.aum_conv1d_tm_chunk_var, a, x, lib, "conv_tm_chunk_var", (len(m.lens), dim, total, x.element_size()))
     return y
 
 
 def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
-                      out=None, lib=None):
+                      out=None, lib=None, peek=False):
     """The selective scan on packed sessions in one launch (aum_scan_tm_chunk_var): state (nrows, dim, dstate) the pool of fp32 caches --
     the rows seq_map names are advanced IN PLACE, the others are not touched; u, delta, z (total, dim) and B, C (total, dstate) packed
     rows in one dtype (row strides free).  Per session bit for bit scan_tm_chunk at batch 1.  Returns (total, dim) in u's dtype.  No
-    device synchronisation."""
+    device synchronisation.  peek (AUM_SCAN_PEEK_LAST): every session's last row is computed and the caches close one row early."""
     lib = lib or get()
     for t in (state, u, delta, z, B, C, out):
         lib.check_tensor(t)
@@ -1106,10 +1108,10 @@ def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None,
         raise RuntimeError(f"scan_tm_chunk_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
                            "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
     check_seq_map("scan_tm_chunk_var", seq_map, u.shape[0], state.shape[0], u.device)
-    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib)
+    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, peek)
 
 
-def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib):
+def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib, peek=False):
     """scan_tm_chunk_var behind its checks: operands scan_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
     total, dim = u.shape
     dstate = state.shape[2]
@@ -1120,6 +1122,8 @@ def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplu
     a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
     a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
     a.total, a.nseq, a.nrows = total, len(m.lens), state.shape[0]
+    if peek:
+        a.flags |= SCAN_PEEK_LAST
     _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(m.lens), dim, total, dstate, u.element_size()))
     return out
 
@@ -1144,15 +1148,34 @@ def _advance_batch(st, rows, chunk_ok, chunk, token):
     return torch.stack([token(st, *[None if t is None else t[:, i] for t in rows]) for i in range(rows[0].shape[1])], dim=1)
 
 
-def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token):
+def _packed_rows(t):
+    """(batch, T, X) rows as one (1, batch * T, X) pack: a view where batch and T share one stride, else a contiguous copy"""
+    if t is None:
+        return None
+    batch, T, X = t.shape
+    if batch == 1 or t.stride(0) == T * t.stride(1):
+        return t.as_strided((1, batch * T, X), (0, t.stride(1), t.stride(2)))
+    return t.contiguous().view(1, batch * T, X)
+
+
+def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token, peek=False):
     """The one ladder under conv1d_stream and scan_stream: advance `cache` IN PLACE (through an fp32 copy, written back, if it is not fp32
     contiguous) by the token-major operands `rows` ((batch, T, .) views or None; rows[0] is what the *_ok predicates look at) with the
     first launch that takes them.  m (a SeqMap its caller checked; rows (1, total, .), cache a pool): var() on the packed rows, else a host
     loop over the sessions (host lengths: no synchronisation), each on its pool row as without m: chunk(), else token() token by token
-    (a (batch, .) rows[0] is one token).  An operand is copied to contiguous rows only where that makes a launch take it."""
+    (a (batch, .) rows[0] is one token).  An operand is copied to contiguous rows only where that makes a launch take it.
+    peek: every session's last row is computed and the cache closes one row early (the flag of the packed kernels -- a fixed batch goes
+    through them with fixed_seq_map; in the host loop a session's last row is advanced on a copy of its cache row)."""
     for t in (cache, *rows):
         lib.check_tensor(t)
     st = cache if cache.dtype == torch.float32 and cache.is_contiguous() else cache.float().contiguous()
+    shape = None
+    if peek and m is None:
+        if rows[0].dim() != 3:
+            raise ValueError("peek takes (batch, T >= 1, .) rows: the last of the T rows is the peek row")
+        shape = rows[0].shape
+        m = fixed_seq_map(shape[0], shape[1], rows[0].device)
+        rows = [_packed_rows(t) for t in rows]
     if m is None:
         out = token(st, *rows) if rows[0].dim() == 2 else _advance_batch(st, rows, chunk_ok, chunk, token)
     elif m.total == 0:
@@ -1164,45 +1187,63 @@ def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token):
             out = var(st, lead, *[_unit_last(t) for t in rows2d[1:]]).unsqueeze(0)
         else:
             outs, o = [], 0
+            cut = lambda a, b: [None if t is None else t[:, a:b] for t in rows]
             for n, r in zip(m.lens, m.rows):
-                if n:
-                    outs.append(_advance_batch(st[r:r + 1], [None if t is None else t[:, o:o + n] for t in rows], chunk_ok, chunk, token))
+                keep = max(n - 1, 0) if peek else n
+                if keep > 0:
+                    outs.append(_advance_batch(st[r:r + 1], cut(o, o + keep), chunk_ok, chunk, token))
+                if n > keep:
+                    outs.append(_advance_batch(st[r:r + 1].clone(), cut(o + keep, o + n), chunk_ok, chunk, token))
                 o += n
             out = torch.cat(outs, dim=1)
     if st is not cache:
         cache.copy_(st)
-    return out
+    return out if shape is None else out.reshape(shape[0], shape[1], -1)
 
 
-def conv1d_stream(x, conv_state, weight, bias=None, silu=True, seq_map=None, lib=None):
+def conv1d_stream(x, conv_state, weight, bias=None, silu=True, seq_map=None, lib=None, peek=False):
     """causal_conv1d.causal_conv1d_update on token-major rows, as Mamba.step_chunk has them: x (batch, T, dim) (a view is read in place),
-    (batch, dim) one token, or with seq_map (trusted: check_seq_map is the caller's) (1, total, dim) over a pool; returns x's shape."""
+    (batch, dim) one token, or with seq_map (trusted: check_seq_map is the caller's) (1, total, dim) over a pool; returns x's shape.
+    peek: the last row of every session (of the T rows without seq_map) is computed, conv_state is advanced by the rows before it."""
     lib = lib or get()
+    if peek and seq_map is None and x.dim() == 3:
+        seq_map_k = fixed_seq_map(x.shape[0], x.shape[1], x.device)
+    else:
+        seq_map_k = seq_map
     return _stream_advance(lib, conv_state, (x,), seq_map,
                            lambda st, x: conv1d_tm_chunk_var_supported(x, st),
-                           lambda st, x: _conv1d_tm_chunk_var(x, st, weight, bias, silu, seq_map, None, lib),
+                           lambda st, x: _conv1d_tm_chunk_var(x, st, weight, bias, silu, seq_map_k, None, lib, peek),
                            lambda st, x: conv1d_tm_chunk_supported(x, st),
                            lambda st, x: conv1d_tm_chunk(x, st, weight, bias, silu, lib),
-                           lambda st, x: conv1d_update(x, st, weight, bias, silu, lib))
+                           lambda st, x: conv1d_update(x, st, weight, bias, silu, lib), peek)
 
 
-def scan_stream(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None, lib=None):
+def scan_stream(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None, lib=None,
+                peek=False):
     """selective_scan_update behind its argument normalisation (operands of one dtype), what Mamba.step_chunk calls: seq_map is trusted
-    (check_seq_map is the caller's)."""
+    (check_seq_map is the caller's).  peek: the last row of every session (of the T rows without seq_map) is computed, state is advanced
+    by the rows before it."""
     lib = lib or get()
     if delta_activated:                 # delta holds softplus(raw + delta_bias) already
         delta_bias, delta_softplus = None, False
+    if peek and seq_map is None and u.dim() == 3:
+        seq_map_k = fixed_seq_map(u.shape[0], u.shape[1], u.device)
+    else:
+        seq_map_k = seq_map
     return _stream_advance(lib, state, (u, delta, z, B, C), seq_map,
                            scan_tm_chunk_var_supported,
                            lambda st, u, dl, z, B, C: _scan_tm_chunk_var(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated,
-                                                                         seq_map, None, lib),
+                                                                         seq_map_k, None, lib, peek),
                            scan_tm_chunk_supported,
                            lambda st, u, dl, z, B, C: scan_tm_chunk(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, lib=lib),
-                           lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib))
+                           lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib), peek)
 
 
 # ---- the block's recurrent middle in one launch (aum_stream_block_tm): conv -> x/dt projections -> scan on packed sessions
 STREAM_NO_COMMIT = 1
+STREAM_PEEK_LAST = 2            # the last row of every session is computed and stored, the caches close one row early
+CONV_PEEK_LAST = 8              # the same for aum_conv1d_tm_chunk_var ...
+SCAN_PEEK_LAST = 64             # ... and aum_scan_tm_chunk_var
 STREAM_BLOCK_MAX_T = 128        # tokens per session and call (aum_stream_block_max_len)
 _fixed_maps = {}
 
@@ -1236,12 +1277,14 @@ def stream_block_supported(x, z, conv_state, state, plan, max_len=1):
             and plan.conv_w.shape == (dim, 4) and plan.A.shape == (dim, 16))
 
 
-def stream_block(xz_x, z, conv_state, state, plan, seq_map=None, commit=True, out=None, lib=None):
+def stream_block(xz_x, z, conv_state, state, plan, seq_map=None, commit=True, out=None, lib=None, peek=False):
     """Conv (SiLU) from the carried window -> x_proj, dt_proj (dt_bias and softplus once) -> selective scan (D, z gate) from the carried
     state, in ONE launch (aum_stream_block_tm): xz_x, z the two halves of the in_proj rows -- (total, dim) packed rows with seq_map
     (trusted: check_seq_map is the caller's), or (batch, T, dim) views of one (batch, T, 2 dim) tensor, session b on cache row b.
     conv_state (nrows, dim, 4) / state (nrows, dim, 16): fp32 pools advanced IN PLACE; commit=False: read and not written.  plan:
     Mamba.stream_params().  Bit for bit conv1d_tm_chunk_var -> xdt_tm_fwd(delta_softplus) -> scan_tm_chunk_var(delta_activated).
+    peek (AUM_STREAM_PEEK_LAST): the last row of every session is a peek row -- computed like any other, the pools advanced by the rows
+    before it (bit for bit a call on those rows, then a commit=False call on the last row).  The peek row counts towards the 128.
     Returns y in xz_x's shape and dtype.  No device synchronisation."""
     lib = lib or get()
     shape = xz_x.shape
@@ -1279,7 +1322,7 @@ def stream_block(xz_x, z, conv_state, state, plan, seq_map=None, commit=True, ou
     a.total, a.nseq, a.nrows, a.max_len = total, len(seq_map.lens), conv_state.shape[0], max_len
     a.dim, a.width, a.dstate, a.rank, a.ncols = dim, 4, 16, plan.w_dt.shape[1], ncols
     a.ldwx, a.ldwdt, a.dtype = plan.w_x.stride(0), plan.w_dt.stride(0), _DT[x2.dtype]
-    a.flags = 0 if commit else STREAM_NO_COMMIT
+    a.flags = (0 if commit else STREAM_NO_COMMIT) | (STREAM_PEEK_LAST if peek else 0)
     _launch(lib.c.aum_stream_block_tm, a, x2, lib, "stream_block", (len(seq_map.lens), dim, total))
     return y.view(shape)
 

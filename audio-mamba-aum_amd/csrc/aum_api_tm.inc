@@ -595,8 +595,10 @@ AUM_API int32_t aum_conv1d_tm_nparts(int32_t batch, int32_t len) { return batch 
 #ifndef AUM_EMU
 template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk(AumConvTmChunkArgs a) { convc_wave<T, SILU>(a, (int)blockIdx.x); }
 template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk(AumScanTmChunkArgs a) { scanc_wave<T, SP, HAS_Z>(a, (int)blockIdx.x); }
-template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk_var(AumConvTmChunkVarArgs a) { convc_var_wave<T, SILU>(a, (int)blockIdx.x); }
-template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk_var(AumScanTmChunkVarArgs a) { scanc_var_wave<T, SP, HAS_Z>(a, (int)blockIdx.x); }
+template <class T, bool SILU, bool PEEK = false> AUM_GLOBAL void k_convt_chunk_var(AumConvTmChunkVarArgs a) { convc_var_wave<T, SILU, PEEK>(a, (int)blockIdx.x); }
+template <class T, bool SP, bool HAS_Z, bool PEEK = false> AUM_GLOBAL void k_stream_scan_chunk_var(AumScanTmChunkVarArgs a) {
+    scanc_var_wave<T, SP, HAS_Z, PEEK>(a, (int)blockIdx.x);
+}
 #endif
 template <class T, bool SILU> static int convc_launch(const AumConvTmChunkArgs& a, aum_stream_t s) {
     const int grid = a.batch * convt_cblocks<T, false>(a.dim);
@@ -623,6 +625,7 @@ AUM_API int aum_conv1d_tm_chunk(const AumConvTmChunkArgs* a, void* stream) {
     const int64_t strides = a->x_bs | a->x_ts | a->y_bs | a->y_ts;
     if ((ptrs & 15) || ((strides * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
     if (a->x == a->y) return AUM_E_UNSUPPORTED;      // rows are fetched ahead of the steps that write them
+    if (a->flags & AUM_CONV_PEEK_LAST) return AUM_E_UNSUPPORTED;       // a flag of the packed entry point
     const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit: one batch entry's rows must fit
     if ((int64_t)a->len * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
     aum_stream_t s = (aum_stream_t)stream;
@@ -681,18 +684,19 @@ static bool stream_var_ok(const int32_t* cu_seqlens, const int32_t* state_indice
     if (((uintptr_t)cu_seqlens | (uintptr_t)state_indices) & 3) { err = AUM_E_UNSUPPORTED; return false; }
     return true;
 }
-template <class T, bool SILU> static int convcv_launch(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
+template <class T, bool SILU, bool PEEK> static int convcv_launch(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
     const int grid = a.nseq * convt_cblocks<T, false>(a.dim);
 #ifdef AUM_EMU
     (void)s;
-    for (int wg = 0; wg < grid; ++wg) convc_var_wave<T, SILU>(a, wg);
+    for (int wg = 0; wg < grid; ++wg) convc_var_wave<T, SILU, PEEK>(a, wg);
 #else
-    AUM_LAUNCH((k_convt_chunk_var<T, SILU>), grid, 0, s, a);
+    AUM_LAUNCH((k_convt_chunk_var<T, SILU, PEEK>), grid, 0, s, a);
 #endif
     return launch_status();
 }
 template <class T> static int convcv_dispatch_t(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
-    return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true>(a, s) : convcv_launch<T, false>(a, s);
+    if (a.flags & AUM_CONV_PEEK_LAST) return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true, true>(a, s) : convcv_launch<T, false, true>(a, s);
+    return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true, false>(a, s) : convcv_launch<T, false, false>(a, s);
 }
 AUM_API int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* a, void* stream) {
     if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
@@ -717,19 +721,22 @@ AUM_API int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* a, void* stream
         default: return convcv_dispatch_t<f16_t>(*a, s);
     }
 }
-template <class T, bool SP, bool HAS_Z> static int scancv_launch(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
+template <class T, bool SP, bool HAS_Z, bool PEEK> static int scancv_launch(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
     const int grid = a.nseq * (a.dim / WAVE);
 #ifdef AUM_EMU
     (void)s;
-    for (int wg = 0; wg < grid; ++wg) scanc_var_wave<T, SP, HAS_Z>(a, wg);
+    for (int wg = 0; wg < grid; ++wg) scanc_var_wave<T, SP, HAS_Z, PEEK>(a, wg);
 #else
-    AUM_LAUNCH((k_stream_scan_chunk_var<T, SP, HAS_Z>), grid, 0, s, a);
+    AUM_LAUNCH((k_stream_scan_chunk_var<T, SP, HAS_Z, PEEK>), grid, 0, s, a);
 #endif
     return launch_status();
 }
+template <class T, bool PEEK> static int scancv_dispatch_p(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
+    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scancv_launch<T, true, true, PEEK>(a, s) : scancv_launch<T, true, false, PEEK>(a, s);
+    return a.z ? scancv_launch<T, false, true, PEEK>(a, s) : scancv_launch<T, false, false, PEEK>(a, s);
+}
 template <class T> static int scancv_dispatch_t(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
-    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scancv_launch<T, true, true>(a, s) : scancv_launch<T, true, false>(a, s);
-    return a.z ? scancv_launch<T, false, true>(a, s) : scancv_launch<T, false, false>(a, s);
+    return (a.flags & AUM_SCAN_PEEK_LAST) ? scancv_dispatch_p<T, true>(a, s) : scancv_dispatch_p<T, false>(a, s);
 }
 AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) {
     if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
@@ -738,7 +745,7 @@ AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) 
     if (a->dim <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
     if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
     if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
-    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED | AUM_SCAN_PEEK_LAST)) return AUM_E_UNSUPPORTED;
     {       // row offsets inside a sequence are 32-bit byte cursors; a sequence has at most `total` rows
         const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
         const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
@@ -751,7 +758,7 @@ AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) 
     AumScanTmChunkVarArgs k = *a;       // the kernels' view: an activated delta carries its bias and softplus already
     if (a->flags & AUM_SCAN_DELTA_ACTIVATED) {
         k.delta_bias = nullptr;
-        k.flags = 0;
+        k.flags = a->flags & AUM_SCAN_PEEK_LAST;
     }
     aum_stream_t s = (aum_stream_t)stream;
     switch (k.dtype) {
@@ -766,6 +773,7 @@ AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) 
 // the operands as the lane-array build's three entry points take them: its aum_xdt_tm_fwd is a plain loop that writes the raw product, so
 // the bias and the softplus are the scan's here (the same function of the same values, rounded in another place than on the device)
 static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumXdtArgs& g, AumScanTmChunkVarArgs& k) {
+    const bool peek = (a.flags & AUM_STREAM_PEEK_LAST) != 0;     // handed on to the conv and the scan; the projections take every row
     const SbScratch so = sb_scratch(a.total, a.dim, a.ncols);
     char* sc = static_cast<char*>(a.scratch);
     void *xc = sc + so.xc * 2, *delta = sc + so.delta * 2, *x_dbl = sc + so.x_dbl * 2;
@@ -773,7 +781,8 @@ static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumX
     c.x = a.x; c.conv_state = a.conv_state; c.weight = a.conv_weight; c.bias = a.conv_bias; c.y = xc;
     c.cu_seqlens = a.cu_seqlens; c.state_indices = a.state_indices;
     c.x_ts = a.x_ts; c.y_ts = a.dim;
-    c.total = a.total; c.nseq = a.nseq; c.nrows = a.nrows; c.dim = a.dim; c.width = a.width; c.dtype = a.dtype; c.flags = AUM_CONV_SILU;
+    c.total = a.total; c.nseq = a.nseq; c.nrows = a.nrows; c.dim = a.dim; c.width = a.width; c.dtype = a.dtype;
+    c.flags = AUM_CONV_SILU | (peek ? AUM_CONV_PEEK_LAST : 0u);
     g = {};
     g.u = xc; g.wx = a.wx; g.wdt = a.wdt; g.x_dbl = x_dbl; g.delta = delta;
     g.ntok = a.total; g.dim = a.dim; g.rank = a.rank; g.ncols = a.ncols;
@@ -786,16 +795,16 @@ static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumX
     k.cu_seqlens = a.cu_seqlens; k.state_indices = a.state_indices;
     k.u_ts = a.dim; k.delta_ts = a.dim; k.z_ts = a.z_ts; k.B_ts = a.ncols; k.C_ts = a.ncols; k.out_ts = a.y_ts;
     k.total = a.total; k.nseq = a.nseq; k.nrows = a.nrows; k.dim = a.dim; k.dstate = a.dstate; k.dtype = a.dtype;
-    k.flags = AUM_SCAN_SOFTPLUS;
+    k.flags = AUM_SCAN_SOFTPLUS | (peek ? AUM_SCAN_PEEK_LAST : 0u);
 }
 #else
-template <class T, bool BF16> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
+template <class T, bool BF16, bool PEEK> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
     const dim3 grid((unsigned)a.nseq), block(SB_NW * 64);
     const bool one = a.rank <= 32, base = a.ncols == XDT_COLS;
-    if (base && one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS>), grid, block, 0, s, a);
-    else if (base) hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS>), grid, block, 0, s, a);
-    else if (one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS_SMALL>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS_SMALL>), grid, block, 0, s, a);
+    if (base && one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS, PEEK>), grid, block, 0, s, a);
+    else if (base) hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS, PEEK>), grid, block, 0, s, a);
+    else if (one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS_SMALL, PEEK>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS_SMALL, PEEK>), grid, block, 0, s, a);
     return launch_status();
 }
 #endif
@@ -812,7 +821,7 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
         return AUM_E_SHAPE;
     if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
     if (a->dtype == AUM_F32) return AUM_E_DTYPE;                  // the projections run on the 16-bit matrix pipe only
-    if (a->flags & ~AUM_STREAM_NO_COMMIT) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~(AUM_STREAM_NO_COMMIT | AUM_STREAM_PEEK_LAST)) return AUM_E_UNSUPPORTED;
     if (a->max_len > SB_MAX_T) return AUM_E_UNSUPPORTED;
     if (a->width != CONVT_W || a->dstate != SCANT_N || !scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
     if ((a->ncols != XDT_COLS && a->ncols != XDT_COLS_SMALL) || a->rank % 8 || a->rank > 64 || a->rank + 2 * SCANT_N > a->ncols || a->dim % 256 ||
@@ -850,7 +859,8 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     return rc;
 #else
     aum_stream_t s = (aum_stream_t)stream;
-    return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true>(*a, s) : sb_launch<f16_t, false>(*a, s);
+    if (a->flags & AUM_STREAM_PEEK_LAST) return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, true>(*a, s) : sb_launch<f16_t, false, true>(*a, s);
+    return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, false>(*a, s) : sb_launch<f16_t, false, false>(*a, s);
 #endif
 }
 #endif

@@ -58,7 +58,8 @@ template <class T> AUM_DEV T* sb_rows(const AumStreamBlockArgs& a, int64_t at, i
     return static_cast<T*>(a.scratch) + at + (int64_t)r0 * pitch;
 }
 
-template <class T, bool BF16, int KS, int NC>
+// PEEK (AUM_STREAM_PEEK_LAST): the units close the caches one row early (stream_tm_kernels.h); the projections take every row
+template <class T, bool BF16, int KS, int NC, bool PEEK = false>
 __global__ __launch_bounds__(SB_NW * 64, 1) void k_stream_block(AumStreamBlockArgs) {
     __shared__ __attribute__((aligned(16))) char lds[aumx::lds_bytes(XDT_MAX_DIM, SB_NW)];
     int r0, len, row, ncb, ngrp;
@@ -74,8 +75,8 @@ __global__ __launch_bounds__(SB_NW * 64, 1) void k_stream_block(AumStreamBlockAr
         const AumStreamBlockArgs& a = sb_args();
         const SbScratch so = sb_scratch(a.total, a.dim, a.ncols);
         const ConvcOps o = {a.conv_weight, a.conv_bias, a.x_ts, (int64_t)a.dim, a.dim, a.width};
-        convc_unit<T, true>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), sb_rows<T>(a, so.xc, r0, a.dim), a.conv_state + (int64_t)row * a.dim * a.width, len,
-                            cb, !(a.flags & AUM_STREAM_NO_COMMIT));
+        convc_unit<T, true, PEEK>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), sb_rows<T>(a, so.xc, r0, a.dim), a.conv_state + (int64_t)row * a.dim * a.width,
+                                  len, cb, !(a.flags & AUM_STREAM_NO_COMMIT));
     }
     __syncthreads();
     // ---- 2. x_proj, dt_proj, softplus ---------------------------------------------------------------------------------------------
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(SB_NW * 64, 1) void k_stream_block(AumStreamBlockAr
         const ScancOps o = {a.A, a.D, nullptr, (int64_t)a.dim, (int64_t)a.dim, a.z_ts, (int64_t)a.ncols, (int64_t)a.ncols, a.y_ts};
         const ScancSeq<T> q = {xc, sb_rows<T>(a, so.delta, r0, a.dim), row_ptr<T>(a.z, (int64_t)r0 * a.z_ts), x_dbl + a.rank, x_dbl + a.rank + SCANT_N,
                                row_ptr<T>(a.y, (int64_t)r0 * a.y_ts), a.state + (int64_t)row * a.dim * SCANT_N, len};
-        scanc_unit<T, false, true>(o, q, grp * WAVE, !(a.flags & AUM_STREAM_NO_COMMIT));
+        scanc_unit<T, false, true, PEEK>(o, q, grp * WAVE, !(a.flags & AUM_STREAM_NO_COMMIT));
     }
 }
 #endif

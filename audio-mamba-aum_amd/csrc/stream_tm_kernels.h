@@ -25,6 +25,15 @@
 // fixed-batch kernel and the packed kernel differ only in where those arguments come from (b * X_bs / b-th cache row; cu_seqlens[i] * X_ts
 // / cache row state_indices[i], wave-uniform values read with plain loads).  An empty sequence, an index outside the pool or a
 // cu_seqlens pair outside [0, total] returns before anything is fetched.
+//
+// PEEK ROW (template parameter PEEK of the two units; AUM_CONV_PEEK_LAST / AUM_SCAN_PEEK_LAST / AUM_STREAM_PEEK_LAST): the last of a
+// sequence's L rows is computed and stored like any other, and the cache is written as after L - 1 rows.  The block loop runs over the
+// first L - 1 rows, the exit stores follow it (none for L == 1: the cache row is not touched), and then ONE more call of the same `step`
+// takes the last row, fetched ahead of the loop, from the registers the exit stores have just read.  The window cannot be rebuilt
+// behind the last step (it holds four inputs; the oldest is gone), so the early state is taken where it exists.  The cache crosses the
+// exit as exact fp32, so the result is bit for bit a call on rows 0 .. L - 2 followed by an uncommitted call on row L - 1.  PEEK is a
+// template parameter because scanc_unit fills the scalar file: with PEEK == false every added expression folds away and the existing
+// kernels compile to what they were; the PEEK kernels are instantiations of their own.
 #pragma once
 #include "conv_tm_kernels.h"
 #include "scan_tm_kernels.h"
@@ -43,7 +52,8 @@ struct ConvcOps {
 
 // unit = (sequence, block of 64 * V channels): L >= 1 rows at x / y (row stride x_ts / y_ts elements), the sequence's cache row `win`.
 // commit == false (aum_stream_block_tm with AUM_STREAM_NO_COMMIT): the cache row is read and not written -- the exit stores are skipped
-template <class T, bool SILU>
+// PEEK: row L - 1 is a peek row -- LC = L - 1 rows go through the loop and into the cache, the last one is stepped behind the exit stores
+template <class T, bool SILU, bool PEEK = false>
 AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb, bool commit = true) {
     constexpr int V = convt_vec<T, false>(), NP = V / 2, ES = (int)sizeof(T), W = CONVT_W;
     AumConvTmArgs s = {};
@@ -55,6 +65,7 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
     convt_lane_setup<T, false>(s, cb, ln);
     const gbuf<T> xb = make_gbuf(x);
     const gbuf<T> yb = make_gbuf(y);
+    const int LC = PEEK ? L - 1 : L;             // the rows the cache takes in
     const vi coff = ln.c0 * ES;
     const int x_tb = (int)a.x_ts * ES, y_tb = (int)a.y_ts * ES;
     vf2 w2[W][NP], bias2[NP];
@@ -114,30 +125,33 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
     auto comp_blk = [&](int itb, const convt_raw<T, false> (&raw)[STREAM_UB]) {
         AUM_UNROLL
         for (int j = 0; j < STREAM_UB; ++j) {
-            if (itb + j < L) step(itb + j, raw[j]);
+            if (itb + j < LC) step(itb + j, raw[j]);
         }
     };
-    convt_raw<T, false> ra[STREAM_UB], rb[STREAM_UB];
-    load_blk(0, ra);
-    for (int itb = 0; itb < L; itb += 2 * STREAM_UB) {
+    convt_raw<T, false> ra[STREAM_UB], rb[STREAM_UB], rp;
+    if (PEEK) rp = convt_load<T, false>(xb, coff, (L - 1) * x_tb);
+    load_blk(0, ra);            // requests are clamped to row L - 1, which exists: an empty loop (PEEK, L == 1) fetches that row only
+    for (int itb = 0; itb < LC; itb += 2 * STREAM_UB) {
         load_blk(itb + STREAM_UB, rb);
         comp_blk(itb, ra);
         load_blk(itb + 2 * STREAM_UB, ra);
         comp_blk(itb + STREAM_UB, rb);
     }
-    // exit: conv_state[j] = input L - width + j = row 4 - width + j
-    if (!commit) return;
-    AUM_UNROLL
-    for (int i = 0; i < W; ++i) {
-        const int j = a.width - W + i;
-        if (j >= 0) {
-            AUM_UNROLL
-            for (int p = 0; p < NP; ++p) {
-                gstore(win, (ln.c0 + 2 * p) * a.width + j, lo2(xr[i][p]), ln.live);
-                gstore(win, (ln.c0 + 2 * p + 1) * a.width + j, hi2(xr[i][p]), ln.live);
+    // exit: conv_state[j] = input LC - width + j = row 4 - width + j
+    if (commit && (!PEEK || LC > 0)) {
+        AUM_UNROLL
+        for (int i = 0; i < W; ++i) {
+            const int j = a.width - W + i;
+            if (j >= 0) {
+                AUM_UNROLL
+                for (int p = 0; p < NP; ++p) {
+                    gstore(win, (ln.c0 + 2 * p) * a.width + j, lo2(xr[i][p]), ln.live);
+                    gstore(win, (ln.c0 + 2 * p + 1) * a.width + j, hi2(xr[i][p]), ln.live);
+                }
             }
         }
     }
+    if (PEEK) step(L - 1, rp);
 }
 
 // fixed batch: unit = (batch entry, channel block), channel block fastest
@@ -161,15 +175,15 @@ AUM_DEV bool stream_seq(const int32_t* cu_seqlens, const int32_t* state_indices,
 }
 
 // packed sessions: unit = (sequence, channel block), channel block fastest
-template <class T, bool SILU>
+template <class T, bool SILU, bool PEEK = false>
 AUM_DEV void convc_var_wave(const AumConvTmChunkVarArgs& a, int wg) {
     const int ncb = convt_cblocks<T, false>(a.dim);
     const int cb = wg % ncb, i = wg / ncb;
     int r0, len, row;
     if (!stream_seq(a.cu_seqlens, a.state_indices, i, a.total, a.nrows, r0, len, row)) return;
     const ConvcOps o = {a.weight, a.bias, a.x_ts, a.y_ts, a.dim, a.width};
-    convc_unit<T, SILU>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), row_ptr<T>(a.y, (int64_t)r0 * a.y_ts), a.conv_state + (int64_t)row * a.dim * a.width,
-                        len, cb);
+    convc_unit<T, SILU, PEEK>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), row_ptr<T>(a.y, (int64_t)r0 * a.y_ts),
+                              a.conv_state + (int64_t)row * a.dim * a.width, len, cb);
 }
 
 // ---- scan ---------------------------------------------------------------------------------------
@@ -189,10 +203,12 @@ template <class T> struct ScancSeq {
 
 // unit = (sequence, group of 64 channels from e0).  SP: delta = softplus(delta + bias); otherwise delta + bias (an activated delta comes
 // with bias == NULL: the launcher drops it).  commit == false: the state row is read and not written (the exit stores are skipped).
-template <class T, bool SP, bool HAS_Z>
+// PEEK: row L - 1 is a peek row -- LC = L - 1 rows go through the loop and into the state, the last one is stepped behind the exit stores
+template <class T, bool SP, bool HAS_Z, bool PEEK = false>
 AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true) {
     constexpr int N = SCANT_N, ES = (int)sizeof(T);
     const int L = q.len;
+    const int LC = PEEK ? L - 1 : L;             // the rows the state takes in
     const vi lane = lane_id();
     const vi ec = lane + e0;                     // dim % 64 == 0: every lane is a channel
     vf2 A2[N / 2];                               // A * log2(e), states (2j, 2j+1)
@@ -277,24 +293,35 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
     auto comp_blk = [&](int itb, const ScancRaw (&raw)[STREAM_UB]) {
         AUM_UNROLL
         for (int j = 0; j < STREAM_UB; ++j) {
-            if (itb + j < L) step(itb + j, raw[j]);
+            if (itb + j < LC) step(itb + j, raw[j]);
         }
     };
     ScancRaw ra[STREAM_UB], rb[STREAM_UB];
-    load_blk(0, ra);
-    for (int itb = 0; itb < L; itb += 2 * STREAM_UB) {
+    load_blk(0, ra);            // requests are clamped to row L - 1, which exists: an empty loop (PEEK, L == 1) fetches that row only
+    for (int itb = 0; itb < LC; itb += 2 * STREAM_UB) {
         load_blk(itb + STREAM_UB, rb);
         comp_blk(itb, ra);
         load_blk(itb + 2 * STREAM_UB, ra);
         comp_blk(itb + STREAM_UB, rb);
     }
-    // exit state
-    if (!commit) return;
-    AUM_UNROLL
-    for (int i = 0; i < N / 4; ++i) {
-        const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
-        gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
+    ScancRaw rp;                // the peek row, fetched here and not ahead of the loop: five more live registers across it are not free in this kernel
+    if (PEEK) {
+        const int it = L - 1;
+        rp.u = gbuf_load_raw(ubuf, el_off, it * u_tb);
+        rp.d = gbuf_load_raw(dbuf, el_off, it * d_tb);
+        if (HAS_Z) rp.z = gbuf_load_raw(zbuf, el_off, it * z_tb);
+        rp.b = gbuf_load_raw(Bbuf, bc_off, it * B_tb);
+        rp.c = gbuf_load_raw(Cbuf, bc_off, it * C_tb);
     }
+    // exit state
+    if (commit && (!PEEK || LC > 0)) {
+        AUM_UNROLL
+        for (int i = 0; i < N / 4; ++i) {
+            const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
+            gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
+        }
+    }
+    if (PEEK) step(L - 1, rp);
 }
 
 // fixed batch: unit = (batch entry, group of 64 channels), channel group fastest
@@ -311,7 +338,7 @@ AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
 }
 
 // packed sessions: unit = (sequence, group of 64 channels), channel group fastest
-template <class T, bool SP, bool HAS_Z>
+template <class T, bool SP, bool HAS_Z, bool PEEK = false>
 AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg) {
     const int ngrp = p.dim / WAVE;
     const int e0 = (wg % ngrp) * WAVE, i = wg / ngrp;
@@ -322,7 +349,7 @@ AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg) {
                            HAS_Z ? row_ptr<T>(p.z, (int64_t)r0 * p.z_ts) : nullptr, row_ptr<T>(p.B, (int64_t)r0 * p.B_ts),
                            row_ptr<T>(p.C, (int64_t)r0 * p.C_ts), row_ptr<T>(p.out, (int64_t)r0 * p.out_ts),
                            p.state + (int64_t)row * p.dim * SCANT_N, len};
-    scanc_unit<T, SP, HAS_Z>(o, q, e0);
+    scanc_unit<T, SP, HAS_Z, PEEK>(o, q, e0);
 }
 
 }  // namespace aum

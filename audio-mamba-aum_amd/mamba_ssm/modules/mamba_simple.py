@@ -248,7 +248,7 @@ class Mamba(nn.Module):
         """drop the cached stream_params(): the next call converts the parameters again (behind a write the key cannot see: `p.data`)"""
         self.__dict__.pop("_stream_params", None)
 
-    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True):
+    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True, peek=False):
         """T >= 1 tokens of streaming inference for the causal block in one pass: (batch, T, d_model) in, (batch, T, d_model) out, the
         caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the
         recurrent middle as ONE launch where aum_hip.stream_block takes the shapes (16-bit activations, fp32 caches, the widths of
@@ -263,7 +263,11 @@ class Mamba(nn.Module):
         tokens of several sessions behind one another, the caches are pools of nrows rows, session i advances row seq_map.rows[i] by
         seq_map.lens[i] tokens (the other rows are not touched).  Only the recurrent stages see the session boundaries (the map checked
         here, once); the projections take the packed rows as they are.
-        commit=False: the caches are read and not written (the one-launch path only: NotImplementedError elsewhere)."""
+        commit=False: the caches are read and not written (the one-launch path only: NotImplementedError elsewhere).
+        peek=True: the LAST row of every session (of the T rows without seq_map) is a peek row -- it runs through the block like any
+        other row and its output is returned, and the caches are advanced by the rows before it only (a cls row behind a hop's tokens:
+        it sees the state they produced, the next hop does not see it).  One launch with the flag where the one-launch path takes the
+        shapes -- the peek row counts towards its 128 -- else the ladder with the two flags; both give the same bits at the kernels."""
         import aum_hip
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
@@ -282,11 +286,11 @@ class Mamba(nn.Module):
         plan = self.stream_params(xz.dtype)
         if self.stream_block_ok(xz, conv_state, ssm_state, plan, seq_map):
             y = aum_hip.stream_block(x if seq_map is None else x[0], z if seq_map is None else z[0], conv_state, ssm_state, plan,
-                                     seq_map=seq_map, commit=commit)
+                                     seq_map=seq_map, commit=commit, peek=peek)
             return self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1), conv_state, ssm_state
         if not commit:
             raise NotImplementedError("step_chunk(commit=False) needs the one-launch path (aum_hip.stream_block_supported)")
-        xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map)
+        xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map, peek=peek)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         xc2 = xc.reshape(batch * T, E)
@@ -300,7 +304,7 @@ class Mamba(nn.Module):
             proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
         proj = proj.view(batch, T, -1)
         y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], plan.D, z,
-                                plan.dt_bias, True, activated, seq_map)
+                                plan.dt_bias, True, activated, seq_map, peek=peek)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
 

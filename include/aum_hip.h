@@ -639,6 +639,7 @@ typedef struct AumConvTmChunkVarArgs {
     int32_t dtype;
     uint32_t flags;
 } AumConvTmChunkVarArgs;
+#define AUM_CONV_PEEK_LAST 8u    /* aum_conv1d_tm_chunk_var only: conv_state is written as after len - 1 rows (see AUM_STREAM_PEEK_LAST) */
 int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* args, void* stream);
 typedef struct AumScanTmChunkVarArgs {
     const void *u, *delta, *z, *B, *C;
@@ -651,6 +652,7 @@ typedef struct AumScanTmChunkVarArgs {
     int32_t dtype;
     uint32_t flags;
 } AumScanTmChunkVarArgs;
+#define AUM_SCAN_PEEK_LAST 64u   /* aum_scan_tm_chunk_var only: state is written as after len - 1 rows (see AUM_STREAM_PEEK_LAST) */
 int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
 
 /*
@@ -675,6 +677,17 @@ int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
  *   would (AUM_E_DTYPE for fp32 activations, AUM_E_UNSUPPORTED, ...) and callers use the three launches.
  *   flags: AUM_STREAM_NO_COMMIT -- the caches are read and not written (the stores that close the conv and the scan are skipped, nothing
  *   else changes): the logits of a session "if the clip ended now" without copying its caches.
+ *   AUM_STREAM_PEEK_LAST (additive to ABI 13) -- the LAST row of every session is a PEEK ROW: it is computed exactly like any other row
+ *   (conv from the window, x/dt projections, scan step from the state, gate) and its y is stored, but conv_state and state are written
+ *   as they stand after the session's first len - 1 rows.  A cls row that rides behind a session's new tokens sees the state the tokens
+ *   produced, and the next call does not see the cls row: "push, then read" in one pass.  Rows 0 .. len - 1 all produce output; for
+ *   len == 1 nothing of the session's cache row is written; the no-op rules are unchanged; max_len counts the peek row (128 rows = 127
+ *   tokens and the peek).  With AUM_STREAM_NO_COMMIT nothing is written, as without the peek.  Per session, y and both cache rows are BIT
+ *   FOR BIT a call without the flag on rows 0 .. len - 2 followed by an AUM_STREAM_NO_COMMIT call on row len - 1 alone (the peek row
+ *   runs the same step routine from the same fp32 window and state).  The same rule as two flags of the packed entry points:
+ *   AUM_CONV_PEEK_LAST for aum_conv1d_tm_chunk_var and AUM_SCAN_PEEK_LAST for aum_scan_tm_chunk_var (any dtype, any of their other
+ *   flags); the three launches with the two flags are bit for bit the one launch with AUM_STREAM_PEEK_LAST.  The fixed-batch entry points
+ *   refuse them (AUM_E_UNSUPPORTED).
  */
 typedef struct AumStreamBlockArgs {
     const void *x, *z;
@@ -691,6 +704,7 @@ typedef struct AumStreamBlockArgs {
     uint32_t flags;
 } AumStreamBlockArgs;
 #define AUM_STREAM_NO_COMMIT 1u
+#define AUM_STREAM_PEEK_LAST 2u  /* the last row of every session is computed and stored, the caches close one row early */
 int aum_stream_block_tm(const AumStreamBlockArgs* args, void* stream);
 int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32_t ncols);
 int32_t aum_stream_block_max_len(void);

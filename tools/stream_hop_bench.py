@@ -21,6 +21,12 @@ three launches (aum_hip.debug.stream_fused off: the path before aum_stream_block
 
     python tools/stream_hop_bench.py --fused-ab [--batch 1 8]        (--count-only a: three launches, b: one)
     python tools/stream_hop_bench.py --fused-ab --pool 8             (--count-only pb0|pc0: three launches, pb|pc: one)
+
+--peek: "push, then tell me what you hear" two ways, same model, same hop, alternating in one process: (a) stream_push followed by
+stream_read (a second pass of the cls row through all blocks), (b) one stream_push(read=True) (the cls row rides behind the hop's
+tokens as a peek row); stream_push alone is timed as the third arm, so the cost of the read is visible in both forms.
+
+    python tools/stream_hop_bench.py --peek [--batch 1 8]            (--count-only a: push + read, b: push(read=True))
 """
 import argparse
 import contextlib
@@ -117,6 +123,44 @@ def fused_ab(model, args, dev):
                           "three_launch_ms_median": round(statistics.median(ta), 4), "three_launch_ms_group_medians": med(ta),
                           "fused_ms_median": round(statistics.median(tb), 4), "fused_ms_group_medians": med(tb),
                           "ratio_three_over_fused": round(statistics.median(ta) / statistics.median(tb), 3)}), flush=True)
+
+
+def hop_push_then_read(model, spec, cache):
+    model.stream_push(spec, cache)
+    return model.stream_read(cache)
+
+
+def hop_push_read(model, spec, cache):
+    return model.stream_push(spec, cache, read=True)[1]
+
+
+def peek_ab(model, args, dev):
+    """--peek: one 8-token hop with its logits as push + stream_read (a) against one stream_push(read=True) (b); the plain push as (c)"""
+    arms = (("push_then_read", hop_push_then_read), ("push_read_one_pass", hop_push_read), ("push_only", hop_push))
+    for B in args.batch:
+        spec = torch.randn(B, 16, 128, device=dev, dtype=torch.bfloat16)
+        caches = [model.allocate_inference_cache(B) for _ in arms]
+        if args.count_only:
+            i = 0 if args.count_only == "a" else 1
+            for _ in range(args.count_hops):
+                arms[i][1](model, spec, caches[i])
+            torch.cuda.synchronize()
+            print(json.dumps({"path": "peek " + arms[i][0], "batch": B, "hops": args.count_hops}))
+            continue
+        for _ in range(args.warm):
+            for (_, fn), c in zip(arms, caches):
+                timed(fn, model, spec, c)
+        times = [[] for _ in arms]
+        for _ in range(args.hops):
+            for t, (_, fn), c in zip(times, arms, caches):
+                t.append(timed(fn, model, spec, c))
+        g = max(args.hops // args.groups, 1)
+        out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "batch": B, "hop_tokens": 8, "hops": args.hops, "warm": args.warm}
+        for (name, _), t in zip(arms, times):
+            out[name + "_ms_median"] = round(statistics.median(t), 4)
+            out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+        out["ratio_two_pass_over_one_pass"] = round(out["push_then_read_ms_median"] / out["push_read_one_pass_ms_median"], 3)
+        print(json.dumps(out), flush=True)
 
 
 def timed(fn, model, spec, cache):
@@ -254,6 +298,7 @@ def main():
     ap.add_argument("--count-only", choices=["a", "b", "pa", "pb", "pc", "lock", "pb0", "pc0"])
     ap.add_argument("--count-hops", type=int, default=4)
     ap.add_argument("--fused-ab", action="store_true", help="stream_push with the block's middle as three launches vs aum_stream_block_tm")
+    ap.add_argument("--peek", action="store_true", help="stream_push + stream_read vs one stream_push(read=True)")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev)
@@ -264,6 +309,10 @@ def main():
     if args.fused_ab:
         with torch.no_grad():
             fused_ab(model, args, dev)
+        return
+    if args.peek:
+        with torch.no_grad():
+            peek_ab(model, args, dev)
         return
     with torch.no_grad():
         for B in args.batch:
