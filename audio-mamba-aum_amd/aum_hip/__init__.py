@@ -1368,19 +1368,26 @@ def xdt_tm_supported(u, wx, wdt):
             and ok_t(u) and ok_t(wx) and ok_t(wdt))
 
 
+def xdt_tm_bwd_widths(dim, rank, dstate, dtype):
+    """the widths aum_xdt_tm_bwd is built for: 16-bit rows of dx_dbl = [dt block (rank) | dB | dC (dstate each)] with rank + 2 * dstate in
+    XDT_COLS_BWD.  What a caller asks before it prepares the transposed weights; xdt_tm_bwd_supported then checks the operands themselves"""
+    return (rank + 2 * dstate in XDT_COLS_BWD and dstate == 16 and dim % 256 == 0 and dim <= XDT_MAX_DIM
+            and dtype in (torch.bfloat16, torch.float16))
+
+
 def xdt_tm_bwd_supported(ddelta, dbc, wdt_t, wx_t, du):
     """shapes aum_xdt_tm_bwd takes (include/aum_hip.h, ABI 10): 16-bit row-major ddelta / du (ntok, dim), fp32 dB | dC rows (ntok, 32),
     x_proj.weight^T (dim, ncols) and dt_proj.weight^T (ncols - 32, dim) with ncols = 80 (AuM-Base: rank 48) or 56 (AuM-Small: rank 24)"""
     if not (ddelta.dim() == 2 and du.shape == ddelta.shape and ddelta.dtype == du.dtype == wdt_t.dtype == wx_t.dtype
-            and ddelta.dtype in (torch.bfloat16, torch.float16) and dbc.dtype == torch.float32 and dbc.dim() == 2):
+            and dbc.dtype == torch.float32 and dbc.dim() == 2):
         return False
     if wx_t.dim() != 2 or wdt_t.dim() != 2:
         return False
     ntok, dim = ddelta.shape
     ncols = wx_t.shape[1]
     ok_t = lambda t, m=8: t.stride(1) == 1 and t.stride(0) % m == 0 and t.data_ptr() % 16 == 0
-    return (ncols in XDT_COLS_BWD and wx_t.shape == (dim, ncols) and wdt_t.shape == (ncols - 32, dim) and dbc.shape == (ntok, 32) and dim % 256 == 0
-            and dim <= XDT_MAX_DIM and ok_t(ddelta) and ok_t(du) and ok_t(wdt_t) and ok_t(wx_t) and ok_t(dbc, 4))
+    return (xdt_tm_bwd_widths(dim, ncols - 32, 16, ddelta.dtype) and wx_t.shape == (dim, ncols) and wdt_t.shape == (ncols - 32, dim)
+            and dbc.shape == (ntok, 32) and ok_t(ddelta) and ok_t(du) and ok_t(wdt_t) and ok_t(wx_t) and ok_t(dbc, 4))
 
 
 def xdt_tm_bwd(ddelta, dbc, wdt_t, wx_t, du, lib=None):

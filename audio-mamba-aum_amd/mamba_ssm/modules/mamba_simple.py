@@ -164,13 +164,7 @@ class Mamba(nn.Module):
                 y = out_f + out_b                                          # (B, E, L) logical, both in xz's storage order
                 if self.if_devide_out:
                     y = y / 2
-                E = y.shape[1]
-                if tm:
-                    # token-major pipelines: y is the transposed view of (B, L, E) rows -- out_proj on the rows (SSI:517 dispatch)
-                    out = ssi.OutProjTmFn.apply(self.out_proj.weight, y.transpose(1, 2).reshape(batch * seqlen, E))
-                else:
-                    y2 = y.permute(1, 0, 2).reshape(E, batch * seqlen)
-                    out = torch.matmul(y2.t(), self.out_proj.weight.t().to(y2.dtype))
+                out = ssi.out_proj_shared(self.out_proj.weight, y, tm)      # (B*L, D): the SSI:517 dispatch in y's storage order
                 if self.out_proj.bias is not None:
                     out = out + self.out_proj.bias.to(out.dtype)
                 out = out.reshape(batch, seqlen, -1)

@@ -53,14 +53,13 @@ def _autocast_dtype():
 # =================================================================================================
 # gradient homes
 # =================================================================================================
-# Under DistributedDataParallel(gradient_as_bucket_view=True) a parameter's gradient lives in a view of a flat bucket.  With
-# zero_grad(set_to_none=True) (torch's default) every backward produces a NEW gradient tensor and the reducer's per-parameter hook copies
-# it into the bucket: 271 copy launches and 2 x 368 MB of traffic per AuM-Base step, 1.3 ms of GPU time with no wire at all
+# Under DistributedDataParallel(gradient_as_bucket_view=True) a parameter's gradient lives in a view of a flat bucket, and with
+# zero_grad(set_to_none=True) every backward produces a NEW gradient tensor that the reducer's hook copies into the bucket
 # (profiles/r06_ddp_overhead.txt).  A parameter that carries `_aum_grad_home` (adopt_grad_homes: the bucket view the reducer gave it in an
 # earlier step) has its gradient WRITTEN there by the kernel that finishes it -- the weight-gradient sums, the scan's parameter sums, the norm's
-# weight sum -- and what the autograd function returns is a fresh alias of that view: the accumulator keeps it without a copy, the
-# reducer's hook finds a gradient that already aliases its bucket and copies nothing.  A stale home (buckets rebuilt, another wrapper) only
-# costs the copy it was meant to save: the reducer then copies as before.
+# weight sum -- and what the autograd function returns is a fresh alias of that view: the accumulator keeps it without a copy, the reducer's
+# hook finds a gradient that already aliases its bucket and copies nothing.  A stale home (buckets rebuilt, another wrapper) only costs the
+# copy it was meant to save: the reducer then copies as before.
 def grad_home(p):
     """where parameter p's gradient is wanted, or None.  Only while p.grad is None: a backward that ACCUMULATES (gradient accumulation,
     no_sync) must not overwrite what it is added to."""
@@ -122,14 +121,12 @@ _A_OWNER = {}           # storage address of a cached A (neg_exp) -> the A_log p
 # =================================================================================================
 # per-forward weight cache
 # =================================================================================================
-# What autocast does per call -- one fp32 -> 16-bit cast kernel per projection weight and layer, plus this package's transposed
-# copies for the data-gradient kernels and the two -exp(A_log) chains -- is ~250 launches of 3-6 us per AuM-Base step.  A model
-# that owns many blocks can do all of it in a handful of launches at the top of its forward (`with step_cache(mixers, dtype)`); the
-# blocks then find their 16-bit weights, the transposes and A here.  Entries live for one forward (the autograd graph keeps what the
-# backward needs); a Mamba block used on its own finds nothing and casts per call, exactly as before.
+# What autocast does per call -- one fp32 -> 16-bit cast kernel per projection weight and layer, plus this package's transposed copies for
+# the data-gradient kernels and the two -exp(A_log) chains -- a model that owns many blocks does in a handful of launches at the top of its
+# forward (`with step_cache(mixers, dtype)`); the blocks then find their 16-bit weights, the transposes and A here.  Entries live for one
+# forward (the autograd graph keeps what the backward needs); a Mamba block used on its own finds nothing and casts per call.
 # NOT thread-safe: the dict is process-global and keyed by id(parameter); two forwards of the SAME model in two threads would pop each
-# other's entries (the result stays right -- a missing entry is a per-call cast -- but the saving is lost).  One forward per process at a
-# time is what the launcher and bench.py do.
+# other's entries (the result stays right -- a missing entry is a per-call cast -- but the saving is lost).
 _STEP_CACHE = {}
 _CAST_HIP = _dbg_env("AUM_CAST_LIB", "0") != "1"         # AUM_DEBUG=1 AUM_CAST_LIB=1: the step cache's casts / transposes as torch copies (A/B)
 
@@ -146,7 +143,7 @@ def step_cache(mixers, dtype):
                 # data gradient on the MFMA kernel: g [tokens, out] @ W [out, in] = gemm_tn(g, W^T [in, out]) -> (N, K) = (in, out)
                 want_t = name in ("x_proj", "dt_proj", "x_proj_b", "dt_proj_b") or (
                     torch.is_grad_enabled() and lin.weight.is_cuda and lin.weight.dim() == 2
-                    and _hip_gemm_ok(lin.weight.new_empty(0, dtype=dtype), lin.weight.shape[1], lin.weight.shape[0]))
+                    and _to_gemm_tn(lin.weight.shape[1], lin.weight.shape[0], dtype, True))
                 groups.setdefault((want_t, tuple(lin.weight.shape), lin.weight.device), []).append(lin.weight)
         a_logs += [p for p in (getattr(m, "A_log", None), getattr(m, "A_b_log", None)) if p is not None]
     mine, a_ptrs = [], []
@@ -333,17 +330,10 @@ def selective_scan_ref(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
 # =================================================================================================
 # fused inner blocks  (SSI:155-633)
 # =================================================================================================
-# The token count of an AuM batch is batch * 513 -- never a multiple of a GEMM tile.  The library's kernels launch one workgroup per
-# output tile, so the 64 tokens past 32768 (B = 64) add a whole extra round of workgroups to a 3-7 round GEMM (cold-cache, one
-# box: in_proj forward 175 vs 144 us, out_proj data gradient 138 vs 90 us for 32832 vs 32768 tokens, profiles/
-# r02_sweep_gemm_tokens.txt).  The four big projection GEMMs are therefore issued as a tile-aligned GEMM over the first
-# n0 = 256 * floor(ntok / 256) tokens plus a small one over the remainder, both writing slices of one output.  AUM_GEMM_TOKEN_SPLIT is
-# a bit mask for A/B runs (1 in_proj forward, 2 out_proj forward, 4 out_proj data gradient, 8 in_proj data gradient).  Same-box A/B of the
-# step: mask 0 / 1 / 2 / 4 / 8 / 15 / 13 = 80.06 / 79.67 / 80.10 / 79.53 / 79.63 / 78.97 / 78.87 ms -> default 13 in rounds 2-4 (the out_proj
-# forward loses what it gains to its 17 us remainder GEMM).  Round 5 re-measured it on the token-major block, where the out_proj data gradient
-# runs on aum_gemm_tn (ragged rows in its stride) and the in_proj data gradient is a different library call than in round 2
-# (profiles/r05_gemm_dispatch_ab.txt, same box x3, ms per step): 13: 61.58 / 61.54 / 61.54, 0: 61.20 / 61.26 / 61.17, 1: 61.17 / 61.26 / 61.19,
-# 8: 61.75 / 61.61 / 61.74 -- the in_proj data gradient's split now COSTS 0.4 ms, the in_proj forward's is level -> default 0 (single GEMMs).
+# The token count of an AuM batch is batch * 513 -- never a multiple of a GEMM tile, and the library launches a whole extra round of workgroups
+# for the ragged tail (profiles/r02_sweep_gemm_tokens.txt).  A projection GEMM can therefore be issued as a tile-aligned GEMM over the first
+# n0 = 256 * floor(ntok / 256) tokens plus a small one over the remainder.  Chosen since round 5: no split (profiles/r05_gemm_dispatch_ab.txt;
+# HISTORY.md 7, rounds 2 and 5).  AUM_DEBUG=1 AUM_GEMM_TOKEN_SPLIT: bit mask, 1 / 2 in / out_proj forward, 8 / 4 their data gradients.
 _TOKEN_SPLIT = int(_dbg_env("AUM_GEMM_TOKEN_SPLIT", "0"))
 
 
@@ -352,34 +342,40 @@ def _tok_n0(ntok, bit, t):
     return n0 if (_TOKEN_SPLIT & bit) and t.is_cuda and ntok >= 8192 and 0 < n0 < ntok else 0
 
 
+def _mm_split(a, b, bit, cols):
+    """a @ b as one GEMM, or as two at the last multiple of 256 tokens (_tok_n0).  The tokens are the rows of a and of the result, or with
+    `cols` the columns of b and of the result"""
+    n0 = _tok_n0(b.shape[1] if cols else a.shape[0], bit, a)
+    if not n0:
+        return torch.matmul(a, b)
+    out = torch.empty((a.shape[0], b.shape[1]), dtype=a.dtype, device=a.device)
+    if cols:
+        torch.matmul(a, b[:, :n0], out=out[:, :n0])
+        torch.matmul(a, b[:, n0:], out=out[:, n0:])
+    else:
+        torch.matmul(a[:n0], b, out=out[:n0])
+        torch.matmul(a[n0:], b, out=out[n0:])
+    return out
+
+
 def _mm_tokens_cols(a, bt, bit):
     """a [M, K] @ bt[ntok, K]^T -> [M, ntok] (tokens = output columns)"""
-    ntok = bt.shape[0]
-    n0 = _tok_n0(ntok, bit, bt)
-    if not n0:
-        return torch.matmul(a, bt.t())
-    out = torch.empty((a.shape[0], ntok), dtype=a.dtype, device=a.device)
-    torch.matmul(a, bt[:n0].t(), out=out[:, :n0])
-    torch.matmul(a, bt[n0:].t(), out=out[:, n0:])
-    return out
+    return _mm_split(a, bt.t(), bit, True)
 
 
 def _mm_tokens_rows(at, b, bit):
     """at[K, ntok]^T @ b [K, N] -> [ntok, N] (tokens = output rows); `at` is the channel-major activation"""
-    ntok = at.shape[1]
-    n0 = _tok_n0(ntok, bit, at)
-    if not n0:
-        return torch.matmul(at.t(), b)
-    out = torch.empty((ntok, b.shape[1]), dtype=at.dtype, device=at.device)
-    torch.matmul(at[:, :n0].t(), b, out=out[:n0])
-    torch.matmul(at[:, n0:].t(), b, out=out[n0:])
-    return out
+    return _mm_split(at.t(), b, bit, False)
 
 
-# split-K counts of the in / out projection weight gradients, in order of preference: the first that divides K = batch * len is
-# used (B = 64, L = 513: 6 and 9; the long-form 8 x 4097 tokens: 4 and 8).  Same-box A/B of the step with the counts of round 1
-# (4, 8): 82.42 -> 81.63 ms; cold-cache sweep of the two GEMMs incl. their partial sums in profiles/r02_sweep_wgrad_splits.txt
-# (out_proj 8 / 9 splits: 123 / 98 us).  AUM_WGRAD_SPLITS="in,out" forces a pair for sweeps.
+def _mm_rows(a, b, bit):
+    """a [ntok, K] @ b [K, N] -> [ntok, N] (tokens = rows of a)"""
+    return _mm_split(a, b, bit, False)
+
+
+# split-K counts of the in / out projection weight gradients, in order of preference: the first that divides K = batch * len is used
+# (B = 64, L = 513: 6 and 9; the long-form 8 x 4097 tokens: 4 and 8).  Chosen on profiles/r02_sweep_wgrad_splits.txt (HISTORY.md 7, round 2);
+# AUM_DEBUG=1 AUM_WGRAD_SPLITS="in,out" forces a pair for sweeps.
 _WGRAD_SPLITS = ((6, 4, 8, 2), (9, 8, 4, 2))
 if _dbg_env("AUM_WGRAD_SPLITS", ""):
     _WGRAD_SPLITS = tuple((int(v),) for v in _dbg_env("AUM_WGRAD_SPLITS", "").split(","))
@@ -392,11 +388,9 @@ def _pick_splits(K, prefs):
 
 
 def split_k_wgrad(a_mk, b_kn, splits, out_dtype=None):
-    """a_mk [M, K] @ b_kn [K, N] with a long K (= batch*len tokens) and a small [M, N] result: the weight-gradient GEMMs
-    of the in/out projections.  hipBLASLt's best single-GEMM solutions keep the matrix pipe 20-31 % busy on these shapes
-    (profiles/r01_mfma_busy.txt: 18-48 output tiles for 256 CUs); splitting K into `splits` batched GEMMs on strided
-    views (no copies) and summing the partial products in fp32 fills the chip (sweep on one box, in/out splits: 4/8 85.0,
-    8/8 86.1, 16/8 85.5, 4/4 85.8, 4/16 85.4, 2/8 85.9 ms per step; single GEMMs 87.9).  AUM_WGRAD_SPLIT=0 restores the single GEMM.
+    """a_mk [M, K] @ b_kn [K, N] with a long K (= batch*len tokens) and a small [M, N] result: the weight-gradient GEMMs of the in/out
+    projections.  A single GEMM has 18-48 output tiles for 256 CUs (profiles/r01_mfma_busy.txt); K is split into `splits` batched GEMMs on
+    strided views (no copies) whose fp32 partial products are summed (HISTORY.md 7, round 1).  AUM_DEBUG=1 AUM_WGRAD_SPLIT=0: the single GEMM.
     out_dtype: the parameter's dtype -- the fp32 sum is handed over as it is instead of being rounded to 16 bits and widened again by
     autograd (two cast launches per weight; the reference's autocast GEMM rounds its weight gradient to 16 bits, this one does not)."""
     K = a_mk.shape[1]
@@ -468,30 +462,11 @@ class InProjFn(torch.autograd.Function):
         return dw, (None if dh is None else dh.to(ctx.hdtype))
 
 
-def _mm_rows(a, b, bit):
-    """a [ntok, K] @ b [K, N] -> [ntok, N] with the tile-aligned token split of _mm_tokens_rows (tokens = rows of a)"""
-    ntok = a.shape[0]
-    n0 = _tok_n0(ntok, bit, a)
-    if not n0:
-        return torch.matmul(a, b)
-    out = torch.empty((ntok, b.shape[1]), dtype=a.dtype, device=a.device)
-    torch.matmul(a[:n0], b, out=out[:n0])
-    torch.matmul(a[n0:], b, out=out[n0:])
-    return out
-
-
-# The K-contiguous projection GEMMs of the token-major block -- in_proj / out_proj forward, and their data gradients against the cached
-# transposed weight -- can run on the hand-written MFMA kernel (aum_hip.gemm_tn, csrc/gemm_kernels.h) whenever the operands qualify
-# (16-bit, device, widths that are multiples of 256 / 64).  Which of them do is decided by the step, not by the kernel alone
-# (profiles/r03_gemm_step_ab.txt, same box, ms per step): library only 67.49; + out_proj data gradient (N = 1536, K = 768) 66.77;
-# + in_proj forward (3072, 768) 66.20 -- alone the kernel is 10 % behind the library on that one, but it takes the 64 ragged rows of
-# 64 x 513 tokens in its stride where the library needs a second launch (152.6 + 19 us); + out_proj forward (768, 1536) 66.93; all four
-# 67.0-70.1 (N = 768 is two tiles per CU: tile quantisation, DESIGN 4.8).  The default ("auto") therefore sends the two N >= 1536 shapes
-# to the kernel; AUM_DEBUG=1 AUM_GEMM=hip sends all four, AUM_GEMM=lib none, AUM_GEMM_SHAPES="NxK,..." another set (A/B runs).  The weight
-# gradients (token-contiguous operands) and everything that does not qualify stay library GEMMs.
 _V2_STREAMS = _dbg_env("AUM_V2_STREAMS", "1") != "0"        # Bi-Bi: the second pipeline on a side stream (mamba_simple.py); 0: in line (A/B)
 _side_streams = {}
 _main_streams = {}
+
+
 def v2_two_streams(params=(), module=None):
     """Bi-Bi's second pipeline on a side stream?  Autograd runs each pipeline's backward on the stream of its forward, so anything that
     consumes a parameter gradient INSIDE backward sees two producer streams.  DistributedDataParallel's reducer orders a bucket's
@@ -557,47 +532,76 @@ _DTPROJ_HIP = _dbg_env("AUM_DTPROJ_LIB", "0") != "1"        # AUM_DEBUG=1 AUM_DT
 # AUM_DEBUG=1 AUM_DELTA_IN_XDT=0: dt_bias and the softplus back inside both token-major scans (A/B).  By default the fused x/dt kernel writes
 # delta = softplus(raw + dt_bias) once and the scans read it as it is (AUM_SCAN_DELTA_ACTIVATED).
 _DELTA_IN_XDT = _dbg_env("AUM_DELTA_IN_XDT", "1") != "0"
+
+
+# =================================================================================================
+# the in / out projections of the token-major block
+# =================================================================================================
+# The K-contiguous projection GEMMs -- in_proj / out_proj forward, and their data gradients against the cached transposed weight -- run on the
+# hand-written MFMA kernel (aum_hip.gemm_tn, csrc/gemm_kernels.h) where the operands qualify AND the step is faster with it: "auto" sends the
+# (N, K) shapes of _HIP_GEMM_FASTER (profiles/r03_gemm_step_ab.txt, r05_gemm_dispatch_ab.txt; HISTORY.md 7, rounds 3 and 5).  AUM_DEBUG=1
+# AUM_GEMM=hip sends every qualifying shape, AUM_GEMM=lib none, AUM_GEMM_SHAPES="NxK,..." another set.  The rest stays a library GEMM.
 _GEMM_MODE = _dbg_env("AUM_GEMM", "auto")
 if _GEMM_MODE not in ("auto", "hip", "lib"):
     raise ValueError("AUM_GEMM takes auto, hip or lib")
 _HIP_GEMM = _GEMM_MODE != "lib"
-# (N, K) of aum_gemm_tn calls that make the STEP faster than the library's solutions do.  Round 5 re-measured the in_proj forward (3072, 768), the default
-# since round 3 on a step A/B "level within the box spread": same box, three alternating rounds (profiles/r05_gemm_dispatch_ab.txt), ms per step --
-# out_proj data gradient only 62.62 / 62.54 / 62.54, both 62.67 / 62.73 / 62.88, in_proj forward only 63.65 / 63.63 / 63.40, library only
-# 63.14 / 63.12 / 62.99: the kernel is 5-8 % behind the library standalone on that shape (155-160 vs 146-148 us) and does not win it back in the
-# step.  The library keeps it; the out_proj data gradient (84 vs 91 us standalone, -0.5 ms in the step) stays on the kernel.
 _HIP_GEMM_FASTER = {(1536, 768), (3072, 768)}
 if _dbg_env("AUM_GEMM_SHAPES", ""):         # A/B runs: another set, "NxK,NxK"
     _HIP_GEMM_FASTER = {tuple(int(v) for v in sh.split("x")) for sh in _dbg_env("AUM_GEMM_SHAPES", "").replace("+", ",").split(",")}
 
 
-def _hip_gemm_ok(a, n, k):
-    return (_HIP_GEMM and a.is_cuda and a.dtype in (torch.bfloat16, torch.float16) and n % aum_hip.GEMM_BN == 0 and k % aum_hip.GEMM_BK == 0
+def _to_gemm_tn(n, k, dtype, is_cuda):
+    """does a [ntok, K] @ [N, K]^T product of this shape go to aum_gemm_tn?  (the operands' strides and alignment: aum_hip.gemm_tn_supported)"""
+    return (_HIP_GEMM and is_cuda and dtype in (torch.bfloat16, torch.float16) and n % aum_hip.GEMM_BN == 0 and k % aum_hip.GEMM_BK == 0
             and (_GEMM_MODE == "hip" or (n, k) in _HIP_GEMM_FASTER))
 
 
-def _gemm_rows(a, w_nk, bit):
-    """a [ntok, K] @ w_nk [N, K]^T -> [ntok, N]"""
-    if _hip_gemm_ok(a, w_nk.shape[0], w_nk.shape[1]) and aum_hip.gemm_tn_supported(a, w_nk):
-        return aum_hip.gemm_tn(a, w_nk)
-    return _mm_rows(a, w_nk.t(), bit)
+def _hip_gemm_ok(a, n, k):
+    return _to_gemm_tn(n, k, a.dtype, a.is_cuda)
 
 
 def _weight_t_for_dgrad(w_param, w_cast, a_is_cuda):
     """the (K, N) -> (N, K) transposed 16-bit copy of a projection weight for the data-gradient GEMM on the MFMA kernel (from the step
     cache when a model filled it), or None when that GEMM stays with the library (which takes the weight as stored)"""
-    n, k = w_cast.shape[1], w_cast.shape[0]          # the data gradient multiplies by w (k = out features, n = in features)
-    if not (_HIP_GEMM and a_is_cuda and w_cast.dtype in (torch.bfloat16, torch.float16) and n % aum_hip.GEMM_BN == 0 and k % aum_hip.GEMM_BK == 0
-            and (_GEMM_MODE == "hip" or (n, k) in _HIP_GEMM_FASTER)):
-        return None
-    return _cast_t(w_param, w_cast.dtype)
+    # the data gradient multiplies by w: k = out features, n = in features
+    return _cast_t(w_param, w_cast.dtype) if _to_gemm_tn(w_cast.shape[1], w_cast.shape[0], w_cast.dtype, a_is_cuda) else None
 
 
-def _gemm_dgrad(g, w_cast, w_t, bit):
-    """g [ntok, K] @ w_cast [K, N] -> [ntok, N]; w_t = w_cast^T contiguous or None"""
-    if w_t is not None and aum_hip.gemm_tn_supported(g, w_t):
-        return aum_hip.gemm_tn(g, w_t)
-    return _mm_rows(g, w_cast, bit)
+# which projection: (token-split bit of the forward, token-split bit of the data gradient, index into _WGRAD_SPLITS)
+_IN_PROJ, _OUT_PROJ = (1, 8, 0), (2, 4, 1)
+
+
+def _proj_fwd(rows, w, proj):
+    """rows [ntok, K] @ w [N, K]^T -> [ntok, N]  (MS:185-189, SSI:517 on token-major rows)"""
+    if _hip_gemm_ok(rows, w.shape[0], w.shape[1]) and aum_hip.gemm_tn_supported(rows, w):
+        return aum_hip.gemm_tn(rows, w)
+    return _mm_rows(rows, w.t(), proj[0])
+
+
+def _proj_bwd(g, rows, w, w_t, proj, wdtype, home, want_rows=True, want_w=True, pending=None):
+    """backward of _proj_fwd for g = d out [ntok, N] in w's dtype -> (d rows, d W).  w_t: _weight_t_for_dgrad's copy or None; wdtype, home: the
+    parameter's dtype and grad_home.  With `pending` d W may be an index into its sums and the caller hands it over (_homed) after run()"""
+    d_rows = None
+    if want_rows:
+        d_rows = aum_hip.gemm_tn(g, w_t) if w_t is not None and aum_hip.gemm_tn_supported(g, w_t) else _mm_rows(g, w, proj[1])
+    dw = _wgrad_tm(g, rows, _WGRAD_SPLITS[proj[2]], wdtype, pending, home=home) if want_w else None
+    return d_rows, (dw if pending is not None else _homed(dw, home))
+
+
+def _proj_tm_forward(ctx, weight, rows2d, proj):
+    w = _cast(weight, _autocast_dtype())
+    rows = rows2d.to(w.dtype)
+    w_t = _weight_t_for_dgrad(weight, w, rows.is_cuda) if ctx.needs_input_grad[1] else None
+    ctx.save_for_backward(w, rows, w_t)
+    ctx.wdtype, ctx.rdtype, ctx.wparam = weight.dtype, rows2d.dtype, weight
+    return _proj_fwd(rows, w, proj)
+
+
+def _proj_tm_backward(ctx, g, proj):
+    w, rows, w_t = ctx.saved_tensors
+    d_rows, dw = _proj_bwd(g.to(w.dtype), rows, w, w_t, proj, ctx.wdtype, grad_home(ctx.wparam), ctx.needs_input_grad[1],
+                           ctx.needs_input_grad[0])
+    return dw, (None if d_rows is None else d_rows.to(ctx.rdtype))
 
 
 class InProjTmFn(torch.autograd.Function):
@@ -606,47 +610,34 @@ class InProjTmFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, hidden2d):
-        w = _cast(weight, _autocast_dtype())
-        h = hidden2d.to(w.dtype)
-        w_t = _weight_t_for_dgrad(weight, w, h.is_cuda) if ctx.needs_input_grad[1] else None
-        ctx.save_for_backward(w, h, w_t)
-        ctx.wdtype, ctx.hdtype = weight.dtype, hidden2d.dtype
-        ctx.wparam = weight
-        return _gemm_rows(h, w, 1)
+        return _proj_tm_forward(ctx, weight, hidden2d, _IN_PROJ)
 
     @staticmethod
     def backward(ctx, dxz2d):
-        w, h, w_t = ctx.saved_tensors
-        dxz2d = dxz2d.to(w.dtype)
-        dh = _gemm_dgrad(dxz2d, w, w_t, 8) if ctx.needs_input_grad[1] else None
-        home = grad_home(ctx.wparam)
-        dw = _homed(_wgrad_tm(dxz2d, h, _WGRAD_SPLITS[0], ctx.wdtype, home=home), home) if ctx.needs_input_grad[0] else None
-        return dw, (None if dh is None else dh.to(ctx.hdtype))
+        return _proj_tm_backward(ctx, dxz2d, _IN_PROJ)
 
 
 class OutProjTmFn(torch.autograd.Function):
     """out2d [B*L, D] = y2d [B*L, E] @ W_out^T on token-major rows (SSI:517 for the Bi-Bi block, whose two pipelines share one out_proj,
-    MS:240-246): the same GEMM dispatch as inside the fused inner functions -- forward and data gradient on aum_gemm_tn where the
-    step is faster with it, the weight gradient as split-K batches."""
+    MS:240-246): the same helpers as the out_proj inside the fused inner functions."""
 
     @staticmethod
     def forward(ctx, weight, y2d):
-        w = _cast(weight, _autocast_dtype())
-        y = y2d.to(w.dtype)
-        w_t = _weight_t_for_dgrad(weight, w, y.is_cuda) if ctx.needs_input_grad[1] else None
-        ctx.save_for_backward(w, y, w_t)
-        ctx.wdtype, ctx.ydtype = weight.dtype, y2d.dtype
-        ctx.wparam = weight
-        return _gemm_rows(y, w, 2)
+        return _proj_tm_forward(ctx, weight, y2d, _OUT_PROJ)
 
     @staticmethod
     def backward(ctx, dout2d):
-        w, y, w_t = ctx.saved_tensors
-        dout2d = dout2d.to(w.dtype)
-        dy = _gemm_dgrad(dout2d, w, w_t, 4) if ctx.needs_input_grad[1] else None
-        home = grad_home(ctx.wparam)
-        dw = _homed(_wgrad_tm(dout2d, y, _WGRAD_SPLITS[1], ctx.wdtype, home=home), home) if ctx.needs_input_grad[0] else None
-        return dw, (None if dy is None else dy.to(ctx.ydtype))
+        return _proj_tm_backward(ctx, dout2d, _OUT_PROJ)
+
+
+def out_proj_shared(weight, y, tm):
+    """out2d [B*L, D] = y W_out^T for Bi-Bi's shared out_proj (MS:240-246); y is (B, E, L) logical in xz's storage order: token-major rows
+    through OutProjTmFn, channel-major as one library GEMM on the [E, B*L] view"""
+    Bsz, E, L = y.shape
+    if tm:
+        return OutProjTmFn.apply(weight, y.transpose(1, 2).reshape(Bsz * L, E))
+    y2 = y.permute(1, 0, 2).reshape(E, Bsz * L)
+    return torch.matmul(y2.t(), weight.t().to(y2.dtype))
 
 
 def token_major_ok(d_inner, d_state, d_conv, dt_rank, dtype=None):
@@ -659,10 +650,9 @@ def token_major_ok(d_inner, d_state, d_conv, dt_rank, dtype=None):
 
 # The time-serial kernels give one wave to 64 channels of one batch entry and direction and walk the WHOLE sequence with it: they need
 # batch * (d_inner / 64) * directions waves to fill 256 CUs x 4 SIMDs -- 1.5 per SIMD for the forward (three resident), 2 per SIMD when a
-# backward follows (two resident at 256 VGPRs).  Short of that (long-form clips at batch 8, single-clip inference, AuM-Small training at
-# batch 64) the chunk-parallel channel-major kernels are the better division: AuM-Small, B = 64 (1536 waves), same box: training 41.2 ms
-# token-major vs 39.7 ms channel-major, forward only 11.3 vs 11.9 ms (profiles/r03_variants_bench.json).  AUM_TM_MIN_WAVES overrides
-# the forward threshold (the training one is 4/3 of it).
+# Fo-Bi backward follows (two resident at 256 VGPRs).  Short of that (long-form clips at batch 8, single-clip inference, AuM-Small training at
+# batch 64) the chunk-parallel channel-major kernels are the better division: profiles/r03_variants_bench.json, r04_variants_bench.json
+# (HISTORY.md 7, round 3).  AUM_DEBUG=1 AUM_TM_MIN_WAVES overrides the forward threshold (the training one is 4/3 of it).
 _TM_MIN_WAVES = int(_dbg_env("AUM_TM_MIN_WAVES", "1536"))
 
 
@@ -679,14 +669,16 @@ def tm_segments(batch, d_inner, seqlen, bidirectional, training, device=None):
     return aum_hip.scan_tm_segments(batch, d_inner, seqlen, bidirectional, training, device=device)
 
 
+def _tm_fills_chip(batch, d_inner, bidirectional, training):
+    """enough waves for the time-serial kernels?  The 4/3 applies to the Fo-Bi backward (three direction pairs per workgroup in three
+    stages); a one-direction launch trains token-major at the forward's threshold"""
+    need = -(-_TM_MIN_WAVES * 4 // 3) if training and bidirectional else _TM_MIN_WAVES
+    return batch * (d_inner // 64) * (2 if bidirectional else 1) >= need
+
+
 def token_major_preferred(batch, d_inner, bidirectional, training=None, seqlen=None):
     training = torch.is_grad_enabled() if training is None else training
-    # (the 4/3 applies to the Fo-Bi backward -- three direction pairs per workgroup in three stages; a one-direction launch of 1536 waves
-    # trains faster token-major: Fo-Fo AuM-Base at batch 64, 54.7 ms against 60.4 ms channel-major, profiles/r03 / r04_variants_bench.json)
-    need = -(-_TM_MIN_WAVES * 4 // 3) if training and bidirectional else _TM_MIN_WAVES
-    if batch * (d_inner // 64) * (2 if bidirectional else 1) >= need:
-        return True
-    return tm_segments(batch, d_inner, seqlen, bidirectional, training) > 1
+    return _tm_fills_chip(batch, d_inner, bidirectional, training) or tm_segments(batch, d_inner, seqlen, bidirectional, training) > 1
 
 
 def _is_tm(xz):
@@ -694,141 +686,156 @@ def _is_tm(xz):
     return xz.dim() == 3 and xz.stride(1) == 1 and xz.shape[1] > 1
 
 
+def _xdt_fwd(conv2d, w_x, w_dt, R, delta_bias, delta_softplus):
+    """x_dbl (BL, R + 2N) = conv2d W_x^T (SSI:467), delta (BL, E) = x_dbl[:, :R] W_dt^T (SSI:468) -> (x_dbl, delta, act_delta).  act_delta:
+    delta left the fused kernel as softplus(raw + dt_bias) (SSI:106-107), the scans read it as it is.  Shapes the kernels refuse fall back
+    to the library products"""
+    if _XDT_HIP and conv2d.is_cuda and aum_hip.xdt_tm_supported(conv2d, w_x, w_dt):
+        act_delta = _DELTA_IN_XDT and bool(delta_softplus)
+        x_dbl, delta = aum_hip.xdt_tm_fwd(conv2d, w_x, w_dt, delta_bias=delta_bias if act_delta else None, delta_softplus=act_delta)
+        return x_dbl, delta, act_delta          # one pass over conv_out
+    x_dbl = torch.matmul(conv2d, w_x.t())
+    if _DTPROJ_HIP and x_dbl.is_cuda and aum_hip.dtproj_tm_supported(x_dbl, R, w_dt):
+        return x_dbl, aum_hip.dtproj_tm_fwd(x_dbl, R, w_dt), False          # the write-bound MFMA kernel
+    return x_dbl, torch.matmul(x_dbl[:, :R], w_dt.t()), False
+
+
+def _xdt_bwd(ddelta2, dbc2, du2, x_dbl, conv2d, w_x, w_dt, w_x_t, w_dt_t, R, pend, home_x, home_dt):
+    """backward of _xdt_fwd: dx_dbl = [ddelta2 W_dt | dbc2] (SSI:570-574, 587), du2 += dx_dbl W_x IN PLACE (SSI:590) and the two weight
+    gradients (SSI:589, 586) -> (dx_dbl, d W_x, d W_dt), the gradients fp32 or indices into pend's sums.  w_x_t, w_dt_t: the transposed
+    weights the forward prepared when aum_xdt_tm_bwd takes the widths, else None: the library's five calls"""
+    hip = w_x_t is not None and aum_hip.xdt_tm_bwd_supported(ddelta2, dbc2, w_dt_t, w_x_t, du2)
+    if hip:
+        dx_dbl = aum_hip.xdt_tm_bwd(ddelta2, dbc2, w_dt_t, w_x_t, du2)          # one pass over ddelta and du
+        if aum_hip.gemm_wgrad_supported(ddelta2, x_dbl[:, :R]) and aum_hip.gemm_wgrad_supported(conv2d, dx_dbl):
+            # the skinny aum_gemm_wgrad; its partial sets join the function's one sum launch (x_proj's stored in the (R + 2N, E) layout)
+            ddt_w = pend.add(aum_hip.gemm_wgrad(ddelta2, x_dbl[:, :R], partials=True), out=home_dt)              # (E, R) fp32
+            dx_w = pend.add(aum_hip.gemm_wgrad(conv2d, dx_dbl, partials=True), x_dbl.shape[1], out=home_x)       # (R + 2N, E) fp32
+            return dx_dbl, dx_w, ddt_w
+        # (what that kernel's argument check would refuse, e.g. 32-bit byte offsets: the library's split-K products below, no raise)
+    else:
+        dx_dbl = torch.empty_like(x_dbl)
+        dx_dbl[:, R:].copy_(dbc2)
+        dx_dbl[:, :R].copy_(torch.matmul(ddelta2, w_dt.to(ddelta2.dtype)))
+    splits = _pick_splits(x_dbl.shape[0], _WGRAD_SPLITS[1])
+    ddt_w = split_k_wgrad(ddelta2.t(), x_dbl[:, :R], splits, torch.float32)
+    dx_w = split_k_wgrad(dx_dbl.t(), conv2d, splits, torch.float32)
+    if not hip:
+        du2.addmm_(dx_dbl, w_x.to(dx_dbl.dtype))
+    return dx_dbl, dx_w, ddt_w
+
+
+def _out_proj_bwd(ctx, dout, w, w_t, out_z2, pend, home):
+    """the out_proj part of both blocks' backward (SSI:540, 563) -> (d out_z in out_z2's layout, d W_out, d bias).  Token-major: out_z2
+    [BL, E], the projection helpers (d W_out possibly an index into pend's sums); channel-major: out_z2 [E, BL], library GEMMs"""
+    dout2 = dout.reshape(out_z2.shape[0 if ctx.tm else 1], -1).to(w.dtype)
+    if ctx.tm:
+        dout_z2, dw = _proj_bwd(dout2, out_z2, w, w_t, _OUT_PROJ, ctx.out_proj_wdtype, home, pending=pend)
+    else:
+        dout_z2 = _mm_tokens_cols(w.t(), dout2, 4)
+        dw = split_k_wgrad(dout2.t(), out_z2.t(), _pick_splits(dout2.shape[0], _WGRAD_SPLITS[1]), ctx.out_proj_wdtype)
+    return dout_z2, dw, (dout2.sum(0) if not ctx.out_proj_bias_is_None else None)
+
+
 def _inner_forward_tm(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b, D,
                       delta_bias, delta_softplus, reverse):
     """_inner_forward on token-major activations: every tensor is (B, L, X) with X contiguous.
-      conv (SSI:463) -> x_dbl = conv_out W_x^T (SSI:467) -> delta = x_dbl[:, :R] W_dt^T (SSI:468) -> B, C = column blocks of x_dbl read in
-      place (SSI:473-493) -> one selective-scan launch, both directions (SSI:499-507) -> out_proj (SSI:517)."""
+      conv (SSI:463) -> x/dt projections (SSI:467-468) -> B, C = column blocks of x_dbl read in place (SSI:473-493) -> one selective-scan
+      launch, both directions (SSI:499-507) -> out_proj (SSI:517)."""
     act = _autocast_dtype()
-    ctx.out_proj_wdtype = out_proj_weight.dtype if out_proj_weight is not None else None
-    x_proj_param, delta_proj_param = x_proj_weight, delta_proj_weight
-    x_proj_weight, delta_proj_weight = _cast(x_proj_weight, act), _cast(delta_proj_weight, act)
-    out_proj_param = out_proj_weight
-    out_proj_weight, out_proj_bias = _cast(out_proj_weight, act), _cast(out_proj_bias, act)
-    out_proj_wt = None
-    if out_proj_weight is not None and any(ctx.needs_input_grad):
-        out_proj_wt = _weight_t_for_dgrad(out_proj_param, out_proj_weight.to(xz.dtype), xz.is_cuda)
+    need_bwd = any(ctx.needs_input_grad)
+    bidir = A_b is not None
     xz_t = xz.transpose(1, 2)                                      # (B, L, 2E), rows contiguous
     Bsz, L, two_e = xz_t.shape
-    E = two_e // 2
-    R = delta_proj_weight.shape[1]
-    N = A.shape[-1]
+    E, R, N = two_e // 2, delta_proj_weight.shape[1], A.shape[-1]
     x, z = xz_t[:, :, :E], xz_t[:, :, E:]
+    # weights: the 16-bit copies, and the transposes the backward's kernels multiply by (from the step cache when the model filled it)
+    w_x, w_dt = _cast(x_proj_weight, act), _cast(delta_proj_weight, act)
+    w_out, out_proj_bias = _cast(out_proj_weight, act), _cast(out_proj_bias, act)
+    w_out_t = _weight_t_for_dgrad(out_proj_weight, w_out.to(xz.dtype), xz.is_cuda) if w_out is not None and need_bwd else None
+    # conv
     conv_w = conv1d_weight.reshape(E, -1)
     conv_out = aum_hip.conv1d_tm_fwd(x, conv_w, conv1d_bias, True, reverse)                 # SSI:463  (B, L, E)
     conv2d = conv_out.view(Bsz * L, E)
-    w_x, w_dt = x_proj_weight.to(conv2d.dtype), delta_proj_weight.to(conv2d.dtype)
-    act_delta = False           # delta leaves the x/dt kernel as softplus(raw + dt_bias): the scans read it as it is
-    if _XDT_HIP and conv2d.is_cuda and aum_hip.xdt_tm_supported(conv2d, w_x, w_dt):
-        act_delta = _DELTA_IN_XDT and bool(delta_softplus)
-        x_dbl, delta = aum_hip.xdt_tm_fwd(conv2d, w_x, w_dt, delta_bias=delta_bias if act_delta else None,
-                                          delta_softplus=act_delta)                           # SSI:467-468 in one pass over conv_out (+ SSI:106-107)
-    else:
-        x_dbl = torch.matmul(conv2d, w_x.t())                                                # SSI:467  (BL, R+2N)
-        delta = None
-    if delta is not None:
-        pass
-    elif _DTPROJ_HIP and x_dbl.is_cuda and aum_hip.dtproj_tm_supported(x_dbl, R, w_dt):
-        delta = aum_hip.dtproj_tm_fwd(x_dbl, R, w_dt)                                        # SSI:468  (BL, E): the write-bound MFMA kernel
-    else:
-        delta = torch.matmul(x_dbl[:, :R], w_dt.t())
+    # x/dt
+    x_dbl, delta, act_delta = _xdt_fwd(conv2d, w_x.to(conv2d.dtype), w_dt.to(conv2d.dtype), R, delta_bias, delta_softplus)
     x3 = x_dbl.view(Bsz, L, R + 2 * N)
     Bm, Cm = x3[:, :, R:R + N], x3[:, :, R + N:]                                            # SSI:479  views, no copies
-    need_bwd = any(ctx.needs_input_grad)
-    # the backward's row pass (aum_xdt_tm_bwd) multiplies by the two small weights the other way round: their transposes, from the
-    # step cache when the model filled it
     w_x_t = w_dt_t = None
-    if need_bwd and _XDT_BWD_HIP and conv2d.is_cuda and R + 2 * N in aum_hip.XDT_COLS_BWD and N == 16 and E % 256 == 0 \
-            and E <= aum_hip.XDT_MAX_DIM and conv2d.dtype in (torch.bfloat16, torch.float16):
-        w_x_t, w_dt_t = _cast_t(x_proj_param, conv2d.dtype), _cast_t(delta_proj_param, conv2d.dtype)
-    ckpt = aum_hip.scan_tm_ckpt(Bsz, L, E, N, A_b is not None, xz.device, dtype=conv_out.dtype) if need_bwd else None
-    waves = Bsz * (E // 64) * (2 if A_b is not None else 1)
-    cut = waves < (-(-_TM_MIN_WAVES * 4 // 3) if need_bwd and A_b is not None else _TM_MIN_WAVES)
+    if need_bwd and _XDT_BWD_HIP and conv2d.is_cuda and aum_hip.xdt_tm_bwd_widths(E, R, N, conv2d.dtype):
+        w_x_t, w_dt_t = _cast_t(x_proj_weight, conv2d.dtype), _cast_t(delta_proj_weight, conv2d.dtype)
+    # scan: rows too few to fill the chip are cut into time segments
+    ckpt = aum_hip.scan_tm_ckpt(Bsz, L, E, N, bidir, xz.device, dtype=conv_out.dtype) if need_bwd else None
+    cut = not _tm_fills_chip(Bsz, E, bidir, need_bwd)
     out_z, out_pre = aum_hip.scan_tm_fwd(conv_out, delta.view(Bsz, L, E), A, Bm, Cm, D, z, delta_bias, delta_softplus,
-                                         reverse if A_b is None else False, A_b=A_b, want_out_pre=need_bwd, ckpt=ckpt,
-                                         segments=tm_segments(Bsz, E, L, A_b is not None, False, device=xz.device) if cut else 1,
+                                         False if bidir else reverse, A_b=A_b, want_out_pre=need_bwd, ckpt=ckpt,
+                                         segments=tm_segments(Bsz, E, L, bidir, False, device=xz.device) if cut else 1,
                                          delta_activated=act_delta)
-    ctx.tm_cut, ctx.act_delta = cut, act_delta
+    # what the backward needs
+    ctx.tm, ctx.tm_cut, ctx.act_delta = True, cut, act_delta
+    ctx.delta_softplus, ctx.reverse = delta_softplus, reverse
+    ctx.has_out_proj, ctx.out_proj_bias_is_None = w_out is not None, out_proj_bias is None
+    ctx.out_proj_wdtype = out_proj_weight.dtype if out_proj_weight is not None else None
     # the scan backward forms d A .* A only for an A that neg_exp took out of THIS forward's cache (its _NegExpFn node is the consumer)
     ctx.A_cached = (need_bwd and A.dtype == torch.float32 and A.is_contiguous() and A.data_ptr() in _A_CACHE_PTRS
-                    and (A_b is None or (A_b.is_contiguous() and A_b.data_ptr() in _A_CACHE_PTRS)))
-    ctx.tm = True
+                    and (not bidir or (A_b.is_contiguous() and A_b.data_ptr() in _A_CACHE_PTRS)))
     # the parameters behind this call's gradients (grad_home looks at them in the backward)
-    ctx.params = dict(conv_w=conv1d_weight, conv_b=conv1d_bias, x_proj=x_proj_param, dt_proj=delta_proj_param, out_proj=out_proj_param, D=D,
-                      dt_bias=delta_bias, A_log=_A_OWNER.get(A.data_ptr()), A_b_log=None if A_b is None else _A_OWNER.get(A_b.data_ptr()))
-    ctx.delta_softplus, ctx.reverse = delta_softplus, reverse
-    ctx.has_out_proj = out_proj_weight is not None
-    ctx.out_proj_bias_is_None = out_proj_bias is None
-    ctx.save_for_backward(xz, conv_w, conv1d_bias, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, D,
-                          delta_bias, out_pre, out_z, ckpt, out_proj_wt, w_x_t, w_dt_t)
-    if out_proj_weight is None:
+    ctx.params = dict(conv_w=conv1d_weight, conv_b=conv1d_bias, x_proj=x_proj_weight, dt_proj=delta_proj_weight, out_proj=out_proj_weight, D=D,
+                      dt_bias=delta_bias, A_log=_A_OWNER.get(A.data_ptr()), A_b_log=_A_OWNER.get(A_b.data_ptr()) if bidir else None)
+    ctx.save_for_backward(xz, conv_w, conv1d_bias, x_dbl, w_x, w_dt, w_out, conv_out, delta, A, A_b, D,
+                          delta_bias, out_pre, out_z, ckpt, w_out_t, w_x_t, w_dt_t)
+    # out_proj
+    if w_out is None:
         return out_z.transpose(1, 2)                                                         # SSI:224  (B, E, L) logical
-    out = _gemm_rows(out_z.view(Bsz * L, E), out_proj_weight.to(out_z.dtype), 2)             # SSI:517
+    out = _proj_fwd(out_z.view(Bsz * L, E), w_out.to(out_z.dtype), _OUT_PROJ)                # SSI:517
     if out_proj_bias is not None:
         out = out + out_proj_bias
     return out.reshape(Bsz, L, -1)
 
 
+_TM_HOMES = ("conv_w", "conv_b", "x_proj", "dt_proj", "out_proj", "D", "dt_bias", "A_log", "A_b_log")
+
+
 def _inner_backward_tm(ctx, dout):
-    (xz, conv_w, conv1d_bias, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, D, delta_bias, out_pre,
-     out_z, ckpt, out_proj_wt, w_x_t, w_dt_t) = ctx.saved_tensors
+    (xz, conv_w, conv1d_bias, x_dbl, w_x, w_dt, w_out, conv_out, delta, A, A_b, D, delta_bias, out_pre,
+     out_z, ckpt, w_out_t, w_x_t, w_dt_t) = ctx.saved_tensors
     xz_t = xz.transpose(1, 2)
     Bsz, L, two_e = xz_t.shape
-    E = two_e // 2
-    R = delta_proj_weight.shape[1]
-    N = A.shape[-1]
+    E, R, N = two_e // 2, w_dt.shape[1], A.shape[-1]
+    bidir = A_b is not None
     x, z = xz_t[:, :, :E], xz_t[:, :, E:]
     dxz_t = torch.empty((Bsz, L, two_e), dtype=xz.dtype, device=xz.device)                   # SSI:537
     dx, dz = dxz_t[:, :, :E], dxz_t[:, :, E:]
-    dout_proj_weight = dout_proj_bias = None
     pend = _PendingSums()
-    H = {k: grad_home(v) for k, v in getattr(ctx, "params", {}).items()}          # where each parameter's gradient is wanted (or None)
-    H = {k: H.get(k) for k in ("conv_w", "conv_b", "x_proj", "dt_proj", "out_proj", "D", "dt_bias", "A_log", "A_b_log")}
+    params = getattr(ctx, "params", {})
+    H = {k: grad_home(params.get(k)) for k in _TM_HOMES}          # where each parameter's gradient is wanted (or None)
+    # out_proj
+    dout_proj_weight = dout_proj_bias = None
     if ctx.has_out_proj:
-        dout2 = dout.reshape(Bsz * L, -1).to(out_proj_weight.dtype)
-        dout_z = _gemm_dgrad(dout2, out_proj_weight, out_proj_wt, 4).view(Bsz, L, E).to(conv_out.dtype)     # SSI:540
-        dout_proj_weight = _wgrad_tm(dout2, out_z.view(Bsz * L, E), _WGRAD_SPLITS[1], ctx.out_proj_wdtype, pend, home=H["out_proj"])     # SSI:563
-        dout_proj_bias = dout2.sum(0) if not ctx.out_proj_bias_is_None else None
+        dout_z, dout_proj_weight, dout_proj_bias = _out_proj_bwd(ctx, dout, w_out, w_out_t, out_z.view(Bsz * L, E), pend, H["out_proj"])
+        dout_z = dout_z.view(Bsz, L, E).to(conv_out.dtype)
     else:
         dout_z = dout.transpose(1, 2)
         dout_z = (dout_z if dout_z.stride(2) == 1 else dout_z.contiguous()).to(xz.dtype)
+    # scan
     x3 = x_dbl.view(Bsz, L, R + 2 * N)
     g = aum_hip.scan_tm_bwd(conv_out, delta.view(Bsz, L, E), A, x3[:, :, R:R + N], x3[:, :, R + N:], D, z, delta_bias, dout_z, out_pre,
-                            ckpt, ctx.delta_softplus, ctx.reverse if A_b is None else False, A_b=A_b, dz_out=dz,
-                            segments=tm_segments(Bsz, E, L, A_b is not None, True, device=conv_out.device) if ctx.tm_cut else 1,
+                            ckpt, ctx.delta_softplus, False if bidir else ctx.reverse, A_b=A_b, dz_out=dz,
+                            segments=tm_segments(Bsz, E, L, bidir, True, device=conv_out.device) if ctx.tm_cut else 1,
                             want_dA_xA=ctx.A_cached, delta_activated=ctx.act_delta,
                             param_out=dict(dD=H["D"], ddelta_bias=H["dt_bias"], dA_xA=H["A_log"], dA_b_xA=H["A_b_log"]))        # SSI:541-561
     if ctx.A_cached:            # A came out of the forward's cache (neg_exp): its d A_log is ready (see _NegExpFn)
         _da_xa_put(g["dA"], g["dA_xA"], A)
-        if A_b is not None:
+        if bidir:
             _da_xa_put(g["dA_b"], g["dA_b_xA"], A_b)
-    du2, ddelta2 = g["du"].view(Bsz * L, E), g["ddelta"].view(Bsz * L, E)
-    dbc2 = g["dBC"].view(Bsz * L, 2 * N)
-    conv2d = conv_out.view(Bsz * L, E)
-    if w_x_t is not None and aum_hip.xdt_tm_bwd_supported(ddelta2, dbc2, w_dt_t, w_x_t, du2):
-        # SSI:570-574, 587, 590 in one pass over ddelta and du (aum_xdt_tm_bwd); the two weight gradients on the skinny form of the
-        # weight-gradient kernel (aum_gemm_wgrad, k = 48 / 80 at AuM-Base, 24 / 56 at AuM-Small): every activation tensor is read once per product
-        dx_dbl = aum_hip.xdt_tm_bwd(ddelta2, dbc2, w_dt_t, w_x_t, du2)
-        # (a shape the kernel's own argument check would refuse -- e.g. a token split beyond 32-bit byte offsets -- takes the library's
-        # split-K products instead of raising inside backward)
-        splits = _pick_splits(Bsz * L, _WGRAD_SPLITS[1])
-        if aum_hip.gemm_wgrad_supported(ddelta2, x_dbl[:, :R]) and aum_hip.gemm_wgrad_supported(conv2d, dx_dbl):
-            # the partial sets join the function's one sum launch, which also stores the x_proj gradient in the parameter's (R + 2N, E) layout
-            ddelta_proj_weight = pend.add(aum_hip.gemm_wgrad(ddelta2, x_dbl[:, :R], partials=True), out=H["dt_proj"])          # SSI:586  (E, R) fp32
-            dx_proj_weight = pend.add(aum_hip.gemm_wgrad(conv2d, dx_dbl, partials=True), R + 2 * N, out=H["x_proj"])          # SSI:589  (R + 2N, E) fp32
-        else:
-            ddelta_proj_weight = split_k_wgrad(ddelta2.t(), x_dbl[:, :R], splits, torch.float32)
-            dx_proj_weight = split_k_wgrad(dx_dbl.t(), conv2d, splits, torch.float32)
-    else:
-        dx_dbl = torch.empty_like(x_dbl)
-        dx_dbl[:, R:].copy_(dbc2)                                                            # SSI:570-574
-        dx_dbl[:, :R].copy_(torch.matmul(ddelta2, delta_proj_weight.to(ddelta2.dtype)))      # SSI:587
-        splits = _pick_splits(Bsz * L, _WGRAD_SPLITS[1])
-        ddelta_proj_weight = split_k_wgrad(ddelta2.t(), x_dbl[:, :R], splits, torch.float32)     # SSI:586
-        dx_proj_weight = split_k_wgrad(dx_dbl.t(), conv2d, splits, torch.float32)            # SSI:589
-        du2.addmm_(dx_dbl, x_proj_weight.to(dx_dbl.dtype))                                   # SSI:590
+    # x/dt
+    dx_dbl, dx_proj_weight, ddelta_proj_weight = _xdt_bwd(
+        g["ddelta"].view(Bsz * L, E), g["dBC"].view(Bsz * L, 2 * N), g["du"].view(Bsz * L, E), x_dbl, conv_out.view(Bsz * L, E), w_x, w_dt,
+        w_x_t, w_dt_t, R, pend, H["x_proj"], H["dt_proj"])
+    # conv
     _, dconv_w, dconv_b = aum_hip.conv1d_tm_bwd(x, conv_w, conv1d_bias, g["du"], True, ctx.reverse, dx_out=dx, partials=True)   # SSI:594
     dconv_w, dconv_b = pend.add(dconv_w, out=H["conv_w"]), (None if dconv_b is None else pend.add(dconv_b, out=H["conv_b"]))
+    # the partial sets of the whole function in one launch
     sums = pend.run()
     dout_proj_weight, ddelta_proj_weight, dx_proj_weight, dconv_w, dconv_b = (
         sums[v] if isinstance(v, _PendingIndex) else v for v in (dout_proj_weight, ddelta_proj_weight, dx_proj_weight, dconv_w, dconv_b))
@@ -949,11 +956,8 @@ def _inner_backward(ctx, dout):
     dx, dz = dxz[:, :E], dxz[:, E:]
     dout_proj_weight = dout_proj_bias = None
     if ctx.has_out_proj:
-        dout2 = dout.reshape(Bsz * L, -1).to(out_proj_weight.dtype)
-        dout_z = _mm_tokens_cols(out_proj_weight.t(), dout2, 4).reshape(E, Bsz, L).permute(1, 0, 2)   # SSI:540
-        dout_proj_weight = split_k_wgrad(dout2.t(), _dm2d(out_z).t(), _pick_splits(dout2.shape[0], _WGRAD_SPLITS[1]),
-                                         ctx.out_proj_wdtype)                                                  # SSI:563
-        dout_proj_bias = dout2.sum(0) if not ctx.out_proj_bias_is_None else None
+        dout_z, dout_proj_weight, dout_proj_bias = _out_proj_bwd(ctx, dout, out_proj_weight, None, _dm2d(out_z), None, None)
+        dout_z = dout_z.reshape(E, Bsz, L).permute(1, 0, 2)
     else:
         dout_z = dout if dout.stride(-1) == 1 else dout.contiguous()
         dout_z = dout_z.to(xz.dtype)
@@ -981,28 +985,23 @@ def _inner_backward(ctx, dout):
                               ctx.delta_softplus, False, dz_out=dz, dmajor=True)
         del gf
     dconv_out, ddelta = g["du"], g["ddelta"]
+    dB_proj_bias = dC_proj_bias = None
+    ddelta2, dconv2 = _dm2d(ddelta), _dm2d(dconv_out)                                        # [E, BL]
     if ctx.proj_kernels:
-        ddelta2, dconv2 = _dm2d(ddelta), _dm2d(dconv_out)
         dx_dbl = aum_hip.proj_bwd_data(ddelta2, delta_proj_wt, x_proj_wt, g["dB"], g["dC"], dconv2, L)   # SSI:570-574, 587, 590
         ddelta_proj_weight = aum_hip.proj_bwd_weight(ddelta2, x_dbl[:R], False)              # SSI:586
         dx_proj_weight = aum_hip.proj_bwd_weight(_dm2d(conv_out), dx_dbl, True)              # SSI:589
-        _, dconv_w, dconv_b = aum_hip.conv1d_bwd(x, conv_w, conv1d_bias, dconv_out, True, ctx.reverse, dx_out=dx)  # SSI:594
-        return dict(dxz=dxz, dconv_w=dconv_w.reshape(E, 1, -1), dconv_b=dconv_b, dx_proj_w=dx_proj_weight,
-                    ddt_proj_w=ddelta_proj_weight, dout_proj_w=dout_proj_weight, dout_proj_b=dout_proj_bias,
-                    dA=g["dA"], dA_b=g.get("dA_b"), dD=g["dD"], ddelta_bias=g["ddelta_bias"],
-                    dB_proj_bias=None, dC_proj_bias=None)
-    dx_dbl = torch.empty_like(x_dbl)
-    dx_dbl3 = dx_dbl.view(Bsz, L, -1)
-    dx_dbl3[:, :, R:R + N].copy_(g["dB"].transpose(1, 2))                                    # SSI:570-574
-    dx_dbl3[:, :, R + N:R + 2 * N].copy_(g["dC"].transpose(1, 2))
-    dB_proj_bias = g["dB"].sum((0, 2)) if not ctx.B_proj_bias_is_None else None
-    dC_proj_bias = g["dC"].sum((0, 2)) if not ctx.C_proj_bias_is_None else None
-    ddelta2 = _dm2d(ddelta)                                                                   # [E, BL]
-    ddelta_proj_weight = torch.matmul(ddelta2, x_dbl[:, :R])                                  # SSI:586
-    dx_dbl[:, :R] = torch.matmul(ddelta2.t(), delta_proj_weight.to(ddelta2.dtype))            # SSI:587
-    dx_proj_weight = torch.matmul(dx_dbl.t(), _dm2d(conv_out).t())                            # SSI:589
-    dconv2 = _dm2d(dconv_out)
-    dconv2.addmm_(x_proj_weight.t().to(dx_dbl.dtype), dx_dbl.t())                             # SSI:590
+    else:
+        dx_dbl = torch.empty_like(x_dbl)
+        dx_dbl3 = dx_dbl.view(Bsz, L, -1)
+        dx_dbl3[:, :, R:R + N].copy_(g["dB"].transpose(1, 2))                                # SSI:570-574
+        dx_dbl3[:, :, R + N:R + 2 * N].copy_(g["dC"].transpose(1, 2))
+        dB_proj_bias = g["dB"].sum((0, 2)) if not ctx.B_proj_bias_is_None else None
+        dC_proj_bias = g["dC"].sum((0, 2)) if not ctx.C_proj_bias_is_None else None
+        ddelta_proj_weight = torch.matmul(ddelta2, x_dbl[:, :R])                              # SSI:586
+        dx_dbl[:, :R] = torch.matmul(ddelta2.t(), delta_proj_weight.to(ddelta2.dtype))        # SSI:587
+        dx_proj_weight = torch.matmul(dx_dbl.t(), _dm2d(conv_out).t())                        # SSI:589
+        dconv2.addmm_(x_proj_weight.t().to(dx_dbl.dtype), dx_dbl.t())                         # SSI:590
     _, dconv_w, dconv_b = aum_hip.conv1d_bwd(x, conv_w, conv1d_bias, dconv_out, True, ctx.reverse, dx_out=dx)  # SSI:594
     return dict(dxz=dxz, dconv_w=dconv_w.reshape(E, 1, -1), dconv_b=dconv_b, dx_proj_w=dx_proj_weight,
                 ddt_proj_w=ddelta_proj_weight, dout_proj_w=dout_proj_weight, dout_proj_b=dout_proj_bias,

@@ -25,9 +25,11 @@ def run(tag, ddp, streams, join):
     if ddp:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[0], gradient_as_bucket_view=True, broadcast_buffers=False)
         if join:
-            net.register_comm_hook(None, ssi.ddp_join_streams_hook())
+            ssi.register_ddp_join_streams(net)
         else:
-            ssi._DDP_STREAM_JOIN = True          # (timing only: two streams without the join)
+            for m in model.modules():            # (timing only: two streams without the join -- the permission the hook's registration gives)
+                if getattr(m, "bimamba_type", None) == "v2":
+                    m._aum_streams_joined = True
     opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=True)
     x = torch.randn(64, 1024, 128, device=dev) * 0.5
     y = torch.zeros(64, 527, device=dev)
@@ -35,7 +37,12 @@ def run(tag, ddp, streams, join):
     lf = torch.nn.BCEWithLogitsLoss()
     calls = {"two": 0, "one": 0}
     real = ssi.v2_two_streams
-    ssi.v2_two_streams = lambda *a: (calls.__setitem__("two" if real(*a) else "one", calls["two" if real(*a) else "one"] + 1), real(*a))[1]
+
+    def counting(*a, **k):
+        two = real(*a, **k)
+        calls["two" if two else "one"] += 1
+        return two
+    ssi.v2_two_streams = counting
 
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16):
