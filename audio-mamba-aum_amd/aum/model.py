@@ -243,16 +243,20 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False):
+    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False, prefill=False):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
         (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
-        are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it"""
+        are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it.
+        prefill=True (fixed-batch caches, no peek row): the mixers take the tokens as a backlog (Mamba.prefill_chunk)"""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
                                            residual_in_fp32=True, eps=layer.norm.eps)
             conv_state, ssm_state = layer_caches[i]
-            hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek)
+            if prefill:
+                hidden, _, _ = layer.mixer.prefill_chunk(hidden, conv_state, ssm_state)
+            else:
+                hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek)
         return hidden, residual
 
     def _read_in_place(self, cls, cache, rows):
@@ -382,11 +386,89 @@ class AudioMamba(nn.Module):
             for r in rows:
                 pool["columns"][r] = 0
 
+    def _check_push(self, what, spec, cache):
+        """stream_prefill's checks, made before anything is touched -> (k new columns, columns so far).  They MIRROR the checks
+        stream_push makes in line (its body is kept as it was) and, per session, those of stream_push_many / stream_prefill_many: a
+        change to one of them belongs in all; folding them into this one helper is a follow-up of its own."""
+        self._check_streamable()
+        if self._is_pool(cache):
+            raise ValueError(f"{what} advances all rows of a cache from allocate_inference_cache together; a pool from "
+                             f"allocate_stream_pool is advanced by {what}_many(specs, pool, sessions)")
+        ph, pw = self.patch_embed.proj.kernel_size
+        nf, nt = self.patch_grid_size
+        if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
+            raise ValueError(f"{what} takes (batch={cache['batch']}, a positive multiple of {pw} frames, {nf * ph} mel bins), got {tuple(spec.shape)}")
+        k, c0 = spec.shape[1] // pw, cache["columns"]
+        if c0 + k > nt:
+            raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
+        return k, c0
+
+    @torch.no_grad()
+    def stream_prefill(self, spec, cache, read=False, return_features=False):
+        """stream_push for a BACKLOG: spec (batch, 16 k, n_mels), the next k time columns of the clip -- seconds or minutes of audio a
+        client arrives with, or the part of a long-form clip recorded so far -- through all blocks from the carried caches, which advance
+        by the k columns exactly as under stream_push (the same checks, the same column count; a refused call changes nothing), and
+        stream_push / stream_read go on from there.  The blocks take the tokens through Mamba.prefill_chunk: the time-parallel conv and
+        the token-major scan of the offline forward, long rows cut into time segments, instead of one serial chain of k n_f steps per
+        wave.  The results agree with stream_push to the kernels' tolerance, not bitwise.
+        It pays from about 64 columns (512 tokens) per session.  Measured on AuM-Base, bf16, batch 1, ONE run per size
+        (profiles/r13_stream_prefill.txt): 64 columns 6.0 ms against 8.6 ms through stream_push, 512 columns (L = 4097) 6.6 ms against
+        52.6 ms, but 31 columns 5.7 ms against 5.3 ms -- up to the 128 tokens of stream_push's one-launch path and a little beyond,
+        stream_push is the faster call, and it keeps the live hops.  The crossing point lies between 248 and 512 tokens and has not been
+        located more finely; a pass costs about 5.7 ms whatever the backlog (per block: a [window ; x] copy, a copy of the conv output
+        and the window write-back next to the kernels -- not profiled).
+        No peek row: read=True is stream_read behind the push -> (columns, logits)."""
+        k, c0 = self._check_push("stream_prefill", spec, cache)
+        x = self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
+        self._stream_layers(x, cache["layers"], prefill=True)
+        cache["columns"] = c0 + k
+        if not read:
+            return cache["columns"]
+        return cache["columns"], self.stream_read(cache, return_features)
+
+    @torch.no_grad()
+    def stream_prefill_many(self, specs, pool, sessions):
+        """The backlog path of a pool (not the per-hop path: that is stream_push_many, one packed pass): specs[i] (16 k_i, n_mels), the
+        next k_i columns of session sessions[i] (distinct rows of a pool from allocate_stream_pool).  A loop over the sessions on the
+        host: each one's cache rows are gathered (index_select), advanced by stream_prefill's pass at batch 1 and scattered back
+        (index_copy_); the other rows are not touched.  Every argument is checked before any cache is touched.  Returns the
+        per-session column counts."""
+        self._check_streamable()
+        rows = self._check_sessions("stream_prefill_many", pool, sessions)
+        ph, pw = self.patch_embed.proj.kernel_size
+        nf, nt = self.patch_grid_size
+        specs = list(specs)
+        if not rows or len(specs) != len(rows):
+            raise ValueError(f"stream_prefill_many: one spectrogram piece per session, got {len(specs)} for the sessions {rows}")
+        ks = []
+        for sp, r in zip(specs, rows):
+            if sp.dim() != 2 or sp.shape[0] == 0 or sp.shape[0] % pw or sp.shape[1] // ph != nf:
+                raise ValueError(f"stream_prefill_many takes (a positive multiple of {pw} frames, {nf * ph} mel bins) per session, got "
+                                 f"{tuple(sp.shape)} for session {r}")
+            k = sp.shape[0] // pw
+            if pool["columns"][r] + k > nt:
+                raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
+            ks.append(k)
+        for sp, r, k in zip(specs, rows, ks):
+            ix = torch.tensor([r], dtype=torch.int64, device=sp.device)
+            one = {i: (c.index_select(0, ix), s.index_select(0, ix)) for i, (c, s) in pool["layers"].items()}
+            c0 = pool["columns"][r]
+            x = self._embed_columns(sp.unsqueeze(0).unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
+            self._stream_layers(x, one, prefill=True)
+            for i, (c, s) in pool["layers"].items():
+                c.index_copy_(0, ix, one[i][0])
+                s.index_copy_(0, ix, one[i][1])
+            pool["columns"][r] = c0 + k
+        return [pool["columns"][r] for r in rows]
+
     @torch.no_grad()
     def stream_push(self, spec, cache, read=False, return_features=False):
         """spec: (batch, 16 k, n_mels) -- the next k time columns of the clip's normalised log-mel spectrogram.  Embeds their
         k x n_f tokens (time-major, each with the position row of its (f, t) cell), runs them through all blocks from the carried caches
         and advances the caches.  Returns the number of columns pushed so far.
+        This is the call for LIVE hops -- a few columns at a time, up to 128 tokens per session in one launch per block; a backlog
+        (a client that joins with buffered audio, a long-form clip to be continued) goes through stream_prefill, which takes the same
+        arguments and leaves the same caches.
         read=True: what stream_read would say behind this push, from the same pass -- the cls row rides behind the new tokens as a peek
         row (Mamba.step_chunk(peek=True)), goes through the final norm and the head, and the caches advance by the tokens only.
         Returns (columns, logits (batch, classes); features with return_features)."""

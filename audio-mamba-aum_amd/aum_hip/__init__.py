@@ -102,6 +102,11 @@ class ScanTmSegBwdArgs(C.Structure):
     _fields_ = [("base", ScanTmBwdArgs), ("segments", _i32), ("reserved", _i32)]
 
 
+class ScanTmFwdStateArgs(C.Structure):
+    _fields_ = [("base", ScanTmFwdArgs), ("state_in", _vp), ("state_out", _vp), ("carry", _vp), ("carry_bytes", _i64), ("segments", _i32),
+                ("reserved", _i32)]
+
+
 class ConvArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "dy", "weight", "bias", "y", "dx", "dweight", "dbias")]
                 + [(n, _i64) for n in ("x_bs", "x_ds", "y_bs", "y_ds", "dy_bs", "dy_ds", "dx_bs", "dx_ds")]
@@ -239,7 +244,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_proj_fwd", "aum_proj_bwd_data",
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
-    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm")}
+    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -651,6 +656,88 @@ def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softpl
     _launch(lib.c.aum_scan_tm_fwd, a, u, lib, "scan_tm_fwd_bidir" if A_b is not None else "scan_tm_fwd",
             (batch, dim, length, dstate, u.element_size(), want_out_pre))
     return out, out_pre
+
+
+def scan_state_supported(t, batch, dim, dstate):
+    """a state of aum_scan_tm_fwd_state: None, or fp32 contiguous (batch, dim, dstate), 16-byte aligned"""
+    return t is None or (t.dim() == 3 and tuple(t.shape) == (batch, dim, dstate) and t.dtype == torch.float32 and t.is_contiguous()
+                         and t.data_ptr() % 16 == 0)
+
+
+def scan_tm_fwd_state_supported(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False,
+                                state_in=None, state_out=None, segments=1):
+    """the limits of aum_scan_tm_fwd_state (include/aum_hip.h): those of scan_tm_fwd for one direction -- dstate == 16, dim % 64 == 0,
+    (batch, len >= 1, dim) token-major rows of one dtype moved as 16-byte chunks, B / C rows 4-byte aligned, an activated delta only
+    for 16-bit rows with z -- and the states fp32 contiguous (batch, dim, 16), 16-byte aligned.  Outside them callers use scan_stream."""
+    if u.dim() != 3 or A.dim() != 2 or u.shape[1] < 1 or not scan_tm_supported(u.shape[2], A.shape[1]) or u.dtype not in _DT:
+        return False
+    batch, length, dim = u.shape
+    dstate, es = A.shape[1], u.element_size()
+    if not (1 <= int(segments) <= SCAN_TM_MAX_SEGMENTS) or A.shape[0] != dim:
+        return False
+    for t, last in ((u, dim), (delta, dim), (z, dim), (B, dstate), (C, dstate)):
+        if t is None:
+            continue
+        if t.dtype != u.dtype or t.dim() != 3 or tuple(t.shape) != (batch, length, last) or (t.stride(2) != 1 and last != 1):
+            return False
+        bs, ts = _tm3(t, "operand", last)
+        if last == dim and (t.data_ptr() % 16 or (ts * es) % 16 or (bs * es) % 16):
+            return False
+        if last == dstate and es == 2 and (t.data_ptr() % 4 or ts % 2 or bs % 2):
+            return False
+        if ts < 0 or ts * es * length >= 2 ** 31:
+            return False
+    if delta_activated and (es == 4 or z is None):
+        return False
+    return scan_state_supported(state_in, batch, dim, dstate) and scan_state_supported(state_out, batch, dim, dstate)
+
+
+def scan_tm_fwd_state(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, state_in=None,
+                      state_out=None, segments=1, out=None, lib=None):
+    """scan_tm_fwd for one direction, entered with a carried state and leaving the state behind the last step (aum_scan_tm_fwd_state):
+    the prefill of a streaming session at the speed of the offline forward, continued by scan_tm_chunk / stream_block on the same cache
+    row.  Operands as scan_tm_fwd; state_in / state_out: fp32 contiguous (batch, dim, 16) or None (a zero entry state / the exit state
+    is not wanted), and they may be ONE tensor (advance in place).  segments > 1: the rows cut into time ranges (scan_tm_segments
+    chooses).  Uncut, the result does not depend on how a stream is cut into calls (bitwise); with state_in None `out` is bit for bit
+    scan_tm_fwd's.  Inference only: no checkpoints, no backward.  Returns out (batch, len, dim) contiguous in u's dtype."""
+    lib = lib or get()
+    for t in (u, delta, z, B, C, state_in, state_out, out):
+        lib.check_tensor(t)
+    if not scan_tm_fwd_state_supported(u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, state_in, state_out, segments):
+        raise RuntimeError(f"scan_tm_fwd_state: unsupported operands u {tuple(u.shape)} {u.dtype} strides {u.stride()}, A {tuple(A.shape)}, state_in "
+                           f"{None if state_in is None else (tuple(state_in.shape), state_in.dtype)}, state_out "
+                           f"{None if state_out is None else (tuple(state_out.shape), state_out.dtype)}, segments {segments} "
+                           "(need token-major 16-byte rows of one dtype, dim % 64 == 0, dstate 16, fp32 contiguous (batch, dim, 16) states)")
+    batch, length, dim = u.shape
+    dstate = A.shape[1]
+    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
+    for t in (A, D, delta_bias):
+        lib.check_tensor(t)
+    if out is None:
+        out = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device)
+    if out.dtype != u.dtype or tuple(out.shape) != (batch, length, dim):
+        raise RuntimeError("scan_tm_fwd_state: out must have u's shape and dtype")
+    sa = ScanTmFwdStateArgs()
+    a = sa.base
+    a.u_bs, a.u_ts = _tm3(u, "u", dim)
+    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
+    if z is not None:
+        a.z_bs, a.z_ts = _tm3(z, "z", dim)
+    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
+    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
+    a.out_bs, a.out_ts = _tm3(out, "out", dim)
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.D, a.delta_bias, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(out)
+    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
+    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    sa.state_in, sa.state_out, sa.segments = _ptr(state_in), _ptr(state_out), int(segments)
+    carry = None
+    if segments > 1:
+        sa.carry_bytes = int(lib.c.aum_scan_tm_seg_carry_bytes(batch, dim, length, dstate, 0, int(segments)))
+        carry = torch.empty((sa.carry_bytes // 4,), dtype=torch.float32, device=u.device)
+        sa.carry = _ptr(carry)
+    _launch(lib.c.aum_scan_tm_fwd_state, sa, u, lib, "scan_tm_fwd_state", (batch, dim, length, dstate, u.element_size(), int(segments)))
+    return out
 
 
 def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_softplus=False, reverse=False, A_b=None, dz_out=None,
@@ -1474,6 +1561,37 @@ def conv1d_tm_fwd(x, weight, bias=None, silu=True, reverse=False, lib=None):
     a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
     a.flags = (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0)
     _launch(lib.c.aum_conv1d_tm_fwd, a, x, lib, "conv_tm_fwd", (batch, dim, length, x.element_size()))
+    return y
+
+
+def conv1d_tm_prefill(x, conv_state, weight, bias=None, silu=True, lib=None):
+    """The causal conv of a BACKLOG entered with a carried window: x (batch, T >= 1, dim) token-major view, conv_state (batch, dim, width)
+    fp32 contiguous, advanced IN PLACE by T tokens -- what conv1d_tm_chunk computes, on the time-parallel kernel of the offline forward
+    and without a kernel of its own: the rows [last width - 1 carried inputs ; x] go through conv1d_tm_fwd and the first width - 1
+    outputs are dropped; the last `width` inputs are then written back into conv_state (T < width: the old entries shift, as in
+    k_convt_chunk).  A zero window gives the same result as the plain causal conv (conv1d_tm_fwd on x alone: its rows before the first
+    are zero).  The carried inputs enter the rows in x's dtype: a window that was filled from activations of that dtype -- every
+    window this library writes -- is carried exactly; conv_state itself only ever holds the inputs as they were (no rounding).
+    Returns y (batch, T, dim) in x's dtype, a view with 16-byte aligned rows."""
+    lib = lib or get()
+    for t in (x, conv_state):
+        lib.check_tensor(t)
+    if not conv1d_tm_chunk_supported(x, conv_state):
+        raise RuntimeError(f"conv1d_tm_prefill: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (batch, T, dim) token-major, 16-byte rows; fp32 contiguous (batch, dim, width <= 4))")
+    batch, T, dim = x.shape
+    width = conv_state.shape[2]
+    if weight.reshape(dim, -1).shape[1] != width:
+        raise RuntimeError("conv1d_tm_prefill: weight (dim, width) and conv_state (rows, dim, width) disagree on the width")
+    rows = torch.empty((batch, width - 1 + T, dim), dtype=x.dtype, device=x.device)
+    rows[:, :width - 1] = conv_state[:, :, 1:].transpose(1, 2)
+    rows[:, width - 1:] = x
+    y = conv1d_tm_fwd(rows, weight, bias, silu, lib=lib)[:, width - 1:]
+    if T >= width:
+        conv_state.copy_(x[:, T - width:].transpose(1, 2))
+    else:
+        conv_state[:, :, :width - T] = conv_state[:, :, T:].clone()
+        conv_state[:, :, width - T:] = x.transpose(1, 2)
     return y
 
 

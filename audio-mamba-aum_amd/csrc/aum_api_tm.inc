@@ -22,6 +22,10 @@ int scan_tm_bwd_f16(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream
 int scan_tm_seg_fwd_f32(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_fwd_bf16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_fwd_f16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s);
+// state in / state out (scant_fwd_state; sg != nullptr: one launch of `phase` 3 or 0 of scant_seg_fwd_state)
+int scan_tm_fwd_state_f32(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
+int scan_tm_fwd_state_bf16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
+int scan_tm_fwd_state_f16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_f32(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_bf16(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_f16(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
@@ -128,17 +132,66 @@ template <class T> static int scan_tm_seg_fwd_t(const AumScanTmFwdArgs& a, const
     }
     return AUM_E_UNSUPPORTED;
 }
+#ifndef AUM_EMU
+template <class T, bool SP, bool HAS_Z>
+__global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd_state(AumScanTmFwdArgs a, ScanTState st) {
+    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    scant_fwd_state<T, SP, HAS_Z>(a, st, (int)blockIdx.x, lds);
+}
+template <class T, int PHASE, bool SP, bool HAS_Z>
+__global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_seg_fwd_state(AumScanTmFwdArgs a, ScanTSeg sg, ScanTState st) {
+    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    scant_seg_fwd_state<T, PHASE, SP, HAS_Z>(a, sg, st, (int)blockIdx.x, lds);
+}
+#endif
+template <class T, bool SP, bool HAS_Z> static int launch_scant_fwd_state(const AumScanTmFwdArgs& a, const ScanTState& st, aum_stream_t s) {
+    const int grid = (a.batch * (a.dim / WAVE) + SCANT_NW - 1) / SCANT_NW;
+#ifdef AUM_EMU
+    (void)s;
+    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
+    for (int wg = 0; wg < grid; ++wg) scant_fwd_state<T, SP, HAS_Z>(a, st, wg, lds.data());
+#else
+    hipLaunchKernelGGL((k_scant_fwd_state<T, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, st);
+#endif
+    return launch_status();
+}
+template <class T, int PHASE, bool SP, bool HAS_Z>
+static int launch_scant_seg_fwd_state(const AumScanTmFwdArgs& a, const ScanTSeg& sg, const ScanTState& st, aum_stream_t s) {
+    const int grid = (a.batch * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
+#ifdef AUM_EMU
+    (void)s;
+    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
+    for (int wg = 0; wg < grid; ++wg) scant_seg_fwd_state<T, PHASE, SP, HAS_Z>(a, sg, st, wg, lds.data());
+#else
+    hipLaunchKernelGGL((k_scant_seg_fwd_state<T, PHASE, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, sg, st);
+#endif
+    return launch_status();
+}
+template <class T> static int scan_tm_fwd_state_t(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) {
+    const bool sp = (a.flags & AUM_SCAN_SOFTPLUS) != 0, hz = a.z != nullptr;
+    if (!sg) {
+        if (sp) return hz ? launch_scant_fwd_state<T, true, true>(a, st, s) : launch_scant_fwd_state<T, true, false>(a, st, s);
+        return hz ? launch_scant_fwd_state<T, false, true>(a, st, s) : launch_scant_fwd_state<T, false, false>(a, st, s);
+    }
+    if (phase == 3) return sp ? launch_scant_seg_fwd_state<T, 3, true, false>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 3, false, false>(a, *sg, st, s);
+    if (phase != 0) return AUM_E_UNSUPPORTED;
+    if (sp) return hz ? launch_scant_seg_fwd_state<T, 0, true, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, true, false>(a, *sg, st, s);
+    return hz ? launch_scant_seg_fwd_state<T, 0, false, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, false, false>(a, *sg, st, s);
+}
 #if AUM_HAS_DTYPE(0)
 int scan_tm_fwd_f32(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<float>(a, s); }
 int scan_tm_seg_fwd_f32(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<float>(a, sg, phase, s); }
+int scan_tm_fwd_state_f32(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<float>(a, st, sg, phase, s); }
 #endif
 #if AUM_HAS_DTYPE(1)
 int scan_tm_fwd_bf16(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<bf16_t>(a, s); }
 int scan_tm_seg_fwd_bf16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<bf16_t>(a, sg, phase, s); }
+int scan_tm_fwd_state_bf16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<bf16_t>(a, st, sg, phase, s); }
 #endif
 #if AUM_HAS_DTYPE(2)
 int scan_tm_fwd_f16(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<f16_t>(a, s); }
 int scan_tm_seg_fwd_f16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<f16_t>(a, sg, phase, s); }
+int scan_tm_fwd_state_f16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<f16_t>(a, st, sg, phase, s); }
 #endif
 #endif
 
@@ -338,6 +391,39 @@ AUM_API int aum_scan_tm_seg_fwd(const AumScanTmSegFwdArgs* sa, void* stream) {
     if (r != AUM_OK) return r;
     sg.dir0 = 1;
     return scan_tm_seg_fwd_any(k, sg, 2, s);
+}
+AUM_API int aum_scan_tm_fwd_state(const AumScanTmFwdStateArgs* sa, void* stream) {
+    if (!sa) return AUM_E_NULL;
+    const AumScanTmFwdArgs* a = &sa->base;
+    const int rc = scan_tm_fwd_check(a);
+    if (rc != AUM_OK) return rc;
+    // an inference path: one direction, forward time, no checkpoints, no pre-gate copy
+    if (a->A_b || a->ckpt || a->out_pre || (a->flags & AUM_SCAN_REVERSE)) return AUM_E_UNSUPPORTED;
+    if ((((uintptr_t)sa->state_in) | ((uintptr_t)sa->state_out)) & 15) return AUM_E_UNSUPPORTED;      // 16-byte accesses
+    if ((int64_t)a->dim * a->dstate * 4 > (((int64_t)1 << 31) - 1)) return AUM_E_UNSUPPORTED;              // 32-bit byte offsets inside a state row
+    if (sa->segments < 1 || sa->segments > AUM_SCAN_TM_MAX_SEGMENTS) return AUM_E_SHAPE;
+    aum_stream_t s = (aum_stream_t)stream;
+    const AumScanTmFwdArgs k = scan_tm_fwd_resolve(*a);
+    const ScanTState st = {sa->state_in, sa->state_out};
+    auto run = [&](const ScanTSeg* sg, int phase) {
+        switch (k.dtype) {
+            case AUM_F32: return scan_tm_fwd_state_f32(k, st, sg, phase, s);
+            case AUM_BF16: return scan_tm_fwd_state_bf16(k, st, sg, phase, s);
+            default: return scan_tm_fwd_state_f16(k, st, sg, phase, s);
+        }
+    };
+    if (sa->segments == 1) return run(nullptr, 0);
+    if (!sa->carry) return AUM_E_NULL;
+    if (sa->carry_bytes < scant_seg_carry_floats(a->batch, a->dim, sa->segments, false) * (int64_t)sizeof(float)) return AUM_E_WORKSPACE;
+    ScanTSeg sg;
+    sg.carry = sa->carry;
+    sg.nseg = sa->segments;
+    sg.seg_len = scant_seg_len(a->len, sa->segments);
+    sg.dir0 = 0;
+    sg.ndl = 1;
+    const int r = run(&sg, 3);
+    if (r != AUM_OK) return r;
+    return run(&sg, 0);
 }
 AUM_API int64_t aum_scan_tm_workspace_bytes(int32_t batch, int32_t dim, int32_t len, int32_t dstate, int32_t bidirectional) {
     if (batch <= 0 || dim <= 0 || len <= 0 || dstate <= 0 || !scant_supported(dim, dstate)) return 0;

@@ -676,6 +676,133 @@ AUM_DEV void scant_seg_fwd(const AumScanTmFwdArgs& p, const ScanTSeg& sg, int wg
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// State in, state out (aum_scan_tm_fwd_state): the one-direction forward-time scan entered with a carried state and leaving the state
+// behind the row's last step -- the hand-off between this kernel (offline speed: blocks staged 16 bytes per lane, long rows cut into
+// time segments) and the streaming kernels of stream_tm_kernels.h, which carry the same (batch, dim, 16) fp32 cache row.  A lane's 16
+// states are 64 contiguous bytes: four 16-byte accesses on entry and on exit, exact fp32.  The steps are scant_fwd_run's PHASE 0, the
+// instantiation k_scant_fwd itself runs without out_pre: a zero entry state gives the bits of aum_scan_tm_fwd.
+//   uncut      x <- state_in (or zero), the row, state_out <- x.  state_in is read before the first step and state_out written behind
+//              the last by the same lane, so the two may be one buffer.
+//   segmented  the carry launch also parks state_in (or zero) as the entry state of range 0 in the X rows of the LAST range's carry slot,
+//              which the carries never use (a last range's exit state enters nothing).  The main launch starts range s from
+//              P_{s-1} ( ... (P_0 entry + X_0) ... ) + X_{s-1} and the wave of the last range stores state_out.  state_in is read by
+//              the carry launch only and state_out written by the main launch only: the stream orders them, so they may be one buffer
+//              here as well.  Ranges past the end of the row (a short row cut often) are empty and hand the state through.
+// ------------------------------------------------------------------------------------------------
+struct ScanTState {
+    const float* in;       // (batch, dim, N) fp32 or NULL (zero)
+    float* out;            // (batch, dim, N) fp32 or NULL (not wanted)
+};
+template <int N> AUM_DEV void scant_state_load(const float* row, vi ec, vf2 (&x)[N / 2]) {
+    const gbuf<float> sbuf = make_gbuf(row);
+    const vi st_off = ec * (N * 4);
+    AUM_UNROLL
+    for (int i = 0; i < N / 4; ++i) {
+        vf t[4];
+        vq_unpack<float>(gbuf_load16(sbuf, st_off + 16 * i, 0), t);
+        x[2 * i] = mk2(t[0], t[1]);
+        x[2 * i + 1] = mk2(t[2], t[3]);
+    }
+}
+template <int N> AUM_DEV void scant_state_store(float* row, vi ec, const vf2 (&x)[N / 2]) {
+    const gbuf<float> sbuf = make_gbuf(row);
+    const vi st_off = ec * (N * 4);
+    AUM_UNROLL
+    for (int i = 0; i < N / 4; ++i) {
+        const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
+        gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
+    }
+}
+
+// workgroup = four waves, four (batch entry, channel group) units, as the one-direction scant_fwd
+template <class T, bool SP, bool HAS_Z>
+AUM_DEV void scant_fwd_state(const AumScanTmFwdArgs& p, const ScanTState& st, int wg, float* lds) {
+    constexpr int N = SCANT_N;
+    constexpr int NW = SCANT_NW;
+    const int gpb = p.dim / WAVE;
+    const int units = p.batch * gpb;
+    vf2 x[AUM_PER_WAVE(NW)][N / 2];
+    AUM_FOR_EACH_WAVE(w, NW) {
+        const int unit = wg * NW + w;
+        if (unit < units) {
+            const int b = unit / gpb, e0 = (unit % gpb) * WAVE;
+            const vi ec = lane_id() + e0;
+            const int64_t row = (int64_t)b * p.dim * N;
+            if (st.in) {
+                scant_state_load<N>(st.in + row, ec, x[AUM_W(w)]);
+            } else {
+                AUM_UNROLL
+                for (int j = 0; j < N / 2; ++j) x[AUM_W(w)][j] = spl2(splat(0.f));
+            }
+            scant_fwd_run<T, N, 0, SP, HAS_Z, false>(p, b, e0, 0, 0, 1, 0, p.len, p.A, 1.f, x[AUM_W(w)], lds + w * scant_lds_wave_floats<T>());
+            if (st.out) scant_state_store<N>(st.out + row, ec, x[AUM_W(w)]);
+        }
+    }
+}
+
+// workgroup = four independent waves; item = (unit * nseg) + segment (one direction: sg.ndl == 1, sg.dir0 == 0).  PHASE 3: the carry
+// launch; PHASE 0: the main launch.
+template <class T, int PHASE, bool SP, bool HAS_Z>
+AUM_DEV void scant_seg_fwd_state(const AumScanTmFwdArgs& p, const ScanTSeg& sg, const ScanTState& st, int wg, float* lds) {
+    static_assert(PHASE == 0 || PHASE == 3, "carry launch or main launch");
+    constexpr int N = SCANT_N;
+    constexpr int NW = SCANT_NW;
+    const int gpb = p.dim / WAVE;
+    const int L = p.len;
+    const int items = p.batch * gpb * sg.nseg;
+    vf2 x[AUM_PER_WAVE(NW)][N / 2], P[AUM_PER_WAVE(NW)][N / 2];
+    AUM_FOR_EACH_WAVE(w, NW) {
+        const int item = wg * NW + w;
+        if (item < items) {
+            const int s = item % sg.nseg, unit = item / sg.nseg;
+            const int b = unit / gpb, e0 = (unit % gpb) * WAVE;
+            const int it0 = s * sg.seg_len < L ? s * sg.seg_len : L;
+            const int it1 = it0 + sg.seg_len < L ? it0 + sg.seg_len : L;
+            const vi ec = lane_id() + e0;
+            float* cb = sg.carry + (int64_t)b * sg.nseg * (2 * N) * p.dim;
+            float* entry = cb + (int64_t)(sg.nseg - 1) * (2 * N) * p.dim + (int64_t)N * p.dim;      // X rows of the last range's slot
+            float* lw = lds + w * scant_lds_wave_floats<T>();
+            const int64_t row = (int64_t)b * p.dim * N;
+            AUM_UNROLL
+            for (int j = 0; j < N / 2; ++j) x[AUM_W(w)][j] = spl2(splat(0.f));
+            if (PHASE == 3) {
+                if (s == sg.nseg - 1) {
+                    if (st.in) scant_state_load<N>(st.in + row, ec, x[AUM_W(w)]);
+                    AUM_UNROLL
+                    for (int n = 0; n < N; ++n)
+                        gstore(entry + (int64_t)n * p.dim, ec, (n & 1) ? hi2(x[AUM_W(w)][n >> 1]) : lo2(x[AUM_W(w)][n >> 1]), ec >= 0);
+                } else {
+                    AUM_UNROLL
+                    for (int j = 0; j < N / 2; ++j) P[AUM_W(w)][j] = spl2(splat(1.f));
+                    scant_fwd_run<T, N, 3, SP, false, false>(p, b, e0, 0, 0, 1, it0, it1, p.A, 1.f, x[AUM_W(w)], lw, nullptr, P[AUM_W(w)]);
+                    float* cs = cb + (int64_t)s * (2 * N) * p.dim;
+                    AUM_UNROLL
+                    for (int n = 0; n < N; ++n) {
+                        gstore(cs + (int64_t)n * p.dim, ec, (n & 1) ? hi2(P[AUM_W(w)][n >> 1]) : lo2(P[AUM_W(w)][n >> 1]), ec >= 0);
+                        gstore(cs + (int64_t)(N + n) * p.dim, ec, (n & 1) ? hi2(x[AUM_W(w)][n >> 1]) : lo2(x[AUM_W(w)][n >> 1]), ec >= 0);
+                    }
+                }
+            } else {
+                AUM_UNROLL
+                for (int j = 0; j < N / 2; ++j)
+                    x[AUM_W(w)][j] = mk2(gload_u(entry + (int64_t)(2 * j) * p.dim, ec), gload_u(entry + (int64_t)(2 * j + 1) * p.dim, ec));
+                for (int sp = 0; sp < s; ++sp) {
+                    const float* cs = cb + (int64_t)sp * (2 * N) * p.dim;
+                    AUM_UNROLL
+                    for (int j = 0; j < N / 2; ++j) {
+                        const vf2 pj = mk2(gload_u(cs + (int64_t)(2 * j) * p.dim, ec), gload_u(cs + (int64_t)(2 * j + 1) * p.dim, ec));
+                        const vf2 xj = mk2(gload_u(cs + (int64_t)(N + 2 * j) * p.dim, ec), gload_u(cs + (int64_t)(N + 2 * j + 1) * p.dim, ec));
+                        x[AUM_W(w)][j] = vfma2(pj, x[AUM_W(w)][j], xj);
+                    }
+                }
+                scant_fwd_run<T, N, 0, SP, HAS_Z, false>(p, b, e0, 0, 0, 1, it0, it1, p.A, 1.f, x[AUM_W(w)], lw);
+                if (st.out && s == sg.nseg - 1) scant_state_store<N>(st.out + row, ec, x[AUM_W(w)]);
+            }
+        }
+    }
+}
+
 // ================================================================================================
 // Backward.  The same division of the work: lane = channel, a wave owns one direction of a channel group and walks its blocks of
 // 8 steps in REVERSE scan order.  A block is processed in passes over state pairs (two states at a time):

@@ -107,6 +107,13 @@ class Mamba(nn.Module):
                 else:
                     out, _, _ = self.step(hidden_states, conv_state, ssm_state)
                 return out
+            # seqlen_offset == 0 (MS:268-271, 300-302): the prompt runs as one sequence and leaves both caches behind.  Where the
+            # token-major kernels take the block's shapes that is prefill_chunk on the zeroed caches; elsewhere the un-fused branch below
+            if self._prefill_ok(hidden_states, conv_state, ssm_state):
+                conv_state.zero_()
+                ssm_state.zero_()
+                out, _, _ = self.prefill_chunk(hidden_states, conv_state, ssm_state)
+                return out if self.init_layer_scale is None else out * self.gamma
         batch, seqlen, _ = hidden_states.shape
         tm = (ssi.TOKEN_MAJOR and self.use_fast_path and inference_params is None
               and not (ssi._REF_DZ_DROP and self.bimamba_type == "v1")      # that option lives in the channel-major block
@@ -299,6 +306,77 @@ class Mamba(nn.Module):
         proj = proj.view(batch, T, -1)
         y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], plan.D, z,
                                 plan.dt_bias, True, activated, seq_map, peek=peek)
+        out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
+        return out, conv_state, ssm_state
+
+    def _prefill_ok(self, hidden_states, conv_state, ssm_state):
+        """forward(x, inference_params) at seqlen_offset == 0: through prefill_chunk?  Only for the causal block with silu, on a DEVICE,
+        with fp32 caches (what the kernels advance in place; the reference's default caches carry the parameters' dtype) and widths for
+        which ssi.token_major_ok holds -- the rule of the offline token-major forward (dt_rank and dt_rank + 2 d_state keep 16-byte
+        rows: dt_rank a multiple of 4 in fp32, of 8 in 16 bits).  Everything else keeps the un-fused branch."""
+        work = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else self.in_proj.weight.dtype
+        return (ssi.TOKEN_MAJOR and self.use_fast_path and self.bimamba_type == "none" and hidden_states.is_cuda and hidden_states.dim() == 3
+                and hidden_states.shape[1] >= 1 and self.activation in ("silu", "swish")
+                and conv_state.dtype == torch.float32 and ssm_state.dtype == torch.float32
+                and ssi.token_major_ok(self.d_inner, self.d_state, self.d_conv, self.dt_rank, work))
+
+    def prefill_supported(self, xz, conv_state, ssm_state):
+        """prefill_chunk's dispatch for these (batch, T, 2E) in_proj rows and fixed-batch caches: what conv1d_tm_prefill and
+        aum_scan_tm_fwd_state take -- silu, x rows the token-major conv takes with an fp32 (batch, E, width <= 4) window, d_state 16,
+        E % 64 == 0, an fp32 contiguous 16-byte aligned (batch, E, 16) state, and B / C columns of the x_dbl rows that are 4-byte aligned
+        for 16-bit activations (an even dt_rank; nothing for fp32).  The 16-byte widths of aum_xdt_tm_fwd are NOT required: where that
+        kernel refuses, the x/dt products are the library's."""
+        import aum_hip
+        batch, T, E2 = xz.shape
+        E, N = E2 // 2, self.d_state
+        return (self.activation in ("silu", "swish") and E == self.d_inner and aum_hip.conv1d_tm_chunk_supported(xz[..., :E], conv_state)
+                and aum_hip.scan_tm_supported(E, N) and aum_hip.scan_state_supported(ssm_state, batch, E, N)
+                and (xz.element_size() == 4 or self.dt_rank % 2 == 0))
+
+    def prefill_chunk(self, hidden_states, conv_state, ssm_state):
+        """A BACKLOG of T >= 1 tokens through the causal block at the speed of the offline forward: step_chunk's contract -- (batch, T,
+        d_model) in and out, the fixed-batch caches conv_state (batch, d_inner, d_conv) and ssm_state (batch, d_inner, d_state) advanced
+        in place by T tokens -- on the time-parallel kernels instead of one serial chain per wave:
+            xz = in_proj(h)                                                      (batch, T, 2E) token-major rows [x | z]
+            xc = aum_hip.conv1d_tm_prefill(x half, conv_state, w, b, silu)       conv1d_tm_fwd on [carried window ; x]
+            (dt, B, C) = x_proj(xc);  delta = dt W_dt^T                          (one fused launch where aum_xdt_tm_fwd takes the shape)
+            y = aum_hip.scan_tm_fwd_state(xc, delta, ..., state_in=ssm_state, state_out=ssm_state, segments=scan_tm_segments(...))
+            out = out_proj(y)
+        step_chunk / step continue from the caches it leaves (and it continues from theirs): the state crosses as exact fp32, the
+        window holds the inputs themselves.  Against step_chunk on the same tokens the results agree to the kernels' tolerance, not
+        bitwise (long rows are cut into time segments, which re-associates the recurrence).  Where the kernels do not take the shapes
+        this IS step_chunk: prefill_supported says which (the blocks of AuM-Tiny, -Small and -Base all take the fast path; an odd
+        dt_rank with 16-bit activations does not)."""
+        import aum_hip
+        if self.bimamba_type != "none":
+            raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
+        if hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
+            raise ValueError("prefill_chunk() takes hidden_states of shape (batch, T >= 1, d_model)")
+        batch, T, _ = hidden_states.shape
+        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        if conv_state.shape[0] != batch or ssm_state.shape[0] != batch:
+            raise ValueError(f"prefill_chunk() advances fixed-batch caches: {conv_state.shape[0]} / {ssm_state.shape[0]} rows for a batch of {batch}")
+        xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
+        x, z = xz[..., :E], xz[..., E:]
+        plan = self.stream_params(xz.dtype)
+        if not self.prefill_supported(xz, conv_state, ssm_state):
+            return self.step_chunk(hidden_states, conv_state, ssm_state)
+        xc = aum_hip.conv1d_tm_prefill(x, conv_state, plan.conv_w, plan.conv_b, True).contiguous()
+        xc2 = xc.view(batch * T, E)
+        activated = False
+        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, plan.w_x, plan.w_dt):
+            proj, delta = aum_hip.xdt_tm_fwd(xc2, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
+            activated = True
+        else:
+            proj = self.x_proj(xc2)
+            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
+            proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
+        proj = proj.view(batch, T, -1)
+        delta = delta.view(batch, T, E)
+        Bm, Cm = proj[..., R:R + N], proj[..., R + N:R + 2 * N]
+        seg = aum_hip.scan_tm_segments(batch, E, T, False, device=xc.device) if xc.is_cuda else 1
+        args = (xc, delta, plan.A, Bm, Cm, plan.D, z, None if activated else plan.dt_bias, not activated, activated)
+        y = aum_hip.scan_tm_fwd_state(*args, state_in=ssm_state, state_out=ssm_state, segments=seg)     # raises where it refuses: no quiet second path
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
 

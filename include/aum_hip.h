@@ -407,6 +407,31 @@ int64_t aum_scan_tm_seg_carry_bytes(int32_t batch, int32_t dim, int32_t len, int
 int64_t aum_scan_tm_seg_workspace_bytes(int32_t batch, int32_t dim, int32_t len, int32_t dstate, int32_t bidirectional, int32_t segments);
 
 /*
+ * aum_scan_tm_fwd with STATE IN and STATE OUT (additive; inference only): the one-direction, forward-time scan entered with a carried
+ * state and leaving the state behind the row's last step -- the prefill of a streaming session (Mamba.forward with inference_params at
+ * seqlen_offset == 0, MS:268-271, 300-302 restated on token-major rows), continued by aum_scan_tm_chunk / aum_stream_block_tm on the same
+ * cache row.
+ *   base:      as aum_scan_tm_fwd (both delta forms, with and without z, fp32 / bf16 / fp16).  A_b, ckpt, out_pre must be NULL and
+ *              AUM_SCAN_REVERSE clear: AUM_E_UNSUPPORTED otherwise (no backward exists for this entry point).
+ *   state_in:  (batch, dim, dstate) fp32 contiguous, 16-byte aligned, or NULL = a zero entry state: `out` is then bit for bit what
+ *              aum_scan_tm_fwd (segments == 1) / aum_scan_tm_seg_fwd (the same segments) writes.
+ *   state_out: the same shape, or NULL; the states behind step len - 1, exact fp32.  May be state_in (advance in place).
+ *   segments:  1 = uncut; 2 .. AUM_SCAN_TM_MAX_SEGMENTS = time ranges as aum_scan_tm_seg_fwd, carry = aum_scan_tm_seg_carry_bytes(batch,
+ *              dim, len, dstate, 0, segments) bytes of scratch.  Uncut, advancing by T1 + T2 steps in one call and by T1, then T2 gives
+ *              bit-identical out and state_out; the segmented form re-associates the recurrence at the range boundaries.
+ */
+typedef struct AumScanTmFwdStateArgs {
+    AumScanTmFwdArgs base;
+    const float* state_in;
+    float* state_out;
+    float* carry;
+    int64_t carry_bytes;
+    int32_t segments;
+    int32_t reserved;
+} AumScanTmFwdStateArgs;
+int aum_scan_tm_fwd_state(const AumScanTmFwdStateArgs* args, void* stream);
+
+/*
  * Depthwise causal conv1d (+ SiLU) on TOKEN-MAJOR activations (ABI 8): the same operator as aum_causal_conv1d_fwd / _bwd
  * (MS:272 causal_conv1d_fn; SSI:463 forward and SSI:594-596 backward call sites) for tensors laid out (batch, len, dim) with the
  * channel contiguous -- the layout of the in_proj output rows [x | z] and of the time-serial scan's operands, so x / dx may be the

@@ -27,6 +27,13 @@ stream_read (a second pass of the cls row through all blocks), (b) one stream_pu
 tokens as a peek row); stream_push alone is timed as the third arm, so the cost of the read is visible in both forms.
 
     python tools/stream_hop_bench.py --peek [--batch 1 8]            (--count-only a: push + read, b: push(read=True))
+
+--prefill COLS: a BACKLOG of COLS time columns (8 COLS tokens) into an empty session two ways, same model, same columns, alternating in
+one process: (a) one stream_push (Mamba.step_chunk: the one-launch middle up to 128 tokens, else the three-launch ladder), (b) one
+stream_prefill (Mamba.prefill_chunk: the time-parallel conv and the token-major scan with state in / state out).  The clip is made
+long enough for the backlog (--prefill 512: 8192 frames, L = 4097).
+
+    python tools/stream_hop_bench.py --prefill 31 [--batch 1]        (--count-only a: stream_push, b: stream_prefill)
 """
 import argparse
 import contextlib
@@ -44,9 +51,9 @@ from aum.model import AUM_SIZES, AudioMamba  # noqa: E402
 from mamba_ssm.ops.triton.layernorm import rms_norm_fn  # noqa: E402
 
 
-def make(size, depth, dev):
+def make(size, depth, dev, frames=1024):
     torch.manual_seed(0)
-    m = AudioMamba(spectrogram_size=(128, 1024), depth=depth, embed_dim=AUM_SIZES[size], num_classes=527, bimamba_type="none",
+    m = AudioMamba(spectrogram_size=(128, frames), depth=depth, embed_dim=AUM_SIZES[size], num_classes=527, bimamba_type="none",
                    use_middle_cls_token=False, use_end_cls_token=True, transpose_token_sequence=True)
     return m.eval().to(dev).to(torch.bfloat16)
 
@@ -160,6 +167,47 @@ def peek_ab(model, args, dev):
             out[name + "_ms_median"] = round(statistics.median(t), 4)
             out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
         out["ratio_two_pass_over_one_pass"] = round(out["push_then_read_ms_median"] / out["push_read_one_pass_ms_median"], 3)
+        print(json.dumps(out), flush=True)
+
+
+def backlog_push(model, spec, cache):
+    cache["columns"] = 0                          # a new session every call: the caches' values do not matter for timing
+    model.stream_push(spec, cache)
+
+
+def backlog_prefill(model, spec, cache):
+    cache["columns"] = 0
+    model.stream_prefill(spec, cache)
+
+
+def prefill_ab(model, args, dev):
+    """--prefill COLS: a backlog of COLS columns as one stream_push (a) against one stream_prefill (b), the arms alternating"""
+    arms = (("push", backlog_push), ("prefill", backlog_prefill))
+    for B in args.batch:
+        spec = torch.randn(B, 16 * args.prefill, 128, device=dev, dtype=torch.bfloat16)
+        caches = [model.allocate_inference_cache(B) for _ in arms]
+        if args.count_only:
+            i = 0 if args.count_only == "a" else 1
+            for _ in range(args.count_hops):
+                arms[i][1](model, spec, caches[i])
+            torch.cuda.synchronize()
+            print(json.dumps({"path": "prefill " + arms[i][0], "batch": B, "columns": args.prefill, "hops": args.count_hops}))
+            continue
+        for _ in range(args.warm):
+            for (_, fn), c in zip(arms, caches):
+                timed(fn, model, spec, c)
+        times = [[] for _ in arms]
+        for _ in range(args.hops):
+            for t, (_, fn), c in zip(times, arms, caches):
+                t.append(timed(fn, model, spec, c))
+        g = max(args.hops // args.groups, 1)
+        out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "batch": B, "columns": args.prefill, "tokens": 8 * args.prefill,
+               "clip_columns": model.patch_grid_size[1], "hops": args.hops, "warm": args.warm}
+        for (name, _), t in zip(arms, times):
+            out[name + "_ms_median"] = round(statistics.median(t), 4)
+            out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+            out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+        out["ratio_push_over_prefill"] = round(out["push_ms_median"] / out["prefill_ms_median"], 3)
         print(json.dumps(out), flush=True)
 
 
@@ -299,9 +347,14 @@ def main():
     ap.add_argument("--count-hops", type=int, default=4)
     ap.add_argument("--fused-ab", action="store_true", help="stream_push with the block's middle as three launches vs aum_stream_block_tm")
     ap.add_argument("--peek", action="store_true", help="stream_push + stream_read vs one stream_push(read=True)")
+    ap.add_argument("--prefill", type=int, default=0, metavar="COLS", help="a backlog of COLS columns: one stream_push vs one stream_prefill")
     args = ap.parse_args()
     dev = "cuda:0"
-    model = make(args.size, args.depth, dev)
+    model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill))
+    if args.prefill:
+        with torch.no_grad():
+            prefill_ab(model, args, dev)
+        return
     if args.pool:
         with torch.no_grad():
             pool_main(model, args, dev)
