@@ -247,14 +247,16 @@ class AudioMamba(nn.Module):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
         (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
         are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it.
-        prefill=True (fixed-batch caches, no peek row): the mixers take the tokens as a backlog (Mamba.prefill_chunk)"""
+        prefill=True (no peek row): the mixers take the tokens as a backlog (Mamba.prefill_chunk; with seq_map the packed backlogs of
+        several sessions over pools)"""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
                                            residual_in_fp32=True, eps=layer.norm.eps)
             conv_state, ssm_state = layer_caches[i]
             if prefill:
-                hidden, _, _ = layer.mixer.prefill_chunk(hidden, conv_state, ssm_state)
+                hidden, _, _ = (layer.mixer.prefill_chunk(hidden, conv_state, ssm_state) if seq_map is None else
+                                layer.mixer.prefill_chunk(hidden, conv_state, ssm_state, seq_map=seq_map))
             else:
                 hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek)
         return hidden, residual
@@ -427,12 +429,17 @@ class AudioMamba(nn.Module):
         return cache["columns"], self.stream_read(cache, return_features)
 
     @torch.no_grad()
-    def stream_prefill_many(self, specs, pool, sessions):
+    def stream_prefill_many(self, specs, pool, sessions, packed=False):
         """The backlog path of a pool (not the per-hop path: that is stream_push_many, one packed pass): specs[i] (16 k_i, n_mels), the
-        next k_i columns of session sessions[i] (distinct rows of a pool from allocate_stream_pool).  A loop over the sessions on the
-        host: each one's cache rows are gathered (index_select), advanced by stream_prefill's pass at batch 1 and scattered back
-        (index_copy_); the other rows are not touched.  Every argument is checked before any cache is touched.  Returns the
-        per-session column counts."""
+        next k_i columns of session sessions[i] (distinct rows of a pool from allocate_stream_pool).  Every argument is checked before
+        any cache is touched.  Returns the per-session column counts.  No peek row and no read=: callers use stream_read.
+        packed=False: a loop over the sessions on the host -- each one's cache rows are gathered (index_select), advanced by
+        stream_prefill's pass at batch 1 and scattered back (index_copy_); the other rows are not touched.  Bit for bit stream_prefill
+        of each session alone.
+        packed=True: ONE pass for all sessions -- one patch-embed GEMM over the frames concatenated in time, each session's position
+        rows gathered from its own offset (as stream_push_many does), then all blocks once on the packed tokens through
+        Mamba.prefill_chunk(seq_map=): only the conv and the scan see the session boundaries, and they advance the pool rows in place
+        (no gather, no scatter).  The same caches and counts to the kernels' tolerance, not bitwise: the GEMMs see another M."""
         self._check_streamable()
         rows = self._check_sessions("stream_prefill_many", pool, sessions)
         ph, pw = self.patch_embed.proj.kernel_size
@@ -449,6 +456,19 @@ class AudioMamba(nn.Module):
             if pool["columns"][r] + k > nt:
                 raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
             ks.append(k)
+        if packed:
+            import aum_hip
+            dev = specs[0].device
+            smap = aum_hip.seq_map([k * nf for k in ks], rows, device=dev)
+            cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
+            if dev.type == "cuda":
+                cols = cols.pin_memory()
+            cols = cols.to(dev, non_blocking=True)
+            x = self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)   # a session's tokens are contiguous
+            self._stream_layers(x, pool["layers"], smap, prefill=True)
+            for r, k in zip(rows, ks):
+                pool["columns"][r] += k
+            return [pool["columns"][r] for r in rows]
         for sp, r, k in zip(specs, rows, ks):
             ix = torch.tensor([r], dtype=torch.int64, device=sp.device)
             one = {i: (c.index_select(0, ix), s.index_select(0, ix)) for i, (c, s) in pool["layers"].items()}

@@ -219,6 +219,18 @@ class ScanTmChunkVarArgs(C.Structure):
                 + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "dstate", "dtype")] + [("flags", _u32)])
 
 
+class ConvTmPrefillVarArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("x", "conv_state", "weight", "bias", "y", "cu_seqlens", "state_indices")] + [(n, _i64) for n in ("x_ts", "y_ts")]
+                + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "width", "dtype")] + [("flags", _u32), ("max_len", _i32)])
+
+
+class ScanTmFwdStateVarArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("u", "delta", "z", "B", "C", "A", "D", "delta_bias", "state", "out", "cu_seqlens", "state_indices")]
+                + [(n, _i64) for n in ("u_ts", "delta_ts", "z_ts", "B_ts", "C_ts", "out_ts")]
+                + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "dstate", "dtype")] + [("flags", _u32)]
+                + [(n, _i32) for n in ("range_len", "max_len", "reserved")] + [("carry", _vp), ("carry_bytes", _i64)])
+
+
 class StreamBlockArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "z", "conv_state", "state", "conv_weight", "conv_bias", "wx", "wdt", "A", "D", "delta_bias", "y", "scratch",
                                     "cu_seqlens", "state_indices")]
@@ -244,7 +256,8 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_fbank_fwd", "aum_frontend_tokens_fwd", "aum_stft_logmel_fwd", "aum_spec_time_warp", "aum_proj_fwd", "aum_proj_bwd_data",
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
-    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state")}
+    "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
+    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -257,6 +270,7 @@ _SIGNATURES.update({
     "aum_sum_rows": ([_vp, _vp, _i64, _i64, _i64, _i32, _vp], C.c_int), "aum_sum_rows_multi": ([_vp, _i32, _vp], C.c_int),
     "aum_cast_bank": ([_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp], C.c_int),
     "aum_stream_block_scratch_bytes": ([_i32] * 3, _i64), "aum_stream_block_max_len": ([], _i32),
+    "aum_scan_tm_fwd_state_var_carry_bytes": ([_i32] * 4, _i64),
 })
 EXPORTS = list(_SIGNATURES)
 
@@ -1212,6 +1226,151 @@ def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplu
     if peek:
         a.flags |= SCAN_PEEK_LAST
     _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(m.lens), dim, total, dstate, u.element_size()))
+    return out
+
+
+# ---- packed prefill: the backlogs of many sessions in one launch per operator (aum_conv1d_tm_prefill_var, aum_scan_tm_fwd_state_var)
+def conv1d_tm_prefill_var_supported(x, conv_state):
+    """the limits of aum_conv1d_tm_prefill_var (include/aum_hip.h): those of conv1d_tm_chunk_var -- packed (total >= 1, dim) rows with
+    16-byte rows, an fp32 contiguous (nrows, dim, width <= 4) pool"""
+    return conv1d_tm_chunk_var_supported(x, conv_state)
+
+
+def conv1d_tm_prefill_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None):
+    """conv1d_tm_prefill on PACKED sessions in one launch (aum_conv1d_tm_prefill_var): x (total, dim) packed rows (row stride free: the x
+    half of in_proj rows), conv_state (nrows, dim, width) the pool of fp32 windows -- each session's rows enter with the window of the
+    row seq_map names for it, read as fp32 in place (no [window ; x] copy, no rounding), and that row then holds the session's last
+    `width` inputs (fewer rows than `width`: the old entries shift); an empty session's row and the rows no session names are not
+    touched.  Time-parallel: one wave per (session, 64 rows, channel block).  Per session, y and the window are bit for bit
+    conv1d_tm_prefill's at batch 1 when the window's values are exact in x's dtype.  Returns y (total, dim) contiguous in x's dtype
+    (out: written there).  Raises where the kernel does not take the operands.  No device synchronisation."""
+    lib = lib or get()
+    for t in (x, conv_state, out):
+        lib.check_tensor(t)
+    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return x.new_empty(x.shape) if out is None else out
+    if not (x.dim() == 2 and x.shape[0] >= 1 and conv1d_tm_prefill_var_supported(x, conv_state)):
+        raise RuntimeError(f"conv1d_tm_prefill_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total >= 1, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
+    check_seq_map("conv1d_tm_prefill_var", seq_map, x.shape[0], conv_state.shape[0], x.device)
+    return _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, seq_map, out, lib)
+
+
+def _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, m, out, lib):
+    """conv1d_tm_prefill_var behind its checks: operands conv1d_tm_prefill_var_supported takes, a map check_seq_map passed, total >= 1"""
+    total, dim = x.shape
+    a = ConvTmPrefillVarArgs()
+    y, _held = _conv_chunk_operands(a, "conv1d_tm_prefill_var", lib, x, conv_state, weight, bias, silu, out)
+    if not y.is_contiguous():
+        raise RuntimeError("conv1d_tm_prefill_var: out must be contiguous")
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
+    a.x_ts, a.y_ts = _tm2(x, "x", dim), dim
+    a.total, a.nseq, a.nrows, a.max_len = total, len(m.lens), conv_state.shape[0], max(m.lens)
+    _launch(lib.c.aum_conv1d_tm_prefill_var, a, x, lib, "conv_tm_prefill_var", (len(m.lens), dim, total, x.element_size()))
+    return y
+
+
+def scan_tm_var_range(lens, dim, nsimd=None, device=None):
+    """range_len of scan_tm_fwd_state_var for sessions of these lengths (0: not cut): the rule of scan_tm_segments with batch := the number
+    of sessions and length := the longest session -- cut only when the longest has >= 1024 steps and the uncut launch is under one wave
+    per two SIMDs, into as many ranges as give every SIMD three waves, ranges no shorter than 128 steps, at most SCAN_TM_MAX_SEGMENTS
+    of them; the range is ceil(longest / ranges) rounded up to the 8-step block.  The rule is inherited from the B = 8, L = 4097
+    measurement of the fixed-batch kernels (profiles/r04_seg_time.json) and is NOT measured for ragged packs: short sessions of a
+    pack leave the ranges past their end empty, so the waves it counts on are fewer than at a fixed batch."""
+    lens = [int(n) for n in lens]
+    longest = max(lens) if lens else 0
+    seg = scan_tm_segments(len(lens), dim, longest, False, nsimd=nsimd, device=device) if longest >= 1 else 1
+    if seg < 2:
+        return 0
+    return -(-(-(-longest // seg)) // SCAN_TM_CK) * SCAN_TM_CK
+
+
+def scan_tm_fwd_state_var_supported(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False,
+                                    range_len=0, max_len=None):
+    """the limits of aum_scan_tm_fwd_state_var (include/aum_hip.h): those of scan_tm_fwd_state on packed rows -- dstate == 16, dim % 64
+    == 0, (total >= 1, dim) rows of one dtype moved as 16-byte chunks, B / C rows 4-byte aligned, an activated delta only for 16-bit
+    rows with z -- the pool fp32 contiguous (nrows, dim, 16), 16-byte aligned, and range_len 0 or a multiple of 8 that cuts the longest
+    session (max_len; None: not known here) into at most SCAN_TM_MAX_SEGMENTS ranges."""
+    if u.dim() != 2 or A.dim() != 2 or u.shape[0] < 1 or not scan_tm_supported(u.shape[1], A.shape[1]) or u.dtype not in _DT:
+        return False
+    total, dim = u.shape
+    dstate, es = A.shape[1], u.element_size()
+    if A.shape[0] != dim:
+        return False
+    for t, last in ((u, dim), (delta, dim), (z, dim), (B, dstate), (C, dstate)):
+        if t is None:
+            continue
+        if t.dtype != u.dtype or t.dim() != 2 or tuple(t.shape) != (total, last) or (t.stride(1) != 1 and last != 1):
+            return False
+        ts = _tm2(t, "operand", last)
+        if last == dim and (t.data_ptr() % 16 or (ts * es) % 16):
+            return False
+        if last == dstate and es == 2 and (t.data_ptr() % 4 or ts % 2):
+            return False
+        if ts < 0 or (ts + dim) * es * total >= 2 ** 31:
+            return False
+    if delta_activated and (es == 4 or z is None):
+        return False
+    range_len = int(range_len)
+    if range_len < 0 or range_len % SCAN_TM_CK:
+        return False
+    if range_len and max_len is not None and -(-int(max_len) // range_len) > SCAN_TM_MAX_SEGMENTS:
+        return False
+    return (state.dim() == 3 and state.shape[0] >= 1 and tuple(state.shape[1:]) == (dim, dstate) and state.dtype == torch.float32
+            and state.is_contiguous() and state.data_ptr() % 16 == 0)
+
+
+def scan_tm_fwd_state_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
+                          range_len=0, out=None, lib=None):
+    """scan_tm_fwd_state on PACKED sessions (aum_scan_tm_fwd_state_var): state (nrows, dim, 16) the pool of fp32 states -- session i runs
+    its rows of the packed u, delta, z (total, dim) and B, C (total, 16) from row seq_map.rows[i], which is advanced IN PLACE; an empty
+    session's row and the rows no session names are not touched.  One direction, forward time, both delta forms, with and without z,
+    fp32 / bf16 / fp16 (row strides free).
+    range_len == 0: uncut, one wave per (session, 64 channels); per session bit for bit scan_tm_fwd_state(segments=1) at batch 1.
+    range_len > 0, a multiple of 8 (scan_tm_var_range chooses): every session is cut into ranges of range_len steps -- at most
+    SCAN_TM_MAX_SEGMENTS for the longest -- a carry launch and a main launch; the ranges past a session's end are empty.  COINCIDENCE:
+    a session of n steps is bit for bit scan_tm_fwd_state(segments=s) at batch 1 with s = ceil(n / range_len) exactly when that call
+    cuts the same ranges, i.e. when ceil(ceil(n / s) / 8) * 8 == range_len (n = 40, 24, 9, 1 at range_len 8: yes; n = 130 at 128: two
+    ranges of 128 + 2 here, of 72 + 58 there -- no); elsewhere the two differ by the re-association at the range boundaries.
+    A session's results do not depend on the other sessions of the call, on its place in the pack or on its pool row (bitwise).
+    Returns out (total, dim) contiguous in u's dtype.  Raises where the kernel does not take the operands.  No device synchronisation."""
+    lib = lib or get()
+    for t in (state, u, delta, z, B, C, out):
+        lib.check_tensor(t)
+    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return u.new_empty(u.shape) if out is None else out
+    max_len = max(seq_map.lens) if isinstance(seq_map, SeqMap) else None
+    if not scan_tm_fwd_state_var_supported(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, range_len, max_len):
+        raise RuntimeError(f"scan_tm_fwd_state_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} strides "
+                           f"{u.stride()}, A {tuple(A.shape)}, range_len {range_len} for a longest session of {max_len} (need packed 16-byte "
+                           "rows of one dtype, dim % 64 == 0, dstate 16, an fp32 contiguous 16-byte aligned (nrows, dim, 16) pool, range_len a "
+                           f"multiple of {SCAN_TM_CK} giving at most {SCAN_TM_MAX_SEGMENTS} ranges)")
+    check_seq_map("scan_tm_fwd_state_var", seq_map, u.shape[0], state.shape[0], u.device)
+    return _scan_tm_fwd_state_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, int(range_len), out, lib)
+
+
+def _scan_tm_fwd_state_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, range_len, out, lib):
+    """scan_tm_fwd_state_var behind its checks: operands scan_tm_fwd_state_var_supported takes, a map check_seq_map passed"""
+    total, dim = u.shape
+    dstate = state.shape[2]
+    a = ScanTmFwdStateVarArgs()
+    out, _held = _scan_chunk_operands(a, "scan_tm_fwd_state_var", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
+    if not out.is_contiguous():
+        raise RuntimeError("scan_tm_fwd_state_var: out must be contiguous")
+    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), dim
+    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
+    a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
+    a.total, a.nseq, a.nrows, a.max_len, a.range_len = total, len(m.lens), state.shape[0], max(m.lens), range_len
+    carry = None
+    if range_len:
+        nranges = -(-max(m.lens) // range_len)
+        a.carry_bytes = int(lib.c.aum_scan_tm_fwd_state_var_carry_bytes(len(m.lens), dim, dstate, nranges))
+        if a.carry_bytes <= 0:
+            raise RuntimeError(f"scan_tm_fwd_state_var: range_len={range_len} ({nranges} ranges) not supported for this shape")
+        carry = torch.empty((a.carry_bytes // 4,), dtype=torch.float32, device=u.device)
+        a.carry = _ptr(carry)
+    _launch(lib.c.aum_scan_tm_fwd_state_var, a, u, lib, "scan_tm_fwd_state_var", (len(m.lens), dim, total, dstate, u.element_size(), range_len))
     return out
 
 

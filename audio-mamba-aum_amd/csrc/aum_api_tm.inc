@@ -5,6 +5,7 @@
 #include "conv_tm_kernels.h"
 #include "stream_tm_kernels.h"
 #include "stream_block_kernels.h"
+#include "stream_prefill_kernels.h"
 
 namespace aum {
 
@@ -26,6 +27,10 @@ int scan_tm_seg_fwd_f16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase
 int scan_tm_fwd_state_f32(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
 int scan_tm_fwd_state_bf16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
 int scan_tm_fwd_state_f16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s);
+// the same on packed sessions (scant_fwd_state_var; sg != nullptr: one launch of `phase` 3 or 0 of scant_seg_fwd_state_var)
+int scan_tm_fwd_state_var_f32(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s);
+int scan_tm_fwd_state_var_bf16(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s);
+int scan_tm_fwd_state_var_f16(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_f32(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_bf16(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
 int scan_tm_seg_bwd_f16(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s);
@@ -178,20 +183,69 @@ template <class T> static int scan_tm_fwd_state_t(const AumScanTmFwdArgs& a, con
     if (sp) return hz ? launch_scant_seg_fwd_state<T, 0, true, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, true, false>(a, *sg, st, s);
     return hz ? launch_scant_seg_fwd_state<T, 0, false, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, false, false>(a, *sg, st, s);
 }
+#ifndef AUM_EMU
+template <class T, bool SP, bool HAS_Z>
+__global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd_state_var(AumScanTmFwdArgs a, ScanTVar v) {
+    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    scant_fwd_state_var<T, SP, HAS_Z>(a, v, (int)blockIdx.x, lds);
+}
+template <class T, int PHASE, bool SP, bool HAS_Z>
+__global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_seg_fwd_state_var(AumScanTmFwdArgs a, ScanTSeg sg, ScanTVar v) {
+    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>(a, sg, v, (int)blockIdx.x, lds);
+}
+#endif
+template <class T, bool SP, bool HAS_Z> static int launch_scant_fwd_state_var(const AumScanTmFwdArgs& a, const ScanTVar& v, aum_stream_t s) {
+    const int grid = (v.nseq * (a.dim / WAVE) + SCANT_NW - 1) / SCANT_NW;
+#ifdef AUM_EMU
+    (void)s;
+    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
+    for (int wg = 0; wg < grid; ++wg) scant_fwd_state_var<T, SP, HAS_Z>(a, v, wg, lds.data());
+#else
+    hipLaunchKernelGGL((k_scant_fwd_state_var<T, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, v);
+#endif
+    return launch_status();
+}
+template <class T, int PHASE, bool SP, bool HAS_Z>
+static int launch_scant_seg_fwd_state_var(const AumScanTmFwdArgs& a, const ScanTSeg& sg, const ScanTVar& v, aum_stream_t s) {
+    const int grid = (v.nseq * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
+#ifdef AUM_EMU
+    (void)s;
+    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
+    for (int wg = 0; wg < grid; ++wg) scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>(a, sg, v, wg, lds.data());
+#else
+    hipLaunchKernelGGL((k_scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, sg, v);
+#endif
+    return launch_status();
+}
+template <class T> static int scan_tm_fwd_state_var_t(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s) {
+    const bool sp = (a.flags & AUM_SCAN_SOFTPLUS) != 0, hz = a.z != nullptr;
+    if (!sg) {
+        if (sp) return hz ? launch_scant_fwd_state_var<T, true, true>(a, v, s) : launch_scant_fwd_state_var<T, true, false>(a, v, s);
+        return hz ? launch_scant_fwd_state_var<T, false, true>(a, v, s) : launch_scant_fwd_state_var<T, false, false>(a, v, s);
+    }
+    if (phase == 3) return sp ? launch_scant_seg_fwd_state_var<T, 3, true, false>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 3, false, false>(a, *sg, v, s);
+    if (phase != 0) return AUM_E_UNSUPPORTED;
+    if (sp) return hz ? launch_scant_seg_fwd_state_var<T, 0, true, true>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 0, true, false>(a, *sg, v, s);
+    return hz ? launch_scant_seg_fwd_state_var<T, 0, false, true>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 0, false, false>(a, *sg, v, s);
+}
 #if AUM_HAS_DTYPE(0)
 int scan_tm_fwd_f32(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<float>(a, s); }
 int scan_tm_seg_fwd_f32(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<float>(a, sg, phase, s); }
 int scan_tm_fwd_state_f32(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<float>(a, st, sg, phase, s); }
+int scan_tm_fwd_state_var_f32(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_var_t<float>(a, v, sg, phase, s); }
 #endif
 #if AUM_HAS_DTYPE(1)
 int scan_tm_fwd_bf16(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<bf16_t>(a, s); }
 int scan_tm_seg_fwd_bf16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<bf16_t>(a, sg, phase, s); }
 int scan_tm_fwd_state_bf16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<bf16_t>(a, st, sg, phase, s); }
+int scan_tm_fwd_state_var_bf16(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_var_t<bf16_t>(a, v, sg, phase, s); }
 #endif
 #if AUM_HAS_DTYPE(2)
 int scan_tm_fwd_f16(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<f16_t>(a, s); }
 int scan_tm_seg_fwd_f16(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) { return scan_tm_seg_fwd_t<f16_t>(a, sg, phase, s); }
 int scan_tm_fwd_state_f16(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_t<f16_t>(a, st, sg, phase, s); }
+int scan_tm_fwd_state_var_f16(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s) { return scan_tm_fwd_state_var_t<f16_t>(a, v, sg, phase, s); }
 #endif
 #endif
 
@@ -948,5 +1002,113 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     if (a->flags & AUM_STREAM_PEEK_LAST) return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, true>(*a, s) : sb_launch<f16_t, false, true>(*a, s);
     return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, false>(*a, s) : sb_launch<f16_t, false, false>(*a, s);
 #endif
+}
+
+// ---- packed prefill (stream_prefill_kernels.h): the backlogs of many sessions, time-parallel conv and state in / state out scan ----
+#ifndef AUM_EMU
+template <class T, bool SILU> AUM_GLOBAL void k_convt_prefill_var(AumConvTmPrefillVarArgs a) { convp_var_wave<T, SILU>(a, (int)blockIdx.x); }
+#endif
+template <class T, bool SILU> static int convpv_launch(const AumConvTmPrefillVarArgs& a, aum_stream_t s) {
+    const int grid = a.nseq * convt_chunks<false>(a.max_len) * convt_cblocks<T, false>(a.dim);
+#ifdef AUM_EMU
+    (void)s;
+    for (int wg = 0; wg < grid; ++wg) convp_var_wave<T, SILU>(a, wg);
+#else
+    AUM_LAUNCH((k_convt_prefill_var<T, SILU>), grid, 0, s, a);
+#endif
+    return launch_status();
+}
+template <class T> static int convpv_dispatch_t(const AumConvTmPrefillVarArgs& a, aum_stream_t s) {
+    return (a.flags & AUM_CONV_SILU) ? convpv_launch<T, true>(a, s) : convpv_launch<T, false>(a, s);
+}
+AUM_API int aum_conv1d_tm_prefill_var(const AumConvTmPrefillVarArgs* a, void* stream) {
+    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
+    int err = 0;
+    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    if (a->dim <= 0 || a->width <= 0 || a->max_len <= 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (a->width > CONVT_W || a->max_len > a->total) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~AUM_CONV_SILU) return AUM_E_UNSUPPORTED;
+    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
+    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
+    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
+    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
+    if ((ptrs & 15) || (((a->x_ts | a->y_ts) * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
+    if (a->x == a->y) return AUM_E_UNSUPPORTED;
+    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit; a sequence has at most `total` rows
+    if ((int64_t)a->total * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
+    if ((int64_t)a->nseq * convt_chunks<false>(a->max_len) * convt_cblocks<float, false>(a->dim) >= lim) return AUM_E_UNSUPPORTED;
+    aum_stream_t s = (aum_stream_t)stream;
+    switch (a->dtype) {
+        case AUM_F32: return convpv_dispatch_t<float>(*a, s);
+        case AUM_BF16: return convpv_dispatch_t<bf16_t>(*a, s);
+        default: return convpv_dispatch_t<f16_t>(*a, s);
+    }
+}
+AUM_API int64_t aum_scan_tm_fwd_state_var_carry_bytes(int32_t nseq, int32_t dim, int32_t dstate, int32_t nranges) {
+    if (nseq <= 0 || dim <= 0 || nranges < 1 || nranges > AUM_SCAN_TM_MAX_SEGMENTS || !scant_supported(dim, dstate)) return 0;
+    return scant_seg_carry_floats(nseq, dim, nranges, false) * (int64_t)sizeof(float);
+}
+AUM_API int aum_scan_tm_fwd_state_var(const AumScanTmFwdStateVarArgs* a, void* stream) {
+    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
+    int err = 0;
+    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    if (a->dim <= 0 || a->dstate <= 0 || a->max_len <= 0 || a->range_len < 0) return AUM_E_SHAPE;
+    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
+    if (!scant_supported(a->dim, a->dstate) || a->max_len > a->total) return AUM_E_UNSUPPORTED;
+    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
+    if (!scan_tm_act_ok(a->flags, a->dtype, a->z)) return AUM_E_UNSUPPORTED;
+    const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
+    if (a->dtype != AUM_F32) {      // 16-bit B / C rows are read as dwords
+        if ((a->B_ts | a->C_ts) & 1) return AUM_E_UNSUPPORTED;
+        if ((((uintptr_t)a->B) | ((uintptr_t)a->C)) & 3) return AUM_E_UNSUPPORTED;
+    }
+    {       // row offsets inside a session are 32-bit byte cursors; a session has at most `total` rows
+        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
+        for (int64_t t : ts)
+            if (t < 0 || (t + a->dim) * es * a->total > lim) return AUM_E_UNSUPPORTED;
+        if ((int64_t)a->dim * a->dstate * 4 > lim) return AUM_E_UNSUPPORTED;
+        // rows are moved as 16-byte chunks, a channel's states too
+        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->state;
+        const int64_t strides = a->u_ts | a->delta_ts | (a->z ? a->z_ts : 0) | a->out_ts;
+        if ((ptrs & 15) || ((strides * es) & 15)) return AUM_E_UNSUPPORTED;
+    }
+    int nranges = 1;
+    if (a->range_len > 0) {
+        if (a->range_len % SCANT_CK) return AUM_E_UNSUPPORTED;
+        nranges = (a->max_len + a->range_len - 1) / a->range_len;
+        if (nranges > AUM_SCAN_TM_MAX_SEGMENTS) return AUM_E_UNSUPPORTED;
+        if (!a->carry) return AUM_E_NULL;
+        if (((uintptr_t)a->carry & 3) || a->carry_bytes < scant_seg_carry_floats(a->nseq, a->dim, nranges, false) * (int64_t)sizeof(float)) return AUM_E_WORKSPACE;
+    }
+    if ((int64_t)a->nseq * (a->dim / WAVE) * nranges > lim) return AUM_E_UNSUPPORTED;
+    // the kernels' view: a fixed-batch argument struct whose "batch entry" b is a packed row (X_bs := X_ts); an activated delta carries
+    // its bias and softplus already
+    AumScanTmFwdArgs k = {};
+    k.u = a->u; k.delta = a->delta; k.z = a->z; k.B = a->B; k.C = a->C;
+    k.A = a->A; k.D = a->D; k.delta_bias = a->delta_bias; k.out = a->out;
+    k.u_bs = k.u_ts = a->u_ts; k.delta_bs = k.delta_ts = a->delta_ts; k.z_bs = k.z_ts = a->z ? a->z_ts : 0;
+    k.B_bs = k.B_ts = a->B_ts; k.C_bs = k.C_ts = a->C_ts; k.out_bs = k.out_ts = a->out_ts;
+    k.batch = a->nseq; k.dim = a->dim; k.len = a->max_len; k.dstate = a->dstate; k.dtype = a->dtype; k.flags = a->flags;
+    k = scan_tm_fwd_resolve(k);
+    const ScanTVar v = {a->cu_seqlens, a->state_indices, a->state, a->total, a->nseq, a->nrows, a->max_len};
+    aum_stream_t s = (aum_stream_t)stream;
+    auto run = [&](const ScanTSeg* sg, int phase) {
+        switch (k.dtype) {
+            case AUM_F32: return scan_tm_fwd_state_var_f32(k, v, sg, phase, s);
+            case AUM_BF16: return scan_tm_fwd_state_var_bf16(k, v, sg, phase, s);
+            default: return scan_tm_fwd_state_var_f16(k, v, sg, phase, s);
+        }
+    };
+    if (a->range_len == 0) return run(nullptr, 0);
+    ScanTSeg sg;
+    sg.carry = a->carry;
+    sg.nseg = nranges;
+    sg.seg_len = a->range_len;
+    sg.dir0 = 0;
+    sg.ndl = 1;
+    const int r = run(&sg, 3);
+    if (r != AUM_OK) return r;
+    return run(&sg, 0);
 }
 #endif

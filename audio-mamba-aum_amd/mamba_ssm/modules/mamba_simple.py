@@ -333,7 +333,55 @@ class Mamba(nn.Module):
                 and aum_hip.scan_tm_supported(E, N) and aum_hip.scan_state_supported(ssm_state, batch, E, N)
                 and (xz.element_size() == 4 or self.dt_rank % 2 == 0))
 
-    def prefill_chunk(self, hidden_states, conv_state, ssm_state):
+    def prefill_packed_supported(self, xz, conv_state, ssm_state, seq_map, range_len=0):
+        """prefill_chunk(seq_map=)'s dispatch, the sibling of prefill_supported for (1, total, 2E) packed in_proj rows and POOLS of caches:
+        what aum_conv1d_tm_prefill_var and aum_scan_tm_fwd_state_var take -- silu, x rows the token-major conv takes with an fp32
+        (nrows, E, width <= 4) pool of windows, d_state 16, E % 64 == 0, an fp32 contiguous 16-byte aligned (nrows, E, 16) pool of states,
+        B / C columns of the x_dbl rows 4-byte aligned for 16-bit activations (an even dt_rank), and a range_len that cuts the longest
+        session into at most 32 ranges."""
+        import aum_hip
+        E2 = xz.shape[2]
+        E, N = E2 // 2, self.d_state
+        return (self.activation in ("silu", "swish") and E == self.d_inner and xz.shape[0] == 1
+                and aum_hip.conv1d_tm_prefill_var_supported(xz[0, :, :E], conv_state)
+                and aum_hip.scan_tm_supported(E, N) and aum_hip.scan_state_supported(ssm_state, ssm_state.shape[0], E, N)
+                and (xz.element_size() == 4 or self.dt_rank % 2 == 0)
+                and range_len % aum_hip.SCAN_TM_CK == 0 and (range_len == 0 or -(-max(seq_map.lens) // range_len) <= aum_hip.SCAN_TM_MAX_SEGMENTS))
+
+    def _prefill_packed(self, hidden_states, conv_state, ssm_state, seq_map):
+        """prefill_chunk with a seq_map: (1, total, d_model) packed backlogs, pools of caches"""
+        import aum_hip
+        if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or conv_state.shape[0] != ssm_state.shape[0]:
+            raise ValueError(f"prefill_chunk(seq_map=): hidden_states (1, total, d_model), pools of one size, not {conv_state.shape[0]} / {ssm_state.shape[0]} rows")
+        aum_hip.check_seq_map("prefill_chunk", seq_map, hidden_states.shape[1], conv_state.shape[0], hidden_states.device)
+        if seq_map.total == 0:
+            return hidden_states.new_empty(hidden_states.shape), conv_state, ssm_state
+        total = hidden_states.shape[1]
+        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        xz = self.in_proj(hidden_states[0]).view(1, total, 2 * E)
+        plan = self.stream_params(xz.dtype)
+        rng = aum_hip.scan_tm_var_range(seq_map.lens, E, device=xz.device) if xz.is_cuda else 0
+        if not self.prefill_packed_supported(xz, conv_state, ssm_state, seq_map, rng):
+            return self.step_chunk(hidden_states, conv_state, ssm_state, seq_map=seq_map)
+        x, z = xz[0, :, :E], xz[0, :, E:]
+        xc = aum_hip._conv1d_tm_prefill_var(x, conv_state, plan.conv_w, plan.conv_b, True, seq_map, None, aum_hip.get())
+        activated = False
+        if xc.is_cuda and aum_hip.xdt_tm_supported(xc, plan.w_x, plan.w_dt):
+            proj, delta = aum_hip.xdt_tm_fwd(xc, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
+            activated = True
+        else:
+            proj = self.x_proj(xc)
+            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
+            proj, delta = proj.to(xc.dtype), delta.to(xc.dtype)
+        args = (ssm_state, xc, delta, plan.A, proj[:, R:R + N], proj[:, R + N:R + 2 * N], plan.D, z, None if activated else plan.dt_bias,
+                not activated, activated)
+        if not aum_hip.scan_tm_fwd_state_var_supported(*args, range_len=rng, max_len=max(seq_map.lens)):      # no quiet second path
+            raise RuntimeError(f"prefill_chunk(seq_map=): aum_scan_tm_fwd_state_var does not take xc {tuple(xc.shape)} {xc.dtype}, delta "
+                               f"{tuple(delta.shape)} strides {delta.stride()}, x_dbl strides {proj.stride()}, range_len {rng}")
+        y = aum_hip._scan_tm_fwd_state_var(*args, seq_map, rng, None, aum_hip.get())      # the map was checked above, once
+        return self.out_proj(y).view(1, total, -1), conv_state, ssm_state
+
+    def prefill_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None):
         """A BACKLOG of T >= 1 tokens through the causal block at the speed of the offline forward: step_chunk's contract -- (batch, T,
         d_model) in and out, the fixed-batch caches conv_state (batch, d_inner, d_conv) and ssm_state (batch, d_inner, d_state) advanced
         in place by T tokens -- on the time-parallel kernels instead of one serial chain per wave:
@@ -346,10 +394,18 @@ class Mamba(nn.Module):
         window holds the inputs themselves.  Against step_chunk on the same tokens the results agree to the kernels' tolerance, not
         bitwise (long rows are cut into time segments, which re-associates the recurrence).  Where the kernels do not take the shapes
         this IS step_chunk: prefill_supported says which (the blocks of AuM-Tiny, -Small and -Base all take the fast path; an odd
-        dt_rank with 16-bit activations does not)."""
+        dt_rank with 16-bit activations does not).
+        seq_map (aum_hip.seq_map): the backlogs of SEVERAL SESSIONS in one pass, as step_chunk(seq_map=) takes their hops -- hidden_states
+        (1, total, d_model) holds the sessions' tokens behind one another, the caches are pools of nrows rows, session i advances row
+        seq_map.rows[i] by seq_map.lens[i] tokens and the other rows are not touched.  The four projections take the packed rows as they
+        are; only aum_hip.conv1d_tm_prefill_var and aum_hip.scan_tm_fwd_state_var (cut into ranges where aum_hip.scan_tm_var_range says
+        so) see the session boundaries.  Against prefill_chunk session by session the results agree to the kernels' tolerance, not
+        bitwise: the GEMMs see another M.  Where prefill_packed_supported refuses, this is step_chunk(seq_map=)."""
         import aum_hip
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
+        if seq_map is not None:
+            return self._prefill_packed(hidden_states, conv_state, ssm_state, seq_map)
         if hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
             raise ValueError("prefill_chunk() takes hidden_states of shape (batch, T >= 1, d_model)")
         batch, T, _ = hidden_states.shape

@@ -734,6 +734,61 @@ int aum_stream_block_tm(const AumStreamBlockArgs* args, void* stream);
 int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32_t ncols);
 int32_t aum_stream_block_max_len(void);
 
+/*
+ * PACKED PREFILL (additive to ABI 13; `Mamba.prefill_chunk(..., seq_map=)`): the BACKLOGS of `nseq` streaming sessions in one pass -- the
+ * time-parallel conv and the state in / state out scan of the offline forward on packed rows, each session entered with and leaving its
+ * own row of the pools.  Packed operands, cu_seqlens, state_indices, total, nseq, nrows and the no-op rule (an empty session, a row
+ * outside the pool, a pair outside [0, total]): as for aum_*_tm_chunk_var.  max_len: the longest session of the call as the host knows
+ * it (>= 1); a session longer than max_len is a no-op.  Two sessions naming one cache row: undefined results for that row.
+ *
+ * aum_conv1d_tm_prefill_var -- y[t] = act(bias + sum_k weight[k] * in[t - (width - 1) + k]) over (the session's window, its rows): the
+ *   steps of aum_conv1d_tm_fwd, one wave per (session, chunk of at most 64 rows, channel block).  The rows before a session's first row
+ *   are conv_state[row, :, 1:], read as fp32 (no rounding, no copy); afterwards conv_state[row] holds the session's last `width` inputs
+ *   (fewer rows than `width`: the old entries shift, as under aum_conv1d_tm_chunk).  x (total, dim) pitch x_ts, y (total, dim) pitch
+ *   y_ts, y != x; every other field, flag (AUM_CONV_SILU) and limit as aum_conv1d_tm_chunk_var.  Per session, y and the window are bit for bit
+ *   what aum_conv1d_tm_fwd gives at batch 1 on the rows [window ; session] when the window's values are exact in `dtype`: the conv is
+ *   not recurrent and a step is the same multiply-adds in the same order wherever the chunk boundaries fall.
+ * aum_scan_tm_fwd_state_var -- aum_scan_tm_fwd_state per session: rows [cu_seqlens[i], cu_seqlens[i + 1]) from state row
+ *   state_indices[i] of state (nrows, dim, 16) fp32, advanced in place.  Forward time, both delta forms (AUM_SCAN_SOFTPLUS /
+ *   AUM_SCAN_DELTA_ACTIVATED), with and without z, fp32 / bf16 / fp16; limits of aum_scan_tm_fwd_state on the packed rows (16-byte rows
+ *   of u, delta, z, out; 4-byte aligned B / C rows; the 32-bit byte cursor applies to `total` rows).
+ *   range_len == 0: uncut, one wave per (session, 64 channels); per session bit for bit aum_scan_tm_fwd_state (segments == 1) at batch 1.
+ *   range_len > 0 (a multiple of AUM_SCAN_TM_CK): every session is cut into ranges of range_len steps, nranges = ceil(max_len /
+ *   range_len) <= AUM_SCAN_TM_MAX_SEGMENTS, a carry launch and a main launch as aum_scan_tm_fwd_state with segments; carry:
+ *   aum_scan_tm_fwd_state_var_carry_bytes(nseq, dim, dstate, nranges) bytes of scratch.  Ranges past a session's end are empty.  A
+ *   session's results are bit for bit aum_scan_tm_fwd_state(segments = ceil(len / range_len)) at batch 1 where that call's ranges are
+ *   range_len steps too; elsewhere they differ by the re-association at the range boundaries.
+ */
+typedef struct AumConvTmPrefillVarArgs {
+    const void* x;
+    float* conv_state;
+    const float *weight, *bias;
+    void* y;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t x_ts, y_ts;
+    int32_t total, nseq, nrows, dim, width;
+    int32_t dtype;
+    uint32_t flags;
+    int32_t max_len;
+} AumConvTmPrefillVarArgs;
+int aum_conv1d_tm_prefill_var(const AumConvTmPrefillVarArgs* args, void* stream);
+typedef struct AumScanTmFwdStateVarArgs {
+    const void *u, *delta, *z, *B, *C;
+    const float *A, *D, *delta_bias;
+    float* state;
+    void* out;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t u_ts, delta_ts, z_ts, B_ts, C_ts, out_ts;
+    int32_t total, nseq, nrows, dim, dstate;
+    int32_t dtype;
+    uint32_t flags;
+    int32_t range_len, max_len, reserved;
+    float* carry;
+    int64_t carry_bytes;
+} AumScanTmFwdStateVarArgs;
+int aum_scan_tm_fwd_state_var(const AumScanTmFwdStateVarArgs* args, void* stream);
+int64_t aum_scan_tm_fwd_state_var_carry_bytes(int32_t nseq, int32_t dim, int32_t dstate, int32_t nranges);
+
 /* Self-tests and calibration (used by tests/ and bench.py; not part of the reference's surface). */
 int aum_abi_version(void);
 /* runs wave_scan_affine<rev> on 64 (P,S) pairs: in/out are device arrays of 128 floats (P[0..63], S[0..63]) */

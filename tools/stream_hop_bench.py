@@ -34,6 +34,13 @@ stream_prefill (Mamba.prefill_chunk: the time-parallel conv and the token-major 
 long enough for the backlog (--prefill 512: 8192 frames, L = 4097).
 
     python tools/stream_hop_bench.py --prefill 31 [--batch 1]        (--count-only a: stream_push, b: stream_prefill)
+
+--prefill-pool S --prefill COLS: S sessions JOIN WITH RAGGED BACKLOGS of COLS, COLS / 2, COLS / 4, ... columns (at least 1 each) into
+empty rows of a pool, two ways alternating in one process, each arm on a pool of its own: (a) stream_prefill_many(packed=False), the host
+loop of S batch-1 passes, (b) stream_prefill_many(packed=True), one packed pass.  Same method: HIP events around each call, warm calls
+discarded, medians of all calls and of the groups, min / max.
+
+    python tools/stream_hop_bench.py --prefill-pool 8 --prefill 64   (--count-only a: the loop, b: the packed pass)
 """
 import argparse
 import contextlib
@@ -211,6 +218,43 @@ def prefill_ab(model, args, dev):
         print(json.dumps(out), flush=True)
 
 
+def prefill_pool_ab(model, args, dev):
+    """--prefill-pool S --prefill COLS: S ragged backlogs into empty pool rows, the host loop (a) against one packed pass (b)"""
+    S = args.prefill_pool
+    ks = [max(args.prefill >> i, 1) for i in range(S)]
+    specs = [torch.randn(16 * k, 128, device=dev, dtype=torch.bfloat16) for k in ks]
+    arms = (("loop", False), ("packed", True))
+    pools = [model.allocate_stream_pool(S) for _ in arms]
+
+    def call(i):
+        pools[i]["columns"] = [0] * S             # new sessions every call: the caches' values do not matter for timing
+        model.stream_prefill_many(specs, pools[i], range(S), packed=arms[i][1])
+
+    if args.count_only:
+        i = 0 if args.count_only == "a" else 1
+        for _ in range(args.count_hops):
+            call(i)
+        torch.cuda.synchronize()
+        print(json.dumps({"path": "prefill-pool " + arms[i][0], "sessions": S, "columns": ks, "hops": args.count_hops}))
+        return
+    for _ in range(args.warm):
+        for i in range(len(arms)):
+            timed_call(lambda: call(i))
+    times = [[] for _ in arms]
+    for _ in range(args.hops):
+        for i, t in enumerate(times):
+            t.append(timed_call(lambda: call(i)))
+    g = max(args.hops // args.groups, 1)
+    out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "sessions": S, "columns": ks, "tokens": 8 * sum(ks),
+           "clip_columns": model.patch_grid_size[1], "hops": args.hops, "warm": args.warm}
+    for (name, _), t in zip(arms, times):
+        out[name + "_ms_median"] = round(statistics.median(t), 4)
+        out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+        out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+    out["ratio_loop_over_packed"] = round(out["loop_ms_median"] / out["packed_ms_median"], 3)
+    print(json.dumps(out), flush=True)
+
+
 def timed(fn, model, spec, cache):
     if cache["columns"] >= model.patch_grid_size[1]:
         cache["columns"] = 0                      # a new clip: the caches' values do not matter for timing
@@ -348,9 +392,17 @@ def main():
     ap.add_argument("--fused-ab", action="store_true", help="stream_push with the block's middle as three launches vs aum_stream_block_tm")
     ap.add_argument("--peek", action="store_true", help="stream_push + stream_read vs one stream_push(read=True)")
     ap.add_argument("--prefill", type=int, default=0, metavar="COLS", help="a backlog of COLS columns: one stream_push vs one stream_prefill")
+    ap.add_argument("--prefill-pool", type=int, default=0, metavar="S",
+                    help="with --prefill COLS: S sessions with backlogs of COLS, COLS / 2, ... columns, stream_prefill_many as a host loop vs packed")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill))
+    if args.prefill_pool:
+        if not args.prefill:
+            ap.error("--prefill-pool S needs --prefill COLS")
+        with torch.no_grad():
+            prefill_pool_ab(model, args, dev)
+        return
     if args.prefill:
         with torch.no_grad():
             prefill_ab(model, args, dev)
