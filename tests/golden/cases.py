@@ -94,6 +94,21 @@ NORM_CASES = [
     ("r7_c100_res_pre", (7,), 100, True, True),
 ]
 
+# checked against the live oracle only (no fixture): the smallest shapes that reach every (TX, TR, NCH | generic) instantiation of
+# rmsnorm_fwd_vec / rmsnorm_bwd_vec (NCH = ceil(cols / 512), cols <= 2048) and rmsnorm_fwd_wave / rmsnorm_bwd_wave (cols > 2048), the
+# row-dealing edges of the backward (8 waves per workgroup, aum_rmsnorm_bwd_partials(rows) waves) and the widest accepted row
+NORM_EDGE_CASES = [
+    ("r9_c384", (9,), 384, True, True),          # AuM-Small's width: NCH 1, partial chunk; backward workgroups of 8 + 1 waves
+    ("r9_c1100", (9,), 1100, True, True),        # NCH 3, ragged last chunk, cols % 8 == 4
+    ("r4_c1537", (4,), 1537, False, True),       # NCH 4, one-element tail, no residual (16-bit residual stream: the saved tensor is x)
+    ("r5_c2048", (5,), 2048, True, True),        # NCH 4 completely full: the widest vectorised row
+    ("r3_c2049", (3,), 2049, True, True),        # the first width that takes the one-wave kernels without AUM_NORM_GENERIC
+    ("r17_c101", (17,), 101, True, False),       # odd cols (16-bit rows 2-byte aligned); backward workgroups of 8 / 8 / 1 waves
+    ("r4097_c8", (4097,), 8, True, True),        # 4096 backward waves, base 1 + rem 1; one lane of 64 active
+    ("r4105_c8", (4105,), 8, True, True),        # base 1 + rem 9: the two-row waves end inside the second backward workgroup
+    ("r2_c16384", (2,), 16384, True, True),      # the widest accepted row: the one-wave backward with 64 KiB of dynamic LDS
+]
+
 # (name, mode, batch, d_model, len)      mode: v1 (Fo-Bi), v2 (Bi-Bi), none (Fo-Fo)
 INNER_CASES = [
     ("v1_d16_l65", "v1", 2, 16, 65),

@@ -12,6 +12,24 @@ from oracle import oracle as O
 
 TOL_F32 = 1e-4      # north_star bar for fp32 is 1e-3; the kernels are held to 1e-4 of the fp64 oracle
 TOL_BF16 = 1e-2     # north_star bar for bf16 I/O
+# A kernel that computes in fp32 from the inputs the oracle gets and rounds a 16-bit output ONCE is off by at most half an ulp of the
+# output type per element: 2^-8 (bf16, 8 significand bits) / 2^-11 (fp16, 11) of the largest element in rel_err's measure.  The factor
+# 1.5 covers the fp32 error under the rounding and one double rounding (fp64 -> fp32 -> 16 bit).
+HALF_ULP_BAR = {torch.bfloat16: 1.5 * 2.0 ** -8, torch.float16: 1.5 * 2.0 ** -11}
+NORM_F32_BAR = 4e-5             # fp32 quantities of the norm kernels, whatever the dtype of x
+# Worst check_norm errors on the MI355X over NORM_CASES + NORM_EDGE_CASES, default and AUM_NORM_GENERIC (the 16-bit columns are the
+# lane-array build's to three digits; the 16384-column backward launches with its 64 KiB of dynamic LDS):
+#   x / residual     y        res_out  dx       dres_in  rstd     dw          bar 16-bit / fp32
+#   f32  / f32       2.1e-7   5.4e-8   1.2e-7   1.2e-7   1.2e-7   3.2e-7      -      / 4e-5
+#   bf16 / f32       3.35e-3  5.7e-8   3.45e-3  9.6e-8   1.1e-7   2.6e-7      5.9e-3 / 4e-5
+#   f16  / f32       3.8e-4   5.7e-8   4.3e-4   9.8e-8   1.1e-7   2.5e-7      7.3e-4 / 4e-5
+#   bf16 / bf16      3.39e-3  3.37e-3  3.47e-3  3.47e-3  2.1e-7   2.6e-7      5.9e-3 / 4e-5
+#   f16  / f16       4.0e-4   4.4e-4   4.3e-4   4.3e-4   1.4e-7   2.5e-7      7.3e-4 / 4e-5
+# check_conv in fp16 on the MI355X over CONV_CASES, both directions: y 4.4e-4, dx 4.4e-4 (bar 7.3e-4); dw 2.2e-7, db 4.5e-7 (bar 4e-5).
+# check_rms_norm_fn_16bit_residual there: bf16 3.7e-3, fp16 2.6e-4 at worst, weight.grad 1.4e-7.
+# (x dtype, residual dtype): the five pairs norm_dispatch instantiates
+NORM_PAIRS = [(torch.float32, torch.float32), (torch.bfloat16, torch.float32), (torch.float16, torch.float32),
+              (torch.bfloat16, torch.bfloat16), (torch.float16, torch.float16)]
 
 
 def T(a, dev, dtype=torch.float32):
@@ -105,6 +123,10 @@ def check_conv(lib, dev, case, dtype=torch.float32, reverse=False, silu=True, ge
     name = case[0]
     d = cases.conv_inputs(*case)
     tol = 1e-5 if dtype == torch.float32 else TOL_BF16
+    if dtype == torch.float16:      # the rule of check_norm's bars: y and dx are rounded once to fp16, dweight / dbias are fp32 sums
+        bars = {"y": HALF_ULP_BAR[dtype], "dx": HALF_ULP_BAR[dtype], "dw": 4e-5, "db": 4e-5}
+    else:
+        bars = {"y": tol, "dx": 4 * tol, "dw": 4 * tol, "db": 4 * tol}
     q = {k: rq(d[k], dtype) for k in ("x", "dout")}
     x, dy = T(d["x"], dev, dtype), T(d["dout"], dev, dtype)
     w, b = T(d["weight"], dev), T(d["bias"], dev)
@@ -115,8 +137,8 @@ def check_conv(lib, dev, case, dtype=torch.float32, reverse=False, silu=True, ge
     errs = {"y": rel_err(N(y), ry), "dx": rel_err(N(dx), rg["dx"]), "dw": rel_err(N(dw), rg["dweight"])}
     if b is not None:
         errs["db"] = rel_err(N(db), rg["dbias"])
-    bad = {k: v for k, v in errs.items() if not v < tol * (4 if k != "y" else 1)}
-    assert not bad, (name, bad)
+    bad = {k: v for k, v in errs.items() if not v < bars[k]}
+    assert not bad, (name, str(dtype), bad)
     return errs
 
 
@@ -154,10 +176,21 @@ def check_conv_tm(lib, dev, case, dtype=torch.float32, reverse=False, silu=True,
     return errs
 
 
+def norm_pair_id(pair):
+    return "x_%s-res_%s" % tuple(str(t).split(".")[-1] for t in pair)
+
+
+def norm_bar(dtype):
+    """the bar of a norm output stored in `dtype`"""
+    return NORM_F32_BAR if dtype == torch.float32 else HALF_ULP_BAR[dtype]
+
+
 def check_norm(lib, dev, case, dtype=torch.float32, res_dtype=torch.float32, generic=False):
+    """aum_rmsnorm_fwd / _bwd against the fp64 oracle on the inputs as rounded to (dtype, res_dtype).  Bars: rstd, dweight and an fp32
+    residual stream NORM_F32_BAR; y, dx and a 16-bit residual stream HALF_ULP_BAR of their type (the kernels keep the fp32 sum x + residual
+    for y, and round each 16-bit output once).  The backward's reference takes the kernel's own residual_out and rstd."""
     name, lead, cols, has_res, prenorm = case
     d = cases.norm_inputs(*case)
-    tol = 1e-5 if dtype == torch.float32 else TOL_BF16
     x = T(d["x"], dev, dtype).reshape(-1, cols)
     res = T(d["residual"], dev, res_dtype)
     res = None if res is None else res.reshape(-1, cols)
@@ -168,6 +201,15 @@ def check_norm(lib, dev, case, dtype=torch.float32, res_dtype=torch.float32, gen
     r = O.rmsnorm_fwd(qx, d["weight"], None, qr, 1e-5, "f64")
     errs = {"y": rel_err(N(y), r["y"]), "res_out": rel_err(N(res_out), r["residual_out"]),
             "rstd": rel_err(N(rstd), r["rstd"])}
+    if has_res and res_dtype != torch.float32:
+        # a 16-bit residual is exact in fp32: the <TX, float> kernel on the same values does the same fp32 operations in the same order,
+        # so y and rstd agree bit for bit (they come from the UNROUNDED fp32 sum) and residual_out is that kernel's rounded once -- sharper
+        # than the half-ulp bar, which a sum rounded to 16 bits before y stays inside.  If this trips while the bars below hold, look at
+        # the two instantiations' code first: a build that contracts or orders their fp32 arithmetic differently is a change of the
+        # kernels' build, not of what they compute, and is settled there (same flags for both), not by dropping the comparison
+        y32, rstd32, res32 = aum_hip.rmsnorm_fwd(x, w, res.float(), 1e-5, residual_dtype=torch.float32, generic=generic, lib=lib)
+        assert torch.equal(y, y32) and torch.equal(rstd, rstd32), (name, str(dtype), "y / rstd differ from the fp32-residual kernel's")
+        assert torch.equal(res_out, res32.to(res_dtype)), (name, str(dtype), "residual_out is not the fp32 sum rounded once")
     dy = T(d["dy"], dev, dtype).reshape(-1, cols)
     dres = None if d["dres"] is None else T(d["dres"], dev, res_out.dtype).reshape(-1, cols)
     dx, dw, dres_in = aum_hip.rmsnorm_bwd(dy, res_out, w, rstd, dres, has_res, x_dtype=dtype, generic=generic, lib=lib)
@@ -177,8 +219,248 @@ def check_norm(lib, dev, case, dtype=torch.float32, res_dtype=torch.float32, gen
     errs["dw"] = rel_err(N(dw), rb["dweight"])
     if has_res:
         errs["dres_in"] = rel_err(N(dres_in), rb["dx"])
-    bad = {k: v for k, v in errs.items() if not v < tol * 4}
-    assert not bad, (name, bad)
+        assert dres_in.dtype == res_out.dtype and (dres_in is dx) == (res_out.dtype == dtype), (name, "dres_in")
+    assert y.dtype == dtype and dx.dtype == dtype and rstd.dtype == torch.float32 and dw.dtype == torch.float32, (name, "output dtypes")
+    assert res_out.dtype == res_dtype and (res_out is x) == (not has_res and res_dtype == dtype), (name, "residual_out")
+    bars = {"y": norm_bar(dtype), "dx": norm_bar(dtype), "res_out": norm_bar(res_out.dtype), "dres_in": norm_bar(res_out.dtype),
+            "rstd": NORM_F32_BAR, "dw": NORM_F32_BAR}
+    bad = {k: (v, bars[k]) for k, v in errs.items() if not v < bars[k]}
+    assert not bad, (name, str(dtype), str(res_dtype), generic, bad)
+    return errs
+
+
+def _norm_operands(case, dev, dtype, res_dtype, pad=0, fill=float("nan")):
+    """x, residual, dy, dres of a norm case as the first `cols` columns of (rows, cols + pad) tensors whose other columns hold `fill`"""
+    name, lead, cols, has_res, prenorm = case
+    d = cases.norm_inputs(*case)
+
+    def mk(a, dt):
+        if a is None:
+            return None
+        t = T(a, dev, dt).reshape(-1, cols)
+        if not pad:
+            return t
+        buf = torch.full((t.shape[0], cols + pad), fill, dtype=dt, device=dev)
+        buf[:, :cols] = t
+        return buf[:, :cols]
+    return mk(d["x"], dtype), mk(d["residual"], res_dtype), mk(d["dy"], dtype), mk(d["dres"], res_dtype), T(d["weight"], dev)
+
+
+def _norm_pair(lib, ops, has_res, dtype, res_dtype, generic, saved=None):
+    """forward + backward through the binding -> dict of every output.  saved: stands in for the forward's residual_out as the backward's
+    saved tensor (the same values in another layout)"""
+    x, res, dy, dres, w = ops
+    y, rstd, res_out = aum_hip.rmsnorm_fwd(x, w, res, 1e-5, residual_dtype=res_dtype, generic=generic, lib=lib)
+    dx, dw, dres_in = aum_hip.rmsnorm_bwd(dy, res_out if saved is None else saved(res_out), w, rstd, dres, has_res, x_dtype=dtype,
+                                          generic=generic, lib=lib)
+    out = dict(y=y, rstd=rstd, res_out=res_out, dx=dx, dw=dw)
+    if has_res:
+        out["dres_in"] = dres_in
+    return out
+
+
+def check_norm_strided(lib, dev, case, dtype, res_dtype, generic=False):
+    """row strides: x, residual, dy, dres and the backward's saved tensor are the first `cols` columns of (rows, cols + 8) tensors whose
+    padding is NaN; every output is bit-equal to the contiguous call on the same values (a padding element that reaches a sum makes it
+    NaN, and NaN != NaN)"""
+    name, lead, cols, has_res, prenorm = case
+    ref = _norm_pair(lib, _norm_operands(case, dev, dtype, res_dtype), has_res, dtype, res_dtype, generic)
+    ops = _norm_operands(case, dev, dtype, res_dtype, pad=8)
+    assert all(t is None or (t.stride(0) == cols + 8 and t.stride(1) == 1) for t in ops[:4])
+
+    def padded(t):
+        buf = torch.full((t.shape[0], cols + 8), float("nan"), dtype=t.dtype, device=t.device)
+        buf[:, :cols] = t
+        return buf[:, :cols]
+    got = _norm_pair(lib, ops, has_res, dtype, res_dtype, generic, saved=padded)
+    assert set(got) == set(ref)
+    for k in ref:
+        assert got[k].dtype == ref[k].dtype and torch.equal(got[k], ref[k]), (name, str(dtype), str(res_dtype), generic, k)
+        assert bool(torch.isfinite(got[k].float()).all()), (name, k, "not finite")
+
+
+NORM_SENTINEL = 7.0     # exact in every dtype; no output of the seeded cases is bit-equal to it along a whole padding column
+
+
+def check_norm_no_overrun(lib, dev, case, dtype, res_dtype, generic=False):
+    """stores past `cols`: the C entry points with y, residual_out, dx and dresidual_in as the first `cols` columns of sentinel-filled
+    (rows, cols + 8) buffers and one sentinel row more of dweight_partial than aum_rmsnorm_bwd_partials(rows).  The [:, :cols] parts are
+    bit-equal to the binding's results (dresidual_in always gets its own buffer here: the binding aliases it to dx on a 16-bit stream), the
+    padding and every partial row from aum_rmsnorm_bwd_partial_rows(...) on still hold the sentinel."""
+    name, lead, cols, has_res, prenorm = case
+    ops = _norm_operands(case, dev, dtype, res_dtype)
+    x, res, dy, dres, w = ops
+    ref = _norm_pair(lib, ops, has_res, dtype, res_dtype, generic)
+    rows, pitch = x.shape[0], cols + 8
+    saved_dtype = ref["res_out"].dtype
+    flags = 2 if generic else 0
+    buf = lambda dt, r=rows, c=pitch: torch.full((r, c), NORM_SENTINEL, dtype=dt, device=dev)
+    y, res_out, dx, dres_in = buf(dtype), buf(saved_dtype), buf(dtype), buf(saved_dtype)
+    rstd = torch.empty(rows, dtype=torch.float32, device=dev)
+    n_alloc = int(lib.c.aum_rmsnorm_bwd_partials(rows))
+    n_used = int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, flags))
+    assert 1 <= n_used <= n_alloc
+    dwp = buf(torch.float32, n_alloc + 1, cols)
+    st = lib.stream(x)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = aum_hip.NormArgs()
+    a.x, a.residual, a.weight, a.y, a.rstd_out = ptr(x), ptr(res), ptr(w), ptr(y), ptr(rstd)
+    a.row_stride_x, a.row_stride_y = cols, pitch
+    if res is not None:
+        a.row_stride_res = cols
+    if has_res or saved_dtype != dtype:                     # the forward writes a residual_out exactly when the binding asks for one
+        a.residual_out, a.row_stride_res_out = ptr(res_out), pitch
+    a.eps, a.rows, a.cols, a.flags = 1e-5, rows, cols, flags
+    a.x_dtype = a.y_dtype = aum_hip._DT[dtype]
+    a.res_dtype = aum_hip._DT[saved_dtype]
+    assert lib.c.aum_rmsnorm_fwd(aum_hip.C_byref(a), st) == 0, (name, "forward refused")
+    b = aum_hip.NormArgs()
+    saved = ref["res_out"]                                   # (rows, cols) contiguous: the forward's residual_out, or x itself
+    b.x, b.dy, b.dresidual_out, b.weight, b.rstd_in = ptr(saved), ptr(dy), ptr(dres), ptr(w), ptr(ref["rstd"])
+    b.dx, b.dweight_partial = ptr(dx), ptr(dwp)
+    b.row_stride_x, b.row_stride_dy, b.row_stride_dx = cols, cols, pitch
+    if dres is not None:
+        b.row_stride_dres_out = cols
+    if has_res:
+        b.dresidual_in, b.row_stride_dres_in = ptr(dres_in), pitch
+    b.rows, b.cols, b.flags = rows, cols, flags
+    b.x_dtype = b.y_dtype = aum_hip._DT[dtype]
+    b.res_dtype = aum_hip._DT[saved_dtype]
+    assert lib.c.aum_rmsnorm_bwd(aum_hip.C_byref(b), st) == 0, (name, "backward refused")
+    tag = (name, str(dtype), str(res_dtype), generic)
+    got = dict(y=y, dx=dx, rstd=rstd)
+    if a.residual_out:
+        got["res_out"] = res_out
+    if has_res:
+        got["dres_in"] = dres_in
+    for k, t in got.items():
+        if k == "rstd":
+            assert torch.equal(t, ref[k]), tag + (k,)
+            continue
+        assert torch.equal(t[:, :cols], ref[k]), tag + (k, "differs from the binding's result")
+        assert bool((t[:, cols:] == NORM_SENTINEL).all()), tag + (k, "wrote past cols")
+    for t, k in ((res_out, "res_out"), (dres_in, "dres_in")):
+        if k not in got:
+            assert bool((t == NORM_SENTINEL).all()), tag + (k, "written though not asked for")
+    assert bool((dwp[n_used:] == NORM_SENTINEL).all()), tag + ("dweight_partial rows beyond aum_rmsnorm_bwd_partial_rows were written",)
+    assert torch.equal(aum_hip.sum_rows(dwp[:n_used], lib), ref["dw"]), tag + ("dw",)
+
+
+def check_norm_refusals(lib, dev):
+    """norm_dispatch's refusals through the C entry points: each returns its error code and leaves the sentinel-filled outputs untouched.
+    Every buffer holds 2 x 16392 elements, so a refusal that failed to happen would still stay inside them."""
+    rows, cols, wide = 2, 16, 16392
+    E_NULL, E_SHAPE, E_DTYPE, E_UNSUPPORTED = -1, -2, -3, -4
+    bf, f32 = torch.bfloat16, torch.float32
+    inp = lambda dt: torch.ones((rows, wide), dtype=dt, device=dev)
+    out = lambda dt: torch.full((rows, wide), NORM_SENTINEL, dtype=dt, device=dev)
+    x, res, dy, dres, w, rstd_in = inp(bf), inp(f32), inp(bf), inp(f32), inp(f32)[0], inp(f32)[0]
+    outs = dict(y=out(bf), residual_out=out(f32), dx=out(bf), dresidual_in=out(f32), rstd_out=out(f32)[0], dweight_partial=out(f32))
+    st = lib.stream(x)
+
+    def args(bwd, **kw):
+        a = aum_hip.NormArgs()
+        a.x, a.weight = x.data_ptr(), w.data_ptr()
+        if bwd:
+            a.x = res.data_ptr()                             # the saved residual_out, res_dtype
+            a.dy, a.dresidual_out, a.rstd_in = dy.data_ptr(), dres.data_ptr(), rstd_in.data_ptr()
+            a.dx, a.dresidual_in, a.dweight_partial = (outs[k].data_ptr() for k in ("dx", "dresidual_in", "dweight_partial"))
+        else:
+            a.residual = res.data_ptr()
+            a.y, a.residual_out, a.rstd_out = (outs[k].data_ptr() for k in ("y", "residual_out", "rstd_out"))
+        for f in ("row_stride_x", "row_stride_res", "row_stride_y", "row_stride_res_out", "row_stride_dy", "row_stride_dres_out",
+                  "row_stride_dx", "row_stride_dres_in"):
+            setattr(a, f, wide)
+        a.eps, a.rows, a.cols = 1e-5, rows, cols
+        a.x_dtype = a.y_dtype = aum_hip.AUM_BF16
+        a.res_dtype = aum_hip.AUM_F32
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def call(bwd, **kw):
+        a = args(bwd, **kw)                                  # held until the call returns: C_byref does not keep the structure alive
+        return (lib.c.aum_rmsnorm_bwd if bwd else lib.c.aum_rmsnorm_fwd)(aum_hip.C_byref(a), st)
+
+    def untouched(what):
+        if dev != "cpu":
+            torch.cuda.synchronize()
+        for k, t in outs.items():
+            assert bool((t == NORM_SENTINEL).all()), (what, k, "a refused call wrote to its outputs")
+    for bwd in (False, True):
+        which = "bwd" if bwd else "fwd"
+        for what, kw, code in (("cols 16385", dict(cols=16385), E_UNSUPPORTED),
+                               ("rows 0", dict(rows=0), E_SHAPE), ("cols 0", dict(cols=0), E_SHAPE),
+                               ("rows -1", dict(rows=-1), E_SHAPE),
+                               ("fp32 x, bf16 residual", dict(x_dtype=aum_hip.AUM_F32, y_dtype=aum_hip.AUM_F32, res_dtype=aum_hip.AUM_BF16), E_DTYPE),
+                               ("bf16 x, fp16 residual", dict(res_dtype=aum_hip.AUM_F16), E_DTYPE),
+                               ("y_dtype != x_dtype", dict(y_dtype=aum_hip.AUM_F16), E_DTYPE),
+                               ("dtype out of range", dict(x_dtype=3, y_dtype=3), E_DTYPE),
+                               ("null weight", dict(weight=None), E_NULL), ("null x", dict(x=None), E_NULL)):
+            assert call(bwd, **kw) == code, (which, what)
+            untouched((which, what))
+    assert lib.c.aum_rmsnorm_fwd(None, st) == E_NULL and lib.c.aum_rmsnorm_bwd(None, st) == E_NULL
+    assert call(False, y=None) == E_NULL
+    for k in ("rstd_in", "dweight_partial", "dy", "dx"):
+        assert call(True, **{k: None}) == E_NULL, ("bwd", k)
+    untouched("null operands")
+    # the same operands unchanged are taken: the refusals above are the named fields', not the set-up's
+    assert call(False) == 0 and call(True) == 0
+    if dev != "cpu":
+        torch.cuda.synchronize()
+    assert bool((outs["y"][:, :cols] != NORM_SENTINEL).all()) and bool((outs["dx"][:, :cols] != NORM_SENTINEL).all())
+    assert bool((outs["y"][:, cols:] == NORM_SENTINEL).all()) and bool((outs["dx"][:, cols:] == NORM_SENTINEL).all())
+
+
+def _rms_norm_fn_reference(x, res, w, gy, gr, eps, dtype):
+    """fp64 torch statement of the fused add + RMSNorm on a 16-bit residual stream and of its backward, on the inputs as the kernel gets
+    them: y and rstd from the unrounded sum, residual_out = that sum (the kernel rounds it once), the backward from residual_out AS
+    ROUNDED (the tensor the forward saved) and the forward's rstd"""
+    v = x.double() if res is None else x.double() + res.double()
+    rstd = torch.rsqrt(v.square().mean(-1, keepdim=True) + eps)
+    wd = w.double()
+    y = v * rstd * wd
+    xhat = v.to(dtype).double() * rstd
+    wdy = wd * gy.double()
+    dx = (wdy - xhat * (xhat * wdy).mean(-1, keepdim=True)) * rstd
+    if gr is not None:
+        dx = dx + gr.double()
+    dw = (gy.double() * xhat).reshape(-1, x.shape[-1]).sum(0)
+    return dict(y=y, res_out=v, dx=dx, dw=dw)
+
+
+def check_rms_norm_fn_16bit_residual(lib, dev, dtype):
+    """mamba_ssm.ops.triton.layernorm.rms_norm_fn through autograd on a 16-bit residual stream (residual_in_fp32=False, the default of the
+    reference's model class): x and residual (2, 9, 384) in `dtype`, prenorm; then the first block's call (no residual, prenorm=False)"""
+    from mamba_ssm.ops.triton.layernorm import rms_norm_fn
+    from stream_prefill_checks import product_lib
+    g = torch.Generator().manual_seed(384)
+    shape, eps = (2, 9, 384), 1e-5
+    r = lambda s=1.0: (s * torch.randn(shape, generator=g)).to(dtype).to(dev)
+    x0, res0, gy, gr = r(), r(2.0), r(), r()
+    w0 = (1 + 0.2 * torch.randn(shape[-1], generator=g)).to(dev)
+    bar16, n = HALF_ULP_BAR[dtype], lambda t: t.detach().double().cpu().numpy()
+    with product_lib(lib):
+        x, res, w = x0.clone().requires_grad_(True), res0.clone().requires_grad_(True), w0.clone().requires_grad_(True)
+        y, res_out = rms_norm_fn(x, w, None, residual=res, prenorm=True, residual_in_fp32=False, eps=eps)
+        assert y.dtype == dtype and res_out.dtype == dtype and y.shape == shape and res_out.shape == shape
+        ((y.float() * gy.float()).sum() + (res_out.float() * gr.float()).sum()).backward()
+        assert x.grad.dtype == dtype and res.grad.dtype == dtype and w.grad.dtype == torch.float32
+        assert torch.equal(x.grad, res.grad), "x.grad and residual.grad are one tensor on a 16-bit stream"
+        ref = _rms_norm_fn_reference(x0, res0, w0, gy, gr, eps, dtype)
+        errs = {"y": (rel_err(n(y), n(ref["y"])), bar16), "res_out": (rel_err(n(res_out), n(ref["res_out"])), bar16),
+                "x.grad": (rel_err(n(x.grad), n(ref["dx"])), bar16), "w.grad": (rel_err(n(w.grad), n(ref["dw"])), NORM_F32_BAR)}
+        # the first block of a 16-bit stream: no residual yet, the saved tensor is x itself
+        x, w = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True)
+        y1 = rms_norm_fn(x, w, None, residual=None, prenorm=False, residual_in_fp32=False, eps=eps)
+        assert torch.is_tensor(y1) and y1.dtype == dtype and y1.shape == shape
+        (y1.float() * gy.float()).sum().backward()
+        assert x.grad.dtype == dtype and w.grad.dtype == torch.float32
+        ref = _rms_norm_fn_reference(x0, None, w0, gy, None, eps, dtype)
+        errs.update({"nores:y": (rel_err(n(y1), n(ref["y"])), bar16), "nores:x.grad": (rel_err(n(x.grad), n(ref["dx"])), bar16),
+                     "nores:w.grad": (rel_err(n(w.grad), n(ref["dw"])), NORM_F32_BAR)})
+    bad = {k: v for k, v in errs.items() if not v[0] < v[1]}
+    assert not bad, (str(dtype), bad)
     return errs
 
 
@@ -394,6 +676,8 @@ def check_scan_tm_grid(lib, dev, Bsz, L, E, rows, entries, chans, split, segment
     out, pre = aum_hip.scan_tm_fwd(u, dl, A, Bm, Cm, D, z, bias, True, A_b=A_b, want_out_pre=True, ckpt=ck, lib=lib, segments=sf)
     g = aum_hip.scan_tm_bwd(u, dl, A, Bm, Cm, D, z, bias, dout, pre, ck, True, A_b=A_b, lib=lib, segments=sb)
     for k, v in g.items():
+        if k == "_ws":              # the launch's scratch, held alive for the caller: torch.empty memory that the kernels need not fill.  A stale
+            continue                # value that reached an output shows in that output, below
         assert v is None or bool(torch.isfinite(v).all()), ("not finite", k, str(dtype), dout_mag)
     f = lambda t: t.float().cpu().numpy()
     worst = {}

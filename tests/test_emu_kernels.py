@@ -142,6 +142,7 @@ def test_conv(emu, case, reverse):
 
 def test_conv_bf16(emu):
     KC.check_conv(emu, "cpu", cases.CONV_CASES[2], torch.bfloat16)
+    KC.check_conv(emu, "cpu", cases.CONV_CASES[2], torch.float16)
 
 
 @pytest.mark.parametrize("case", [c for c in cases.CONV_CASES if 512 <= c[3] <= 520], ids=lambda c: c[0])
@@ -156,6 +157,35 @@ def test_conv_rows_kernels_16bit(emu, case, reverse):
 def test_norm(emu, case):
     KC.check_norm(emu, "cpu", case, torch.float32)
     KC.check_norm(emu, "cpu", case, torch.bfloat16, torch.float32)
+    KC.check_norm(emu, "cpu", case, torch.float16, torch.float32)
+    KC.check_norm(emu, "cpu", case, torch.bfloat16, torch.bfloat16)
+    KC.check_norm(emu, "cpu", case, torch.float16, torch.float16)
+
+
+@pytest.mark.parametrize("case", cases.NORM_EDGE_CASES, ids=lambda c: c[0])
+@pytest.mark.parametrize("pair", KC.NORM_PAIRS, ids=KC.norm_pair_id)
+def test_norm_edge_cases(emu, case, pair):
+    """every (TX, TR, NCH | one-wave) instantiation of the norm kernels at the smallest shape that reaches it, vs the fp64 oracle"""
+    KC.check_norm(emu, "cpu", case, *pair)
+    if case[2] <= 2048:
+        KC.check_norm(emu, "cpu", case, *pair, generic=True)
+
+
+@pytest.mark.parametrize("case", ["r9_c1100", "r3_c2049"])
+@pytest.mark.parametrize("res_dtype", [torch.float32, torch.bfloat16], ids=["res_f32", "res_bf16"])
+def test_norm_row_strides_and_overrun(emu, case, res_dtype):
+    c = [x for x in cases.NORM_EDGE_CASES if x[0] == case][0]
+    KC.check_norm_strided(emu, "cpu", c, torch.bfloat16, res_dtype)
+    KC.check_norm_no_overrun(emu, "cpu", c, torch.bfloat16, res_dtype)
+
+
+def test_norm_refusals(emu):
+    KC.check_norm_refusals(emu, "cpu")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_rms_norm_fn_16bit_residual(emu, dtype):
+    KC.check_rms_norm_fn_16bit_residual(emu, "cpu", dtype)
 
 
 def test_generic_conv_and_norm_kernels(emu):
@@ -165,6 +195,8 @@ def test_generic_conv_and_norm_kernels(emu):
         KC.check_conv(emu, "cpu", case, torch.float32, reverse=True, generic=True)
     for case in cases.NORM_CASES:
         KC.check_norm(emu, "cpu", case, torch.float32, generic=True)
+        KC.check_norm(emu, "cpu", case, torch.bfloat16, torch.float32, generic=True)
+        KC.check_norm(emu, "cpu", case, torch.bfloat16, torch.bfloat16, generic=True)
 
 
 @pytest.mark.parametrize("case", cases.PROJ_CASES, ids=lambda c: c[0])

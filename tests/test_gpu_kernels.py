@@ -153,6 +153,7 @@ def test_conv(lib, case, reverse):
     KC.check_conv(lib, "cuda", case, torch.float32, reverse=reverse)
     KC.check_conv(lib, "cuda", case, torch.float32, reverse=reverse, silu=False)
     KC.check_conv(lib, "cuda", case, torch.bfloat16, reverse=reverse)
+    KC.check_conv(lib, "cuda", case, torch.float16, reverse=reverse)
 
 
 @pytest.mark.parametrize("case", cases.NORM_CASES, ids=lambda c: c[0])
@@ -160,6 +161,34 @@ def test_norm(lib, case):
     KC.check_norm(lib, "cuda", case, torch.float32)
     KC.check_norm(lib, "cuda", case, torch.bfloat16, torch.float32)
     KC.check_norm(lib, "cuda", case, torch.float16, torch.float32)
+    KC.check_norm(lib, "cuda", case, torch.bfloat16, torch.bfloat16)
+    KC.check_norm(lib, "cuda", case, torch.float16, torch.float16)
+
+
+@pytest.mark.parametrize("case", cases.NORM_EDGE_CASES, ids=lambda c: c[0])
+@pytest.mark.parametrize("pair", KC.NORM_PAIRS, ids=KC.norm_pair_id)
+def test_norm_edge_cases(lib, case, pair):
+    """every (TX, TR, NCH | one-wave) instantiation of the norm kernels at the smallest shape that reaches it, vs the fp64 oracle"""
+    KC.check_norm(lib, "cuda", case, *pair)
+    if case[2] <= 2048:
+        KC.check_norm(lib, "cuda", case, *pair, generic=True)
+
+
+@pytest.mark.parametrize("case", ["r9_c1100", "r3_c2049"])
+@pytest.mark.parametrize("res_dtype", [torch.float32, torch.bfloat16], ids=["res_f32", "res_bf16"])
+def test_norm_row_strides_and_overrun(lib, case, res_dtype):
+    c = [x for x in cases.NORM_EDGE_CASES if x[0] == case][0]
+    KC.check_norm_strided(lib, "cuda", c, torch.bfloat16, res_dtype)
+    KC.check_norm_no_overrun(lib, "cuda", c, torch.bfloat16, res_dtype)
+
+
+def test_norm_refusals(lib):
+    KC.check_norm_refusals(lib, "cuda")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_rms_norm_fn_16bit_residual(lib, dtype):
+    KC.check_rms_norm_fn_16bit_residual(lib, "cuda", dtype)
 
 
 def test_scan_full_size_properties(lib):
@@ -202,6 +231,8 @@ def test_generic_conv_and_norm_kernels(lib):
         KC.check_conv(lib, "cuda", case, torch.float32, reverse=True, generic=True)
     for case in cases.NORM_CASES:
         KC.check_norm(lib, "cuda", case, torch.float32, generic=True)
+        KC.check_norm(lib, "cuda", case, torch.bfloat16, torch.float32, generic=True)
+        KC.check_norm(lib, "cuda", case, torch.bfloat16, torch.bfloat16, generic=True)
 
 
 @pytest.mark.parametrize("case", cases.PROJ_CASES, ids=lambda c: c[0])
