@@ -2,6 +2,10 @@
 // (element type, steps-per-lane K, direction mode) and launch.  Included by aum_hip.hip (device build)
 // and by tests/emu/aum_emu.cpp (lane-array build, tests only) so both share one dispatcher.
 //
+// Every kernel is started by AUM_LAUNCH (launch.h): grid, workgroup size, stream, the kernel's LDS, the k_* entry, its workgroup body
+// and the entry's arguments -- a loop of the body over the grid in the lane-array build.  A kernel's LDS is an Lds<> type stated once,
+// next to its entry.  Runtime flags, mode / K and the dtype reach template parameters through with_bool / with_int / by_dtype.
+//
 // AUM_DTYPE_ONLY (optional, 0/1/2) restricts a translation unit to one activation dtype so the device
 // library can be compiled as parallel objects; AUM_API_PART selects which entry points a TU defines.
 
@@ -15,9 +19,7 @@
 #include "proj_kernels.h"
 #include "frontend_kernels.h"
 #include "conv_rows_kernels.h"
-#ifdef AUM_EMU
-#include <vector>
-#endif
+#include "launch.h"
 #ifndef AUM_API_PART
 #define AUM_API_PART 0
 #endif
@@ -26,56 +28,63 @@ namespace aum {
 
 #ifdef AUM_EMU
 #define AUM_GLOBAL
-typedef void* aum_stream_t;
 #else
 #define AUM_GLOBAL __global__ __launch_bounds__(64)
-typedef hipStream_t aum_stream_t;
 #endif
 
 #ifndef AUM_SCANWG_FWD_MINW
 #define AUM_SCANWG_FWD_MINW 4      // waves per SIMD the forward scan is compiled for (<= 128 VGPRs: two 8-wave workgroups per CU)
 #endif
-// ---- kernel entries --------------------------------------------------------------------------
+// ---- kernel entries and their LDS --------------------------------------------------------------
+typedef Lds<float, SCAN_LDS_FLOATS> ScanLds;
+typedef Lds<float, CONV_LDS_FLOATS> ConvLds;
+template <int K, int TAIL, bool CT = false> using ScanWgFwdLds = Lds<float, scanwg_fwd_lds_floats<K, TAIL, CT>()>;
+template <int K, int TAIL> using ScanWgBwdLds = Lds<float, scanwg_bwd_lds_floats<K, TAIL>()>;
+template <int TAIL> using ScanHBwdLds = Lds<float, scanh_bwd_lds_floats<TAIL>()>;
+template <int TAIL> using ScanHChunkedLds = Lds<float, scanh_chunked_lds_floats<TAIL>()>;
+typedef Lds<float, scanr_fwd_lds_floats()> ScanRFwdLds;
+typedef Lds<float, scanr_bwd_lds_floats()> ScanRBwdLds;
+template <int NCH> using NormBwdVecLds = Lds<float, (NORM_BWD_NW - 1) * NCH * 512>;
 #ifndef AUM_EMU
 template <class T, int K, int MODE> AUM_GLOBAL void k_scan_fwd(AumScanFwdArgs a) {
-    __shared__ float lds[SCAN_LDS_FLOATS];
+    __shared__ float lds[ScanLds::n];
     scan_fwd_wave<T, K, MODE>(a, (int)blockIdx.x, lds);
 }
 template <class T, int K, int MODE> AUM_GLOBAL void k_scan_bwd(AumScanBwdArgs a) {
-    __shared__ float lds[SCAN_LDS_FLOATS];
+    __shared__ float lds[ScanLds::n];
     scan_bwd_wave<T, K, MODE>(a, (int)blockIdx.x, lds);
 }
 template <class T, int K, int TAIL, int MODE> __global__ __launch_bounds__(SCANWG_NW * 64, AUM_SCANWG_FWD_MINW) void k_scanwg_fwd(AumScanFwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanwg_fwd_lds_floats<K, TAIL>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanWgFwdLds<K, TAIL>::n];
     scanwg_fwd<T, K, TAIL, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int MODE> __global__ __launch_bounds__(SCANWG_NW * 64, AUM_SCANWG_FWD_MINW) void k_scanwg_fwd_ct(AumScanFwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanwg_fwd_lds_floats<8, 1, true>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanWgFwdLds<8, 1, true>::n];
     scanwg_fwd_ct<T, 8, 1, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int K, int TAIL, int MODE> __global__ __launch_bounds__(SCANWG_NW * 64) void k_scanwg_bwd(AumScanBwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanwg_bwd_lds_floats<K, TAIL>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanWgBwdLds<K, TAIL>::n];
     scanwg_bwd<T, K, TAIL, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int TAIL, int MODE> __global__ __launch_bounds__(scanh_nw(MODE) * 64) void k_scanh_bwd(AumScanBwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanh_bwd_lds_floats<TAIL>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanHBwdLds<TAIL>::n];
     scanh_bwd<T, TAIL, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int TAIL, int MODE> __global__ __launch_bounds__(SCANH_CH_NW * 64) void k_scanh_bwd_chunked(AumScanBwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanh_chunked_lds_floats<TAIL>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanHChunkedLds<TAIL>::n];
     scanh_bwd_chunked<T, TAIL, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int MODE> __global__ __launch_bounds__(SCANR_FWD_NW * 64, AUM_SCANR_FWD_MINW) void k_scanr_fwd(AumScanFwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanr_fwd_lds_floats()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanRFwdLds::n];
     scanr_fwd<T, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T, int MODE> __global__ __launch_bounds__(scanr_bwd_nw(MODE) * 64) void k_scanr_bwd(AumScanBwdArgs a, int rows_per_wg) {
-    __shared__ __attribute__((aligned(16))) float lds[scanr_bwd_lds_floats()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanRBwdLds::n];
     scanr_bwd<T, MODE>(a, (int)blockIdx.x, lds, rows_per_wg);
 }
 template <class T> AUM_GLOBAL void k_conv_fwd(AumConvArgs a) { conv_fwd_wave<T>(a, (int)blockIdx.x); }
 template <class T> AUM_GLOBAL void k_conv_bwd(AumConvArgs a) {
-    __shared__ float lds[CONV_LDS_FLOATS];
+    __shared__ float lds[ConvLds::n];
     conv_bwd_wave<T>(a, (int)blockIdx.x, lds);
 }
 template <class T, bool REV> AUM_GLOBAL void k_conv4_fwd(AumConvArgs a) { conv4_fwd_wave<T, REV>(a, (int)blockIdx.x); }
@@ -83,12 +92,10 @@ template <class T, bool REV> AUM_GLOBAL void k_conv4_bwd(AumConvArgs a) { conv4_
 template <class T, bool REV> AUM_GLOBAL void k_conv4_rows_fwd(AumConvArgs a) { conv4_rows_fwd_wave<T, REV>(a, (int)blockIdx.x); }
 template <class T, bool REV> AUM_GLOBAL void k_conv4_rows_bwd(AumConvArgs a) { conv4_rows_bwd_wave<T, REV>(a, (int)blockIdx.x); }
 template <class TX, class TR, int NCH> AUM_GLOBAL void k_norm_fwd_vec(AumNormArgs a) { rmsnorm_fwd_vec<TX, TR, NCH>(a, (int)blockIdx.x); }
-#ifndef AUM_EMU
 template <class TX, class TR, int NCH> __global__ __launch_bounds__(NORM_BWD_NW * 64) void k_norm_bwd_vec(AumNormArgs a, int n_waves) {
-    __shared__ __attribute__((aligned(16))) float lds[(NORM_BWD_NW - 1) * NCH * 512];
+    __shared__ __attribute__((aligned(16))) float lds[NormBwdVecLds<NCH>::n];
     rmsnorm_bwd_vec<TX, TR, NCH>(a, (int)blockIdx.x, n_waves, lds);
 }
-#endif
 template <class TX, class TR> AUM_GLOBAL void k_norm_fwd(AumNormArgs a) { rmsnorm_fwd_wave<TX, TR>(a, (int)blockIdx.x); }
 template <class TX, class TR> AUM_GLOBAL void k_norm_bwd(AumNormArgs a, int n_partials) {
     extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
@@ -109,11 +116,6 @@ AUM_GLOBAL void k_selftest_scan(const float* in, float* out, int rev) {
     out[64 + threadIdx.x] = S;
 }
 #endif
-#define AUM_LAUNCH(kernel, grid, lds_bytes, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(64), (lds_bytes), (stream), __VA_ARGS__)
-static int launch_status() { return hipGetLastError() == hipSuccess ? AUM_OK : AUM_E_LAUNCH; }
-#else
-static int launch_status() { return AUM_OK; }
 #endif
 
 // ---- steps-per-lane selection -----------------------------------------------------------------
@@ -184,172 +186,78 @@ static int scanwg_ct_rows(int batch, int dim) {
     return AUM_SCANWG_CT_ROWS ? AUM_SCANWG_CT_ROWS : 2 * SCANWG_NW;
 }
 
+static int scan_rows_grid(int batch, int dim, int rows) { return batch * ((dim + rows - 1) / rows); }
 template <class T, int K, int TAIL, int MODE> static int launch_scanwg_fwd(const AumScanFwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanwg_fwd_lds_floats<K, TAIL>());
-    for (int wg = 0; wg < grid; ++wg) scanwg_fwd<T, K, TAIL, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanwg_fwd<T, K, TAIL, MODE>), dim3((unsigned)grid), dim3(SCANWG_NW * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(scan_rows_grid(a.batch, a.dim, rows), SCANWG_NW * 64, s, (ScanWgFwdLds<K, TAIL>{}), (k_scanwg_fwd<T, K, TAIL, MODE>),
+                      (scanwg_fwd<T, K, TAIL, MODE>(a, wg, lds, rows)), a, rows);
 }
 // rows of 512*m + 1 steps (long-form clips), one direction: <8,1> geometry walked in 512-step chunks
 template <class T, int MODE> static int launch_scanwg_fwd_ct(const AumScanFwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanwg_fwd_lds_floats<8, 1, true>());
-    for (int wg = 0; wg < grid; ++wg) scanwg_fwd_ct<T, 8, 1, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanwg_fwd_ct<T, MODE>), dim3((unsigned)grid), dim3(SCANWG_NW * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(scan_rows_grid(a.batch, a.dim, rows), SCANWG_NW * 64, s, (ScanWgFwdLds<8, 1, true>{}), (k_scanwg_fwd_ct<T, MODE>),
+                      (scanwg_fwd_ct<T, 8, 1, MODE>(a, wg, lds, rows)), a, rows);
 }
 template <class T, int K, int TAIL, int MODE> static int launch_scanwg_bwd(const AumScanBwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
+    const int grid = scan_rows_grid(a.batch, a.dim, rows);
     if constexpr (K == 8 && TAIL == 1) {      // the AuM row shape: one row per wave, half-packed slots (scan_half_kernels.h)
-        if (scanh_selected(K, TAIL, (a.len + ScanGeo<K, TAIL>::S - 1) / ScanGeo<K, TAIL>::S, a.len, a.dstate, a.flags)) {
-#ifdef AUM_EMU
-            (void)s;
-            std::vector<float> lds(scanh_bwd_lds_floats<TAIL>());
-            for (int wg = 0; wg < grid; ++wg) scanh_bwd<T, TAIL, MODE>(a, wg, lds.data(), rows);
-#else
-            hipLaunchKernelGGL((k_scanh_bwd<T, TAIL, MODE>), dim3((unsigned)grid), dim3(scanh_nw(MODE) * 64), 0, s, a, rows);
-#endif
-            return launch_status();
-        }
+        if (scanh_selected(K, TAIL, (a.len + ScanGeo<K, TAIL>::S - 1) / ScanGeo<K, TAIL>::S, a.len, a.dstate, a.flags))
+            return AUM_LAUNCH(grid, scanh_nw(MODE) * 64, s, (ScanHBwdLds<TAIL>{}), (k_scanh_bwd<T, TAIL, MODE>),
+                              (scanh_bwd<T, TAIL, MODE>(a, wg, lds, rows)), a, rows);
     }
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanwg_bwd_lds_floats<K, TAIL>());
-    for (int wg = 0; wg < grid; ++wg) scanwg_bwd<T, K, TAIL, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanwg_bwd<T, K, TAIL, MODE>), dim3((unsigned)grid), dim3(SCANWG_NW * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANWG_NW * 64, s, (ScanWgBwdLds<K, TAIL>{}), (k_scanwg_bwd<T, K, TAIL, MODE>),
+                      (scanwg_bwd<T, K, TAIL, MODE>(a, wg, lds, rows)), a, rows);
 }
 
 // long rows of 512*m (+1) steps, one direction: one row per wave, chunked (scan_half_kernels.h)
 template <class T, int TAIL, int MODE> static int launch_scanh_chunked(const AumScanBwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanh_chunked_lds_floats<TAIL>());
-    for (int wg = 0; wg < grid; ++wg) scanh_bwd_chunked<T, TAIL, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanh_bwd_chunked<T, TAIL, MODE>), dim3((unsigned)grid), dim3(SCANH_CH_NW * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(scan_rows_grid(a.batch, a.dim, rows), SCANH_CH_NW * 64, s, (ScanHChunkedLds<TAIL>{}), (k_scanh_bwd_chunked<T, TAIL, MODE>),
+                      (scanh_bwd_chunked<T, TAIL, MODE>(a, wg, lds, rows)), a, rows);
 }
 
 // the L = 513 row kernels (scan_row_kernels.h); plan marker {8, 1, SCANR_PLAN_TAIL}
 constexpr int SCANR_PLAN_TAIL = 2;
 template <class T, int MODE> static int launch_scanr_fwd(const AumScanFwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanr_fwd_lds_floats());
-    for (int wg = 0; wg < grid; ++wg) scanr_fwd<T, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanr_fwd<T, MODE>), dim3((unsigned)grid), dim3(SCANR_FWD_NW * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(scan_rows_grid(a.batch, a.dim, rows), SCANR_FWD_NW * 64, s, (ScanRFwdLds{}), (k_scanr_fwd<T, MODE>),
+                      (scanr_fwd<T, MODE>(a, wg, lds, rows)), a, rows);
 }
 template <class T, int MODE> static int launch_scanr_bwd(const AumScanBwdArgs& a, int rows, aum_stream_t s) {
-    const int grid = a.batch * ((a.dim + rows - 1) / rows);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(scanr_bwd_lds_floats());
-    for (int wg = 0; wg < grid; ++wg) scanr_bwd<T, MODE>(a, wg, lds.data(), rows);
-#else
-    hipLaunchKernelGGL((k_scanr_bwd<T, MODE>), dim3((unsigned)grid), dim3(scanr_bwd_nw(MODE) * 64), 0, s, a, rows);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(scan_rows_grid(a.batch, a.dim, rows), scanr_bwd_nw(MODE) * 64, s, (ScanRBwdLds{}), (k_scanr_bwd<T, MODE>),
+                      (scanr_bwd<T, MODE>(a, wg, lds, rows)), a, rows);
 }
 
 template <class T, int K, int MODE> static int launch_scan_fwd(const AumScanFwdArgs& a, int grid, aum_stream_t s) {
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCAN_LDS_FLOATS);
-    for (int wg = 0; wg < grid; ++wg) scan_fwd_wave<T, K, MODE>(a, wg, lds.data());
-#else
-    AUM_LAUNCH((k_scan_fwd<T, K, MODE>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (ScanLds{}), (k_scan_fwd<T, K, MODE>), (scan_fwd_wave<T, K, MODE>(a, wg, lds)), a);
 }
 template <class T, int K, int MODE> static int launch_scan_bwd(const AumScanBwdArgs& a, int grid, aum_stream_t s) {
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCAN_LDS_FLOATS);
-    for (int wg = 0; wg < grid; ++wg) scan_bwd_wave<T, K, MODE>(a, wg, lds.data());
-#else
-    AUM_LAUNCH((k_scan_bwd<T, K, MODE>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (ScanLds{}), (k_scan_bwd<T, K, MODE>), (scan_bwd_wave<T, K, MODE>(a, wg, lds)), a);
 }
 
-#define AUM_K_SWITCH(FN, T, MODE, ...)                                   \
-    switch (plan.K) {                                                    \
-        case 1: return FN<T, 1, MODE>(__VA_ARGS__);                      \
-        case 4: return FN<T, 4, MODE>(__VA_ARGS__);                      \
-        case 9: return FN<T, 9, MODE>(__VA_ARGS__);                      \
-        case 16: return FN<T, 16, MODE>(__VA_ARGS__);                    \
-        default: return AUM_E_UNSUPPORTED;                               \
-    }
-#define AUM_WGK_SWITCH(FN, T, MODE, ...)                                 \
-    switch (plan.K * 2 + plan.tail) {                                    \
-        case 2: return FN<T, 1, 0, MODE>(__VA_ARGS__);                   \
-        case 3: return FN<T, 1, 1, MODE>(__VA_ARGS__);                   \
-        case 6: return FN<T, 3, 0, MODE>(__VA_ARGS__);                   \
-        case 10: return FN<T, 5, 0, MODE>(__VA_ARGS__);                  \
-        case 14: return FN<T, 7, 0, MODE>(__VA_ARGS__);                  \
-        case 17: return FN<T, 8, 1, MODE>(__VA_ARGS__);                  \
-        case 18: return FN<T, 9, 0, MODE>(__VA_ARGS__);                  \
-        default: return AUM_E_UNSUPPORTED;                               \
-    }
+// plan.K (generic kernels) and plan.K * 2 + plan.tail (workgroup kernels) into template parameters
+template <class F> static int with_scan_k(int K, F&& f) { return with_int<1, 4, 9, 16>(K, f); }
+template <class F> static int with_scanwg_kt(const ScanPlan& plan, F&& f) {
+    return with_int<2, 3, 6, 10, 14, 17, 18>(plan.K * 2 + plan.tail, f);
+}
 
 // grid < 0 selects the workgroup kernels with rows_per_wg = -grid
+// mode: 0 forward, 1 reverse, anything else the bidirectional kernels (2)
 template <class T> static int scan_fwd_t(const AumScanFwdArgs& a, ScanPlan plan, int mode, int grid, aum_stream_t s) {
-    if (grid < 0 && plan.tail == SCANR_PLAN_TAIL) {
-        if (mode == 0) return launch_scanr_fwd<T, 0>(a, -grid, s);
-        if (mode == 1) return launch_scanr_fwd<T, 1>(a, -grid, s);
-        return launch_scanr_fwd<T, 2>(a, -grid, s);
-    }
-    if (grid < 0 && plan.K == 8 && plan.nchunks > 1) {      // the plan aum_selective_scan_fwd makes for scanwg_ct_selected rows
-        if (mode == 0) return launch_scanwg_fwd_ct<T, 0>(a, -grid, s);
-        if (mode == 1) return launch_scanwg_fwd_ct<T, 1>(a, -grid, s);
-        return AUM_E_UNSUPPORTED;
-    }
-    if (grid < 0) {
-        if (mode == 0) { AUM_WGK_SWITCH(launch_scanwg_fwd, T, 0, a, -grid, s) }
-        if (mode == 1) { AUM_WGK_SWITCH(launch_scanwg_fwd, T, 1, a, -grid, s) }
-        AUM_WGK_SWITCH(launch_scanwg_fwd, T, 2, a, -grid, s)
-    }
-    if (mode == 0) { AUM_K_SWITCH(launch_scan_fwd, T, 0, a, grid, s) }
-    if (mode == 1) { AUM_K_SWITCH(launch_scan_fwd, T, 1, a, grid, s) }
-    AUM_K_SWITCH(launch_scan_fwd, T, 2, a, grid, s)
+    if (mode != 0 && mode != 1) mode = 2;
+    if (grid < 0 && plan.tail == SCANR_PLAN_TAIL) return with_int<0, 1, 2>(mode, [&](auto m) { return launch_scanr_fwd<T, m>(a, -grid, s); });
+    if (grid < 0 && plan.K == 8 && plan.nchunks > 1)      // the plan aum_selective_scan_fwd makes for scanwg_ct_selected rows
+        return with_int<0, 1>(mode, [&](auto m) { return launch_scanwg_fwd_ct<T, m>(a, -grid, s); });
+    return with_int<0, 1, 2>(mode, [&](auto m) {
+        if (grid < 0) return with_scanwg_kt(plan, [&](auto kt) { return launch_scanwg_fwd<T, kt / 2, kt % 2, m>(a, -grid, s); });
+        return with_scan_k(plan.K, [&](auto k) { return launch_scan_fwd<T, k, m>(a, grid, s); });
+    });
 }
 template <class T> static int scan_bwd_t(const AumScanBwdArgs& a, ScanPlan plan, int mode, int grid, aum_stream_t s) {
-    if (grid < 0 && plan.tail == SCANR_PLAN_TAIL) {
-        if (mode == 0) return launch_scanr_bwd<T, 0>(a, -grid, s);
-        if (mode == 1) return launch_scanr_bwd<T, 1>(a, -grid, s);
-        return launch_scanr_bwd<T, 2>(a, -grid, s);
-    }
-    if (grid < 0 && plan.K == 8 && plan.nchunks > 1) {      // the plan aum_selective_scan_bwd makes for scanh_chunked_selected rows
-        if (mode == 0) return plan.tail ? launch_scanh_chunked<T, 1, 0>(a, -grid, s) : launch_scanh_chunked<T, 0, 0>(a, -grid, s);
-        if (mode == 1) return plan.tail ? launch_scanh_chunked<T, 1, 1>(a, -grid, s) : launch_scanh_chunked<T, 0, 1>(a, -grid, s);
-        return AUM_E_UNSUPPORTED;
-    }
-    if (grid < 0) {
-        if (mode == 0) { AUM_WGK_SWITCH(launch_scanwg_bwd, T, 0, a, -grid, s) }
-        if (mode == 1) { AUM_WGK_SWITCH(launch_scanwg_bwd, T, 1, a, -grid, s) }
-        AUM_WGK_SWITCH(launch_scanwg_bwd, T, 2, a, -grid, s)
-    }
-    if (mode == 0) { AUM_K_SWITCH(launch_scan_bwd, T, 0, a, grid, s) }
-    if (mode == 1) { AUM_K_SWITCH(launch_scan_bwd, T, 1, a, grid, s) }
-    AUM_K_SWITCH(launch_scan_bwd, T, 2, a, grid, s)
+    if (mode != 0 && mode != 1) mode = 2;
+    if (grid < 0 && plan.tail == SCANR_PLAN_TAIL) return with_int<0, 1, 2>(mode, [&](auto m) { return launch_scanr_bwd<T, m>(a, -grid, s); });
+    if (grid < 0 && plan.K == 8 && plan.nchunks > 1)      // the plan aum_selective_scan_bwd makes for scanh_chunked_selected rows
+        return with_int<0, 1>(mode, [&](auto m) { return with_int<0, 1>(plan.tail ? 1 : 0, [&](auto t) { return launch_scanh_chunked<T, t, m>(a, -grid, s); }); });
+    return with_int<0, 1, 2>(mode, [&](auto m) {
+        if (grid < 0) return with_scanwg_kt(plan, [&](auto kt) { return launch_scanwg_bwd<T, kt / 2, kt % 2, m>(a, -grid, s); });
+        return with_scan_k(plan.K, [&](auto k) { return launch_scan_bwd<T, k, m>(a, grid, s); });
+    });
 }
 
 #if defined(AUM_DTYPE_ONLY)
@@ -396,41 +304,27 @@ int proj_f16(const AumProjArgs& a, bool bwd, aum_stream_t s);
 int projw_bf16(const AumProjWArgs& a, int chunk, aum_stream_t s);
 int projw_f16(const AumProjWArgs& a, int chunk, aum_stream_t s);
 #if AUM_API_PART == 4 || AUM_API_PART == 0
+typedef Lds<uint16_t, PJ_LDS_ELEMS> ProjLds;
+typedef Lds<uint16_t, PJW_LDS_ELEMS> ProjWLds;
 #ifndef AUM_EMU
 template <class T, int NCB, bool TWO> __global__ __launch_bounds__(PJ_NW * 64) void k_proj_fwd(AumProjArgs a) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[PJ_LDS_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[ProjLds::n];
     proj_fwd_wg<T, NCB, TWO>(a, (int)blockIdx.x, lds);
 }
 template <class T, int NDB, int NRC> __global__ __launch_bounds__(PJ_NW * 64) void k_proj_bwd_data(AumProjArgs a) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[PJ_LDS_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[ProjLds::n];
     proj_bwd_data_wg<T, NDB, NRC>(a, (int)blockIdx.x, lds);
 }
 template <class T> __global__ __launch_bounds__(PJW_NW * 64) void k_proj_bwd_weight(AumProjWArgs a, int chunk) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[PJW_LDS_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t lds[ProjWLds::n];
     proj_bwd_weight_wg<T>(a, chunk, (int)blockIdx.x, lds);
 }
 #endif
 template <class T, int NCB, bool TWO> static int proj_fwd_launch(const AumProjArgs& a, aum_stream_t s) {
-    const int grid = (int)((a.ntok + PJ_TT - 1) / PJ_TT);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<uint16_t> lds(PJ_LDS_ELEMS);
-    for (int wg = 0; wg < grid; ++wg) proj_fwd_wg<T, NCB, TWO>(a, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_proj_fwd<T, NCB, TWO>), dim3((unsigned)grid), dim3(PJ_NW * 64), 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH((a.ntok + PJ_TT - 1) / PJ_TT, PJ_NW * 64, s, (ProjLds{}), (k_proj_fwd<T, NCB, TWO>), (proj_fwd_wg<T, NCB, TWO>(a, wg, lds)), a);
 }
 template <class T, int NDB, int NRC> static int proj_bwd_launch(const AumProjArgs& a, aum_stream_t s) {
-    const int grid = (int)((a.ntok + PJ_TT - 1) / PJ_TT);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<uint16_t> lds(PJ_LDS_ELEMS);
-    for (int wg = 0; wg < grid; ++wg) proj_bwd_data_wg<T, NDB, NRC>(a, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_proj_bwd_data<T, NDB, NRC>), dim3((unsigned)grid), dim3(PJ_NW * 64), 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH((a.ntok + PJ_TT - 1) / PJ_TT, PJ_NW * 64, s, (ProjLds{}), (k_proj_bwd_data<T, NDB, NRC>), (proj_bwd_data_wg<T, NDB, NRC>(a, wg, lds)), a);
 }
 // shapes are compile-time in the kernels: forward (column blocks of R+2N, R > 32), backward (column blocks of R, 32-row
 // k-chunks of R+2N).  R <= 64 and R+2N <= 80 bound the table.
@@ -452,15 +346,8 @@ template <class T> static int proj_t(const AumProjArgs& a, bool bwd, aum_stream_
     return AUM_E_UNSUPPORTED;
 }
 template <class T> static int projw_t(const AumProjWArgs& a, int chunk, aum_stream_t s) {
-    const int grid = (a.dim + PJW_ROWS - 1) / PJW_ROWS * a.nsplit;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<uint16_t> lds(PJW_LDS_ELEMS);
-    for (int wg = 0; wg < grid; ++wg) proj_bwd_weight_wg<T>(a, chunk, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_proj_bwd_weight<T>), dim3((unsigned)grid), dim3(PJW_NW * 64), 0, s, a, chunk);
-#endif
-    return launch_status();
+    return AUM_LAUNCH((a.dim + PJW_ROWS - 1) / PJW_ROWS * a.nsplit, PJW_NW * 64, s, (ProjWLds{}), (k_proj_bwd_weight<T>),
+                      (proj_bwd_weight_wg<T>(a, chunk, wg, lds)), a, chunk);
 }
 #if AUM_HAS_DTYPE(1)
 int proj_bf16(const AumProjArgs& a, bool bwd, aum_stream_t s) { return proj_t<bf16_t>(a, bwd, s); }
@@ -560,19 +447,18 @@ __global__ void k_scan_reduce(ScanReduceArgs a) {
     }
 }
 #endif
-static int scan_reduce_launch(const ScanReduceArgs& a, aum_stream_t s) {
 #ifdef AUM_EMU
-    (void)s;
+static void scan_reduce_host(const ScanReduceArgs& a) {       // what k_scan_reduce computes, as one plain loop
     for (int k = 0; k < a.nseg; ++k)
         for (int64_t i = 0; i < a.seg[k].inner; ++i) {
             float acc = 0.f;
             for (int o = 0; o < a.seg[k].outer; ++o) acc += a.seg[k].src[(int64_t)o * a.seg[k].inner + i];
             a.seg[k].dst[i] += acc;
         }
-#else
-    hipLaunchKernelGGL(k_scan_reduce, dim3(512, (unsigned)a.nseg), dim3(256), 0, s, a);
+}
 #endif
-    return launch_status();
+static int scan_reduce_launch(const ScanReduceArgs& a, aum_stream_t s) {
+    return AUM_LAUNCH((Grid2{512, (unsigned)a.nseg}), 256, s, (NoLds{}), k_scan_reduce, (AUM_HOST_LOOP(scan_reduce_host(a))), a);
 }
 
 AUM_API int64_t aum_selective_scan_ckpt_bytes(int32_t batch, int32_t dim, int32_t len, int32_t dstate) {
@@ -653,11 +539,7 @@ AUM_API int aum_selective_scan_fwd(const AumScanFwdArgs* a, void* stream) {
         grid = -scanr_fwd_rows_for(a->batch, a->dim);
     }
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return scan_fwd_f32(*a, plan, mode, grid, s);
-        case AUM_BF16: return scan_fwd_bf16(*a, plan, mode, grid, s);
-        default: return scan_fwd_f16(*a, plan, mode, grid, s);
-    }
+    return AUM_BY_DTYPE_X(a->dtype, scan_fwd, *a, plan, mode, grid, s);
 }
 
 AUM_API int aum_selective_scan_bwd(const AumScanBwdArgs* a, void* stream) {
@@ -698,12 +580,7 @@ AUM_API int aum_selective_scan_bwd(const AumScanBwdArgs* a, void* stream) {
         const int64_t need = (int64_t)grid * SCAN_R * plan.nchunks * a->dstate * (int64_t)sizeof(float);
         if (!a->workspace || a->workspace_bytes < need) return AUM_E_WORKSPACE;
     }
-    int rc2;
-    switch (a->dtype) {
-        case AUM_F32: rc2 = scan_bwd_f32(*a, plan, mode, grid, s); break;
-        case AUM_BF16: rc2 = scan_bwd_bf16(*a, plan, mode, grid, s); break;
-        default: rc2 = scan_bwd_f16(*a, plan, mode, grid, s); break;
-    }
+    const int rc2 = AUM_BY_DTYPE_X(a->dtype, scan_bwd, *a, plan, mode, grid, s);
     if (rc2 != AUM_OK || !wgk) return rc2;
     // second stage: sum the per-workgroup / per-batch partials into the (accumulate-into) outputs
     const ScanWgWs L = scanwg_ws_layout(a->batch, a->dim, a->len, a->dstate, rows, plan.nchunks, bidir);
@@ -725,45 +602,21 @@ AUM_API int aum_selective_scan_bwd(const AumScanBwdArgs* a, void* stream) {
 // the AuM row shape (512 + up to 8 tail steps, 16-bit activations): several rows of one channel per wave, one pass per row
 template <class T, bool REV> static int conv4_rows_launch(const AumConvArgs& a, bool bwd, aum_stream_t s) {
     const int grid = a.dim * ((a.batch + CONVR_ROWS - 1) / CONVR_ROWS);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) {
-        if (bwd) conv4_rows_bwd_wave<T, REV>(a, wg); else conv4_rows_fwd_wave<T, REV>(a, wg);
-    }
-#else
-    if (bwd) AUM_LAUNCH((k_conv4_rows_bwd<T, REV>), grid, 0, s, a); else AUM_LAUNCH((k_conv4_rows_fwd<T, REV>), grid, 0, s, a);
-#endif
-    return launch_status();
+    if (bwd) return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_conv4_rows_bwd<T, REV>), (conv4_rows_bwd_wave<T, REV>(a, wg)), a);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_conv4_rows_fwd<T, REV>), (conv4_rows_fwd_wave<T, REV>(a, wg)), a);
 }
 template <class T, bool REV> static int conv4_launch(const AumConvArgs& a, bool bwd, aum_stream_t s) {
     if constexpr (sizeof(T) == 2) {
         if (convr_shape_ok(a.len)) return conv4_rows_launch<T, REV>(a, bwd, s);
     }
-    const int grid = a.batch * a.dim;
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) {
-        if (bwd) conv4_bwd_wave<T, REV>(a, wg); else conv4_fwd_wave<T, REV>(a, wg);
-    }
-#else
-    if (bwd) AUM_LAUNCH((k_conv4_bwd<T, REV>), grid, 0, s, a); else AUM_LAUNCH((k_conv4_fwd<T, REV>), grid, 0, s, a);
-#endif
-    return launch_status();
+    if (bwd) return AUM_LAUNCH(a.batch * a.dim, 64, s, (NoLds{}), (k_conv4_bwd<T, REV>), (conv4_bwd_wave<T, REV>(a, wg)), a);
+    return AUM_LAUNCH(a.batch * a.dim, 64, s, (NoLds{}), (k_conv4_fwd<T, REV>), (conv4_fwd_wave<T, REV>(a, wg)), a);
 }
 template <class T> static int conv_launch(const AumConvArgs& a, bool bwd, aum_stream_t s) {
     if (a.width == 4 && !(a.flags & AUM_CONV_GENERIC))
-        return (a.flags & AUM_CONV_REVERSE) ? conv4_launch<T, true>(a, bwd, s) : conv4_launch<T, false>(a, bwd, s);
-    const int grid = a.batch * a.dim;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(CONV_LDS_FLOATS);
-    for (int wg = 0; wg < grid; ++wg) {
-        if (bwd) conv_bwd_wave<T>(a, wg, lds.data()); else conv_fwd_wave<T>(a, wg);
-    }
-#else
-    if (bwd) AUM_LAUNCH((k_conv_bwd<T>), grid, 0, s, a); else AUM_LAUNCH((k_conv_fwd<T>), grid, 0, s, a);
-#endif
-    return launch_status();
+        return with_bool((a.flags & AUM_CONV_REVERSE) != 0, [&](auto rev) { return conv4_launch<T, rev>(a, bwd, s); });
+    if (bwd) return AUM_LAUNCH(a.batch * a.dim, 64, s, (ConvLds{}), (k_conv_bwd<T>), (conv_bwd_wave<T>(a, wg, lds)), a);
+    return AUM_LAUNCH(a.batch * a.dim, 64, s, (NoLds{}), (k_conv_fwd<T>), (conv_fwd_wave<T>(a, wg)), a);
 }
 static int conv_check(const AumConvArgs* a, bool bwd) {
     if (!a || !a->x || !a->weight) return AUM_E_NULL;
@@ -776,12 +629,7 @@ static int conv_check(const AumConvArgs* a, bool bwd) {
 static int conv_dispatch(const AumConvArgs* a, bool bwd, void* stream) {
     int rc = conv_check(a, bwd);
     if (rc) return rc;
-    aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return conv_launch<float>(*a, bwd, s);
-        case AUM_BF16: return conv_launch<bf16_t>(*a, bwd, s);
-        default: return conv_launch<f16_t>(*a, bwd, s);
-    }
+    return AUM_BY_DTYPE_T(a->dtype, conv_launch, *a, bwd, (aum_stream_t)stream);
 }
 AUM_API int aum_causal_conv1d_fwd(const AumConvArgs* a, void* stream) { return conv_dispatch(a, false, stream); }
 AUM_API int aum_causal_conv1d_bwd(const AumConvArgs* a, void* stream) { return conv_dispatch(a, true, stream); }
@@ -800,40 +648,19 @@ AUM_API int aum_rmsnorm_bwd_partial_rows(int32_t rows, int32_t cols, uint32_t fl
 
 template <class TX, class TR, int NCH> static int norm_vec_launch(const AumNormArgs& a, bool bwd, aum_stream_t s) {
     const int np = aum_rmsnorm_bwd_partials(a.rows);
-#ifdef AUM_EMU
-    (void)s;
-    const int nwg = (np + NORM_BWD_NW - 1) / NORM_BWD_NW;
-    std::vector<float> lds((NORM_BWD_NW - 1) * NCH * 512);
-    if (bwd) for (int wg = 0; wg < nwg; ++wg) rmsnorm_bwd_vec<TX, TR, NCH>(a, wg, np, lds.data());
-    else for (int wg = 0; wg < a.rows; ++wg) rmsnorm_fwd_vec<TX, TR, NCH>(a, wg);
-#else
-    const int nwg = (np + NORM_BWD_NW - 1) / NORM_BWD_NW;
-    if (bwd) hipLaunchKernelGGL((k_norm_bwd_vec<TX, TR, NCH>), dim3((unsigned)nwg), dim3(NORM_BWD_NW * 64), 0, s, a, np);
-    else AUM_LAUNCH((k_norm_fwd_vec<TX, TR, NCH>), a.rows, 0, s, a);
-#endif
-    return launch_status();
+    if (bwd) return AUM_LAUNCH((np + NORM_BWD_NW - 1) / NORM_BWD_NW, NORM_BWD_NW * 64, s, (NormBwdVecLds<NCH>{}), (k_norm_bwd_vec<TX, TR, NCH>),
+                               (rmsnorm_bwd_vec<TX, TR, NCH>(a, wg, np, lds)), a, np);
+    return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd_vec<TX, TR, NCH>), (rmsnorm_fwd_vec<TX, TR, NCH>(a, wg)), a);
 }
 template <class TX, class TR> static int norm_launch(const AumNormArgs& a, bool bwd, aum_stream_t s) {
     if (norm_is_vec(a.cols, a.flags)) {
-        switch ((a.cols + 511) / 512) {
-            case 1: return norm_vec_launch<TX, TR, 1>(a, bwd, s);
-            case 2: return norm_vec_launch<TX, TR, 2>(a, bwd, s);
-            case 3: return norm_vec_launch<TX, TR, 3>(a, bwd, s);
-            default: return norm_vec_launch<TX, TR, 4>(a, bwd, s);
-        }
+        const int nch = (a.cols + 511) / 512;
+        return with_int<1, 2, 3, 4>(nch < 4 ? nch : 4, [&](auto n) { return norm_vec_launch<TX, TR, n>(a, bwd, s); });
     }
     const int np = aum_rmsnorm_bwd_partials(a.rows);
-    const int lds_floats = ((a.cols + WAVE - 1) / WAVE) * WAVE;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(lds_floats);
-    if (bwd) for (int wg = 0; wg < np; ++wg) rmsnorm_bwd_wave<TX, TR>(a, wg, np, lds.data());
-    else for (int wg = 0; wg < a.rows; ++wg) rmsnorm_fwd_wave<TX, TR>(a, wg);
-#else
-    if (bwd) AUM_LAUNCH((k_norm_bwd<TX, TR>), np, lds_floats * sizeof(float), s, a, np);
-    else AUM_LAUNCH((k_norm_fwd<TX, TR>), a.rows, 0, s, a);
-#endif
-    return launch_status();
+    const DynLds row = {((a.cols + WAVE - 1) / WAVE) * WAVE};
+    if (bwd) return AUM_LAUNCH(np, 64, s, (row), (k_norm_bwd<TX, TR>), (rmsnorm_bwd_wave<TX, TR>(a, wg, np, lds)), a, np);
+    return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd<TX, TR>), (rmsnorm_fwd_wave<TX, TR>(a, wg)), a);
 }
 static int norm_dispatch(const AumNormArgs* a, bool bwd, void* stream) {
     if (!a || !a->x || !a->weight) return AUM_E_NULL;
@@ -845,11 +672,7 @@ static int norm_dispatch(const AumNormArgs* a, bool bwd, void* stream) {
     aum_stream_t s = (aum_stream_t)stream;
     // residual stream is fp32 (residual_in_fp32) or shares the activation dtype
     if (a->res_dtype == AUM_F32) {
-        switch (a->x_dtype) {
-            case AUM_F32: return norm_launch<float, float>(*a, bwd, s);
-            case AUM_BF16: return norm_launch<bf16_t, float>(*a, bwd, s);
-            default: return norm_launch<f16_t, float>(*a, bwd, s);
-        }
+        return by_dtype(a->x_dtype, norm_launch<float, float>, norm_launch<bf16_t, float>, norm_launch<f16_t, float>, *a, bwd, s);
     }
     if (a->res_dtype != a->x_dtype) return AUM_E_DTYPE;
     if (a->x_dtype == AUM_BF16) return norm_launch<bf16_t, bf16_t>(*a, bwd, s);
@@ -859,13 +682,15 @@ AUM_API int aum_rmsnorm_fwd(const AumNormArgs* a, void* stream) { return norm_di
 AUM_API int aum_rmsnorm_bwd(const AumNormArgs* a, void* stream) { return norm_dispatch(a, true, stream); }
 
 // ---- fbank frontend ----------------------------------------------------------------------------
+typedef Lds<float, FBANK_LDS_FLOATS> FbankLds;
+typedef Lds<float, FBANK_NW * FBW_WAVE_FLOATS> FbankWLds;
 #ifndef AUM_EMU
 __global__ __launch_bounds__(FBANK_THREADS) void k_fbank(AumFbankArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[FBANK_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds[FbankLds::n];
     fbank_frame(a, (int)blockIdx.x, lds);
 }
 __global__ __launch_bounds__(FBANK_THREADS) void k_fbank_w(AumFbankArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[FBANK_NW * FBW_WAVE_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds[FbankWLds::n];
     fbank_frames_wg(a, (int)blockIdx.x, lds);
 }
 #endif
@@ -876,23 +701,16 @@ AUM_API int aum_fbank_fwd(const AumFbankArgs* a, void* stream) {
     if (a->num_frames < 0 || (a->num_frames > 0 && (int64_t)(a->num_frames - 1) * a->shift + a->win > a->n_samples)) return AUM_E_SHAPE;
     const int grid = a->batch * a->target_length;
     const bool per_wave = a->padded == FBW_N;      // the 16 kHz / 25 ms configuration: one wavefront per frame
-    const int grid_w = (grid + FBW_WG_FRAMES - 1) / FBW_WG_FRAMES;
-#ifdef AUM_EMU
-    (void)stream;
-    std::vector<float> lds(FBANK_LDS_FLOATS > FBANK_NW * FBW_WAVE_FLOATS ? FBANK_LDS_FLOATS : FBANK_NW * FBW_WAVE_FLOATS);
-    if (per_wave) for (int wg = 0; wg < grid_w; ++wg) fbank_frames_wg(*a, wg, lds.data());
-    else for (int wg = 0; wg < grid; ++wg) fbank_frame(*a, wg, lds.data());
-#else
-    if (per_wave) hipLaunchKernelGGL(k_fbank_w, dim3((unsigned)grid_w), dim3(FBANK_THREADS), 0, (aum_stream_t)stream, *a);
-    else hipLaunchKernelGGL(k_fbank, dim3((unsigned)grid), dim3(FBANK_THREADS), 0, (aum_stream_t)stream, *a);
-#endif
-    return launch_status();
+    aum_stream_t s = (aum_stream_t)stream;
+    if (per_wave) return AUM_LAUNCH((grid + FBW_WG_FRAMES - 1) / FBW_WG_FRAMES, FBANK_THREADS, s, (FbankWLds{}), k_fbank_w, (fbank_frames_wg(*a, wg, lds)), *a);
+    return AUM_LAUNCH(grid, FBANK_THREADS, s, (FbankLds{}), k_fbank, (fbank_frame(*a, wg, lds)), *a);
 }
 
 // ---- EPIC-Sounds frontend: log-mel (librosa-style STFT) and the SpecAugment time warp ------------------------------
+typedef Lds<float, STFT_LDS_FLOATS> StftLds;
 #ifndef AUM_EMU
 __global__ __launch_bounds__(STFT_THREADS) void k_stft_logmel(AumStftArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[STFT_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds[StftLds::n];
     stft_logmel_frame(a, (int)blockIdx.x, lds);
 }
 __global__ __launch_bounds__(STFT_THREADS) void k_spec_time_warp(AumTimeWarpArgs a) { spec_time_warp_wg(a, (int)blockIdx.x); }
@@ -903,15 +721,7 @@ AUM_API int aum_stft_logmel_fwd(const AumStftArgs* a, void* stream) {
         return AUM_E_SHAPE;
     if (a->n_fft < 256 || a->n_fft > AUM_STFT_MAX_FFT || (a->n_fft & (a->n_fft - 1)) || a->win > a->n_fft) return AUM_E_UNSUPPORTED;
     if ((int64_t)a->batch * a->target_length > 0x7fffffff) return AUM_E_SHAPE;
-    const int grid = a->batch * a->target_length;
-#ifdef AUM_EMU
-    (void)stream;
-    std::vector<float> lds(STFT_LDS_FLOATS);
-    for (int wg = 0; wg < grid; ++wg) stft_logmel_frame(*a, wg, lds.data());
-#else
-    hipLaunchKernelGGL(k_stft_logmel, dim3((unsigned)grid), dim3(STFT_THREADS), 0, (aum_stream_t)stream, *a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(a->batch * a->target_length, STFT_THREADS, (aum_stream_t)stream, (StftLds{}), k_stft_logmel, (stft_logmel_frame(*a, wg, lds)), *a);
 }
 AUM_API int aum_spec_time_warp(const AumTimeWarpArgs* a, void* stream) {
     if (!a || !a->in || !a->table || !a->out) return AUM_E_NULL;
@@ -921,34 +731,22 @@ AUM_API int aum_spec_time_warp(const AumTimeWarpArgs* a, void* stream) {
     if (per_clip + WAVE > 0x7fffffff || a->in_bs < per_clip || a->out_bs < per_clip) return AUM_E_SHAPE;
     const int64_t grid = (per_clip * a->batch + STFT_THREADS - 1) / STFT_THREADS;
     if (grid > 0x7fffffff) return AUM_E_SHAPE;
-#ifdef AUM_EMU
-    (void)stream;
-    for (int64_t wg = 0; wg < grid; ++wg) spec_time_warp_wg(*a, (int)wg);
-#else
-    hipLaunchKernelGGL(k_spec_time_warp, dim3((unsigned)grid), dim3(STFT_THREADS), 0, (aum_stream_t)stream, *a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, STFT_THREADS, (aum_stream_t)stream, (NoLds{}), k_spec_time_warp, (spec_time_warp_wg(*a, wg)), *a);
 }
 
 // ---- waveform -> tokens in one launch ------------------------------------------------------------
+typedef Lds<float, FT_LDS_FLOATS> FrontendLds;
+typedef Lds<uint16_t, FT_TILE> FrontendTile;
 #ifndef AUM_EMU
 template <class T, class TO> __global__ __launch_bounds__(FT_NW * 64, 4) void k_frontend_tokens(AumFrontendArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[FT_LDS_FLOATS];
-    __shared__ __attribute__((aligned(16))) uint16_t tile[FT_TILE];
+    __shared__ __attribute__((aligned(16))) float lds[FrontendLds::n];
+    __shared__ __attribute__((aligned(16))) uint16_t tile[FrontendTile::n];
     frontend_tokens_wg<T, TO>(a, (int)blockIdx.x, lds, tile);
 }
 #endif
 template <class T, class TO> static int frontend_launch(const AumFrontendArgs& a, aum_stream_t s) {
-    const int grid = a.fbank.batch * (a.fbank.target_length / FT_FRAMES);
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(FT_LDS_FLOATS);
-    std::vector<uint16_t> tile(FT_TILE);
-    for (int wg = 0; wg < grid; ++wg) frontend_tokens_wg<T, TO>(a, wg, lds.data(), tile.data());
-#else
-    hipLaunchKernelGGL((k_frontend_tokens<T, TO>), dim3((unsigned)grid), dim3(FT_NW * 64), 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(a.fbank.batch * (a.fbank.target_length / FT_FRAMES), FT_NW * 64, s, (FrontendLds{}, FrontendTile{}), (k_frontend_tokens<T, TO>),
+                      (frontend_tokens_wg<T, TO>(a, wg, lds, lds2)), a);
 }
 AUM_API int aum_frontend_tokens_fwd(const AumFrontendArgs* a, void* stream) {
     if (!a) return AUM_E_NULL;
@@ -1009,27 +807,15 @@ AUM_API int aum_proj_bwd_weight(const AumProjWArgs* a, void* stream) {
     return a->dtype == AUM_BF16 ? projw_bf16(*a, chunk, (aum_stream_t)stream) : projw_f16(*a, chunk, (aum_stream_t)stream);
 }
 
-// ---- self-test / calibration -------------------------------------------------------------------
-AUM_API int aum_selftest_wave_scan(const float* in, float* out, int rev, void* stream) {
-    if (!in || !out) return AUM_E_NULL;
+// ---- self-test / calibration, sums and copies: kernels whose lane-array form is one plain host loop (a grid of one) -------
 #ifdef AUM_EMU
-    (void)stream;
+static void selftest_scan_host(const float* in, float* out, int rev) {
     vf P, S;
     for (int l = 0; l < 64; ++l) { P.v[l] = in[l]; S.v[l] = in[64 + l]; }
     if (rev) wave_scan_affine<true>(P, S); else wave_scan_affine<false>(P, S);
     for (int l = 0; l < 64; ++l) { out[l] = P.v[l]; out[64 + l] = S.v[l]; }
-#else
-    AUM_LAUNCH(k_selftest_scan, 1, 0, (aum_stream_t)stream, in, out, rev);
-#endif
-    return launch_status();
 }
-
-// wave_sum32 on 32 x 64 values (in[k][lane]); out[lane] = total of value wave_sum32_value_of_lane(lane); out[64 + lane] = wave_sum16 of
-// the first 16 values.  out: 2 x 64 floats
-AUM_API int aum_selftest_wave_sum32(const float* in, float* out, void* stream) {
-    if (!in || !out) return AUM_E_NULL;
-#ifdef AUM_EMU
-    (void)stream;
+static void selftest_sum32_host(const float* in, float* out) {
     vf v[32];
     for (int k = 0; k < 32; ++k)
         for (int l = 0; l < 64; ++l) v[k].v[l] = in[k * 64 + l];
@@ -1038,10 +824,36 @@ AUM_API int aum_selftest_wave_sum32(const float* in, float* out, void* stream) {
     const vf r16 = wave_sum16(w);
     const vf r = wave_sum32(v);
     for (int l = 0; l < 64; ++l) { out[l] = r.v[l]; out[64 + l] = r16.v[l]; }
-#else
-    AUM_LAUNCH(k_selftest_sum32, 1, 0, (aum_stream_t)stream, in, out);
+}
+template <class T> static void sum_rows_host(const T* p, float* dst, int64_t batch, int64_t outer, int64_t inner) {
+    for (int64_t b = 0; b < batch; ++b)
+        for (int64_t i = 0; i < inner; ++i) {
+            float acc = 0.f;
+            for (int64_t o = 0; o < outer; ++o) acc += elem_to_f32(p[(b * outer + o) * inner + i]);
+            dst[b * inner + i] = acc;
+        }
+}
+static void sum_rows_multi_host(const AumSumJob* jobs, int njobs) {
+    for (int q = 0; q < njobs; ++q) {
+        const AumSumJob& j = jobs[q];
+        for (int64_t i = 0; i < j.inner; ++i) {
+            float acc = 0.f;
+            for (int64_t o = 0; o < j.outer; ++o) acc += j.src[o * j.inner + i];
+            j.dst[j.tr_cols > 0 ? (i % j.tr_cols) * (j.inner / j.tr_cols) + i / j.tr_cols : i] = acc;
+        }
+    }
+}
 #endif
-    return launch_status();
+AUM_API int aum_selftest_wave_scan(const float* in, float* out, int rev, void* stream) {
+    if (!in || !out) return AUM_E_NULL;
+    return AUM_LAUNCH(1, 64, (aum_stream_t)stream, (NoLds{}), k_selftest_scan, (AUM_HOST_LOOP(selftest_scan_host(in, out, rev))), in, out, rev);
+}
+
+// wave_sum32 on 32 x 64 values (in[k][lane]); out[lane] = total of value wave_sum32_value_of_lane(lane); out[64 + lane] = wave_sum16 of
+// the first 16 values.  out: 2 x 64 floats
+AUM_API int aum_selftest_wave_sum32(const float* in, float* out, void* stream) {
+    if (!in || !out) return AUM_E_NULL;
+    return AUM_LAUNCH(1, 64, (aum_stream_t)stream, (NoLds{}), k_selftest_sum32, (AUM_HOST_LOOP(selftest_sum32_host(in, out))), in, out);
 }
 
 // row groups per workgroup: enough workgroups to cover the chip when `inner` is small (norm partials: 2048 x 768), one row group
@@ -1051,40 +863,19 @@ static int sum_rows_rg(int64_t work, int64_t outer) {
 }
 
 template <class T> static int sum_rows_t(const void* src, float* dst, int64_t batch, int64_t outer, int64_t inner, aum_stream_t s) {
-#ifdef AUM_EMU
-    (void)s;
-    const T* p = static_cast<const T*>(src);
-    for (int64_t b = 0; b < batch; ++b)
-        for (int64_t i = 0; i < inner; ++i) {
-            float acc = 0.f;
-            for (int64_t o = 0; o < outer; ++o) acc += elem_to_f32(p[(b * outer + o) * inner + i]);
-            dst[b * inner + i] = acc;
-        }
-#else
     const int64_t cols = inner / 8;
     const T* p = static_cast<const T*>(src);
-#define AUM_SR(RG) hipLaunchKernelGGL((k_sum_rows<T, RG>), dim3((unsigned)((cols + 256 / RG - 1) / (256 / RG)), (unsigned)batch), dim3(256), 0, s, p, dst, outer, inner)
-    switch (sum_rows_rg(cols * batch, outer)) {       // column groups over all batch entries
-        case 1: AUM_SR(1); break;
-        case 4: AUM_SR(4); break;
-        case 16: AUM_SR(16); break;
-        default: AUM_SR(64); break;
-    }
-#undef AUM_SR
-#endif
-    return launch_status();
+    return with_int<1, 4, 16, 64>(sum_rows_rg(cols * batch, outer), [&](auto rg) {       // column groups over all batch entries
+        return AUM_LAUNCH((Grid2{(unsigned)((cols + 256 / rg - 1) / (256 / rg)), (unsigned)batch}), 256, s, (NoLds{}), (k_sum_rows<T, rg>),
+                          (AUM_HOST_LOOP(sum_rows_host(p, dst, batch, outer, inner))), p, dst, outer, inner);
+    });
 }
 AUM_API int aum_sum_rows(const void* src, float* dst, int64_t batch, int64_t outer, int64_t inner, int32_t src_dtype, void* stream) {
     if (!src || !dst) return AUM_E_NULL;
     if (batch <= 0 || batch > 65535 || outer <= 0 || inner <= 0 || (inner & 7)) return AUM_E_SHAPE;
     if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 3)) return AUM_E_SHAPE;          // dst: any float address (a gradient's view in a bucket)
-    aum_stream_t s = (aum_stream_t)stream;
-    switch (src_dtype) {
-        case AUM_F32: return sum_rows_t<float>(src, dst, batch, outer, inner, s);
-        case AUM_BF16: return sum_rows_t<bf16_t>(src, dst, batch, outer, inner, s);
-        case AUM_F16: return sum_rows_t<f16_t>(src, dst, batch, outer, inner, s);
-        default: return AUM_E_DTYPE;
-    }
+    if (src_dtype < 0 || src_dtype > 2) return AUM_E_DTYPE;
+    return AUM_BY_DTYPE_T(src_dtype, sum_rows_t, src, dst, batch, outer, inner, (aum_stream_t)stream);
 }
 
 AUM_API int aum_sum_rows_multi(const AumSumJob* jobs, int32_t njobs, void* stream) {
@@ -1096,16 +887,8 @@ AUM_API int aum_sum_rows_multi(const AumSumJob* jobs, int32_t njobs, void* strea
         if (j.outer <= 0 || j.inner <= 0 || (j.inner & 7) || j.inner > (int64_t)1 << 30 || j.tr_cols < 0 || (j.tr_cols > 0 && j.inner % j.tr_cols)) return AUM_E_SHAPE;
         if ((((uintptr_t)j.src) & 15) || (((uintptr_t)j.dst) & 3)) return AUM_E_SHAPE;
     }
-#ifdef AUM_EMU
-    (void)stream;
-    for (int q = 0; q < njobs; ++q) {
-        const AumSumJob& j = jobs[q];
-        for (int64_t i = 0; i < j.inner; ++i) {
-            float acc = 0.f;
-            for (int64_t o = 0; o < j.outer; ++o) acc += j.src[o * j.inner + i];
-            j.dst[j.tr_cols > 0 ? (i % j.tr_cols) * (j.inner / j.tr_cols) + i / j.tr_cols : i] = acc;
-        }
-    }
+#ifdef AUM_EMU      // the kernel takes its jobs as SumJobs, a device-only struct of conv_norm_kernels.h: the two builds marshal differently
+    return AUM_LAUNCH(1, 256, (aum_stream_t)stream, (NoLds{}), k_sum_rows_multi, (AUM_HOST_LOOP(sum_rows_multi_host(jobs, njobs))), jobs);
 #else
     static_assert(SUM_MAX_JOBS == AUM_SUM_MAX_JOBS, "header and kernel disagree");
     SumJobs js{};
@@ -1120,23 +903,16 @@ AUM_API int aum_sum_rows_multi(const AumSumJob* jobs, int32_t njobs, void* strea
         js.wg_end[q] = (int32_t)wgs;
     }
     if (wgs > 0x7fffffff) return AUM_E_SHAPE;
-    hipLaunchKernelGGL(k_sum_rows_multi, dim3((unsigned)wgs), dim3(256), 0, (aum_stream_t)stream, js);
+    return AUM_LAUNCH(wgs, 256, (aum_stream_t)stream, (NoLds{}), k_sum_rows_multi, (0), js);
 #endif
-    return launch_status();
 }
 
 AUM_API int aum_hbm_copy(const void* src, void* dst, int64_t bytes, void* stream) {
     if (!src || !dst) return AUM_E_NULL;
     if (bytes <= 0 || (bytes & 15)) return AUM_E_SHAPE;
-#ifdef AUM_EMU
-    (void)stream;
-    memcpy(dst, src, (size_t)bytes);
-#else
     if (bytes / 16 / 256 >= ((int64_t)1 << 31) - 1) return AUM_E_SHAPE;
-    hipLaunchKernelGGL(k_hbm_copy, dim3((unsigned)((bytes / 16 + 255) / 256)), dim3(256), 0, (aum_stream_t)stream, (const float4*)src,
-                       (float4*)dst, bytes / 16);
-#endif
-    return launch_status();
+    return AUM_LAUNCH((bytes / 16 + 255) / 256, 256, (aum_stream_t)stream, (NoLds{}), k_hbm_copy, (AUM_HOST_LOOP(memcpy(dst, src, (size_t)bytes))),
+                      (const float4*)src, (float4*)dst, bytes / 16);
 }
 
 #endif

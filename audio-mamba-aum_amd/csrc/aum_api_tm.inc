@@ -1,4 +1,6 @@
-// aum_api_tm.inc -- C-ABI entry points, kernel entries and launchers of the time-serial token-major scan (scan_tm_kernels.h).
+// aum_api_tm.inc -- C-ABI entry points, kernel entries and launchers of the time-serial token-major scan (scan_tm_kernels.h), the
+// token-major conv and the streaming kernels.  Launches, LDS and flag / dtype dispatch as in aum_api.inc: AUM_LAUNCH, Lds<>, with_bool /
+// with_int / by_dtype of launch.h.
 // Included at the end of aum_api.inc.  AUM_API_PART 5 / 6 (with AUM_DTYPE_ONLY) are the forward / backward kernel objects of the
 // device library; part 3 holds the extern "C" surface; part 0 (the lane-array test build) holds everything.
 #include "scan_tm_kernels.h"
@@ -57,11 +59,14 @@ static ScanTWs scant_ws_layout(int batch, int dim, int len, int dstate, bool bid
     return w;
 }
 
+// the LDS of every forward / backward kernel of scan_tm_kernels.h
+template <class T> using ScanTFwdLds = Lds<float, SCANT_NW * scant_lds_wave_floats<T>()>;
+template <class T> using ScanTBwdLds = Lds<float, SCANT_NW * scant_bwd_lds_wave_floats<T>()>;
 #if AUM_API_PART == 5 || AUM_API_PART == 0
 #ifndef AUM_EMU
 template <class T, bool SP, bool HAS_Z, bool HAS_PRE, bool BIDIR>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd(AumScanTmFwdArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
 #ifdef AUM_SCANT_TRACE      // tools/tm_trace.py builds only: where and when every wave ran (a.ckpt is the trace buffer: 12 x uint64 per wave)
     unsigned long long* tr = reinterpret_cast<unsigned long long*>(a.ckpt) + ((size_t)blockIdx.x * SCANT_NW + threadIdx.x / 64) * 12;
     const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
@@ -83,151 +88,96 @@ __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd
 template <class T, bool SP, bool HAS_Z, bool HAS_PRE, bool BIDIR> static int launch_scant_fwd(const AumScanTmFwdArgs& a, aum_stream_t s) {
     constexpr int UPW = scant_units_per_wg<BIDIR>();
     const int grid = (a.batch * (a.dim / WAVE) + UPW - 1) / UPW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_fwd<T, SP, HAS_Z, HAS_PRE, BIDIR>(a, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_fwd<T, SP, HAS_Z, HAS_PRE, BIDIR>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_fwd<T, SP, HAS_Z, HAS_PRE, BIDIR>), (scant_fwd<T, SP, HAS_Z, HAS_PRE, BIDIR>(a, wg, lds)), a);
 }
 template <class T> static int scan_tm_fwd_t(const AumScanTmFwdArgs& a, aum_stream_t s) {
-    const int key = ((a.flags & AUM_SCAN_SOFTPLUS) ? 8 : 0) | (a.z ? 4 : 0) | (a.out_pre ? 2 : 0) | (a.A_b ? 1 : 0);
-    switch (key) {
-#define AUM_TMF(K) case K: return launch_scant_fwd<T, ((K) & 8) != 0, ((K) & 4) != 0, ((K) & 2) != 0, ((K) & 1) != 0>(a, s);
-        AUM_TMF(0) AUM_TMF(1) AUM_TMF(2) AUM_TMF(3) AUM_TMF(4) AUM_TMF(5) AUM_TMF(6) AUM_TMF(7)
-        AUM_TMF(8) AUM_TMF(9) AUM_TMF(10) AUM_TMF(11) AUM_TMF(12) AUM_TMF(13) AUM_TMF(14) AUM_TMF(15)
-#undef AUM_TMF
-    }
-    return AUM_E_UNSUPPORTED;
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) { return with_bool(a.z != nullptr, [&](auto hz) {
+        return with_bool(a.out_pre != nullptr, [&](auto pre) { return with_bool(a.A_b != nullptr, [&](auto bidir) {
+            return launch_scant_fwd<T, sp, hz, pre, bidir>(a, s); }); }); }); });
 }
 #ifndef AUM_EMU
 template <class T, int PHASE, bool SP, bool HAS_Z, bool HAS_PRE>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_seg_fwd(AumScanTmFwdArgs a, ScanTSeg sg) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
     scant_seg_fwd<T, PHASE, SP, HAS_Z, HAS_PRE>(a, sg, (int)blockIdx.x, lds);
 }
 #endif
 template <class T, int PHASE, bool SP, bool HAS_Z, bool HAS_PRE> static int launch_scant_seg_fwd(const AumScanTmFwdArgs& a, const ScanTSeg& sg, aum_stream_t s) {
     const int grid = (a.batch * (a.dim / WAVE) * sg.nseg * sg.ndl + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_seg_fwd<T, PHASE, SP, HAS_Z, HAS_PRE>(a, sg, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_seg_fwd<T, PHASE, SP, HAS_Z, HAS_PRE>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, sg);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_seg_fwd<T, PHASE, SP, HAS_Z, HAS_PRE>), (scant_seg_fwd<T, PHASE, SP, HAS_Z, HAS_PRE>(a, sg, wg, lds)), a, sg);
 }
 template <class T> static int scan_tm_seg_fwd_t(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) {
-    const bool sp = (a.flags & AUM_SCAN_SOFTPLUS) != 0;
-    if (phase == 3) return sp ? launch_scant_seg_fwd<T, 3, true, false, false>(a, sg, s) : launch_scant_seg_fwd<T, 3, false, false, false>(a, sg, s);
-    if (phase == 4) {
-        if (a.z) return sp ? launch_scant_seg_fwd<T, 4, true, true, false>(a, sg, s) : launch_scant_seg_fwd<T, 4, false, true, false>(a, sg, s);
-        return sp ? launch_scant_seg_fwd<T, 4, true, false, false>(a, sg, s) : launch_scant_seg_fwd<T, 4, false, false, false>(a, sg, s);
-    }
-    const int key = (sp ? 4 : 0) | (a.z ? 2 : 0) | (a.out_pre ? 1 : 0);
-    switch (phase * 8 + key) {
-#define AUM_TMS(P, K) case (P) * 8 + (K): return launch_scant_seg_fwd<T, P, ((K) & 4) != 0, ((K) & 2) != 0, ((K) & 1) != 0>(a, sg, s);
-#define AUM_TMS8(P) AUM_TMS(P, 0) AUM_TMS(P, 1) AUM_TMS(P, 2) AUM_TMS(P, 3) AUM_TMS(P, 4) AUM_TMS(P, 5) AUM_TMS(P, 6) AUM_TMS(P, 7)
-        AUM_TMS8(0) AUM_TMS8(1) AUM_TMS8(2)
-#undef AUM_TMS8
-#undef AUM_TMS
-    }
-    return AUM_E_UNSUPPORTED;
+    // phase 3 (carries): no z, no pre-gate copy; phase 4 (adjoint carries): no pre-gate copy; phases 0 - 2: every form
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        if (phase == 3) return launch_scant_seg_fwd<T, 3, sp, false, false>(a, sg, s);
+        return with_bool(a.z != nullptr, [&](auto hz) {
+            if (phase == 4) return launch_scant_seg_fwd<T, 4, sp, hz, false>(a, sg, s);
+            return with_bool(a.out_pre != nullptr, [&](auto pre) {
+                return with_int<0, 1, 2>(phase, [&](auto ph) { return launch_scant_seg_fwd<T, ph, sp, hz, pre>(a, sg, s); }); });
+        });
+    });
 }
 #ifndef AUM_EMU
 template <class T, bool SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd_state(AumScanTmFwdArgs a, ScanTState st) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
     scant_fwd_state<T, SP, HAS_Z>(a, st, (int)blockIdx.x, lds);
 }
 template <class T, int PHASE, bool SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_seg_fwd_state(AumScanTmFwdArgs a, ScanTSeg sg, ScanTState st) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
     scant_seg_fwd_state<T, PHASE, SP, HAS_Z>(a, sg, st, (int)blockIdx.x, lds);
 }
 #endif
 template <class T, bool SP, bool HAS_Z> static int launch_scant_fwd_state(const AumScanTmFwdArgs& a, const ScanTState& st, aum_stream_t s) {
     const int grid = (a.batch * (a.dim / WAVE) + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_fwd_state<T, SP, HAS_Z>(a, st, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_fwd_state<T, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, st);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_fwd_state<T, SP, HAS_Z>), (scant_fwd_state<T, SP, HAS_Z>(a, st, wg, lds)), a, st);
 }
 template <class T, int PHASE, bool SP, bool HAS_Z>
 static int launch_scant_seg_fwd_state(const AumScanTmFwdArgs& a, const ScanTSeg& sg, const ScanTState& st, aum_stream_t s) {
     const int grid = (a.batch * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_seg_fwd_state<T, PHASE, SP, HAS_Z>(a, sg, st, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_seg_fwd_state<T, PHASE, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, sg, st);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_seg_fwd_state<T, PHASE, SP, HAS_Z>), (scant_seg_fwd_state<T, PHASE, SP, HAS_Z>(a, sg, st, wg, lds)), a, sg, st);
 }
 template <class T> static int scan_tm_fwd_state_t(const AumScanTmFwdArgs& a, const ScanTState& st, const ScanTSeg* sg, int phase, aum_stream_t s) {
-    const bool sp = (a.flags & AUM_SCAN_SOFTPLUS) != 0, hz = a.z != nullptr;
-    if (!sg) {
-        if (sp) return hz ? launch_scant_fwd_state<T, true, true>(a, st, s) : launch_scant_fwd_state<T, true, false>(a, st, s);
-        return hz ? launch_scant_fwd_state<T, false, true>(a, st, s) : launch_scant_fwd_state<T, false, false>(a, st, s);
-    }
-    if (phase == 3) return sp ? launch_scant_seg_fwd_state<T, 3, true, false>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 3, false, false>(a, *sg, st, s);
-    if (phase != 0) return AUM_E_UNSUPPORTED;
-    if (sp) return hz ? launch_scant_seg_fwd_state<T, 0, true, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, true, false>(a, *sg, st, s);
-    return hz ? launch_scant_seg_fwd_state<T, 0, false, true>(a, *sg, st, s) : launch_scant_seg_fwd_state<T, 0, false, false>(a, *sg, st, s);
+    // segmented: phase 3 (carries, no z) and phase 0 only
+    if (sg && phase != 3 && phase != 0) return AUM_E_UNSUPPORTED;
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        if (sg && phase == 3) return launch_scant_seg_fwd_state<T, 3, sp, false>(a, *sg, st, s);
+        return with_bool(a.z != nullptr, [&](auto hz) {
+            return sg ? launch_scant_seg_fwd_state<T, 0, sp, hz>(a, *sg, st, s) : launch_scant_fwd_state<T, sp, hz>(a, st, s);
+        });
+    });
 }
 #ifndef AUM_EMU
 template <class T, bool SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_fwd_state_var(AumScanTmFwdArgs a, ScanTVar v) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
     scant_fwd_state_var<T, SP, HAS_Z>(a, v, (int)blockIdx.x, lds);
 }
 template <class T, int PHASE, bool SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_FWD_MINW) void k_scant_seg_fwd_state_var(AumScanTmFwdArgs a, ScanTSeg sg, ScanTVar v) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTFwdLds<T>::n];
     scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>(a, sg, v, (int)blockIdx.x, lds);
 }
 #endif
 template <class T, bool SP, bool HAS_Z> static int launch_scant_fwd_state_var(const AumScanTmFwdArgs& a, const ScanTVar& v, aum_stream_t s) {
     const int grid = (v.nseq * (a.dim / WAVE) + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_fwd_state_var<T, SP, HAS_Z>(a, v, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_fwd_state_var<T, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, v);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_fwd_state_var<T, SP, HAS_Z>), (scant_fwd_state_var<T, SP, HAS_Z>(a, v, wg, lds)), a, v);
 }
 template <class T, int PHASE, bool SP, bool HAS_Z>
 static int launch_scant_seg_fwd_state_var(const AumScanTmFwdArgs& a, const ScanTSeg& sg, const ScanTVar& v, aum_stream_t s) {
     const int grid = (v.nseq * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>(a, sg, v, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, sg, v);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTFwdLds<T>{}), (k_scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>), (scant_seg_fwd_state_var<T, PHASE, SP, HAS_Z>(a, sg, v, wg, lds)), a, sg, v);
 }
 template <class T> static int scan_tm_fwd_state_var_t(const AumScanTmFwdArgs& a, const ScanTVar& v, const ScanTSeg* sg, int phase, aum_stream_t s) {
-    const bool sp = (a.flags & AUM_SCAN_SOFTPLUS) != 0, hz = a.z != nullptr;
-    if (!sg) {
-        if (sp) return hz ? launch_scant_fwd_state_var<T, true, true>(a, v, s) : launch_scant_fwd_state_var<T, true, false>(a, v, s);
-        return hz ? launch_scant_fwd_state_var<T, false, true>(a, v, s) : launch_scant_fwd_state_var<T, false, false>(a, v, s);
-    }
-    if (phase == 3) return sp ? launch_scant_seg_fwd_state_var<T, 3, true, false>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 3, false, false>(a, *sg, v, s);
-    if (phase != 0) return AUM_E_UNSUPPORTED;
-    if (sp) return hz ? launch_scant_seg_fwd_state_var<T, 0, true, true>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 0, true, false>(a, *sg, v, s);
-    return hz ? launch_scant_seg_fwd_state_var<T, 0, false, true>(a, *sg, v, s) : launch_scant_seg_fwd_state_var<T, 0, false, false>(a, *sg, v, s);
+    // segmented: phase 3 (carries, no z) and phase 0 only
+    if (sg && phase != 3 && phase != 0) return AUM_E_UNSUPPORTED;
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        if (sg && phase == 3) return launch_scant_seg_fwd_state_var<T, 3, sp, false>(a, *sg, v, s);
+        return with_bool(a.z != nullptr, [&](auto hz) {
+            return sg ? launch_scant_seg_fwd_state_var<T, 0, sp, hz>(a, *sg, v, s) : launch_scant_fwd_state_var<T, sp, hz>(a, v, s);
+        });
+    });
 }
 #if AUM_HAS_DTYPE(0)
 int scan_tm_fwd_f32(const AumScanTmFwdArgs& a, aum_stream_t s) { return scan_tm_fwd_t<float>(a, s); }
@@ -256,7 +206,7 @@ int scan_tm_fwd_state_var_f16(const AumScanTmFwdArgs& a, const ScanTVar& v, cons
 #ifndef AUM_EMU
 template <class T, int SP, bool HAS_Z, bool BIDIR>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_bwd(AumScanTmBwdArgs a, ScanTBwdOut wo) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_bwd_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTBwdLds<T>::n];
 #ifdef AUM_SCANT_TRACE      // tools/tm_trace.py builds only: 16 x uint64 per wave behind the partials of the workspace
     unsigned long long* tr = wo.trace + ((size_t)blockIdx.x * SCANT_NW + threadIdx.x / 64) * 16;
     const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
@@ -276,68 +226,36 @@ __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_bwd
 #endif
 template <class T, int SP, bool HAS_Z, bool BIDIR> static int launch_scant_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) {
     const int grid = scant_bwd_wgs<BIDIR>(a.batch * (a.dim / WAVE));
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_bwd_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_bwd<T, SP, HAS_Z, BIDIR>(a, wo, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_bwd<T, SP, HAS_Z, BIDIR>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, wo);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTBwdLds<T>{}), (k_scant_bwd<T, SP, HAS_Z, BIDIR>), (scant_bwd<T, SP, HAS_Z, BIDIR>(a, wo, wg, lds)), a, wo);
 }
 template <class T> static int scan_tm_bwd_t(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) {
     if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {       // built for the product path only: 16-bit activations with z (scan_tm_bwd_any checks)
         if constexpr (sizeof(T) == 2)
-            return a.A_b ? launch_scant_bwd<T, SCANT_SP_ACT, true, true>(a, wo, s) : launch_scant_bwd<T, SCANT_SP_ACT, true, false>(a, wo, s);
+            return with_bool(a.A_b != nullptr, [&](auto bidir) { return launch_scant_bwd<T, SCANT_SP_ACT, true, bidir>(a, wo, s); });
         return AUM_E_UNSUPPORTED;
     }
-    const int key = ((a.flags & AUM_SCAN_SOFTPLUS) ? 4 : 0) | (a.z ? 2 : 0) | (a.A_b ? 1 : 0);
-    switch (key) {
-#define AUM_TMB(K) case K: return launch_scant_bwd<T, ((K) & 4) ? SCANT_SP_IN : SCANT_SP_NONE, ((K) & 2) != 0, ((K) & 1) != 0>(a, wo, s);
-        AUM_TMB(0) AUM_TMB(1) AUM_TMB(2) AUM_TMB(3) AUM_TMB(4) AUM_TMB(5) AUM_TMB(6) AUM_TMB(7)
-#undef AUM_TMB
-    }
-    return AUM_E_UNSUPPORTED;
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) { return with_bool(a.z != nullptr, [&](auto hz) {
+        return with_bool(a.A_b != nullptr, [&](auto bidir) { return launch_scant_bwd<T, sp ? SCANT_SP_IN : SCANT_SP_NONE, hz, bidir>(a, wo, s); }); }); });
 }
 #ifndef AUM_EMU
 template <class T, int PHASE, int SP, bool HAS_Z>
 __global__ __launch_bounds__(SCANT_NW * 64, AUM_SCANT_BWD_MINW) void k_scant_seg_bwd(AumScanTmBwdArgs a, ScanTBwdOut wo, ScanTSeg sg) {
-    __shared__ __attribute__((aligned(16))) float lds[SCANT_NW * scant_bwd_lds_wave_floats<T>()];
+    __shared__ __attribute__((aligned(16))) float lds[ScanTBwdLds<T>::n];
     scant_seg_bwd<T, PHASE, SP, HAS_Z>(a, wo, sg, (int)blockIdx.x, lds);
 }
 #endif
 template <class T, int PHASE, int SP, bool HAS_Z>
 static int launch_scant_seg_bwd(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, aum_stream_t s) {
     const int grid = (a.batch * (a.dim / WAVE) * sg.nseg + SCANT_NW - 1) / SCANT_NW;
-#ifdef AUM_EMU
-    (void)s;
-    std::vector<float> lds(SCANT_NW * scant_bwd_lds_wave_floats<T>());
-    for (int wg = 0; wg < grid; ++wg) scant_seg_bwd<T, PHASE, SP, HAS_Z>(a, wo, sg, wg, lds.data());
-#else
-    hipLaunchKernelGGL((k_scant_seg_bwd<T, PHASE, SP, HAS_Z>), dim3((unsigned)grid), dim3(SCANT_NW * 64), 0, s, a, wo, sg);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, SCANT_NW * 64, s, (ScanTBwdLds<T>{}), (k_scant_seg_bwd<T, PHASE, SP, HAS_Z>), (scant_seg_bwd<T, PHASE, SP, HAS_Z>(a, wo, sg, wg, lds)), a, wo, sg);
 }
 template <class T> static int scan_tm_seg_bwd_t(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, const ScanTSeg& sg, int phase, aum_stream_t s) {
     if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {
-        if constexpr (sizeof(T) == 2) {
-            switch (phase) {
-                case 0: return launch_scant_seg_bwd<T, 0, SCANT_SP_ACT, true>(a, wo, sg, s);
-                case 1: return launch_scant_seg_bwd<T, 1, SCANT_SP_ACT, true>(a, wo, sg, s);
-                case 2: return launch_scant_seg_bwd<T, 2, SCANT_SP_ACT, true>(a, wo, sg, s);
-            }
-        }
+        if constexpr (sizeof(T) == 2) return with_int<0, 1, 2>(phase, [&](auto ph) { return launch_scant_seg_bwd<T, ph, SCANT_SP_ACT, true>(a, wo, sg, s); });
         return AUM_E_UNSUPPORTED;
     }
-    const int key = ((a.flags & AUM_SCAN_SOFTPLUS) ? 2 : 0) | (a.z ? 1 : 0);
-    switch (phase * 4 + key) {
-#define AUM_TMS(P, K) case (P) * 4 + (K): return launch_scant_seg_bwd<T, P, ((K) & 2) ? SCANT_SP_IN : SCANT_SP_NONE, ((K) & 1) != 0>(a, wo, sg, s);
-#define AUM_TMS4(P) AUM_TMS(P, 0) AUM_TMS(P, 1) AUM_TMS(P, 2) AUM_TMS(P, 3)
-        AUM_TMS4(0) AUM_TMS4(1) AUM_TMS4(2)
-#undef AUM_TMS4
-#undef AUM_TMS
-    }
-    return AUM_E_UNSUPPORTED;
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) { return with_bool(a.z != nullptr, [&](auto hz) {
+        return with_int<0, 1, 2>(phase, [&](auto ph) { return launch_scant_seg_bwd<T, ph, sp ? SCANT_SP_IN : SCANT_SP_NONE, hz>(a, wo, sg, s); }); }); });
 }
 #if AUM_HAS_DTYPE(0)
 int scan_tm_bwd_f32(const AumScanTmBwdArgs& a, const ScanTBwdOut& wo, aum_stream_t s) { return scan_tm_bwd_t<float>(a, wo, s); }
@@ -364,8 +282,8 @@ AUM_API int32_t aum_scan_tm_ckpt_rows(int32_t dtype) {
 // AUM_SCAN_DELTA_ACTIVATED (16-bit activations with z): delta already holds softplus(raw + delta_bias).  The forward reads it as it is -- the
 // kernels without bias and softplus; the backward keeps the softplus derivative (SCANT_SP_ACT) and still writes ddelta_bias.
 static bool scan_tm_act_ok(uint32_t flags, int32_t dtype, const void* z) { return !(flags & AUM_SCAN_DELTA_ACTIVATED) || (dtype != AUM_F32 && z); }
-static AumScanTmFwdArgs scan_tm_fwd_resolve(const AumScanTmFwdArgs& a) {
-    AumScanTmFwdArgs r = a;
+template <class A> static A scan_tm_fwd_resolve(const A& a) {       // the kernels' view of a forward's arguments (fixed batch, chunk, packed chunk)
+    A r = a;
     if (a.flags & AUM_SCAN_DELTA_ACTIVATED) {
         r.delta_bias = nullptr;
         r.flags &= ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED);
@@ -403,18 +321,10 @@ AUM_API int aum_scan_tm_fwd(const AumScanTmFwdArgs* a, void* stream) {
     if (rc != AUM_OK) return rc;
     aum_stream_t s = (aum_stream_t)stream;
     const AumScanTmFwdArgs k = scan_tm_fwd_resolve(*a);
-    switch (k.dtype) {
-        case AUM_F32: return scan_tm_fwd_f32(k, s);
-        case AUM_BF16: return scan_tm_fwd_bf16(k, s);
-        default: return scan_tm_fwd_f16(k, s);
-    }
+    return AUM_BY_DTYPE_X(k.dtype, scan_tm_fwd, k, s);
 }
 static int scan_tm_seg_fwd_any(const AumScanTmFwdArgs& a, const ScanTSeg& sg, int phase, aum_stream_t s) {
-    switch (a.dtype) {
-        case AUM_F32: return scan_tm_seg_fwd_f32(a, sg, phase, s);
-        case AUM_BF16: return scan_tm_seg_fwd_bf16(a, sg, phase, s);
-        default: return scan_tm_seg_fwd_f16(a, sg, phase, s);
-    }
+    return AUM_BY_DTYPE_X(a.dtype, scan_tm_seg_fwd, a, sg, phase, s);
 }
 AUM_API int64_t aum_scan_tm_seg_carry_bytes(int32_t batch, int32_t dim, int32_t len, int32_t dstate, int32_t bidirectional, int32_t segments) {
     if (batch <= 0 || dim <= 0 || len <= 0 || segments < 2 || !scant_supported(dim, dstate)) return 0;
@@ -460,11 +370,7 @@ AUM_API int aum_scan_tm_fwd_state(const AumScanTmFwdStateArgs* sa, void* stream)
     const AumScanTmFwdArgs k = scan_tm_fwd_resolve(*a);
     const ScanTState st = {sa->state_in, sa->state_out};
     auto run = [&](const ScanTSeg* sg, int phase) {
-        switch (k.dtype) {
-            case AUM_F32: return scan_tm_fwd_state_f32(k, st, sg, phase, s);
-            case AUM_BF16: return scan_tm_fwd_state_bf16(k, st, sg, phase, s);
-            default: return scan_tm_fwd_state_f16(k, st, sg, phase, s);
-        }
+        return AUM_BY_DTYPE_X(k.dtype, scan_tm_fwd_state, k, st, sg, phase, s);
     };
     if (sa->segments == 1) return run(nullptr, 0);
     if (!sa->carry) return AUM_E_NULL;
@@ -543,9 +449,8 @@ __global__ __launch_bounds__(256) void k_scant_bwd_reduce(ScanTReduceArgs a) {
     }
 }
 #endif
-static int scant_reduce_launch(const ScanTReduceArgs& a, aum_stream_t s) {
 #ifdef AUM_EMU
-    (void)s;
+static void scant_reduce_host(const ScanTReduceArgs& a) {      // what k_scant_bwd_reduce computes, as plain loops
     const int64_t ntok = (int64_t)a.batch * a.len;
     const int K = 2 * a.dstate;
     for (int64_t tok = 0; tok < ntok; ++tok)
@@ -572,10 +477,10 @@ static int scant_reduce_launch(const ScanTReduceArgs& a, aum_stream_t s) {
         if (a.dD) a.dD[e] = accD;
         if (a.dbias) a.dbias[e] = accb;
     }
-#else
-    hipLaunchKernelGGL(k_scant_bwd_reduce, dim3(2048), dim3(256), 0, s, a);
+}
 #endif
-    return launch_status();
+static int scant_reduce_launch(const ScanTReduceArgs& a, aum_stream_t s) {
+    return AUM_LAUNCH(2048, 256, s, (NoLds{}), k_scant_bwd_reduce, (AUM_HOST_LOOP(scant_reduce_host(a))), a);
 }
 
 static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
@@ -628,11 +533,7 @@ static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
     if (act) k.delta_bias = nullptr;
     int rc = AUM_OK;
     if (nseg == 1) {
-        switch (k.dtype) {
-            case AUM_F32: rc = scan_tm_bwd_f32(k, wo, s); break;
-            case AUM_BF16: rc = scan_tm_bwd_bf16(k, wo, s); break;
-            default: rc = scan_tm_bwd_f16(k, wo, s); break;
-        }
+        rc = AUM_BY_DTYPE_X(k.dtype, scan_tm_bwd, k, wo, s);
     } else {
         ScanTSeg sg;
         sg.carry = ws + L.carry;
@@ -657,11 +558,7 @@ static int scan_tm_bwd_any(const AumScanTmBwdArgs* a, int nseg, void* stream) {
         for (int d = 0; d < (bidir ? 2 : 1) && rc == AUM_OK; ++d) {
             sg.dir0 = d;
             const int phase = bidir ? 1 + d : 0;
-            switch (k.dtype) {
-                case AUM_F32: rc = scan_tm_seg_bwd_f32(k, wo, sg, phase, s); break;
-                case AUM_BF16: rc = scan_tm_seg_bwd_bf16(k, wo, sg, phase, s); break;
-                default: rc = scan_tm_seg_bwd_f16(k, wo, sg, phase, s); break;
-            }
+            rc = AUM_BY_DTYPE_X(k.dtype, scan_tm_seg_bwd, k, wo, sg, phase, s);
         }
     }
     if (rc != AUM_OK) return rc;
@@ -690,18 +587,11 @@ template <class T, bool SILU> AUM_GLOBAL void k_convt_bwd(AumConvTmArgs a) { con
 #endif
 template <class T, bool SILU> static int convt_launch(const AumConvTmArgs& a, bool bwd, aum_stream_t s) {
     const int grid = bwd ? a.batch * convt_chunks<true>(a.len) * convt_cblocks<T, true>(a.dim) : a.batch * convt_chunks<false>(a.len) * convt_cblocks<T, false>(a.dim);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) {
-        if (bwd) convt_bwd_wave<T, SILU>(a, wg); else convt_fwd_wave<T, SILU>(a, wg);
-    }
-#else
-    if (bwd) AUM_LAUNCH((k_convt_bwd<T, SILU>), grid, 0, s, a); else AUM_LAUNCH((k_convt_fwd<T, SILU>), grid, 0, s, a);
-#endif
-    return launch_status();
+    if (bwd) return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_bwd<T, SILU>), (convt_bwd_wave<T, SILU>(a, wg)), a);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_fwd<T, SILU>), (convt_fwd_wave<T, SILU>(a, wg)), a);
 }
 template <class T> static int convt_dispatch_t(const AumConvTmArgs& a, bool bwd, aum_stream_t s) {
-    return (a.flags & AUM_CONV_SILU) ? convt_launch<T, true>(a, bwd, s) : convt_launch<T, false>(a, bwd, s);
+    return with_bool((a.flags & AUM_CONV_SILU) != 0, [&](auto silu) { return convt_launch<T, silu>(a, bwd, s); });
 }
 static int convt_dispatch(const AumConvTmArgs* a, bool bwd, void* stream) {
     if (!a || !a->x || !a->weight) return AUM_E_NULL;
@@ -720,16 +610,68 @@ static int convt_dispatch(const AumConvTmArgs* a, bool bwd, void* stream) {
     const int64_t ts = a->x_ts > (bwd ? (a->dy_ts > a->dx_ts ? a->dy_ts : a->dx_ts) : a->y_ts) ? a->x_ts : (bwd ? (a->dy_ts > a->dx_ts ? a->dy_ts : a->dx_ts) : a->y_ts);
     if ((int64_t)a->len * ts * es >= lim) return AUM_E_UNSUPPORTED;
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return convt_dispatch_t<float>(*a, bwd, s);
-        case AUM_BF16: return convt_dispatch_t<bf16_t>(*a, bwd, s);
-        default: return convt_dispatch_t<f16_t>(*a, bwd, s);
-    }
+    return AUM_BY_DTYPE_T(a->dtype, convt_dispatch_t, *a, bwd, s);
 }
 AUM_API int aum_conv1d_tm_fwd(const AumConvTmArgs* a, void* stream) { return convt_dispatch(a, false, stream); }
 AUM_API int aum_conv1d_tm_bwd(const AumConvTmArgs* a, void* stream) { return convt_dispatch(a, true, stream); }
 /* 1 when this build sums the dB / dC terms of 16-bit activations on the matrix pipe (terms rounded to bf16): tests bound them accordingly */
 AUM_API int32_t aum_conv1d_tm_nparts(int32_t batch, int32_t len) { return batch > 0 && len > 0 ? convt_nparts(batch, len) : 0; }
+
+// ---- operand checks of the streaming entry points: what the three conv entries share, and what the three scan entries share ----
+// Each entry hands in what differs: `var` (packed sessions, else nullptr), counts_ok (its own row counts > 0), rows (the most rows a 32-bit
+// byte cursor spans: len or total), allowed (flag bits it takes), fits (its own limits), units (grid factor next to the channel blocks; 0: none).
+// Refusals in this order: AUM_E_NULL (operands), the packed map's code, AUM_E_SHAPE, AUM_E_DTYPE, then AUM_E_UNSUPPORTED for everything else.
+struct StreamVar { const int32_t *cu_seqlens, *state_indices; int total, nseq, nrows; };
+static int stream_var_check(const StreamVar* v) {
+    if (!v) return AUM_OK;
+    if (!v->cu_seqlens) return AUM_E_NULL;
+    if (v->total <= 0 || v->nseq <= 0 || v->nrows <= 0) return AUM_E_SHAPE;
+    if (((uintptr_t)v->cu_seqlens | (uintptr_t)v->state_indices) & 3) return AUM_E_UNSUPPORTED;
+    return AUM_OK;
+}
+// bs: x_bs | y_bs where batch strides exist, else 0
+template <class A> static int conv_stream_check(const A& a, const StreamVar* var, bool counts_ok, int64_t rows, int64_t bs, uint32_t allowed, bool fits,
+                                                int64_t units) {
+    if (!a.x || !a.conv_state || !a.weight || !a.y) return AUM_E_NULL;
+    if (const int rc = stream_var_check(var)) return rc;
+    if (a.dim <= 0 || a.width <= 0 || !counts_ok) return AUM_E_SHAPE;
+    if (a.dtype < 0 || a.dtype > 2) return AUM_E_DTYPE;
+    if (a.width > CONVT_W || !fits || (a.flags & ~allowed)) return AUM_E_UNSUPPORTED;
+    const int64_t es = a.dtype == AUM_F32 ? 4 : 2;
+    if (a.dim % (16 / es)) return AUM_E_UNSUPPORTED;
+    if (a.x_ts < 0 || a.y_ts < 0) return AUM_E_UNSUPPORTED;
+    const uintptr_t ptrs = (uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.weight | (uintptr_t)a.bias;
+    if ((ptrs & 15) || (((bs | a.x_ts | a.y_ts) * es) & 15) || ((uintptr_t)a.conv_state & 3)) return AUM_E_UNSUPPORTED;
+    if (a.x == a.y) return AUM_E_UNSUPPORTED;      // rows are fetched ahead of the steps that write them
+    const int64_t lim = (int64_t)1 << 31;         // buffer offsets are 32-bit: the rows of one batch entry / one sequence must fit
+    if (rows * (a.x_ts > a.y_ts ? a.x_ts : a.y_ts) * es >= lim || (int64_t)a.dim * a.width * 4 >= lim) return AUM_E_UNSUPPORTED;
+    if (units * convt_cblocks<float, false>(a.dim) >= lim) return AUM_E_UNSUPPORTED;
+    return AUM_OK;
+}
+// rows16: the rows move as 16-byte chunks and B / C as dwords (the state in / state out kernels); else element by element (the chunk kernels)
+template <class A> static int scan_stream_check(const A& a, const StreamVar* var, bool counts_ok, int64_t rows, uint32_t allowed, bool fits, int64_t units,
+                                                bool rows16) {
+    if (!a.u || !a.delta || !a.B || !a.C || !a.A || !a.state || !a.out) return AUM_E_NULL;
+    if (const int rc = stream_var_check(var)) return rc;
+    if (a.dim <= 0 || a.dstate <= 0 || !counts_ok) return AUM_E_SHAPE;
+    if (a.dtype < 0 || a.dtype > 2) return AUM_E_DTYPE;
+    if (!scant_supported(a.dim, a.dstate) || !fits || (a.flags & ~allowed)) return AUM_E_UNSUPPORTED;
+    if (rows16 && !scan_tm_act_ok(a.flags, a.dtype, a.z)) return AUM_E_UNSUPPORTED;
+    const int64_t es = a.dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
+    if (rows16 && a.dtype != AUM_F32 && (((a.B_ts | a.C_ts) & 1) || ((((uintptr_t)a.B) | ((uintptr_t)a.C)) & 3))) return AUM_E_UNSUPPORTED;
+    const int64_t ts[] = {a.u_ts, a.delta_ts, a.z ? a.z_ts : 0, a.out_ts, a.B_ts, a.C_ts};      // row offsets are 32-bit byte cursors
+    for (int64_t t : ts)
+        if (t < 0 || (t + a.dim) * es * rows > lim) return AUM_E_UNSUPPORTED;
+    if ((int64_t)a.dim * a.dstate * 4 > lim || units * (a.dim / WAVE) > lim) return AUM_E_UNSUPPORTED;
+    const uintptr_t rowp = (uintptr_t)a.u | (uintptr_t)a.delta | (uintptr_t)a.z | (uintptr_t)a.out;
+    if (rows16) {
+        const int64_t strides = a.u_ts | a.delta_ts | (a.z ? a.z_ts : 0) | a.out_ts;
+        if (((rowp | (uintptr_t)a.state) & 15) || ((strides * es) & 15)) return AUM_E_UNSUPPORTED;
+    } else if (((rowp | (uintptr_t)a.B | (uintptr_t)a.C) & (uintptr_t)(es - 1)) || ((uintptr_t)a.state & 15)) {
+        return AUM_E_UNSUPPORTED;       // elements aligned; a channel's states move as 16-byte chunks
+    }
+    return AUM_OK;
+}
 
 // ---- chunked streaming inference (stream_tm_kernels.h): T tokens per call from carried caches ------
 #ifndef AUM_EMU
@@ -742,170 +684,62 @@ template <class T, bool SP, bool HAS_Z, bool PEEK = false> AUM_GLOBAL void k_str
 #endif
 template <class T, bool SILU> static int convc_launch(const AumConvTmChunkArgs& a, aum_stream_t s) {
     const int grid = a.batch * convt_cblocks<T, false>(a.dim);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) convc_wave<T, SILU>(a, wg);
-#else
-    AUM_LAUNCH((k_convt_chunk<T, SILU>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_chunk<T, SILU>), (convc_wave<T, SILU>(a, wg)), a);
 }
 template <class T> static int convc_dispatch_t(const AumConvTmChunkArgs& a, aum_stream_t s) {
-    return (a.flags & AUM_CONV_SILU) ? convc_launch<T, true>(a, s) : convc_launch<T, false>(a, s);
+    return with_bool((a.flags & AUM_CONV_SILU) != 0, [&](auto silu) { return convc_launch<T, silu>(a, s); });
 }
 AUM_API int aum_conv1d_tm_chunk(const AumConvTmChunkArgs* a, void* stream) {
-    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
-    if (a->batch <= 0 || a->dim <= 0 || a->len <= 0 || a->width <= 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (a->width > CONVT_W) return AUM_E_UNSUPPORTED;
-    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
-    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
-    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
-    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
-    const int64_t strides = a->x_bs | a->x_ts | a->y_bs | a->y_ts;
-    if ((ptrs & 15) || ((strides * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
-    if (a->x == a->y) return AUM_E_UNSUPPORTED;      // rows are fetched ahead of the steps that write them
-    if (a->flags & AUM_CONV_PEEK_LAST) return AUM_E_UNSUPPORTED;       // a flag of the packed entry point
-    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit: one batch entry's rows must fit
-    if ((int64_t)a->len * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
+    if (!a) return AUM_E_NULL;
+    if (const int rc = conv_stream_check(*a, nullptr, a->batch > 0 && a->len > 0, a->len, a->x_bs | a->y_bs, ~(uint32_t)AUM_CONV_PEEK_LAST, true, 0)) return rc;
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return convc_dispatch_t<float>(*a, s);
-        case AUM_BF16: return convc_dispatch_t<bf16_t>(*a, s);
-        default: return convc_dispatch_t<f16_t>(*a, s);
-    }
+    return AUM_BY_DTYPE_T(a->dtype, convc_dispatch_t, *a, s);
 }
 template <class T, bool SP, bool HAS_Z> static int scanc_launch(const AumScanTmChunkArgs& a, aum_stream_t s) {
     const int grid = a.batch * (a.dim / WAVE);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) scanc_wave<T, SP, HAS_Z>(a, wg);
-#else
-    AUM_LAUNCH((k_stream_scan_chunk<T, SP, HAS_Z>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_stream_scan_chunk<T, SP, HAS_Z>), (scanc_wave<T, SP, HAS_Z>(a, wg)), a);
 }
 template <class T> static int scanc_dispatch_t(const AumScanTmChunkArgs& a, aum_stream_t s) {
-    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scanc_launch<T, true, true>(a, s) : scanc_launch<T, true, false>(a, s);
-    return a.z ? scanc_launch<T, false, true>(a, s) : scanc_launch<T, false, false>(a, s);
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) { return with_bool(a.z != nullptr, [&](auto hz) { return scanc_launch<T, sp, hz>(a, s); }); });
 }
 AUM_API int aum_scan_tm_chunk(const AumScanTmChunkArgs* a, void* stream) {
-    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
-    if (a->batch <= 0 || a->dim <= 0 || a->len <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
-    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
-    {       // row offsets inside a batch entry are 32-bit byte cursors
-        const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
-        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
-        for (int64_t t : ts)
-            if (t < 0 || (t + a->dim) * es * a->len > lim) return AUM_E_UNSUPPORTED;
-        if ((int64_t)a->dim * a->dstate * 4 > lim) return AUM_E_UNSUPPORTED;
-        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->B | (uintptr_t)a->C;
-        if ((ptrs & (uintptr_t)(es - 1)) || ((uintptr_t)a->state & 15)) return AUM_E_UNSUPPORTED;       // elements aligned; a channel's states move as 16-byte chunks
-    }
-    AumScanTmChunkArgs k = *a;          // the kernels' view: an activated delta carries its bias and softplus already
-    if (a->flags & AUM_SCAN_DELTA_ACTIVATED) {
-        k.delta_bias = nullptr;
-        k.flags = 0;
-    }
+    if (!a) return AUM_E_NULL;
+    if (const int rc = scan_stream_check(*a, nullptr, a->batch > 0 && a->len > 0, a->len, AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED, true, 0, false)) return rc;
+    const AumScanTmChunkArgs k = scan_tm_fwd_resolve(*a);
     aum_stream_t s = (aum_stream_t)stream;
-    switch (k.dtype) {
-        case AUM_F32: return scanc_dispatch_t<float>(k, s);
-        case AUM_BF16: return scanc_dispatch_t<bf16_t>(k, s);
-        default: return scanc_dispatch_t<f16_t>(k, s);
-    }
+    return AUM_BY_DTYPE_T(k.dtype, scanc_dispatch_t, k, s);
 }
 
 // ---- the same on packed sessions: (sequence, channel block) units, rows and cache row from cu_seqlens / state_indices ----
-static bool stream_var_ok(const int32_t* cu_seqlens, const int32_t* state_indices, int total, int nseq, int nrows, int& err) {
-    if (!cu_seqlens) { err = AUM_E_NULL; return false; }
-    if (total <= 0 || nseq <= 0 || nrows <= 0) { err = AUM_E_SHAPE; return false; }
-    if (((uintptr_t)cu_seqlens | (uintptr_t)state_indices) & 3) { err = AUM_E_UNSUPPORTED; return false; }
-    return true;
-}
 template <class T, bool SILU, bool PEEK> static int convcv_launch(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
     const int grid = a.nseq * convt_cblocks<T, false>(a.dim);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) convc_var_wave<T, SILU, PEEK>(a, wg);
-#else
-    AUM_LAUNCH((k_convt_chunk_var<T, SILU, PEEK>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_chunk_var<T, SILU, PEEK>), (convc_var_wave<T, SILU, PEEK>(a, wg)), a);
 }
 template <class T> static int convcv_dispatch_t(const AumConvTmChunkVarArgs& a, aum_stream_t s) {
-    if (a.flags & AUM_CONV_PEEK_LAST) return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true, true>(a, s) : convcv_launch<T, false, true>(a, s);
-    return (a.flags & AUM_CONV_SILU) ? convcv_launch<T, true, false>(a, s) : convcv_launch<T, false, false>(a, s);
+    return with_bool((a.flags & AUM_CONV_PEEK_LAST) != 0, [&](auto peek) { return with_bool((a.flags & AUM_CONV_SILU) != 0, [&](auto silu) { return convcv_launch<T, silu, peek>(a, s); }); });
 }
 AUM_API int aum_conv1d_tm_chunk_var(const AumConvTmChunkVarArgs* a, void* stream) {
-    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
-    int err = 0;
-    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
-    if (a->dim <= 0 || a->width <= 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (a->width > CONVT_W) return AUM_E_UNSUPPORTED;
-    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
-    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
-    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
-    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
-    if ((ptrs & 15) || (((a->x_ts | a->y_ts) * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
-    if (a->x == a->y) return AUM_E_UNSUPPORTED;
-    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit; a sequence has at most `total` rows
-    if ((int64_t)a->total * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
-    if ((int64_t)a->nseq * convt_cblocks<float, false>(a->dim) >= lim) return AUM_E_UNSUPPORTED;
+    if (!a) return AUM_E_NULL;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = conv_stream_check(*a, &var, true, a->total, 0, ~0u, true, a->nseq)) return rc;
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return convcv_dispatch_t<float>(*a, s);
-        case AUM_BF16: return convcv_dispatch_t<bf16_t>(*a, s);
-        default: return convcv_dispatch_t<f16_t>(*a, s);
-    }
+    return AUM_BY_DTYPE_T(a->dtype, convcv_dispatch_t, *a, s);
 }
 template <class T, bool SP, bool HAS_Z, bool PEEK> static int scancv_launch(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
     const int grid = a.nseq * (a.dim / WAVE);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) scanc_var_wave<T, SP, HAS_Z, PEEK>(a, wg);
-#else
-    AUM_LAUNCH((k_stream_scan_chunk_var<T, SP, HAS_Z, PEEK>), grid, 0, s, a);
-#endif
-    return launch_status();
-}
-template <class T, bool PEEK> static int scancv_dispatch_p(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
-    if (a.flags & AUM_SCAN_SOFTPLUS) return a.z ? scancv_launch<T, true, true, PEEK>(a, s) : scancv_launch<T, true, false, PEEK>(a, s);
-    return a.z ? scancv_launch<T, false, true, PEEK>(a, s) : scancv_launch<T, false, false, PEEK>(a, s);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_stream_scan_chunk_var<T, SP, HAS_Z, PEEK>), (scanc_var_wave<T, SP, HAS_Z, PEEK>(a, wg)), a);
 }
 template <class T> static int scancv_dispatch_t(const AumScanTmChunkVarArgs& a, aum_stream_t s) {
-    return (a.flags & AUM_SCAN_PEEK_LAST) ? scancv_dispatch_p<T, true>(a, s) : scancv_dispatch_p<T, false>(a, s);
+    return with_bool((a.flags & AUM_SCAN_PEEK_LAST) != 0, [&](auto peek) { return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        return with_bool(a.z != nullptr, [&](auto hz) { return scancv_launch<T, sp, hz, peek>(a, s); }); }); });
 }
 AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) {
-    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
-    int err = 0;
-    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
-    if (a->dim <= 0 || a->dstate <= 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (!scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
-    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED | AUM_SCAN_PEEK_LAST)) return AUM_E_UNSUPPORTED;
-    {       // row offsets inside a sequence are 32-bit byte cursors; a sequence has at most `total` rows
-        const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
-        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
-        for (int64_t t : ts)
-            if (t < 0 || (t + a->dim) * es * a->total > lim) return AUM_E_UNSUPPORTED;
-        if ((int64_t)a->dim * a->dstate * 4 > lim || (int64_t)a->nseq * (a->dim / WAVE) > lim) return AUM_E_UNSUPPORTED;
-        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->B | (uintptr_t)a->C;
-        if ((ptrs & (uintptr_t)(es - 1)) || ((uintptr_t)a->state & 15)) return AUM_E_UNSUPPORTED;
-    }
-    AumScanTmChunkVarArgs k = *a;       // the kernels' view: an activated delta carries its bias and softplus already
-    if (a->flags & AUM_SCAN_DELTA_ACTIVATED) {
-        k.delta_bias = nullptr;
-        k.flags = a->flags & AUM_SCAN_PEEK_LAST;
-    }
+    if (!a) return AUM_E_NULL;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = scan_stream_check(*a, &var, true, a->total, AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED | AUM_SCAN_PEEK_LAST, true, a->nseq, false)) return rc;
+    const AumScanTmChunkVarArgs k = scan_tm_fwd_resolve(*a);
     aum_stream_t s = (aum_stream_t)stream;
-    switch (k.dtype) {
-        case AUM_F32: return scancv_dispatch_t<float>(k, s);
-        case AUM_BF16: return scancv_dispatch_t<bf16_t>(k, s);
-        default: return scancv_dispatch_t<f16_t>(k, s);
-    }
+    return AUM_BY_DTYPE_T(k.dtype, scancv_dispatch_t, k, s);
 }
 
 // ---- conv -> x/dt projections -> scan of packed sessions in one launch (stream_block_kernels.h) ----
@@ -939,13 +773,11 @@ static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumX
 }
 #else
 template <class T, bool BF16, bool PEEK> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
-    const dim3 grid((unsigned)a.nseq), block(SB_NW * 64);
-    const bool one = a.rank <= 32, base = a.ncols == XDT_COLS;
-    if (base && one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS, PEEK>), grid, block, 0, s, a);
-    else if (base) hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS, PEEK>), grid, block, 0, s, a);
-    else if (one) hipLaunchKernelGGL((k_stream_block<T, BF16, 1, XDT_COLS_SMALL, PEEK>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_stream_block<T, BF16, 2, XDT_COLS_SMALL, PEEK>), grid, block, 0, s, a);
-    return launch_status();
+    return with_bool(a.rank <= 32, [&](auto one) {
+        return with_bool(a.ncols == XDT_COLS, [&](auto base) {
+            return AUM_LAUNCH(a.nseq, SB_NW * 64, s, (NoLds{}), (k_stream_block<T, BF16, one ? 1 : 2, base ? XDT_COLS : XDT_COLS_SMALL, PEEK>), (0), a);
+        });
+    });
 }
 #endif
 AUM_API int32_t aum_stream_block_max_len(void) { return SB_MAX_T; }
@@ -955,8 +787,8 @@ AUM_API int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32
 }
 AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     if (!a || !a->x || !a->z || !a->conv_state || !a->state || !a->conv_weight || !a->wx || !a->wdt || !a->A || !a->y || !a->scratch) return AUM_E_NULL;
-    int err = 0;
-    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = stream_var_check(&var)) return rc;
     if (a->dim <= 0 || a->width <= 0 || a->dstate <= 0 || a->rank <= 0 || a->ncols <= 0 || a->max_len <= 0 || a->ldwx < a->dim || a->ldwdt < a->rank)
         return AUM_E_SHAPE;
     if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
@@ -999,8 +831,8 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     return rc;
 #else
     aum_stream_t s = (aum_stream_t)stream;
-    if (a->flags & AUM_STREAM_PEEK_LAST) return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, true>(*a, s) : sb_launch<f16_t, false, true>(*a, s);
-    return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, false>(*a, s) : sb_launch<f16_t, false, false>(*a, s);
+    return with_bool((a->flags & AUM_STREAM_PEEK_LAST) != 0, [&](auto peek) {
+        return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, peek>(*a, s) : sb_launch<f16_t, false, peek>(*a, s); });
 #endif
 }
 
@@ -1010,69 +842,31 @@ template <class T, bool SILU> AUM_GLOBAL void k_convt_prefill_var(AumConvTmPrefi
 #endif
 template <class T, bool SILU> static int convpv_launch(const AumConvTmPrefillVarArgs& a, aum_stream_t s) {
     const int grid = a.nseq * convt_chunks<false>(a.max_len) * convt_cblocks<T, false>(a.dim);
-#ifdef AUM_EMU
-    (void)s;
-    for (int wg = 0; wg < grid; ++wg) convp_var_wave<T, SILU>(a, wg);
-#else
-    AUM_LAUNCH((k_convt_prefill_var<T, SILU>), grid, 0, s, a);
-#endif
-    return launch_status();
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_prefill_var<T, SILU>), (convp_var_wave<T, SILU>(a, wg)), a);
 }
 template <class T> static int convpv_dispatch_t(const AumConvTmPrefillVarArgs& a, aum_stream_t s) {
-    return (a.flags & AUM_CONV_SILU) ? convpv_launch<T, true>(a, s) : convpv_launch<T, false>(a, s);
+    return with_bool((a.flags & AUM_CONV_SILU) != 0, [&](auto silu) { return convpv_launch<T, silu>(a, s); });
 }
 AUM_API int aum_conv1d_tm_prefill_var(const AumConvTmPrefillVarArgs* a, void* stream) {
-    if (!a || !a->x || !a->conv_state || !a->weight || !a->y) return AUM_E_NULL;
-    int err = 0;
-    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
-    if (a->dim <= 0 || a->width <= 0 || a->max_len <= 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (a->width > CONVT_W || a->max_len > a->total) return AUM_E_UNSUPPORTED;
-    if (a->flags & ~AUM_CONV_SILU) return AUM_E_UNSUPPORTED;
-    const int64_t es = a->dtype == AUM_F32 ? 4 : 2;
-    if (a->dim % (16 / es)) return AUM_E_UNSUPPORTED;
-    if (a->x_ts < 0 || a->y_ts < 0) return AUM_E_UNSUPPORTED;
-    const uintptr_t ptrs = (uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->weight | (uintptr_t)a->bias;
-    if ((ptrs & 15) || (((a->x_ts | a->y_ts) * es) & 15) || ((uintptr_t)a->conv_state & 3)) return AUM_E_UNSUPPORTED;
-    if (a->x == a->y) return AUM_E_UNSUPPORTED;
-    const int64_t lim = (int64_t)1 << 31;       // buffer offsets are 32-bit; a sequence has at most `total` rows
-    if ((int64_t)a->total * (a->x_ts > a->y_ts ? a->x_ts : a->y_ts) * es >= lim || (int64_t)a->dim * a->width * 4 >= lim) return AUM_E_UNSUPPORTED;
-    if ((int64_t)a->nseq * convt_chunks<false>(a->max_len) * convt_cblocks<float, false>(a->dim) >= lim) return AUM_E_UNSUPPORTED;
+    if (!a) return AUM_E_NULL;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = conv_stream_check(*a, &var, a->max_len > 0, a->total, 0, AUM_CONV_SILU, a->max_len <= a->total,
+                                         (int64_t)a->nseq * convt_chunks<false>(a->max_len > 0 ? a->max_len : 1)))
+        return rc;
     aum_stream_t s = (aum_stream_t)stream;
-    switch (a->dtype) {
-        case AUM_F32: return convpv_dispatch_t<float>(*a, s);
-        case AUM_BF16: return convpv_dispatch_t<bf16_t>(*a, s);
-        default: return convpv_dispatch_t<f16_t>(*a, s);
-    }
+    return AUM_BY_DTYPE_T(a->dtype, convpv_dispatch_t, *a, s);
 }
 AUM_API int64_t aum_scan_tm_fwd_state_var_carry_bytes(int32_t nseq, int32_t dim, int32_t dstate, int32_t nranges) {
     if (nseq <= 0 || dim <= 0 || nranges < 1 || nranges > AUM_SCAN_TM_MAX_SEGMENTS || !scant_supported(dim, dstate)) return 0;
     return scant_seg_carry_floats(nseq, dim, nranges, false) * (int64_t)sizeof(float);
 }
 AUM_API int aum_scan_tm_fwd_state_var(const AumScanTmFwdStateVarArgs* a, void* stream) {
-    if (!a || !a->u || !a->delta || !a->B || !a->C || !a->A || !a->state || !a->out) return AUM_E_NULL;
-    int err = 0;
-    if (!stream_var_ok(a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows, err)) return err;
-    if (a->dim <= 0 || a->dstate <= 0 || a->max_len <= 0 || a->range_len < 0) return AUM_E_SHAPE;
-    if (a->dtype < 0 || a->dtype > 2) return AUM_E_DTYPE;
-    if (!scant_supported(a->dim, a->dstate) || a->max_len > a->total) return AUM_E_UNSUPPORTED;
-    if (a->flags & ~(AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED)) return AUM_E_UNSUPPORTED;
-    if (!scan_tm_act_ok(a->flags, a->dtype, a->z)) return AUM_E_UNSUPPORTED;
-    const int64_t es = a->dtype == AUM_F32 ? 4 : 2, lim = ((int64_t)1 << 31) - 1;
-    if (a->dtype != AUM_F32) {      // 16-bit B / C rows are read as dwords
-        if ((a->B_ts | a->C_ts) & 1) return AUM_E_UNSUPPORTED;
-        if ((((uintptr_t)a->B) | ((uintptr_t)a->C)) & 3) return AUM_E_UNSUPPORTED;
-    }
-    {       // row offsets inside a session are 32-bit byte cursors; a session has at most `total` rows
-        const int64_t ts[] = {a->u_ts, a->delta_ts, a->z ? a->z_ts : 0, a->out_ts, a->B_ts, a->C_ts};
-        for (int64_t t : ts)
-            if (t < 0 || (t + a->dim) * es * a->total > lim) return AUM_E_UNSUPPORTED;
-        if ((int64_t)a->dim * a->dstate * 4 > lim) return AUM_E_UNSUPPORTED;
-        // rows are moved as 16-byte chunks, a channel's states too
-        const uintptr_t ptrs = (uintptr_t)a->u | (uintptr_t)a->delta | (uintptr_t)a->z | (uintptr_t)a->out | (uintptr_t)a->state;
-        const int64_t strides = a->u_ts | a->delta_ts | (a->z ? a->z_ts : 0) | a->out_ts;
-        if ((ptrs & 15) || ((strides * es) & 15)) return AUM_E_UNSUPPORTED;
-    }
+    if (!a) return AUM_E_NULL;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = scan_stream_check(*a, &var, a->max_len > 0 && a->range_len >= 0, a->total, AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED,
+                                         a->max_len <= a->total, 0, true))
+        return rc;
+    const int64_t lim = ((int64_t)1 << 31) - 1;
     int nranges = 1;
     if (a->range_len > 0) {
         if (a->range_len % SCANT_CK) return AUM_E_UNSUPPORTED;
@@ -1094,11 +888,7 @@ AUM_API int aum_scan_tm_fwd_state_var(const AumScanTmFwdStateVarArgs* a, void* s
     const ScanTVar v = {a->cu_seqlens, a->state_indices, a->state, a->total, a->nseq, a->nrows, a->max_len};
     aum_stream_t s = (aum_stream_t)stream;
     auto run = [&](const ScanTSeg* sg, int phase) {
-        switch (k.dtype) {
-            case AUM_F32: return scan_tm_fwd_state_var_f32(k, v, sg, phase, s);
-            case AUM_BF16: return scan_tm_fwd_state_var_bf16(k, v, sg, phase, s);
-            default: return scan_tm_fwd_state_var_f16(k, v, sg, phase, s);
-        }
+        return AUM_BY_DTYPE_X(k.dtype, scan_tm_fwd_state_var, k, v, sg, phase, s);
     };
     if (a->range_len == 0) return run(nullptr, 0);
     ScanTSeg sg;
