@@ -121,6 +121,18 @@ INNER_CASES = [
     ("v1_d16_l1025", "v1", 1, 16, 1025),
 ]
 
+# checked against the live fp64 oracle only (no fixture): the smallest blocks at the widths the 16-bit kernels take -- d_inner 768 / 1536,
+# dt_rank 24 / 48 (x_dbl rows of 56 / 80 columns): the fused x/dt kernels, the skinny weight-gradient GEMMs, aum_gemm_tn's widths
+INNER_WIDE_CASES = [
+    ("v1_d384_l65", "v1", 2, 384, 65),       # 130 tokens: a ragged last 16-token x/dt wave, one ragged 256-row GEMM block, 56-column rows
+    ("none_d384_l65", "none", 2, 384, 65),   # one direction at AuM-Small's widths
+    ("v2_d384_l65", "v2", 2, 384, 65),       # two parameter sets, the second pipeline time-reversed, (of + ob) / 2
+    ("v1_d768_l65", "v1", 2, 768, 65),       # AuM-Base widths: two dt K-steps, 80 columns, both W_x K-halves
+    ("none_d768_l9", "none", 3, 768, 9),     # 27 tokens: fewer than two 16-token waves, rows of one 8-step block + 1
+    ("v2_d768_l65", "v2", 2, 768, 65),
+    ("v1_d384_l513", "v1", 1, 384, 513),     # the model's own row length (64 blocks + the cls step, a direction pair meeting mid-row), one clip
+]
+
 
 def _rng(tag):
     seed = int.from_bytes(tag.encode(), "little") % (2 ** 31 - 1)
