@@ -1598,18 +1598,24 @@ def dtproj_tm_fwd(x_dbl, rank, w, lib=None):
 
 
 XDT_COLS, XDT_MAX_DIM = 80, 1536
-XDT_COLS_FWD = (80, 56)        # x_dbl widths aum_xdt_tm_fwd is built for (AuM-Base, AuM-Small)
+XDT_COLS_FWD = (80, 56, 48)    # x_dbl widths aum_xdt_tm_fwd is built for (AuM-Base, AuM-Small, AuM-Tiny's 44 padded: Mamba.stream_params)
 XDT_COLS_BWD = (80, 56)        # ... and aum_xdt_tm_bwd, each with its own dt_rank = width - 32 (48, 24) only
 
 
+def xdt_fwd_shape_ok(ncols, dim):
+    """the rule of csrc/xdt_args.h (xdt_fwd_shape_ok), shared by aum_xdt_tm_fwd and aum_stream_block_tm: a width the kernels are built for
+    and W_x K-halves of whole 64-column steps"""
+    return ncols in XDT_COLS_FWD and dim > 0 and dim % 128 == 0 and dim <= XDT_MAX_DIM
+
+
 def xdt_tm_supported(u, wx, wdt):
-    """shapes aum_xdt_tm_fwd takes (include/aum_hip.h, ABI 9): 16-bit row-major conv_out (ntok, dim), x_proj.weight (80, dim),
+    """shapes aum_xdt_tm_fwd takes (include/aum_hip.h, ABI 9): 16-bit row-major conv_out (ntok, dim), x_proj.weight (80 / 56 / 48, dim),
     dt_proj.weight (dim, rank)"""
     if not (u.dim() == 2 and wx.dim() == 2 and wdt.dim() == 2 and u.dtype == wx.dtype == wdt.dtype and u.dtype in (torch.bfloat16, torch.float16)):
         return False
     dim, rank = u.shape[1], wdt.shape[1]
     ok_t = lambda t: t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
-    return (wx.shape[0] in XDT_COLS_FWD and wx.shape[1] == dim and wdt.shape[0] == dim and dim % 256 == 0 and dim <= XDT_MAX_DIM and rank % 8 == 0
+    return (xdt_fwd_shape_ok(wx.shape[0], dim) and wx.shape[1] == dim and wdt.shape[0] == dim and rank % 8 == 0
             and rank <= 64 and rank <= wx.shape[0]
             and ok_t(u) and ok_t(wx) and ok_t(wdt))
 
@@ -1658,7 +1664,7 @@ def xdt_tm_bwd(ddelta, dbc, wdt_t, wx_t, du, lib=None):
 
 
 def xdt_tm_fwd(u, wx, wdt, lib=None, delta_bias=None, delta_softplus=False):
-    """(x_dbl (ntok, 80), delta (ntok, dim)) = (u @ wx^T, x_dbl[:, :rank] @ wdt^T) in one pass over u (SSI:467-468 on token-major rows).
+    """(x_dbl (ntok, ncols), delta (ntok, dim)) = (u @ wx^T, x_dbl[:, :rank] @ wdt^T) in one pass over u (SSI:467-468 on token-major rows).
     delta_softplus: delta = softplus(x_dbl[:, :rank] @ wdt^T + delta_bias) instead, rounded once -- the activated delta a token-major scan
     takes with delta_activated=True (delta_bias: (dim) fp32 or None)."""
     lib = lib or get()

@@ -774,8 +774,8 @@ static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumX
 #else
 template <class T, bool BF16, bool PEEK> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
     return with_bool(a.rank <= 32, [&](auto one) {
-        return with_bool(a.ncols == XDT_COLS, [&](auto base) {
-            return AUM_LAUNCH(a.nseq, SB_NW * 64, s, (NoLds{}), (k_stream_block<T, BF16, one ? 1 : 2, base ? XDT_COLS : XDT_COLS_SMALL, PEEK>), (0), a);
+        return with_int<XDT_COLS, XDT_COLS_SMALL, XDT_COLS_TINY>(a.ncols, [&](auto nc) {
+            return AUM_LAUNCH(a.nseq, SB_NW * 64, s, (NoLds{}), (k_stream_block<T, BF16, one ? 1 : 2, nc, PEEK>), (0), a);
         });
     });
 }
@@ -796,8 +796,7 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     if (a->flags & ~(AUM_STREAM_NO_COMMIT | AUM_STREAM_PEEK_LAST)) return AUM_E_UNSUPPORTED;
     if (a->max_len > SB_MAX_T) return AUM_E_UNSUPPORTED;
     if (a->width != CONVT_W || a->dstate != SCANT_N || !scant_supported(a->dim, a->dstate)) return AUM_E_UNSUPPORTED;
-    if ((a->ncols != XDT_COLS && a->ncols != XDT_COLS_SMALL) || a->rank % 8 || a->rank > 64 || a->rank + 2 * SCANT_N > a->ncols || a->dim % 256 ||
-        a->dim > XDT_MAX_DIM || a->ldwx % 8 || a->ldwdt % 8)
+    if (!aumx::xdt_fwd_shape_ok(a->ncols, a->dim) || a->rank % 8 || a->rank > 64 || a->rank + 2 * SCANT_N > a->ncols || a->ldwx % 8 || a->ldwdt % 8)
         return AUM_E_UNSUPPORTED;
     if (a->x_ts < a->dim || a->z_ts < a->dim || a->y_ts < a->dim || ((a->x_ts | a->z_ts | a->y_ts) & 7)) return AUM_E_UNSUPPORTED;
     {

@@ -110,8 +110,11 @@ template <int NW, int NC, bool SP> static void xdt_launch_nc(const AumXdtArgs& g
 }
 template <int NW> static void xdt_launch(const AumXdtArgs& g, hipStream_t s) {
     const bool sp = (g.flags & AUM_XDT_DELTA_SOFTPLUS) != 0;
-    if (g.ncols == XDT_COLS) sp ? xdt_launch_nc<NW, XDT_COLS, true>(g, s) : xdt_launch_nc<NW, XDT_COLS, false>(g, s);
-    else sp ? xdt_launch_nc<NW, XDT_COLS_SMALL, true>(g, s) : xdt_launch_nc<NW, XDT_COLS_SMALL, false>(g, s);
+    switch (g.ncols) {          // the widths of xdt_fwd_shape_ok, each by name: any other width launches nothing (xdt_check refused it before)
+        case XDT_COLS: sp ? xdt_launch_nc<NW, XDT_COLS, true>(g, s) : xdt_launch_nc<NW, XDT_COLS, false>(g, s); break;
+        case XDT_COLS_SMALL: sp ? xdt_launch_nc<NW, XDT_COLS_SMALL, true>(g, s) : xdt_launch_nc<NW, XDT_COLS_SMALL, false>(g, s); break;
+        case XDT_COLS_TINY: sp ? xdt_launch_nc<NW, XDT_COLS_TINY, true>(g, s) : xdt_launch_nc<NW, XDT_COLS_TINY, false>(g, s); break;
+    }
 }
 
 extern "C" int aum_xdt_tm_fwd(const AumXdtArgs* p, void* stream) {

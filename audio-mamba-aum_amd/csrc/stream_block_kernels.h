@@ -7,7 +7,8 @@
 // owns a session and walks its rows through three phases:
 //   1. conv:  the waves share out the session's channel blocks, each a convc_unit (stream_tm_kernels.h) -> xc
 //   2. x/dt:  the body of k_xdt_tm_fwd (xdt_fwd_body.inc) on the session's rows as workgroup 0 of a stream of `len` tokens: W_x and W_dt through LDS,
-//             the products on the matrix pipe (v_mfma_f32_16x16x32), SB_NW * 16 tokens at most -> x_dbl, delta
+//             the products on the matrix pipe (v_mfma_f32_16x16x32), SB_NW * 16 tokens at most -> x_dbl, delta.  NC = 80 / 56 / 48 columns
+//             (AuM-Base / -Small / -Tiny's padded rows, xdt_args.h); B | C sit at x_dbl + rank at every width
 //   3. scan:  the waves share out the session's groups of 64 channels, each a scanc_unit (delta activated, z gate) -> y
 // The step routines are the ones the three kernels run, so y and both cache rows are bit for bit theirs (every step is the same
 // instruction sequence on the same values: -ffp-contract=off, and an MFMA column -- a token -- does not depend on its neighbours).

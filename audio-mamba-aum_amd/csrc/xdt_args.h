@@ -7,6 +7,8 @@
 
 #define XDT_COLS 80          // columns of x_dbl = dt_rank + 2 d_state the kernels are built for (AuM-Base: 48 + 32)
 #define XDT_COLS_SMALL 56    // ... and for AuM-Small's 24 + 32 (forward: any rank % 8 == 0; backward: the pairs (80, 48) and (56, 24) only)
+#define XDT_COLS_TINY 48     // ... and, forward only, AuM-Tiny's 12 + 32 PADDED to three column fragments: [dt 12 | 4 zero columns | B 16 | C 16] with
+                             // rank 16 -- the zero rows 12..15 of W_x and zero columns 12..15 of W_dt are the caller's (Mamba.stream_params)
 #ifndef XDT_TOK_W
 #define XDT_TOK_W 16         // tokens per wave
 #endif
@@ -15,6 +17,14 @@
 #define XDT_MAX_DIM 1536     // W_x passes through LDS in two K-halves of XDT_COLS rows: 80 x (768 x 2 + 16) bytes
 
 namespace aumx {
+// THE shapes of the forward pass (k_xdt_tm_fwd, and k_stream_block around the same body); aum_hip.xdt_tm_supported states the same rule.
+//   ncols: a width the body is instantiated for.
+//   dim % 128: W_x passes through LDS in two K-halves walked in steps of 64 columns, so a half is a whole number of steps.  Everything
+//     else the body does with dim is implied: the conv_out prefetch ring runs over dim / 64 steps (an even count: it ends after two or
+//     after four steps of a round), a W_dt channel half is dim / 2 channels = dim / 64 pairs of 32, its bias is staged as dim / 8 float4.
+inline bool xdt_fwd_shape_ok(int ncols, int dim) {
+    return (ncols == XDT_COLS || ncols == XDT_COLS_SMALL || ncols == XDT_COLS_TINY) && dim > 0 && dim % 128 == 0 && dim <= XDT_MAX_DIM;
+}
 inline int xdt_check(const AumXdtArgs* p) {
     if (!p || !p->u || !p->wx || !p->wdt || !p->x_dbl || !p->delta) return AUM_E_NULL;
     const AumXdtArgs& g = *p;
@@ -22,7 +32,7 @@ inline int xdt_check(const AumXdtArgs* p) {
         g.ldd < g.dim)
         return AUM_E_SHAPE;
     if (g.dtype != AUM_BF16 && g.dtype != AUM_F16) return AUM_E_DTYPE;
-    if ((g.ncols != XDT_COLS && g.ncols != XDT_COLS_SMALL) || g.rank % 8 || g.rank > 64 || g.rank > g.ncols || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
+    if (!xdt_fwd_shape_ok(g.ncols, g.dim) || g.rank % 8 || g.rank > 64 || g.rank > g.ncols) return AUM_E_UNSUPPORTED;
     if (g.ldu % 8 || g.ldwx % 8 || g.ldwdt % 8 || g.ldx % 8 || g.ldd % 8) return AUM_E_UNSUPPORTED;
     if (((uintptr_t)g.u | (uintptr_t)g.wx | (uintptr_t)g.wdt | (uintptr_t)g.x_dbl | (uintptr_t)g.delta) & 15u) return AUM_E_UNSUPPORTED;
     // the bias is staged 16 bytes at a time and only ever added together with the softplus

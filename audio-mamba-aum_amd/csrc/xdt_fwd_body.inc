@@ -4,7 +4,7 @@
 // The including scope provides: template constants BF16, KS, NW, NC, SOFTPLUS;  AumXdtArgs g;  char* lds (lds_bytes(XDT_MAX_DIM, NW) bytes of
 // LDS, 16-byte aligned);  XDT_BODY_WG, the workgroup's index in the token stream (NW * XDT_TOK_W tokens each).
     constexpr int NCF = (NC + 15) / 16;
-    constexpr int XP = NC == 80 ? 176 : 144;             // bytes per tile row: an odd number of 16-byte chunks (conflict-free fragment reads)
+    constexpr int XP = NC == 80 ? 176 : 144;             // bytes per tile row: an odd number of 16-byte chunks (conflict-free fragment reads); 56, 48: 9
     static_assert(NC % 8 == 0 && NCF * 32 <= XP && XP <= aumx::XP, "tile row holds every fragment column");
     const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int rho = lane & 15, kg = lane >> 4;
@@ -38,7 +38,7 @@
     // conv_out rows arrive through a ring of four register sets indexed by the (unrolled) step: a set is refilled, four steps ahead, right
     // after the MFMAs that read it were issued.  (Rotating three sets through register copies -- the first version -- made every copy wait
     // for its load: the prefetch distance collapsed to one step.)
-    const int nsteps = KH / 64, total = E / 64;               // steps per K-half; dim % 256 == 0 -> total % 4 == 0
+    const int nsteps = KH / 64, total = E / 64;               // steps per K-half; dim % 128 == 0 (xdt_fwd_shape_ok) -> total is even
     s8v ur[4][NTF][2];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -48,6 +48,7 @@
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int s = s0 + j;
+            if (j == 2 && s >= total) break;                  // dim % 256 == 128: the last round has two steps (sets 2, 3 were not refilled)
             if (s == 0 || s == nsteps) {                      // a K-half of W_x through LDS
                 __syncthreads();                              // everybody is done with the previous contents of the slab
                 stage_rows<NW * 64>(slab, SP, static_cast<const char*>(g.wx) + (int64_t)(s / nsteps) * KH * 2, (int64_t)g.ldwx * 2, NC, KH / 8, tid);
@@ -81,7 +82,7 @@
     __builtin_amdgcn_s_waitcnt(0xc07f);                              // lgkmcnt(0): the wave's own LDS writes have landed (nobody else reads this tile)
     {
         char* xo = static_cast<char*>(g.x_dbl);
-        constexpr int PIECES = NC * 2 / 16;                          // 10 / 7 per token row
+        constexpr int PIECES = NC * 2 / 16;                          // 10 / 7 / 6 per token row
         for (int idx = lane; idx < XDT_TOK_W * PIECES; idx += 64) {
             const int tk = idx / PIECES, pc = idx - tk * PIECES;
             if (t0 + tk < g.ntok)

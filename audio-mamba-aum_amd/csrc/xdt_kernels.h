@@ -95,7 +95,10 @@ __device__ __forceinline__ void stage_rows(char* dst, int dst_pitch, const char*
 // 16 -- 8 waves make 257 workgroups, a second round for ONE workgroup on 256 CUs (97 us, cold caches); 9 waves make 228 of them (one round).
 // NC = columns of x_dbl: 80 (AuM-Base: dt_rank 48 + 2 x 16) or 56 (AuM-Small: 24 + 32).  56 is three and a half column fragments: the
 // fourth fragment multiplies eight weight rows that do not exist (whatever the slab holds behind row 55) -- their products are columns 56..63
-// of the wave's tile, inside the row's padding, which nothing reads.
+// of the wave's tile, inside the row's padding, which nothing reads.  48 (AuM-Tiny: dt_rank 12 padded to 16 by the caller, + 32) is exactly three
+// fragments.  dim: xdt_fwd_shape_ok (xdt_args.h) -- K-halves of whole 64-column steps.  The slab's 16-byte row padding makes the pitch of a
+// half of 64 m columns 4 (8 m + 1) dwords, an odd multiple of four: a fragment's 16 rows start in 16 different 4-dword bank groups for every m
+// (m = 3 at dim 384 as at the multiples of 128 columns the padding was chosen for).
 template <bool BF16, int KS, int NW, int NC, bool SOFTPLUS>
 __global__ __launch_bounds__(NW * 64, 1) void k_xdt_tm_fwd(AumXdtArgs g) {
     __shared__ __attribute__((aligned(16))) char lds[lds_bytes(XDT_MAX_DIM, NW)];       // 143 KB at 8 waves: one workgroup per CU

@@ -25,7 +25,11 @@ from mamba_ssm.ops.triton.selective_state_update import selective_state_update
 
 # What streaming inference reads of a block's parameters, converted ONCE (Mamba.stream_params): conv_w (E, width) / conv_b fp32 contiguous and
 # 16-byte aligned, A = -exp(A_log) (E, N), D, dt_bias fp32, w_x = x_proj.weight and w_dt = dt_proj.weight in the working 16-bit (or fp32) dtype.
-StreamParams = collections.namedtuple("StreamParams", "conv_w conv_b A D dt_bias w_x w_dt dtype")
+# b_off: the column of B in the rows w_x produces (C follows at b_off + d_state) and the rank w_dt contracts: dt_rank, except in the PADDED
+# layout of a 16-bit plan whose dt_rank is no multiple of 8 (AuM-Tiny: 12), where w_x (48, E) is [dt 12 | 4 zero rows | B 16 | C 16] and
+# w_dt (E, 16) has zero columns 12..15 -- the x/dt kernels' 48-column width.  The pad columns of x_dbl are exact zeros and add +0 terms to
+# delta: the numbers are those of the unpadded products.
+StreamParams = collections.namedtuple("StreamParams", "conv_w conv_b A D dt_bias w_x w_dt dtype b_off")
 
 
 class Mamba(nn.Module):
@@ -238,10 +242,17 @@ class Mamba(nn.Module):
         hit = self.__dict__.get("_stream_params")
         if hit is not None and hit[0] == key:
             return hit[1]
-        E = self.d_inner
+        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        w_x, w_dt, b_off = self.x_proj.weight.detach().to(dtype), self.dt_proj.weight.detach().to(dtype), R
+        Rp = -(-R // 8) * 8
+        if Rp != R and dtype in (torch.bfloat16, torch.float16) and N == 16 and aum_hip.xdt_fwd_shape_ok(Rp + 2 * N, E):
+            # the padded layout (StreamParams): only where the kernels take the padded shape and would refuse the plain one
+            px, pdt = w_x.new_zeros(Rp + 2 * N, E), w_dt.new_zeros(E, Rp)
+            px[:R], px[Rp:] = w_x[:R], w_x[R:]
+            pdt[:, :R] = w_dt
+            w_x, w_dt, b_off = px, pdt, Rp
         plan = StreamParams(aum_hip._al16(aum_hip._f32c(self.conv1d.weight.reshape(E, -1))), aum_hip._al16(aum_hip._f32c(self.conv1d.bias)),
-                            -torch.exp(self.A_log.float()), aum_hip._f32c(self.D), aum_hip._f32c(self.dt_proj.bias),
-                            self.x_proj.weight.detach().to(dtype), self.dt_proj.weight.detach().to(dtype), dtype)
+                            -torch.exp(self.A_log.float()), aum_hip._f32c(self.D), aum_hip._f32c(self.dt_proj.bias), w_x, w_dt, dtype, b_off)
         self.__dict__["_stream_params"] = (key, plan)
         return plan
 
@@ -304,7 +315,8 @@ class Mamba(nn.Module):
             delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
             proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
         proj = proj.view(batch, T, -1)
-        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., R:R + N], proj[..., R + N:R + 2 * N], plan.D, z,
+        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
+        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., Bo:Bo + N], proj[..., Bo + N:Bo + 2 * N], plan.D, z,
                                 plan.dt_bias, True, activated, seq_map, peek=peek)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
@@ -373,7 +385,8 @@ class Mamba(nn.Module):
             proj = self.x_proj(xc)
             delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
             proj, delta = proj.to(xc.dtype), delta.to(xc.dtype)
-        args = (ssm_state, xc, delta, plan.A, proj[:, R:R + N], proj[:, R + N:R + 2 * N], plan.D, z, None if activated else plan.dt_bias,
+        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
+        args = (ssm_state, xc, delta, plan.A, proj[:, Bo:Bo + N], proj[:, Bo + N:Bo + 2 * N], plan.D, z, None if activated else plan.dt_bias,
                 not activated, activated)
         if not aum_hip.scan_tm_fwd_state_var_supported(*args, range_len=rng, max_len=max(seq_map.lens)):      # no quiet second path
             raise RuntimeError(f"prefill_chunk(seq_map=): aum_scan_tm_fwd_state_var does not take xc {tuple(xc.shape)} {xc.dtype}, delta "
@@ -429,7 +442,8 @@ class Mamba(nn.Module):
             proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
         proj = proj.view(batch, T, -1)
         delta = delta.view(batch, T, E)
-        Bm, Cm = proj[..., R:R + N], proj[..., R + N:R + 2 * N]
+        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
+        Bm, Cm = proj[..., Bo:Bo + N], proj[..., Bo + N:Bo + 2 * N]
         seg = aum_hip.scan_tm_segments(batch, E, T, False, device=xc.device) if xc.is_cuda else 1
         args = (xc, delta, plan.A, Bm, Cm, plan.D, z, None if activated else plan.dt_bias, not activated, activated)
         y = aum_hip.scan_tm_fwd_state(*args, state_in=ssm_state, state_out=ssm_state, segments=seg)     # raises where it refuses: no quiet second path

@@ -522,7 +522,7 @@ int aum_dtproj_tm_fwd(const AumDtProjArgs* args, void* stream);
  * scan with AUM_SCAN_DELTA_ACTIVATED reads; delta_bias: (dim) fp32, 16-byte aligned, or NULL (no bias).
  *   u: (ntok, dim) rows of pitch ldu (conv_out);  wx: (ncols, dim) pitch ldwx;  wdt: (dim, rank) pitch ldwdt;
  *   x_dbl (out): (ntok, ncols) pitch ldx;  delta (out): (ntok, dim) pitch ldd.  Pitches in ELEMENTS, all tensors `dtype` (AUM_BF16 / AUM_F16).
- *   Built for ncols == 80 or 56 (dt_rank + 2 d_state of AuM-Base / AuM-Small), dim % 256 == 0, dim <= 1536, rank % 8 == 0, rank <= 64, pitches % 8 == 0,
+ *   Built for ncols == 80, 56 (dt_rank + 2 d_state of AuM-Base / AuM-Small) or 48 (AuM-Tiny's 12 + 32 padded by the caller to [dt 12 | 4 zero | B | C], rank 16), dim % 128 == 0, dim <= 1536, rank % 8 == 0, rank <= 64, pitches % 8 == 0,
  *   16-byte aligned pointers; anything else AUM_E_UNSUPPORTED (callers use a GEMM for x_dbl and aum_dtproj_tm_fwd).  delta is computed from
  *   the ROUNDED x_dbl, as the two separate products do.
  */
@@ -697,7 +697,7 @@ int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
  *   longest session of the call as the host knows it, <= aum_stream_block_max_len() (128); a session longer than max_len is a no-op.
  *   scratch: aum_stream_block_scratch_bytes(total, dim, ncols) bytes, 16-byte aligned -- xc, delta and x_dbl of the call; a session's
  *   workgroup touches the rows of its own session only.
- *   Built for width == 4, dstate == 16 and the shapes of aum_xdt_tm_fwd (dim % 256 == 0, dim <= 1536, ncols 80 or 56, rank % 8 == 0,
+ *   Built for width == 4, dstate == 16 and the shapes of aum_xdt_tm_fwd (dim % 128 == 0, dim <= 1536, ncols 80, 56 or 48, rank % 8 == 0,
  *   rank <= 64, rank + 32 <= ncols, pitches % 8 == 0, 16-byte aligned pointers); anything else returns the error the three entry points
  *   would (AUM_E_DTYPE for fp32 activations, AUM_E_UNSUPPORTED, ...) and callers use the three launches.
  *   flags: AUM_STREAM_NO_COMMIT -- the caches are read and not written (the stores that close the conv and the scan are skipped, nothing
