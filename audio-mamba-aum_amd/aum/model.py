@@ -332,30 +332,10 @@ class AudioMamba(nn.Module):
         tokens as a peek row (Mamba.step_chunk(peek=True): it sees the state the tokens produced, the caches do not take it in).
         Returns (column counts, logits (len(sessions), classes) in the order of `sessions`; features with return_features)."""
         import aum_hip
-        self._check_streamable()
-        rows = self._check_sessions("stream_push_many", pool, sessions)
-        ph, pw = self.patch_embed.proj.kernel_size
-        nf, nt = self.patch_grid_size
-        specs = list(specs)
-        if not rows or len(specs) != len(rows):
-            raise ValueError(f"stream_push_many: one spectrogram piece per session, got {len(specs)} for the sessions {rows}")
-        ks = []
-        for sp, r in zip(specs, rows):
-            if sp.dim() != 2 or sp.shape[0] == 0 or sp.shape[0] % pw or sp.shape[1] // ph != nf:
-                raise ValueError(f"stream_push_many takes (a positive multiple of {pw} frames, {nf * ph} mel bins) per session, got "
-                                 f"{tuple(sp.shape)} for session {r}")
-            k = sp.shape[0] // pw
-            if pool["columns"][r] + k > nt:
-                raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
-            ks.append(k)
-        dev = specs[0].device
+        ks, c0s, rows, specs = self._check_push("stream_push_many", specs, pool, sessions)
+        nf, dev = self.patch_grid_size[0], specs[0].device
         smap = aum_hip.seq_map([k * nf + (1 if read else 0) for k in ks], rows, device=dev)
-        # the position row of every new column: one host-built index vector, uploaded like the sequence map
-        cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
-        if dev.type == "cuda":
-            cols = cols.pin_memory()
-        cols = cols.to(dev, non_blocking=True)
-        x = self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)   # a session's tokens are contiguous
+        x = self._pack_columns(specs, ks, c0s)
         out = None
         if read:                # a session's tokens, then its cls row; the last row of session i is row cu[i + 1] - 1 of the pack
             cls = self._cls_row()[0].to(x.dtype)
@@ -371,9 +351,7 @@ class AudioMamba(nn.Module):
             out = self._head_rows(hidden[0].index_select(0, last), residual[0].index_select(0, last), return_features)
         else:
             self._stream_layers(x, pool["layers"], smap)
-        for r, k in zip(rows, ks):
-            pool["columns"][r] += k
-        counts = [pool["columns"][r] for r in rows]
+        counts = self._commit_columns(pool, ks, rows)
         return (counts, out) if read else counts
 
     def stream_reset(self, pool, sessions):
@@ -388,22 +366,61 @@ class AudioMamba(nn.Module):
             for r in rows:
                 pool["columns"][r] = 0
 
-    def _check_push(self, what, spec, cache):
-        """stream_prefill's checks, made before anything is touched -> (k new columns, columns so far).  They MIRROR the checks
-        stream_push makes in line (its body is kept as it was) and, per session, those of stream_push_many / stream_prefill_many: a
-        change to one of them belongs in all; folding them into this one helper is a follow-up of its own."""
+    def _check_push(self, what, specs, cache, sessions=None):
+        """The checks of every call that advances caches (`what`: stream_push / stream_prefill and their _many forms), made before
+        anything is touched -> (ks, c0s, rows, specs): the new columns and the columns so far of every session, its cache row and its
+        piece.  sessions None: the fixed-batch form -- specs is ONE (batch, 16 k, n_mels) tensor for all rows of a cache from
+        allocate_inference_cache (one k, one c0, rows None).  Else the pool form: specs[i] (16 k_i, n_mels) for row sessions[i] of a
+        pool from allocate_stream_pool."""
         self._check_streamable()
-        if self._is_pool(cache):
-            raise ValueError(f"{what} advances all rows of a cache from allocate_inference_cache together; a pool from "
-                             f"allocate_stream_pool is advanced by {what}_many(specs, pool, sessions)")
         ph, pw = self.patch_embed.proj.kernel_size
         nf, nt = self.patch_grid_size
-        if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
-            raise ValueError(f"{what} takes (batch={cache['batch']}, a positive multiple of {pw} frames, {nf * ph} mel bins), got {tuple(spec.shape)}")
-        k, c0 = spec.shape[1] // pw, cache["columns"]
-        if c0 + k > nt:
-            raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
-        return k, c0
+        if sessions is None:
+            spec = specs
+            if self._is_pool(cache):
+                raise ValueError(f"{what} advances all rows of a cache from allocate_inference_cache together; a pool from "
+                                 f"allocate_stream_pool is advanced by {what}_many(specs, pool, sessions)")
+            if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
+                raise ValueError(f"{what} takes (batch={cache['batch']}, a positive multiple of {pw} frames, {nf * ph} mel bins), got {tuple(spec.shape)}")
+            k, c0 = spec.shape[1] // pw, cache["columns"]
+            if c0 + k > nt:
+                raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
+            return [k], [c0], None, [spec]
+        rows = self._check_sessions(what, cache, sessions)
+        specs = list(specs)
+        if not rows or len(specs) != len(rows):
+            raise ValueError(f"{what}: one spectrogram piece per session, got {len(specs)} for the sessions {rows}")
+        ks = []
+        for sp, r in zip(specs, rows):
+            if sp.dim() != 2 or sp.shape[0] == 0 or sp.shape[0] % pw or sp.shape[1] // ph != nf:
+                raise ValueError(f"{what} takes (a positive multiple of {pw} frames, {nf * ph} mel bins) per session, got "
+                                 f"{tuple(sp.shape)} for session {r}")
+            k = sp.shape[0] // pw
+            if cache["columns"][r] + k > nt:
+                raise ValueError(f"the clip has {nt} time columns: session {r} pushed {cache['columns'][r]}, {k} more do not fit")
+            ks.append(k)
+        return ks, [cache["columns"][r] for r in rows], rows, specs
+
+    def _pack_columns(self, specs, ks, c0s):
+        """The frames of several sessions, specs[i] (16 k_i, n_mels) from column c0s[i] on, concatenated in time -> their (1, sum k_i nf, Dm)
+        packed tokens, a session's tokens contiguous and time-major, each with the position row of its own (f, t) cell: one patch-embed
+        GEMM, the position rows gathered by one host-built index vector, uploaded like the sequence map"""
+        dev = specs[0].device
+        cols = torch.tensor([c0 + j for c0, k in zip(c0s, ks) for j in range(k)], dtype=torch.int64)
+        if dev.type == "cuda":
+            cols = cols.pin_memory()
+        cols = cols.to(dev, non_blocking=True)
+        return self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)
+
+    @staticmethod
+    def _commit_columns(cache, ks, rows):
+        """the column counts behind a pass -> the new counts (rows None: the one count of a fixed-batch cache)"""
+        if rows is None:
+            cache["columns"] += ks[0]
+            return cache["columns"]
+        for r, k in zip(rows, ks):
+            cache["columns"][r] += k
+        return [cache["columns"][r] for r in rows]
 
     @torch.no_grad()
     def stream_prefill(self, spec, cache, read=False, return_features=False):
@@ -420,13 +437,11 @@ class AudioMamba(nn.Module):
         located more finely; a pass costs about 5.7 ms whatever the backlog (per block: a [window ; x] copy, a copy of the conv output
         and the window write-back next to the kernels -- not profiled).
         No peek row: read=True is stream_read behind the push -> (columns, logits)."""
-        k, c0 = self._check_push("stream_prefill", spec, cache)
+        (k,), (c0,), _, _ = self._check_push("stream_prefill", spec, cache)
         x = self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
         self._stream_layers(x, cache["layers"], prefill=True)
-        cache["columns"] = c0 + k
-        if not read:
-            return cache["columns"]
-        return cache["columns"], self.stream_read(cache, return_features)
+        n = self._commit_columns(cache, [k], None)
+        return (n, self.stream_read(cache, return_features)) if read else n
 
     @torch.no_grad()
     def stream_prefill_many(self, specs, pool, sessions, packed=False):
@@ -440,45 +455,21 @@ class AudioMamba(nn.Module):
         rows gathered from its own offset (as stream_push_many does), then all blocks once on the packed tokens through
         Mamba.prefill_chunk(seq_map=): only the conv and the scan see the session boundaries, and they advance the pool rows in place
         (no gather, no scatter).  The same caches and counts to the kernels' tolerance, not bitwise: the GEMMs see another M."""
-        self._check_streamable()
-        rows = self._check_sessions("stream_prefill_many", pool, sessions)
-        ph, pw = self.patch_embed.proj.kernel_size
-        nf, nt = self.patch_grid_size
-        specs = list(specs)
-        if not rows or len(specs) != len(rows):
-            raise ValueError(f"stream_prefill_many: one spectrogram piece per session, got {len(specs)} for the sessions {rows}")
-        ks = []
-        for sp, r in zip(specs, rows):
-            if sp.dim() != 2 or sp.shape[0] == 0 or sp.shape[0] % pw or sp.shape[1] // ph != nf:
-                raise ValueError(f"stream_prefill_many takes (a positive multiple of {pw} frames, {nf * ph} mel bins) per session, got "
-                                 f"{tuple(sp.shape)} for session {r}")
-            k = sp.shape[0] // pw
-            if pool["columns"][r] + k > nt:
-                raise ValueError(f"the clip has {nt} time columns: session {r} pushed {pool['columns'][r]}, {k} more do not fit")
-            ks.append(k)
+        ks, c0s, rows, specs = self._check_push("stream_prefill_many", specs, pool, sessions)
         if packed:
             import aum_hip
-            dev = specs[0].device
-            smap = aum_hip.seq_map([k * nf for k in ks], rows, device=dev)
-            cols = torch.tensor([pool["columns"][r] + j for r, k in zip(rows, ks) for j in range(k)], dtype=torch.int64)
-            if dev.type == "cuda":
-                cols = cols.pin_memory()
-            cols = cols.to(dev, non_blocking=True)
-            x = self._embed_columns(torch.cat(specs, dim=0).unsqueeze(0).unsqueeze(1).transpose(2, 3), cols)   # a session's tokens are contiguous
-            self._stream_layers(x, pool["layers"], smap, prefill=True)
-            for r, k in zip(rows, ks):
-                pool["columns"][r] += k
-            return [pool["columns"][r] for r in rows]
-        for sp, r, k in zip(specs, rows, ks):
+            smap = aum_hip.seq_map([k * self.patch_grid_size[0] for k in ks], rows, device=specs[0].device)
+            self._stream_layers(self._pack_columns(specs, ks, c0s), pool["layers"], smap, prefill=True)
+            return self._commit_columns(pool, ks, rows)
+        for sp, r, k, c0 in zip(specs, rows, ks, c0s):
             ix = torch.tensor([r], dtype=torch.int64, device=sp.device)
             one = {i: (c.index_select(0, ix), s.index_select(0, ix)) for i, (c, s) in pool["layers"].items()}
-            c0 = pool["columns"][r]
             x = self._embed_columns(sp.unsqueeze(0).unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
             self._stream_layers(x, one, prefill=True)
             for i, (c, s) in pool["layers"].items():
                 c.index_copy_(0, ix, one[i][0])
                 s.index_copy_(0, ix, one[i][1])
-            pool["columns"][r] = c0 + k
+            self._commit_columns(pool, [k], [r])
         return [pool["columns"][r] for r in rows]
 
     @torch.no_grad()
@@ -492,26 +483,14 @@ class AudioMamba(nn.Module):
         read=True: what stream_read would say behind this push, from the same pass -- the cls row rides behind the new tokens as a peek
         row (Mamba.step_chunk(peek=True)), goes through the final norm and the head, and the caches advance by the tokens only.
         Returns (columns, logits (batch, classes); features with return_features)."""
-        self._check_streamable()
-        if self._is_pool(cache):
-            raise ValueError("stream_push advances all rows of a cache from allocate_inference_cache together; a pool from "
-                             "allocate_stream_pool is advanced by stream_push_many(specs, pool, sessions)")
-        ph, pw = self.patch_embed.proj.kernel_size
-        nf, nt = self.patch_grid_size
-        if spec.dim() != 3 or spec.shape[0] != cache["batch"] or spec.shape[1] == 0 or spec.shape[1] % pw or spec.shape[2] // ph != nf:
-            raise ValueError(f"stream_push takes (batch={cache['batch']}, a positive multiple of {pw} frames, {nf * ph} mel bins), got {tuple(spec.shape)}")
-        k, c0 = spec.shape[1] // pw, cache["columns"]
-        if c0 + k > nt:
-            raise ValueError(f"the clip has {nt} time columns: {c0} pushed, {k} more do not fit")
+        (k,), (c0,), _, _ = self._check_push("stream_push", spec, cache)
         x = self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
         if not read:
             self._stream_layers(x, cache["layers"])
-            cache["columns"] = c0 + k
-            return cache["columns"]
+            return self._commit_columns(cache, [k], None)
         x = torch.cat((x, self._cls_row().to(x.dtype).expand(x.shape[0], -1, -1)), dim=1)
         hidden, residual = self._stream_layers(x, cache["layers"], peek=True)
-        cache["columns"] = c0 + k
-        return cache["columns"], self._head_rows(hidden[:, -1], residual[:, -1], return_features)
+        return self._commit_columns(cache, [k], None), self._head_rows(hidden[:, -1], residual[:, -1], return_features)
 
     @torch.no_grad()
     def stream_read(self, cache, return_features=False, sessions=None):
@@ -519,16 +498,13 @@ class AudioMamba(nn.Module):
         every block takes the one-launch path, Mamba.step_chunk(commit=False); otherwise from a copy -- also where a row is named
         twice), then the final norm and the head.  After all columns of a clip have been pushed this is model(spec).  sessions: read
         those rows only, (len(sessions), ...) in that order; None: every row (of a pool too)."""
-        import aum_hip
         self._check_streamable()
         rows = None
         if sessions is not None:
             rows = self._check_sessions("stream_read", cache, sessions, writes=False)
             if not rows:
                 raise ValueError("stream_read: at least one session")
-        n = cache["batch"] if rows is None else len(rows)
-        pe = self.pos_embed.pos_embed
-        cls = (self.cls_token + pe[:, :1]).expand(n, -1, -1)
+        cls = self._cls_row().expand(cache["batch"] if rows is None else len(rows), -1, -1)
         done = self._read_in_place(cls, cache, rows) if rows is None or len(set(rows)) == len(rows) else None
         if done is not None:
             hidden, residual = done
@@ -539,9 +515,7 @@ class AudioMamba(nn.Module):
                 idx = torch.tensor(rows, dtype=torch.int64)
                 copies = {i: (c.index_select(0, idx.to(c.device)), s.index_select(0, idx.to(s.device))) for i, (c, s) in cache["layers"].items()}
             hidden, residual = self._stream_layers(cls, copies)
-        f = rms_norm_fn(hidden[:, 0], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual[:, 0],
-                        prenorm=False, residual_in_fp32=True)
-        return f if return_features else self.head(f)
+        return self._head_rows(hidden[:, 0], residual[:, 0], return_features)
 
     def forward(self, x, return_features=False, frontend=None):
         """x: (B, T, F) normalised log-mel spectrogram, or -- with frontend=aum.frontend.WaveInput -- (B, n_samples) waveform"""

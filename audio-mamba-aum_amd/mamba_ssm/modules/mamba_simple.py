@@ -260,6 +260,33 @@ class Mamba(nn.Module):
         """drop the cached stream_params(): the next call converts the parameters again (behind a write the key cannot see: `p.data`)"""
         self.__dict__.pop("_stream_params", None)
 
+    @staticmethod
+    def _check_packed(what, hidden_states, conv_state, ssm_state, seq_map):
+        """The entry check of the packed form of `what` (step_chunk / prefill_chunk with a seq_map): hidden_states (1, total, d_model),
+        pools of one size, and the map against them (aum_hip.check_seq_map, once per call) -> False where the map holds no token."""
+        import aum_hip
+        if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or conv_state.shape[0] != ssm_state.shape[0]:
+            raise ValueError(f"{what}(seq_map=): hidden_states (1, total, d_model), pools of one size, not {conv_state.shape[0]} / {ssm_state.shape[0]} rows")
+        aum_hip.check_seq_map(what, seq_map, hidden_states.shape[1], conv_state.shape[0], hidden_states.device)
+        return seq_map.total != 0
+
+    def _xdt_stage(self, xc2, plan):
+        """The x/dt stage of step_chunk's ladder and of both prefill bodies: the contiguous (ntok, E) conv output -> (delta (ntok, E), B and
+        C (ntok, N) as column views of the x_dbl rows, activated).  One fused launch where aum_xdt_tm_fwd takes the shape -- delta then
+        carries dt_bias and the softplus (activated) -- else x_proj and dt_proj from the library, cast to the working dtype, bias and
+        softplus left to the scan (MS:340).  How the scan is told is the caller's: the scans' operand checks differ."""
+        import aum_hip
+        N, R = self.d_state, self.dt_rank
+        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, plan.w_x, plan.w_dt):
+            proj, delta = aum_hip.xdt_tm_fwd(xc2, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
+            Bo, activated = plan.b_off, True                                    # plan.w_x's rows may be padded (StreamParams) ...
+        else:
+            proj = self.x_proj(xc2)
+            delta = F.linear(proj[:, :R], self.dt_proj.weight)
+            proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
+            Bo, activated = R, False                                            # ... x_proj's are not
+        return delta, proj[:, Bo:Bo + N], proj[:, Bo + N:Bo + 2 * N], activated
+
     def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True, peek=False):
         """T >= 1 tokens of streaming inference for the causal block in one pass: (batch, T, d_model) in, (batch, T, d_model) out, the
         caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the
@@ -284,15 +311,12 @@ class Mamba(nn.Module):
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
         if seq_map is not None:
-            if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or conv_state.shape[0] != ssm_state.shape[0]:
-                raise ValueError(f"step_chunk(seq_map=): hidden_states (1, total, d_model), pools of one size, not {conv_state.shape[0]} / {ssm_state.shape[0]} rows")
-            aum_hip.check_seq_map("step_chunk", seq_map, hidden_states.shape[1], conv_state.shape[0], hidden_states.device)
-            if seq_map.total == 0:
+            if not self._check_packed("step_chunk", hidden_states, conv_state, ssm_state, seq_map):
                 return hidden_states.new_empty(hidden_states.shape), conv_state, ssm_state
         elif hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
             raise ValueError("step_chunk() takes hidden_states of shape (batch, T >= 1, d_model)")
         batch, T, _ = hidden_states.shape
-        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        E, N = self.d_inner, self.d_state
         xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
         x, z = xz[..., :E], xz[..., E:]
         plan = self.stream_params(xz.dtype)
@@ -305,18 +329,8 @@ class Mamba(nn.Module):
         xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map, peek=peek)
         if not xc.is_contiguous():
             xc = xc.contiguous()
-        xc2 = xc.reshape(batch * T, E)
-        activated = False
-        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, plan.w_x, plan.w_dt):
-            proj, delta = aum_hip.xdt_tm_fwd(xc2, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
-            activated = True
-        else:
-            proj = self.x_proj(xc2)
-            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
-            proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
-        proj = proj.view(batch, T, -1)
-        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
-        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, proj[..., Bo:Bo + N], proj[..., Bo + N:Bo + 2 * N], plan.D, z,
+        delta, Bm, Cm, activated = self._xdt_stage(xc.reshape(batch * T, E), plan)
+        y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, Bm.view(batch, T, N), Cm.view(batch, T, N), plan.D, z,
                                 plan.dt_bias, True, activated, seq_map, peek=peek)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
@@ -332,6 +346,14 @@ class Mamba(nn.Module):
                 and conv_state.dtype == torch.float32 and ssm_state.dtype == torch.float32
                 and ssi.token_major_ok(self.d_inner, self.d_state, self.d_conv, self.dt_rank, work))
 
+    def _prefill_block_ok(self, xz):
+        """what prefill_supported and prefill_packed_supported ask of the block itself for these (., ., 2E) in_proj rows: silu, rows of
+        this block, a width aum_scan_tm_fwd takes, and 4-byte aligned B / C columns (an even dt_rank for 16-bit activations)"""
+        import aum_hip
+        E = xz.shape[2] // 2
+        return (self.activation in ("silu", "swish") and E == self.d_inner and aum_hip.scan_tm_supported(E, self.d_state)
+                and (xz.element_size() == 4 or self.dt_rank % 2 == 0))
+
     def prefill_supported(self, xz, conv_state, ssm_state):
         """prefill_chunk's dispatch for these (batch, T, 2E) in_proj rows and fixed-batch caches: what conv1d_tm_prefill and
         aum_scan_tm_fwd_state take -- silu, x rows the token-major conv takes with an fp32 (batch, E, width <= 4) window, d_state 16,
@@ -339,11 +361,9 @@ class Mamba(nn.Module):
         for 16-bit activations (an even dt_rank; nothing for fp32).  The 16-byte widths of aum_xdt_tm_fwd are NOT required: where that
         kernel refuses, the x/dt products are the library's."""
         import aum_hip
-        batch, T, E2 = xz.shape
-        E, N = E2 // 2, self.d_state
-        return (self.activation in ("silu", "swish") and E == self.d_inner and aum_hip.conv1d_tm_chunk_supported(xz[..., :E], conv_state)
-                and aum_hip.scan_tm_supported(E, N) and aum_hip.scan_state_supported(ssm_state, batch, E, N)
-                and (xz.element_size() == 4 or self.dt_rank % 2 == 0))
+        E = xz.shape[2] // 2
+        return (self._prefill_block_ok(xz) and aum_hip.conv1d_tm_chunk_supported(xz[..., :E], conv_state)
+                and aum_hip.scan_state_supported(ssm_state, xz.shape[0], E, self.d_state))
 
     def prefill_packed_supported(self, xz, conv_state, ssm_state, seq_map, range_len=0):
         """prefill_chunk(seq_map=)'s dispatch, the sibling of prefill_supported for (1, total, 2E) packed in_proj rows and POOLS of caches:
@@ -352,24 +372,18 @@ class Mamba(nn.Module):
         B / C columns of the x_dbl rows 4-byte aligned for 16-bit activations (an even dt_rank), and a range_len that cuts the longest
         session into at most 32 ranges."""
         import aum_hip
-        E2 = xz.shape[2]
-        E, N = E2 // 2, self.d_state
-        return (self.activation in ("silu", "swish") and E == self.d_inner and xz.shape[0] == 1
-                and aum_hip.conv1d_tm_prefill_var_supported(xz[0, :, :E], conv_state)
-                and aum_hip.scan_tm_supported(E, N) and aum_hip.scan_state_supported(ssm_state, ssm_state.shape[0], E, N)
-                and (xz.element_size() == 4 or self.dt_rank % 2 == 0)
+        E = xz.shape[2] // 2
+        return (self._prefill_block_ok(xz) and xz.shape[0] == 1 and aum_hip.conv1d_tm_prefill_var_supported(xz[0, :, :E], conv_state)
+                and aum_hip.scan_state_supported(ssm_state, ssm_state.shape[0], E, self.d_state)
                 and range_len % aum_hip.SCAN_TM_CK == 0 and (range_len == 0 or -(-max(seq_map.lens) // range_len) <= aum_hip.SCAN_TM_MAX_SEGMENTS))
 
     def _prefill_packed(self, hidden_states, conv_state, ssm_state, seq_map):
         """prefill_chunk with a seq_map: (1, total, d_model) packed backlogs, pools of caches"""
         import aum_hip
-        if hidden_states.dim() != 3 or hidden_states.shape[0] != 1 or conv_state.shape[0] != ssm_state.shape[0]:
-            raise ValueError(f"prefill_chunk(seq_map=): hidden_states (1, total, d_model), pools of one size, not {conv_state.shape[0]} / {ssm_state.shape[0]} rows")
-        aum_hip.check_seq_map("prefill_chunk", seq_map, hidden_states.shape[1], conv_state.shape[0], hidden_states.device)
-        if seq_map.total == 0:
+        if not self._check_packed("prefill_chunk", hidden_states, conv_state, ssm_state, seq_map):
             return hidden_states.new_empty(hidden_states.shape), conv_state, ssm_state
         total = hidden_states.shape[1]
-        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        E = self.d_inner
         xz = self.in_proj(hidden_states[0]).view(1, total, 2 * E)
         plan = self.stream_params(xz.dtype)
         rng = aum_hip.scan_tm_var_range(seq_map.lens, E, device=xz.device) if xz.is_cuda else 0
@@ -377,20 +391,11 @@ class Mamba(nn.Module):
             return self.step_chunk(hidden_states, conv_state, ssm_state, seq_map=seq_map)
         x, z = xz[0, :, :E], xz[0, :, E:]
         xc = aum_hip._conv1d_tm_prefill_var(x, conv_state, plan.conv_w, plan.conv_b, True, seq_map, None, aum_hip.get())
-        activated = False
-        if xc.is_cuda and aum_hip.xdt_tm_supported(xc, plan.w_x, plan.w_dt):
-            proj, delta = aum_hip.xdt_tm_fwd(xc, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
-            activated = True
-        else:
-            proj = self.x_proj(xc)
-            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
-            proj, delta = proj.to(xc.dtype), delta.to(xc.dtype)
-        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
-        args = (ssm_state, xc, delta, plan.A, proj[:, Bo:Bo + N], proj[:, Bo + N:Bo + 2 * N], plan.D, z, None if activated else plan.dt_bias,
-                not activated, activated)
+        delta, Bm, Cm, activated = self._xdt_stage(xc, plan)
+        args = (ssm_state, xc, delta, plan.A, Bm, Cm, plan.D, z, None if activated else plan.dt_bias, not activated, activated)
         if not aum_hip.scan_tm_fwd_state_var_supported(*args, range_len=rng, max_len=max(seq_map.lens)):      # no quiet second path
             raise RuntimeError(f"prefill_chunk(seq_map=): aum_scan_tm_fwd_state_var does not take xc {tuple(xc.shape)} {xc.dtype}, delta "
-                               f"{tuple(delta.shape)} strides {delta.stride()}, x_dbl strides {proj.stride()}, range_len {rng}")
+                               f"{tuple(delta.shape)} strides {delta.stride()}, x_dbl strides {Bm.stride()}, range_len {rng}")
         y = aum_hip._scan_tm_fwd_state_var(*args, seq_map, rng, None, aum_hip.get())      # the map was checked above, once
         return self.out_proj(y).view(1, total, -1), conv_state, ssm_state
 
@@ -422,7 +427,7 @@ class Mamba(nn.Module):
         if hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
             raise ValueError("prefill_chunk() takes hidden_states of shape (batch, T >= 1, d_model)")
         batch, T, _ = hidden_states.shape
-        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        E, N = self.d_inner, self.d_state
         if conv_state.shape[0] != batch or ssm_state.shape[0] != batch:
             raise ValueError(f"prefill_chunk() advances fixed-batch caches: {conv_state.shape[0]} / {ssm_state.shape[0]} rows for a batch of {batch}")
         xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
@@ -431,21 +436,10 @@ class Mamba(nn.Module):
         if not self.prefill_supported(xz, conv_state, ssm_state):
             return self.step_chunk(hidden_states, conv_state, ssm_state)
         xc = aum_hip.conv1d_tm_prefill(x, conv_state, plan.conv_w, plan.conv_b, True).contiguous()
-        xc2 = xc.view(batch * T, E)
-        activated = False
-        if xc2.is_cuda and aum_hip.xdt_tm_supported(xc2, plan.w_x, plan.w_dt):
-            proj, delta = aum_hip.xdt_tm_fwd(xc2, plan.w_x, plan.w_dt, delta_bias=plan.dt_bias, delta_softplus=True)
-            activated = True
-        else:
-            proj = self.x_proj(xc2)
-            delta = F.linear(proj[:, :R], self.dt_proj.weight)                  # the bias is added inside the scan (MS:340)
-            proj, delta = proj.to(xc2.dtype), delta.to(xc2.dtype)
-        proj = proj.view(batch, T, -1)
-        delta = delta.view(batch, T, E)
-        Bo = plan.b_off if activated else R                                 # plan.w_x's rows may be padded (StreamParams); x_proj's are not
-        Bm, Cm = proj[..., Bo:Bo + N], proj[..., Bo + N:Bo + 2 * N]
+        delta, Bm, Cm, activated = self._xdt_stage(xc.view(batch * T, E), plan)
         seg = aum_hip.scan_tm_segments(batch, E, T, False, device=xc.device) if xc.is_cuda else 1
-        args = (xc, delta, plan.A, Bm, Cm, plan.D, z, None if activated else plan.dt_bias, not activated, activated)
+        args = (xc, delta.view(batch, T, E), plan.A, Bm.view(batch, T, N), Cm.view(batch, T, N), plan.D, z, None if activated else plan.dt_bias,
+                not activated, activated)
         y = aum_hip.scan_tm_fwd_state(*args, state_in=ssm_state, state_out=ssm_state, segments=seg)     # raises where it refuses: no quiet second path
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
