@@ -243,12 +243,12 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False, prefill=False):
+    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False, prefill=False, peek_every=None):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
         (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
         are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it.
         prefill=True (no peek row): the mixers take the tokens as a backlog (Mamba.prefill_chunk; with seq_map the packed backlogs of
-        several sessions over pools)"""
+        several sessions over pools).  peek_every=P (not with the others): a peek row behind every P committed rows of every session."""
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
@@ -258,7 +258,8 @@ class AudioMamba(nn.Module):
                 hidden, _, _ = (layer.mixer.prefill_chunk(hidden, conv_state, ssm_state) if seq_map is None else
                                 layer.mixer.prefill_chunk(hidden, conv_state, ssm_state, seq_map=seq_map))
             else:
-                hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek)
+                hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek,
+                                                      **({} if peek_every is None else {"peek_every": peek_every}))
         return hidden, residual
 
     def _read_in_place(self, cls, cache, rows):
@@ -491,6 +492,49 @@ class AudioMamba(nn.Module):
         x = torch.cat((x, self._cls_row().to(x.dtype).expand(x.shape[0], -1, -1)), dim=1)
         hidden, residual = self._stream_layers(x, cache["layers"], peek=True)
         return self._commit_columns(cache, [k], None), self._head_rows(hidden[:, -1], residual[:, -1], return_features)
+
+    def _with_cls_rows(self, x):
+        """(B, K n_f, Dm) time-major tokens of K columns -> (B, K (n_f + 1), Dm): the cls row behind every column's n_f tokens"""
+        nf = self.patch_grid_size[0]
+        Bsz, K = x.shape[0], x.shape[1] // nf
+        cls = self._cls_row().to(x.dtype).reshape(1, 1, 1, -1).expand(Bsz, K, 1, -1)
+        return torch.cat((x.reshape(Bsz, K, nf, -1), cls), dim=2).reshape(Bsz, K * (nf + 1), -1)
+
+    def _timeline_rows(self, hidden, residual, return_features):
+        """the cls rows of _with_cls_rows' layout out of the last block's output and residual -> (B K, classes): final norm and head"""
+        nf = self.patch_grid_size[0]
+        pick = lambda t: t.reshape(-1, nf + 1, t.shape[-1])[:, nf]
+        return self._head_rows(pick(hidden), pick(residual), return_features)
+
+    @torch.no_grad()
+    def stream_timeline(self, spec, cache, return_features=False):
+        """The logits "if the clip ended now" after EVERY one of the next k time columns, in one pass: spec (batch, 16 k, n_mels) as
+        stream_push takes it (the same checks; a refused call changes nothing).  The rows of a batch entry are
+        [column c0's n_f tokens | cls | column c0 + 1's tokens | cls | ...]: every cls row is a peek row (Mamba.step_chunk(peek_every=n_f))
+        -- it sees the state the columns up to its own produced and is not taken into the caches.  Returns (columns, logits
+        (batch, k, classes); features with return_features): logits[:, j] is what stream_push(column c0 + j, read=True) would have
+        returned, to the kernels' tolerance (the GEMMs see another row count).  The caches and the column count advance as under
+        stream_push of the k columns: stream_push / stream_read / stream_prefill / stream_timeline go on from there."""
+        (k,), (c0,), _, _ = self._check_push("stream_timeline", spec, cache)
+        x = self._with_cls_rows(self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k)))
+        hidden, residual = self._stream_layers(x, cache["layers"], peek_every=self.patch_grid_size[0])
+        out = self._timeline_rows(hidden, residual, return_features)
+        return self._commit_columns(cache, [k], None), out.reshape(x.shape[0], k, -1)
+
+    @torch.no_grad()
+    def stream_timeline_many(self, specs, pool, sessions, return_features=False):
+        """stream_timeline on a pool: specs[i] (16 k_i, n_mels), the next k_i columns of session sessions[i] (distinct rows of a pool from
+        allocate_stream_pool), every session at its own offset and with its own k_i, in ONE packed pass -- packer, position rows and
+        sequence map as in stream_push_many, the sessions k_i (n_f + 1) rows long.  Returns (the per-session column counts,
+        [logits_i (k_i, classes)] in the order of `sessions`)."""
+        import aum_hip
+        ks, c0s, rows, specs = self._check_push("stream_timeline_many", specs, pool, sessions)
+        nf = self.patch_grid_size[0]
+        smap = aum_hip.seq_map([k * (nf + 1) for k in ks], rows, device=specs[0].device)
+        x = self._with_cls_rows(self._pack_columns(specs, ks, c0s))
+        hidden, residual = self._stream_layers(x, pool["layers"], smap, peek_every=nf)
+        out = self._timeline_rows(hidden, residual, return_features)
+        return self._commit_columns(pool, ks, rows), list(out.split(ks, dim=0))
 
     @torch.no_grad()
     def stream_read(self, cache, return_features=False, sessions=None):

@@ -219,6 +219,14 @@ class ScanTmChunkVarArgs(C.Structure):
                 + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "dstate", "dtype")] + [("flags", _u32)])
 
 
+class ConvTmChunkPeeksArgs(C.Structure):
+    _fields_ = [("base", ConvTmChunkVarArgs), ("peek_every", _i32), ("reserved", _i32)]
+
+
+class ScanTmChunkPeeksArgs(C.Structure):
+    _fields_ = [("base", ScanTmChunkVarArgs), ("peek_every", _i32), ("reserved", _i32)]
+
+
 class ConvTmPrefillVarArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "conv_state", "weight", "bias", "y", "cu_seqlens", "state_indices")] + [(n, _i64) for n in ("x_ts", "y_ts")]
                 + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "width", "dtype")] + [("flags", _u32), ("max_len", _i32)])
@@ -257,7 +265,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
-    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var")}
+    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -1180,18 +1188,47 @@ def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=Non
     return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, peek)
 
 
-def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib, peek=False):
-    """conv1d_tm_chunk_var behind its checks: operands conv1d_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
+def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib, peek=False, peek_every=None):
+    """conv1d_tm_chunk_var behind its checks: operands conv1d_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1.
+    peek_every: the same operands through aum_conv1d_tm_chunk_peeks"""
     total, dim = x.shape
-    a = ConvTmChunkVarArgs()
+    pa = ConvTmChunkPeeksArgs()
+    a = pa.base                         # a view of pa's first field
     y, _held = _conv_chunk_operands(a, "conv1d_tm_chunk_var", lib, x, conv_state, weight, bias, silu, out)
     a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
     a.x_ts, a.y_ts = _tm2(x, "x", dim), _tm2(y, "out", dim)
     a.total, a.nseq, a.nrows = total, len(m.lens), conv_state.shape[0]
+    if peek_every is not None:
+        pa.peek_every = peek_every
+        _launch(lib.c.aum_conv1d_tm_chunk_peeks, pa, x, lib, "conv1d_tm_chunk_peeks", (len(m.lens), dim, total, x.element_size()))
+        return y
     if peek:
         a.flags |= CONV_PEEK_LAST
     _launch(lib.c.aum_conv1d_tm_chunk_var, a, x, lib, "conv_tm_chunk_var", (len(m.lens), dim, total, x.element_size()))
     return y
+
+
+def _peek_period(name, peek_every):
+    if isinstance(peek_every, bool) or not isinstance(peek_every, int) or not 1 <= peek_every < 1 << 31:
+        raise ValueError(f"{name}: peek_every is the number of committed rows before each peek row, an int >= 1, not {peek_every!r}")
+    return peek_every
+
+
+def conv1d_tm_chunk_peeks(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None, peek_every=None):
+    """conv1d_tm_chunk_var with a peek row behind every peek_every committed rows of each session (aum_conv1d_tm_chunk_peeks): row j of a
+    session is a peek row iff (j + 1) % (peek_every + 1) == 0 -- computed and stored like any other, the window not moved.  Per session
+    bit for bit conv1d_tm_chunk_var(peek=True) on one group of peek_every + 1 rows after the other, then a plain call on the rest."""
+    lib = lib or get()
+    peek_every = _peek_period("conv1d_tm_chunk_peeks", peek_every)
+    for t in (x, conv_state, out):
+        lib.check_tensor(t)
+    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return x.new_empty(x.shape) if out is None else out
+    if not conv1d_tm_chunk_var_supported(x, conv_state):
+        raise RuntimeError(f"conv1d_tm_chunk_peeks: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
+    check_seq_map("conv1d_tm_chunk_peeks", seq_map, x.shape[0], conv_state.shape[0], x.device)
+    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, False, peek_every)
 
 
 def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
@@ -1212,21 +1249,46 @@ def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None,
     return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, peek)
 
 
-def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib, peek=False):
-    """scan_tm_chunk_var behind its checks: operands scan_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1"""
+def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib, peek=False, peek_every=None):
+    """scan_tm_chunk_var behind its checks: operands scan_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1.
+    peek_every: the same operands through aum_scan_tm_chunk_peeks"""
     total, dim = u.shape
     dstate = state.shape[2]
-    a = ScanTmChunkVarArgs()
+    pa = ScanTmChunkPeeksArgs()
+    a = pa.base                         # a view of pa's first field
     out, _held = _scan_chunk_operands(a, "scan_tm_chunk_var", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
     a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
     a.z_ts = 0 if z is None else _tm2(z, "z", dim)
     a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
     a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
     a.total, a.nseq, a.nrows = total, len(m.lens), state.shape[0]
+    if peek_every is not None:
+        pa.peek_every = peek_every
+        _launch(lib.c.aum_scan_tm_chunk_peeks, pa, u, lib, "scan_tm_chunk_peeks", (len(m.lens), dim, total, dstate, u.element_size()))
+        return out
     if peek:
         a.flags |= SCAN_PEEK_LAST
     _launch(lib.c.aum_scan_tm_chunk_var, a, u, lib, "scan_tm_chunk_var", (len(m.lens), dim, total, dstate, u.element_size()))
     return out
+
+
+def scan_tm_chunk_peeks(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
+                        out=None, lib=None, peek_every=None):
+    """scan_tm_chunk_var with a peek row behind every peek_every committed rows of each session (aum_scan_tm_chunk_peeks): row j of a
+    session is a peek row iff (j + 1) % (peek_every + 1) == 0 -- one step from the current state and the gate, stored like any other
+    row, the state not updated.  Per session bit for bit scan_tm_chunk_var(peek=True) on one group of peek_every + 1 rows after the
+    other, then a plain call on the rest."""
+    lib = lib or get()
+    peek_every = _peek_period("scan_tm_chunk_peeks", peek_every)
+    for t in (state, u, delta, z, B, C, out):
+        lib.check_tensor(t)
+    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return u.new_empty(u.shape) if out is None else out
+    if not scan_tm_chunk_var_supported(state, u):
+        raise RuntimeError(f"scan_tm_chunk_peeks: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
+                           "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
+    check_seq_map("scan_tm_chunk_peeks", seq_map, u.shape[0], state.shape[0], u.device)
+    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, False, peek_every)
 
 
 # ---- packed prefill: the backlogs of many sessions in one launch per operator (aum_conv1d_tm_prefill_var, aum_scan_tm_fwd_state_var)
@@ -1404,21 +1466,39 @@ def _packed_rows(t):
     return t.contiguous().view(1, batch * T, X)
 
 
-def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token, peek=False):
+def _peek_cuts(n, peek, peek_every):
+    """the n rows of one session as the host loop advances them: [(first, end, committed)] -- runs of committed rows, each peek row alone"""
+    if peek_every is not None:
+        cuts = []
+        for g in range(0, n, peek_every + 1):
+            cuts.append((g, min(g + peek_every, n), True))
+            if g + peek_every < n:
+                cuts.append((g + peek_every, g + peek_every + 1, False))
+        return cuts
+    keep = max(n - 1, 0) if peek else n
+    return ([(0, keep, True)] if keep > 0 else []) + ([(keep, n, False)] if n > keep else [])
+
+
+def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token, peek=False, peek_every=None):
     """The one ladder under conv1d_stream and scan_stream: advance `cache` IN PLACE (through an fp32 copy, written back, if it is not fp32
     contiguous) by the token-major operands `rows` ((batch, T, .) views or None; rows[0] is what the *_ok predicates look at) with the
     first launch that takes them.  m (a SeqMap its caller checked; rows (1, total, .), cache a pool): var() on the packed rows, else a host
     loop over the sessions (host lengths: no synchronisation), each on its pool row as without m: chunk(), else token() token by token
     (a (batch, .) rows[0] is one token).  An operand is copied to contiguous rows only where that makes a launch take it.
     peek: every session's last row is computed and the cache closes one row early (the flag of the packed kernels -- a fixed batch goes
-    through them with fixed_seq_map; in the host loop a session's last row is advanced on a copy of its cache row)."""
+    through them with fixed_seq_map; in the host loop a session's last row is advanced on a copy of its cache row).
+    peek_every (not with peek): a peek row behind every peek_every committed rows of each session -- var() is then the *_chunk_peeks
+    launch; the host loop advances every peek row on a copy of the cache row, group by group."""
+    if peek and peek_every is not None:
+        raise ValueError("peek (the last row of every session) and peek_every (a peek row every so many rows) exclude each other")
     for t in (cache, *rows):
         lib.check_tensor(t)
     st = cache if cache.dtype == torch.float32 and cache.is_contiguous() else cache.float().contiguous()
     shape = None
-    if peek and m is None:
+    if (peek or peek_every is not None) and m is None:
         if rows[0].dim() != 3:
-            raise ValueError("peek takes (batch, T >= 1, .) rows: the last of the T rows is the peek row")
+            raise ValueError("peek takes (batch, T >= 1, .) rows: the last of the T rows is the peek row" if peek else
+                             "peek_every takes (batch, T >= 1, .) rows")
         shape = rows[0].shape
         m = fixed_seq_map(shape[0], shape[1], rows[0].device)
         rows = [_packed_rows(t) for t in rows]
@@ -1435,11 +1515,8 @@ def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token, pe
             outs, o = [], 0
             cut = lambda a, b: [None if t is None else t[:, a:b] for t in rows]
             for n, r in zip(m.lens, m.rows):
-                keep = max(n - 1, 0) if peek else n
-                if keep > 0:
-                    outs.append(_advance_batch(st[r:r + 1], cut(o, o + keep), chunk_ok, chunk, token))
-                if n > keep:
-                    outs.append(_advance_batch(st[r:r + 1].clone(), cut(o + keep, o + n), chunk_ok, chunk, token))
+                for a, b, keep in _peek_cuts(n, peek, peek_every):
+                    outs.append(_advance_batch(st[r:r + 1] if keep else st[r:r + 1].clone(), cut(o + a, o + b), chunk_ok, chunk, token))
                 o += n
             out = torch.cat(outs, dim=1)
     if st is not cache:
@@ -1447,42 +1524,48 @@ def _stream_advance(lib, cache, rows, m, var_ok, var, chunk_ok, chunk, token, pe
     return out if shape is None else out.reshape(shape[0], shape[1], -1)
 
 
-def conv1d_stream(x, conv_state, weight, bias=None, silu=True, seq_map=None, lib=None, peek=False):
+def conv1d_stream(x, conv_state, weight, bias=None, silu=True, seq_map=None, lib=None, peek=False, peek_every=None):
     """causal_conv1d.causal_conv1d_update on token-major rows, as Mamba.step_chunk has them: x (batch, T, dim) (a view is read in place),
     (batch, dim) one token, or with seq_map (trusted: check_seq_map is the caller's) (1, total, dim) over a pool; returns x's shape.
-    peek: the last row of every session (of the T rows without seq_map) is computed, conv_state is advanced by the rows before it."""
+    peek: the last row of every session (of the T rows without seq_map) is computed, conv_state is advanced by the rows before it.
+    peek_every (not with peek): a peek row behind every peek_every committed rows of each session (conv1d_tm_chunk_peeks)."""
     lib = lib or get()
-    if peek and seq_map is None and x.dim() == 3:
+    if peek_every is not None:
+        peek_every = _peek_period("conv1d_stream", peek_every)
+    if (peek or peek_every is not None) and seq_map is None and x.dim() == 3:
         seq_map_k = fixed_seq_map(x.shape[0], x.shape[1], x.device)
     else:
         seq_map_k = seq_map
     return _stream_advance(lib, conv_state, (x,), seq_map,
                            lambda st, x: conv1d_tm_chunk_var_supported(x, st),
-                           lambda st, x: _conv1d_tm_chunk_var(x, st, weight, bias, silu, seq_map_k, None, lib, peek),
+                           lambda st, x: _conv1d_tm_chunk_var(x, st, weight, bias, silu, seq_map_k, None, lib, peek, peek_every),
                            lambda st, x: conv1d_tm_chunk_supported(x, st),
                            lambda st, x: conv1d_tm_chunk(x, st, weight, bias, silu, lib),
-                           lambda st, x: conv1d_update(x, st, weight, bias, silu, lib), peek)
+                           lambda st, x: conv1d_update(x, st, weight, bias, silu, lib), peek, peek_every)
 
 
 def scan_stream(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None, lib=None,
-                peek=False):
+                peek=False, peek_every=None):
     """selective_scan_update behind its argument normalisation (operands of one dtype), what Mamba.step_chunk calls: seq_map is trusted
     (check_seq_map is the caller's).  peek: the last row of every session (of the T rows without seq_map) is computed, state is advanced
-    by the rows before it."""
+    by the rows before it.  peek_every (not with peek): a peek row behind every peek_every committed rows of each session
+    (scan_tm_chunk_peeks)."""
     lib = lib or get()
+    if peek_every is not None:
+        peek_every = _peek_period("scan_stream", peek_every)
     if delta_activated:                 # delta holds softplus(raw + delta_bias) already
         delta_bias, delta_softplus = None, False
-    if peek and seq_map is None and u.dim() == 3:
+    if (peek or peek_every is not None) and seq_map is None and u.dim() == 3:
         seq_map_k = fixed_seq_map(u.shape[0], u.shape[1], u.device)
     else:
         seq_map_k = seq_map
     return _stream_advance(lib, state, (u, delta, z, B, C), seq_map,
                            scan_tm_chunk_var_supported,
                            lambda st, u, dl, z, B, C: _scan_tm_chunk_var(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated,
-                                                                         seq_map_k, None, lib, peek),
+                                                                         seq_map_k, None, lib, peek, peek_every),
                            scan_tm_chunk_supported,
                            lambda st, u, dl, z, B, C: scan_tm_chunk(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, lib=lib),
-                           lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib), peek)
+                           lambda st, u, dl, z, B, C: state_update(st, u, dl, A, B, C, D, z, delta_bias, delta_softplus, lib=lib), peek, peek_every)
 
 
 # ---- the block's recurrent middle in one launch (aum_stream_block_tm): conv -> x/dt projections -> scan on packed sessions

@@ -681,6 +681,10 @@ template <class T, bool SILU, bool PEEK = false> AUM_GLOBAL void k_convt_chunk_v
 template <class T, bool SP, bool HAS_Z, bool PEEK = false> AUM_GLOBAL void k_stream_scan_chunk_var(AumScanTmChunkVarArgs a) {
     scanc_var_wave<T, SP, HAS_Z, PEEK>(a, (int)blockIdx.x);
 }
+template <class T, bool SILU> AUM_GLOBAL void k_convt_chunk_peeks(AumConvTmChunkVarArgs a, int pe) { convc_var_wave<T, SILU, false, true>(a, (int)blockIdx.x, pe); }
+template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_stream_scan_chunk_peeks(AumScanTmChunkVarArgs a, int pe) {
+    scanc_var_wave<T, SP, HAS_Z, false, true>(a, (int)blockIdx.x, pe);
+}
 #endif
 template <class T, bool SILU> static int convc_launch(const AumConvTmChunkArgs& a, aum_stream_t s) {
     const int grid = a.batch * convt_cblocks<T, false>(a.dim);
@@ -740,6 +744,41 @@ AUM_API int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* a, void* stream) 
     const AumScanTmChunkVarArgs k = scan_tm_fwd_resolve(*a);
     aum_stream_t s = (aum_stream_t)stream;
     return AUM_BY_DTYPE_T(k.dtype, scancv_dispatch_t, k, s);
+}
+
+// ---- packed sessions with a peek row behind every peek_every rows (PEEKS of convc_unit / scanc_unit): the operands, checks and grids of
+// the packed entry points above; the PEEK_LAST flags are not theirs (AUM_E_UNSUPPORTED), peek_every < 1 is AUM_E_SHAPE ----
+template <class T, bool SILU> static int convcp_launch(const AumConvTmChunkVarArgs& a, int pe, aum_stream_t s) {
+    const int grid = a.nseq * convt_cblocks<T, false>(a.dim);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convt_chunk_peeks<T, SILU>), (convc_var_wave<T, SILU, false, true>(a, wg, pe)), a, pe);
+}
+template <class T> static int convcp_dispatch_t(const AumConvTmChunkVarArgs& a, int pe, aum_stream_t s) {
+    return with_bool((a.flags & AUM_CONV_SILU) != 0, [&](auto silu) { return convcp_launch<T, silu>(a, pe, s); });
+}
+AUM_API int aum_conv1d_tm_chunk_peeks(const AumConvTmChunkPeeksArgs* pa, void* stream) {
+    if (!pa) return AUM_E_NULL;
+    const AumConvTmChunkVarArgs* a = &pa->base;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = conv_stream_check(*a, &var, pa->peek_every >= 1, a->total, 0, ~(uint32_t)AUM_CONV_PEEK_LAST, true, a->nseq)) return rc;
+    aum_stream_t s = (aum_stream_t)stream;
+    return AUM_BY_DTYPE_T(a->dtype, convcp_dispatch_t, *a, (int)pa->peek_every, s);
+}
+template <class T, bool SP, bool HAS_Z> static int scancp_launch(const AumScanTmChunkVarArgs& a, int pe, aum_stream_t s) {
+    const int grid = a.nseq * (a.dim / WAVE);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_stream_scan_chunk_peeks<T, SP, HAS_Z>), (scanc_var_wave<T, SP, HAS_Z, false, true>(a, wg, pe)), a, pe);
+}
+template <class T> static int scancp_dispatch_t(const AumScanTmChunkVarArgs& a, int pe, aum_stream_t s) {
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        return with_bool(a.z != nullptr, [&](auto hz) { return scancp_launch<T, sp, hz>(a, pe, s); }); });
+}
+AUM_API int aum_scan_tm_chunk_peeks(const AumScanTmChunkPeeksArgs* pa, void* stream) {
+    if (!pa) return AUM_E_NULL;
+    const AumScanTmChunkVarArgs* a = &pa->base;
+    const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
+    if (const int rc = scan_stream_check(*a, &var, pa->peek_every >= 1, a->total, AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED, true, a->nseq, false)) return rc;
+    const AumScanTmChunkVarArgs k = scan_tm_fwd_resolve(*a);
+    aum_stream_t s = (aum_stream_t)stream;
+    return AUM_BY_DTYPE_T(k.dtype, scancp_dispatch_t, k, (int)pa->peek_every, s);
 }
 
 // ---- conv -> x/dt projections -> scan of packed sessions in one launch (stream_block_kernels.h) ----

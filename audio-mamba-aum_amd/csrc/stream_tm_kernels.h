@@ -34,6 +34,16 @@
 // exit as exact fp32, so the result is bit for bit a call on rows 0 .. L - 2 followed by an uncommitted call on row L - 1.  PEEK is a
 // template parameter because scanc_unit fills the scalar file: with PEEK == false every added expression folds away and the existing
 // kernels compile to what they were; the PEEK kernels are instantiations of their own.
+//
+// PEEK ROWS EVERY P ROWS (template parameter PEEKS of the two units with the period `pe` = P >= 1; aum_conv1d_tm_chunk_peeks /
+// aum_scan_tm_chunk_peeks): row j of a sequence (counted from its first row in the call) is a peek row iff (j + 1) % (P + 1) == 0 -- a
+// cls row behind every time column of a clip, all columns in one pass.  All L rows go through the block loop and the SAME `step`; a peek
+// row's step leaves the carried registers alone: the conv does not move the window, the scan steps into temporaries (the vfma2 results
+// the output is summed from) and does not copy them back.  Which rows those are depends on the row index only (a wave-uniform scalar:
+// the index of the next peek row, moved on by P + 1 behind each), so a row is the same instruction sequence on the same fp32 values
+// whether it commits or not, and per sequence y and the cache row are bit for bit the chain of PEEK (PEEK_LAST) calls on one group of
+// P + 1 rows after the other, then a plain call on the trailing partial group.  The exit stores stay behind the loop and the fetch
+// scheme is unchanged.  With PEEKS == false the added expressions fold away (as for PEEK); PEEK and PEEKS are never set together.
 #pragma once
 #include "conv_tm_kernels.h"
 #include "scan_tm_kernels.h"
@@ -53,8 +63,10 @@ struct ConvcOps {
 // unit = (sequence, block of 64 * V channels): L >= 1 rows at x / y (row stride x_ts / y_ts elements), the sequence's cache row `win`.
 // commit == false (aum_stream_block_tm with AUM_STREAM_NO_COMMIT): the cache row is read and not written -- the exit stores are skipped
 // PEEK: row L - 1 is a peek row -- LC = L - 1 rows go through the loop and into the cache, the last one is stepped behind the exit stores
-template <class T, bool SILU, bool PEEK = false>
-AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb, bool commit = true) {
+// PEEKS: every (pe + 1)-th row is a peek row -- all L rows go through the loop, a peek row's step does not move the window
+template <class T, bool SILU, bool PEEK = false, bool PEEKS = false>
+AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, int L, int cb, bool commit = true, int pe = 0) {
+    static_assert(!(PEEK && PEEKS), "one peek row behind the rows, or one every pe rows");
     constexpr int V = convt_vec<T, false>(), NP = V / 2, ES = (int)sizeof(T), W = CONVT_W;
     AumConvTmArgs s = {};
     s.weight = a.weight;
@@ -101,8 +113,9 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
             raw[j] = convt_load<T, false>(xb, coff, it * x_tb);
         }
     };
-    // one step: y = act(bias + w0 x[t-3] + w1 x[t-2] + w2 x[t-1] + w3 x[t]) in that order, then the window moves by one row
-    auto step = [&](int it, const convt_raw<T, false>& raw) {
+    // one step: y = act(bias + w0 x[t-3] + w1 x[t-2] + w2 x[t-1] + w3 x[t]) in that order, then the window moves by one row (adv; a
+    // peek row of PEEKS leaves it where it is)
+    auto step = [&](int it, const convt_raw<T, false>& raw, bool adv) {
         vf2 xn[NP];
         unpack2(raw, xn);
         vf y[V];
@@ -115,17 +128,24 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
             if (SILU) acc = acc * vsigmoid2(acc);
             y[2 * p] = lo2(acc);
             y[2 * p + 1] = hi2(acc);
-            AUM_UNROLL
-            for (int k = 0; k < W - 1; ++k) xr[k][p] = xr[k + 1][p];
-            xr[W - 1][p] = xn[p];
+            if (!PEEKS || adv) {
+                AUM_UNROLL
+                for (int k = 0; k < W - 1; ++k) xr[k][p] = xr[k + 1][p];
+                xr[W - 1][p] = xn[p];
+            }
         }
         if (all_live) convt_store<T, false>(yb, coff, it * y_tb, y);
         else convt_store_m<T, false>(yb, coff, it * y_tb, y, ln.live);
     };
+    int next_peek = pe;                         // PEEKS: the index of the next peek row
     auto comp_blk = [&](int itb, const convt_raw<T, false> (&raw)[STREAM_UB]) {
         AUM_UNROLL
         for (int j = 0; j < STREAM_UB; ++j) {
-            if (itb + j < LC) step(itb + j, raw[j]);
+            if (itb + j < LC) {
+                const bool pk = PEEKS && itb + j == next_peek;
+                if (pk) next_peek += pe + 1;
+                step(itb + j, raw[j], !pk);
+            }
         }
     };
     convt_raw<T, false> ra[STREAM_UB], rb[STREAM_UB], rp;
@@ -151,7 +171,7 @@ AUM_DEV void convc_unit(const ConvcOps& a, const T* x, const T* y, float* win, i
             }
         }
     }
-    if (PEEK) step(L - 1, rp);
+    if (PEEK) step(L - 1, rp, true);
 }
 
 // fixed batch: unit = (batch entry, channel block), channel block fastest
@@ -175,15 +195,15 @@ AUM_DEV bool stream_seq(const int32_t* cu_seqlens, const int32_t* state_indices,
 }
 
 // packed sessions: unit = (sequence, channel block), channel block fastest
-template <class T, bool SILU, bool PEEK = false>
-AUM_DEV void convc_var_wave(const AumConvTmChunkVarArgs& a, int wg) {
+template <class T, bool SILU, bool PEEK = false, bool PEEKS = false>
+AUM_DEV void convc_var_wave(const AumConvTmChunkVarArgs& a, int wg, int pe = 0) {
     const int ncb = convt_cblocks<T, false>(a.dim);
     const int cb = wg % ncb, i = wg / ncb;
     int r0, len, row;
     if (!stream_seq(a.cu_seqlens, a.state_indices, i, a.total, a.nrows, r0, len, row)) return;
     const ConvcOps o = {a.weight, a.bias, a.x_ts, a.y_ts, a.dim, a.width};
-    convc_unit<T, SILU, PEEK>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), row_ptr<T>(a.y, (int64_t)r0 * a.y_ts),
-                              a.conv_state + (int64_t)row * a.dim * a.width, len, cb);
+    convc_unit<T, SILU, PEEK, PEEKS>(o, row_ptr<T>(a.x, (int64_t)r0 * a.x_ts), row_ptr<T>(a.y, (int64_t)r0 * a.y_ts),
+                                     a.conv_state + (int64_t)row * a.dim * a.width, len, cb, true, pe);
 }
 
 // ---- scan ---------------------------------------------------------------------------------------
@@ -204,8 +224,10 @@ template <class T> struct ScancSeq {
 // unit = (sequence, group of 64 channels from e0).  SP: delta = softplus(delta + bias); otherwise delta + bias (an activated delta comes
 // with bias == NULL: the launcher drops it).  commit == false: the state row is read and not written (the exit stores are skipped).
 // PEEK: row L - 1 is a peek row -- LC = L - 1 rows go through the loop and into the state, the last one is stepped behind the exit stores
-template <class T, bool SP, bool HAS_Z, bool PEEK = false>
-AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true) {
+// PEEKS: every (pe + 1)-th row is a peek row -- all L rows go through the loop, a peek row's step does not take its result into the state
+template <class T, bool SP, bool HAS_Z, bool PEEK = false, bool PEEKS = false>
+AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true, int pe = 0) {
+    static_assert(!(PEEK && PEEKS), "one peek row behind the rows, or one every pe rows");
     constexpr int N = SCANT_N, ES = (int)sizeof(T);
     const int L = q.len;
     const int LC = PEEK ? L - 1 : L;             // the rows the state takes in
@@ -250,14 +272,15 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
     };
     // one step (the arithmetic of scant_fwd_run's `step`, stage by stage over the eight state pairs):
     //   dl = softplus?(delta + bias);  a = exp2(dl A log2e);  x = a x + (dl u) B;  y = <x, C> + D u;  out = y z sigmoid(z)
-    auto step = [&](int it, const ScancRaw& r) {
+    // The new state is formed in xn and the output summed from it; adv: it becomes the state (a peek row of PEEKS drops it)
+    auto step = [&](int it, const ScancRaw& r, bool adv) {
         vf dl = raw_to_f32<T>(r.d) + biasv;
         if (SP) dl = vsoftplus(dl);
         const vf uu = raw_to_f32<T>(r.u);
         const vf du = dl * uu;
         const vf bv = raw_to_f32<T>(r.b), cv = raw_to_f32<T>(r.c);
         const vf2 dl2 = spl2(dl), du2 = spl2(du);
-        vf2 a[N / 2], Bp[N / 2], Cp[N / 2];
+        vf2 a[N / 2], Bp[N / 2], Cp[N / 2], xn[N / 2];
         AUM_UNROLL
         for (int j = 0; j < N / 2; ++j) {
             Bp[j] = mk2(splat(readlane(bv, 2 * j)), splat(readlane(bv, 2 * j + 1)));
@@ -276,24 +299,33 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
         for (int j = 0; j < N / 2; ++j) a[j] = vexp2_2(a[j]);
         if (HAS_Z) ez = vexp2(ez);
         AUM_UNROLL
-        for (int j = 0; j < N / 2; ++j) x[j] = vfma2(a[j], x[j], Bp[j]);
+        for (int j = 0; j < N / 2; ++j) xn[j] = vfma2(a[j], x[j], Bp[j]);
         vf sg = splat(1.f);
         if (HAS_Z) sg = vrcp(ez + 1.0f);
         vf2 y2[4];
         AUM_UNROLL
-        for (int j = 0; j < 4; ++j) y2[j] = x[j] * Cp[j];
+        for (int j = 0; j < 4; ++j) y2[j] = xn[j] * Cp[j];
         AUM_UNROLL
-        for (int j = 4; j < N / 2; ++j) y2[j & 3] = vfma2(x[j], Cp[j], y2[j & 3]);
+        for (int j = 4; j < N / 2; ++j) y2[j & 3] = vfma2(xn[j], Cp[j], y2[j & 3]);
+        if (!PEEKS || adv) {
+            AUM_UNROLL
+            for (int j = 0; j < N / 2; ++j) x[j] = xn[j];
+        }
         const vf2 ysum = (y2[0] + y2[1]) + (y2[2] + y2[3]);
         const vf ys = lo2(ysum) + hi2(ysum);
         vf tot = vfma(uu, Dv, ys);
         if (HAS_Z) tot = tot * (zz * sg);
         gbuf_store(obuf, el_off, it * o_tb, tot);
     };
+    int next_peek = pe;                         // PEEKS: the index of the next peek row
     auto comp_blk = [&](int itb, const ScancRaw (&raw)[STREAM_UB]) {
         AUM_UNROLL
         for (int j = 0; j < STREAM_UB; ++j) {
-            if (itb + j < LC) step(itb + j, raw[j]);
+            if (itb + j < LC) {
+                const bool pk = PEEKS && itb + j == next_peek;
+                if (pk) next_peek += pe + 1;
+                step(itb + j, raw[j], !pk);
+            }
         }
     };
     ScancRaw ra[STREAM_UB], rb[STREAM_UB];
@@ -321,7 +353,7 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
             gbuf_store16(sbuf, st_off + 16 * i, 0, vq_pack<float>(t));
         }
     }
-    if (PEEK) step(L - 1, rp);
+    if (PEEK) step(L - 1, rp, true);
 }
 
 // fixed batch: unit = (batch entry, group of 64 channels), channel group fastest
@@ -338,8 +370,8 @@ AUM_DEV void scanc_wave(const AumScanTmChunkArgs& p, int wg) {
 }
 
 // packed sessions: unit = (sequence, group of 64 channels), channel group fastest
-template <class T, bool SP, bool HAS_Z, bool PEEK = false>
-AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg) {
+template <class T, bool SP, bool HAS_Z, bool PEEK = false, bool PEEKS = false>
+AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg, int pe = 0) {
     const int ngrp = p.dim / WAVE;
     const int e0 = (wg % ngrp) * WAVE, i = wg / ngrp;
     int r0, len, row;
@@ -349,7 +381,7 @@ AUM_DEV void scanc_var_wave(const AumScanTmChunkVarArgs& p, int wg) {
                            HAS_Z ? row_ptr<T>(p.z, (int64_t)r0 * p.z_ts) : nullptr, row_ptr<T>(p.B, (int64_t)r0 * p.B_ts),
                            row_ptr<T>(p.C, (int64_t)r0 * p.C_ts), row_ptr<T>(p.out, (int64_t)r0 * p.out_ts),
                            p.state + (int64_t)row * p.dim * SCANT_N, len};
-    scanc_unit<T, SP, HAS_Z, PEEK>(o, q, e0);
+    scanc_unit<T, SP, HAS_Z, PEEK, PEEKS>(o, q, e0, true, pe);
 }
 
 }  // namespace aum

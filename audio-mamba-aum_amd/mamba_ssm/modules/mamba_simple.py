@@ -287,7 +287,7 @@ class Mamba(nn.Module):
             Bo, activated = R, False                                            # ... x_proj's are not
         return delta, proj[:, Bo:Bo + N], proj[:, Bo + N:Bo + 2 * N], activated
 
-    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True, peek=False):
+    def step_chunk(self, hidden_states, conv_state, ssm_state, seq_map=None, commit=True, peek=False, peek_every=None):
         """T >= 1 tokens of streaming inference for the causal block in one pass: (batch, T, d_model) in, (batch, T, d_model) out, the
         caches advanced in place by T tokens -- what T calls of step() compute, with the projections as one small GEMM each and the
         recurrent middle as ONE launch where aum_hip.stream_block takes the shapes (16-bit activations, fp32 caches, the widths of
@@ -306,10 +306,16 @@ class Mamba(nn.Module):
         peek=True: the LAST row of every session (of the T rows without seq_map) is a peek row -- it runs through the block like any
         other row and its output is returned, and the caches are advanced by the rows before it only (a cls row behind a hop's tokens:
         it sees the state they produced, the next hop does not see it).  One launch with the flag where the one-launch path takes the
-        shapes -- the peek row counts towards its 128 -- else the ladder with the two flags; both give the same bits at the kernels."""
+        shapes -- the peek row counts towards its 128 -- else the ladder with the two flags; both give the same bits at the kernels.
+        peek_every=P (an int >= 1; not with peek=True or commit=False): a peek row behind every P committed rows of every session -- row j
+        of a session is a peek row iff (j + 1) % (P + 1) == 0 (the cls row behind every time column: AudioMamba.stream_timeline).  Always
+        the ladder, conv and scan through aum_hip.conv1d_tm_chunk_peeks / scan_tm_chunk_peeks (the one-launch kernel has no peek
+        period); the caches are bit for bit those of peek=True calls on one group of P + 1 rows after the other."""
         import aum_hip
         if self.bimamba_type != "none":
             raise NotImplementedError("inference caches only make sense for the causal (bimamba_type='none') block")
+        if peek_every is not None and (peek or not commit):
+            raise ValueError("step_chunk(peek_every=) excludes peek=True and commit=False")
         if seq_map is not None:
             if not self._check_packed("step_chunk", hidden_states, conv_state, ssm_state, seq_map):
                 return hidden_states.new_empty(hidden_states.shape), conv_state, ssm_state
@@ -320,18 +326,19 @@ class Mamba(nn.Module):
         xz = self.in_proj(hidden_states.reshape(batch * T, -1)).view(batch, T, 2 * E)
         x, z = xz[..., :E], xz[..., E:]
         plan = self.stream_params(xz.dtype)
-        if self.stream_block_ok(xz, conv_state, ssm_state, plan, seq_map):
+        if peek_every is None and self.stream_block_ok(xz, conv_state, ssm_state, plan, seq_map):
             y = aum_hip.stream_block(x if seq_map is None else x[0], z if seq_map is None else z[0], conv_state, ssm_state, plan,
                                      seq_map=seq_map, commit=commit, peek=peek)
             return self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1), conv_state, ssm_state
         if not commit:
             raise NotImplementedError("step_chunk(commit=False) needs the one-launch path (aum_hip.stream_block_supported)")
-        xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map, peek=peek)
+        xc = aum_hip.conv1d_stream(x, conv_state, plan.conv_w, plan.conv_b, self.activation in ("silu", "swish"), seq_map, peek=peek,
+                                   peek_every=peek_every)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         delta, Bm, Cm, activated = self._xdt_stage(xc.reshape(batch * T, E), plan)
         y = aum_hip.scan_stream(ssm_state, xc, delta.view(batch, T, E), plan.A, Bm.view(batch, T, N), Cm.view(batch, T, N), plan.D, z,
-                                plan.dt_bias, True, activated, seq_map, peek=peek)
+                                plan.dt_bias, True, activated, seq_map, peek=peek, peek_every=peek_every)
         out = self.out_proj(y.reshape(batch * T, E)).view(batch, T, -1)
         return out, conv_state, ssm_state
 

@@ -681,6 +681,27 @@ typedef struct AumScanTmChunkVarArgs {
 int aum_scan_tm_chunk_var(const AumScanTmChunkVarArgs* args, void* stream);
 
 /*
+ * PEEK ROWS EVERY P ROWS (additive to ABI 13; `Mamba.step_chunk(..., peek_every=)`, `AudioMamba.stream_timeline`): the packed entry
+ * points above with an uncommitted row behind every P = peek_every >= 1 committed rows -- the cls row behind every time column of a
+ * clip, "what would the logits be if the clip ended now" after each column, all in one pass.
+ *   Within every sequence, row j (0-based, counted from the sequence's first row IN THIS CALL) is a peek row iff (j + 1) % (P + 1) == 0.
+ *   A peek row is computed and stored like any other row (conv: from the window of the last committed inputs plus its own input; scan:
+ *   one step from the current state, then the gate) and neither shifts the window nor updates the state: on exit the cache row holds what
+ *   the committed rows alone produce.  A length that is not a multiple of P + 1 is fine (the trailing rows are committed rows); a
+ *   sequence shorter than P + 1 has no peek row.
+ *   Per sequence, y and the cache row are BIT FOR BIT what aum_*_tm_chunk_var gives when the sequence is cut into groups of P + 1 rows,
+ *   called with AUM_*_PEEK_LAST on one full group after the other and once more, without the flag, on the trailing partial group (the
+ *   kernels run the same step routine; whether a row commits depends on its index only).
+ *   `base`: every field, flag, dtype and limit of aum_conv1d_tm_chunk_var / aum_scan_tm_chunk_var, the no-op rules for empty sequences
+ *   and for out-of-range rows or pairs, and the 32-bit cursor limit on `total`.  Refused with nothing touched: peek_every < 1
+ *   (AUM_E_SHAPE); base.flags carrying AUM_CONV_PEEK_LAST / AUM_SCAN_PEEK_LAST (AUM_E_UNSUPPORTED).  reserved: 0.
+ */
+typedef struct AumConvTmChunkPeeksArgs { AumConvTmChunkVarArgs base; int32_t peek_every; int32_t reserved; } AumConvTmChunkPeeksArgs;
+typedef struct AumScanTmChunkPeeksArgs { AumScanTmChunkVarArgs base; int32_t peek_every; int32_t reserved; } AumScanTmChunkPeeksArgs;
+int aum_conv1d_tm_chunk_peeks(const AumConvTmChunkPeeksArgs* args, void* stream);
+int aum_scan_tm_chunk_peeks(const AumScanTmChunkPeeksArgs* args, void* stream);
+
+/*
  * The recurrent middle of the causal block on packed sessions in ONE launch (additive to ABI 13; `Mamba.step_chunk` through
  * aum_hip.stream_block): from the x half of the in_proj rows to the gated scan output,
  *     xc = silu(conv(x) from conv_state);  x_dbl = xc . wx^T;  delta = softplus(x_dbl[:, :rank] . wdt^T + delta_bias);

@@ -41,6 +41,13 @@ loop of S batch-1 passes, (b) stream_prefill_many(packed=True), one packed pass.
 discarded, medians of all calls and of the groups, min / max.
 
     python tools/stream_hop_bench.py --prefill-pool 8 --prefill 64   (--count-only a: the loop, b: the packed pass)
+
+--timeline COLS: the logits after EVERY one of COLS time columns of a new session two ways, same model, same columns, alternating in one
+process: (a) the loop of COLS single-column stream_push(read=True) calls (one pass per column), (b) one stream_timeline of the COLS
+columns (one pass over COLS x 9 rows, the cls row behind every column as a peek row).  One timed call is the whole clip piece in both
+arms.  Same method: HIP events around each call, warm calls discarded, medians of all calls and of the groups, min / max.
+
+    python tools/stream_hop_bench.py --timeline 64 [--batch 1]       (--count-only a: the per-column loop, b: stream_timeline)
 """
 import argparse
 import contextlib
@@ -215,6 +222,47 @@ def prefill_ab(model, args, dev):
             out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
             out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
         out["ratio_push_over_prefill"] = round(out["push_ms_median"] / out["prefill_ms_median"], 3)
+        print(json.dumps(out), flush=True)
+
+
+def timeline_loop(model, spec, cache):
+    cache["columns"] = 0                          # a new session every call: the caches' values do not matter for timing
+    return [model.stream_push(spec[:, 16 * j:16 * (j + 1)], cache, read=True)[1] for j in range(spec.shape[1] // 16)]
+
+
+def timeline_one_pass(model, spec, cache):
+    cache["columns"] = 0
+    return model.stream_timeline(spec, cache)[1]
+
+
+def timeline_ab(model, args, dev):
+    """--timeline COLS: the logits after every one of COLS columns as COLS stream_push(read=True) calls (a) against one stream_timeline (b)"""
+    arms = (("loop", timeline_loop), ("timeline", timeline_one_pass))
+    for B in args.batch:
+        spec = torch.randn(B, 16 * args.timeline, 128, device=dev, dtype=torch.bfloat16)
+        caches = [model.allocate_inference_cache(B) for _ in arms]
+        if args.count_only:
+            i = 0 if args.count_only == "a" else 1
+            for _ in range(args.count_hops):
+                arms[i][1](model, spec, caches[i])
+            torch.cuda.synchronize()
+            print(json.dumps({"path": "timeline " + arms[i][0], "batch": B, "columns": args.timeline, "hops": args.count_hops}))
+            continue
+        for _ in range(args.warm):
+            for (_, fn), c in zip(arms, caches):
+                timed(fn, model, spec, c)
+        times = [[] for _ in arms]
+        for _ in range(args.hops):
+            for t, (_, fn), c in zip(times, arms, caches):
+                t.append(timed(fn, model, spec, c))
+        g = max(args.hops // args.groups, 1)
+        out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "batch": B, "columns": args.timeline, "rows_one_pass": 9 * args.timeline,
+               "clip_columns": model.patch_grid_size[1], "hops": args.hops, "warm": args.warm}
+        for (name, _), t in zip(arms, times):
+            out[name + "_ms_median"] = round(statistics.median(t), 4)
+            out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+            out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+        out["ratio_loop_over_timeline"] = round(out["loop_ms_median"] / out["timeline_ms_median"], 3)
         print(json.dumps(out), flush=True)
 
 
@@ -394,9 +442,15 @@ def main():
     ap.add_argument("--prefill", type=int, default=0, metavar="COLS", help="a backlog of COLS columns: one stream_push vs one stream_prefill")
     ap.add_argument("--prefill-pool", type=int, default=0, metavar="S",
                     help="with --prefill COLS: S sessions with backlogs of COLS, COLS / 2, ... columns, stream_prefill_many as a host loop vs packed")
+    ap.add_argument("--timeline", type=int, default=0, metavar="COLS",
+                    help="the logits after every one of COLS columns: COLS stream_push(read=True) calls vs one stream_timeline")
     args = ap.parse_args()
     dev = "cuda:0"
-    model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill))
+    model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill, 16 * args.timeline))
+    if args.timeline:
+        with torch.no_grad():
+            timeline_ab(model, args, dev)
+        return
     if args.prefill_pool:
         if not args.prefill:
             ap.error("--prefill-pool S needs --prefill COLS")
