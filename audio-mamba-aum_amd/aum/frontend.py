@@ -67,6 +67,47 @@ class WaveInput:
                                  noise=self.noise)
 
 
+class WaveStream:
+    """What streaming from raw audio carries between pushes (AudioMamba.allocate_wave_stream builds it, stream_push_wave* advance it):
+    the pool of sample tails -- one (win + 15 shift) row per session, the samples neighbouring frames share plus those of a column
+    that is not whole yet -- and per session, on the host, the tail length, the samples pushed, the frames emitted and `ended`.
+    A separate object: the caches and pools of the model keep their keys.  A push holds every frame to the bits of fbank_fwd on the
+    whole clip.  The offline loader subtracts the clip's mean first (dataloader.py:101), which a stream cannot know: the kernel removes
+    each frame's own mean before anything else, so a constant offset cancels in exact arithmetic and to rounding in fp32 (DESIGN.md
+    states the measured residual)."""
+
+    def __init__(self, sessions, frontend, target_length, device):
+        if int(sessions) < 1:
+            raise ValueError("WaveStream: at least one session")
+        if not isinstance(frontend, WaveInput):
+            raise TypeError("WaveStream: frontend must be an aum.frontend.WaveInput")
+        if frontend.aug is not None or frontend.noise is not None:
+            raise ValueError("WaveStream: augmentation and noise are not applied to streams (frontend.aug / frontend.noise must be None)")
+        if frontend.target_length != target_length:
+            raise ValueError(f"WaveStream: the frontend pads clips to target_length {frontend.target_length}, the model's clip has {target_length} frames")
+        t = frontend.tables.tables
+        if t["padded"] != 512:
+            raise ValueError(f"WaveStream: streaming log-mel takes the padded == 512 tables (16 kHz, 25 ms windows), got padded {t['padded']}")
+        self.frontend, self.sessions, self.target_length = frontend, int(sessions), int(target_length)
+        self.win, self.shift = t["win"], t["shift"]
+        self.cap = self.win + 15 * self.shift
+        self.max_samples = self.win + (self.target_length - 1) * self.shift          # the samples of a clip's frame grid
+        self.tails = torch.zeros((self.sessions, self.cap), dtype=torch.float32, device=device)
+        self.tail_len = [0] * self.sessions
+        self.samples = [0] * self.sessions
+        self.frames = [0] * self.sessions
+        self.ended = [False] * self.sessions
+
+    def reset(self, sessions):
+        """the rows are free for new clips (next to AudioMamba.stream_reset of the pool); the tail rows need no clearing: a row is read
+        up to its tail length only"""
+        rows = [int(r) for r in sessions]
+        if rows and (min(rows) < 0 or max(rows) >= self.sessions):
+            raise ValueError(f"WaveStream.reset: the sessions {rows} are not all rows of a stream of {self.sessions}")
+        for r in rows:
+            self.tail_len[r], self.samples[r], self.frames[r], self.ended[r] = 0, 0, 0, False
+
+
 def prepare_wave(wave, n_valid, tables, aug=None):
     """Mean removal (dataloader.py:101) and, for ragged batches, the per-clip frame counts in column 0 of the augmentation
     table: the host-side half of wav2fbank / wav2fbank_ragged, shared with the one-launch path."""

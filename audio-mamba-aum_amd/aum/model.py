@@ -493,6 +493,125 @@ class AudioMamba(nn.Module):
         hidden, residual = self._stream_layers(x, cache["layers"], peek=True)
         return self._commit_columns(cache, [k], None), self._head_rows(hidden[:, -1], residual[:, -1], return_features)
 
+    # ---- streaming from raw audio: PCM hops of any size, the log-mel stage carried by a WaveStream ----
+    def allocate_wave_stream(self, sessions, frontend):
+        """The state stream_push_wave / stream_push_wave_many carry next to a cache of `sessions` rows (allocate_inference_cache or
+        allocate_stream_pool): an aum.frontend.WaveStream -- the pool of sample tails and the host counters.  frontend: an
+        aum.frontend.WaveInput without aug / noise whose target_length is the model's clip (16 n_t frames), padded == 512 tables."""
+        from .frontend import WaveStream
+        self._check_streamable()
+        return WaveStream(sessions, frontend, self.patch_embed.proj.kernel_size[1] * self.patch_grid_size[1], self.pos_embed.pos_embed.device)
+
+    def _plan_wave(self, what, waves, cache, wave_stream, rows, end):
+        """The checks of a push of raw audio, made before anything is touched -> the aum_hip.WaveMap of the call (host lists checked, one
+        upload) and the whole new columns of every session.  waves[i] (m_i,) fp32 on the tails' device for row rows[i] (rows None: row i)."""
+        import aum_hip
+        from .frontend import WaveStream
+        ws = wave_stream
+        if not isinstance(ws, WaveStream):
+            raise TypeError(f"{what}: wave_stream must come from allocate_wave_stream")
+        if ws.sessions != cache["batch"]:
+            raise ValueError(f"{what}: the wave stream was built for {ws.sessions} sessions, the cache has {cache['batch']} rows")
+        pw, (nf, nt) = self.patch_embed.proj.kernel_size[1], self.patch_grid_size
+        if ws.target_length != pw * nt or ws.frontend.tables.tables["mel_w"].shape[0] // self.patch_embed.proj.kernel_size[0] != nf:
+            raise ValueError(f"{what}: the wave stream was built for clips of {ws.target_length} frames, the model's clip has {pw * nt}")
+        idx = list(range(len(waves))) if rows is None else rows
+        ends = [bool(end)] * len(idx) if isinstance(end, (bool, int)) else [bool(e) for e in end]
+        if len(ends) != len(idx):
+            raise ValueError(f"{what}: one end flag per session, got {len(ends)} for {len(idx)} sessions")
+        ms, frames, n_real = [], [], []
+        for w, r, e in zip(waves, idx, ends):
+            if not torch.is_tensor(w) or w.dim() != 1 or w.dtype != torch.float32 or w.device != ws.tails.device:
+                got = f"{tuple(w.shape)} {w.dtype} on {w.device}" if torch.is_tensor(w) else type(w).__name__
+                raise ValueError(f"{what} takes (samples,) fp32 on {ws.tails.device} per session, got {got} for session {r}")
+            if ws.ended[r]:
+                raise ValueError(f"{what}: the clip of session {r} has ended; stream_reset and wave_stream.reset free the row")
+            done = cache["columns"][r] if self._is_pool(cache) else cache["columns"]
+            if done * pw != ws.frames[r]:
+                raise ValueError(f"{what}: session {r} has {done} columns in the cache and {ws.frames[r]} frames in the wave stream: they "
+                                 "do not belong together")
+            n = ws.samples[r] + w.shape[0]
+            if n > ws.max_samples:
+                raise ValueError(f"the clip has {ws.max_samples} samples ({nt} time columns): session {r} pushed {ws.samples[r]}, "
+                                 f"{w.shape[0]} more do not fit")
+            avail = 0 if n < ws.win else 1 + (n - ws.win) // ws.shift
+            ms.append(w.shape[0])
+            frames.append(ws.target_length - ws.frames[r] if e else (avail - ws.frames[r]) // pw * pw)
+            n_real.append(avail if e else -1)
+        wmap = aum_hip.wave_map(ms, [ws.tail_len[r] for r in idx], frames, [ws.frames[r] for r in idx], n_real, rows, device=ws.tails.device,
+                                win=ws.win, shift=ws.shift)
+        return wmap, [f // pw for f in frames], ends
+
+    def _wave_frames(self, wave, wmap, wave_stream, idx, ends):
+        """the one fbank_stream launch of a push and the host counters behind it -> the new frames (total, n_mels)"""
+        import aum_hip
+        ws, fe = wave_stream, wave_stream.frontend
+        frames = aum_hip.fbank_stream(wave, wmap, ws.tails, fe.tables.tables, fe.norm_mean, fe.norm_std)
+        for i, r in enumerate(idx):
+            ws.tail_len[r], ws.samples[r], ws.frames[r] = wmap.new_tail_lens[i], ws.samples[r] + wmap.samples[i], ws.frames[r] + wmap.frames[i]
+            ws.ended[r] = ws.ended[r] or ends[i]
+        return frames.to(self.patch_embed.proj.weight.dtype)        # a model held in 16 bits takes its frames in 16 bits (no-op in fp32)
+
+    @torch.no_grad()
+    def stream_push_wave_many(self, waves, pool, wave_stream, sessions, read=False, end=False, return_features=False):
+        """stream_push_many from RAW AUDIO: waves[i] (m_i,) fp32 on the device, m_i >= 0 -- the next samples of the clip of session
+        sessions[i] (distinct rows of a pool from allocate_stream_pool), in hops of any size.  wave_stream (allocate_wave_stream) holds
+        what the hops leave over: the 240 samples neighbouring frames share and the samples of a column that is not whole yet.  The host
+        works out how many whole new columns k_i every session covers; their frames come from ONE fbank_stream launch (every frame
+        bit-identical to the same row of fbank_fwd on the whole clip, however the stream is cut), the sessions with k_i >= 1 go through
+        stream_push_many unchanged, the others only grow their tail.  Returns what stream_push_many returns, in the order of `sessions`;
+        with read=True a session without a new column is read by stream_read.
+        end (a bool, or one per session): the clip ends with these samples -- its remaining real frames (1 + (n - win) // shift of
+        the n samples pushed, none if n < win) and the padding rows up to the clip's 16 n_t frames are pushed, stream_read then equals the
+        model on fbank_fwd(whole wave, target_length), and the session refuses further pushes until stream_reset(pool, rows) and
+        wave_stream.reset(rows).  Samples beyond the clip's frame grid (n > win + (16 n_t - 1) shift) do not fit, with or without end.
+        Every argument is checked before anything is written: a refused call changes neither tails nor counters nor caches.
+        The offline loader subtracts the clip's mean before the kernel, which a stream cannot; the kernel removes each frame's own mean
+        first, so a constant offset cancels in exact arithmetic (the fp32 residual measured on a test tone is stated in DESIGN.md)."""
+        self._check_streamable()
+        rows = self._check_sessions("stream_push_wave_many", pool, sessions)
+        waves = list(waves)
+        if not rows or len(waves) != len(rows):
+            raise ValueError(f"stream_push_wave_many: one waveform piece per session, got {len(waves)} for the sessions {rows}")
+        wmap, ks, ends = self._plan_wave("stream_push_wave_many", waves, pool, wave_stream, rows, end)
+        frames = self._wave_frames(waves[0] if len(waves) == 1 else torch.cat(waves), wmap, wave_stream, rows, ends)
+        pieces = frames.split(list(wmap.frames), dim=0)
+        go = [i for i, k in enumerate(ks) if k >= 1]
+        out = None
+        if go:
+            out = self.stream_push_many([pieces[i] for i in go], pool, [rows[i] for i in go], read=read, return_features=return_features)
+        counts = [pool["columns"][r] for r in rows]
+        if not read:
+            return counts
+        if len(go) == len(rows):
+            return counts, out[1]
+        stay = [i for i, k in enumerate(ks) if k < 1]
+        quiet = self.stream_read(pool, return_features, sessions=[rows[i] for i in stay])
+        if not go:
+            return counts, quiet
+        order = torch.tensor(go + stay, dtype=torch.int64).argsort().to(quiet.device)
+        return counts, torch.cat((out[1].to(quiet.dtype), quiet), dim=0).index_select(0, order)
+
+    @torch.no_grad()
+    def stream_push_wave(self, wave, cache, wave_stream, read=False, end=False, return_features=False):
+        """stream_push from raw audio, the fixed-batch, lockstep form: wave (batch, m) fp32, the next m >= 0 samples of every row of a
+        cache from allocate_inference_cache; the same kernel as stream_push_wave_many under a map in which session b owns row b.  Whole
+        new columns go through stream_push; returns the columns pushed so far, with read=True (columns, logits) -- stream_read where no
+        column was completed.  end (one bool): the clips end here, as in stream_push_wave_many."""
+        self._check_streamable()
+        if self._is_pool(cache):
+            raise ValueError("stream_push_wave advances all rows of a cache from allocate_inference_cache together; a pool from "
+                             "allocate_stream_pool is advanced by stream_push_wave_many(waves, pool, wave_stream, sessions)")
+        if not torch.is_tensor(wave) or wave.dim() != 2 or wave.shape[0] != cache["batch"] or not isinstance(end, (bool, int)):
+            raise ValueError(f"stream_push_wave takes (batch={cache['batch']}, samples) fp32 and one end flag, got "
+                             f"{tuple(wave.shape) if torch.is_tensor(wave) else type(wave).__name__}")
+        wave = wave.contiguous()
+        wmap, ks, ends = self._plan_wave("stream_push_wave", list(wave), cache, wave_stream, None, end)
+        frames = self._wave_frames(wave.reshape(-1), wmap, wave_stream, range(wave.shape[0]), ends)
+        if ks[0] >= 1:
+            return self.stream_push(frames.reshape(wave.shape[0], wmap.frames[0], -1), cache, read=read, return_features=return_features)
+        return (cache["columns"], self.stream_read(cache, return_features)) if read else cache["columns"]
+
     def _with_cls_rows(self, x):
         """(B, K n_f, Dm) time-major tokens of K columns -> (B, K (n_f + 1), Dm): the cls row behind every column's n_f tokens"""
         nf = self.patch_grid_size[0]

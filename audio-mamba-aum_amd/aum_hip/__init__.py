@@ -154,6 +154,11 @@ class FrontendArgs(C.Structure):
                 + [("tokens_bs", _i64)] + [(n, _i32) for n in ("dim", "cls_pos", "dtype", "out_dtype")] + [("flags", _u32)])
 
 
+class FbankStreamArgs(C.Structure):
+    _fields_ = ([("fbank", FbankArgs)] + [(n, _vp) for n in ("cu_samples", "cu_frames", "tail_len", "idx", "first_frame", "n_real", "tails")]
+                + [(n, _i32) for n in ("total_samples", "total_frames", "nseq", "nrows", "cap", "reserved")])
+
+
 class ProjArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("act", "w_x", "w_dt", "x_dbl", "out_act", "dB", "dC")]
                 + [(n, _i64) for n in ("dB_bs", "dB_ns", "dC_bs", "dC_ns", "ntok")]
@@ -265,7 +270,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
-    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks")}
+    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -2025,6 +2030,126 @@ def _fill_fbank(a, lib, wave, tables, target_length, norm_mean, norm_std, preemp
         assert noise.shape == (batch, target_length, num_mel)
         lib.check_tensor(noise)
         a.noise = _ptr(noise)
+
+
+FBANK_STREAM_MAX_CAP = 2816     # FBS_MAX_CAP of csrc/fbank_kernels.h: the longest tail row the tail launch holds in registers
+
+
+class WaveMap(typing.NamedTuple):
+    """Where the sessions of one fbank_stream call are (wave_map builds it): session i brings samples[i] new samples behind the
+    tail_lens[i] it holds in pool row rows[i], gets frames[i] new frames from clip index first_frames[i] on (those with clip index >=
+    n_real[i] >= 0 are padding rows) and holds new_tail_lens[i] samples afterwards.  The host tuples, and the int32 device tensors the
+    kernels read (one buffer: cu_samples | cu_frames | tail_len | first_frame | n_real | idx)."""
+    samples: tuple
+    tail_lens: tuple
+    frames: tuple
+    first_frames: tuple
+    n_real: tuple
+    rows: tuple
+    new_tail_lens: tuple
+    cap: int
+    total_samples: int
+    total_frames: int
+    cu_samples: torch.Tensor
+    cu_frames: torch.Tensor
+    tail_len: torch.Tensor
+    first_frame: torch.Tensor
+    n_real_t: torch.Tensor
+    idx: typing.Optional[torch.Tensor]
+
+
+def wave_map(sample_counts, tail_lens, frame_counts, first_frames, n_real, rows=None, *, device, win=400, shift=160):
+    """Built once per push of raw audio: per session the new samples m_i >= 0, the samples its tail row holds (0 <= tail_len < cap =
+    win + 15 shift), its new frames >= 0 with the clip index of the first, the clip's real frame count (n_real < 0: no limit) and its
+    pool row (distinct, >= 0; None: session i owns row i) -- checked here, on the host: every real frame must lie inside the samples
+    there are (frames_i shift + (win - shift) <= tail_len_i + m_i), and the tail that remains must fit its row.  The five int32 arrays
+    the kernel reads (and the rows) go to `device` in ONE pinned, non-blocking upload, as seq_map's do."""
+    ms, tls, frs = tuple(int(n) for n in sample_counts), tuple(int(n) for n in tail_lens), tuple(int(n) for n in frame_counts)
+    ffs, nrs = tuple(int(n) for n in first_frames), tuple(int(n) for n in n_real)
+    n = len(ms)
+    cap = win + 15 * shift
+    if not n or not (len(tls) == len(frs) == len(ffs) == len(nrs) == n):
+        raise ValueError(f"wave_map: one entry per session in every list, got {len(ms)}, {len(tls)}, {len(frs)}, {len(ffs)}, {len(nrs)}")
+    if min(ms) < 0 or min(frs) < 0 or min(ffs) < 0:
+        raise ValueError(f"wave_map: sample counts, frame counts and first frames >= 0, got {ms}, {frs}, {ffs}")
+    if min(tls) < 0 or max(tls) >= cap:
+        raise ValueError(f"wave_map: a tail holds 0 <= tail_len < {cap} samples, got {tls}")
+    rws = tuple(range(n)) if rows is None else tuple(int(r) for r in rows)
+    if len(rws) != n or min(rws) < 0 or len(set(rws)) != n:
+        raise ValueError(f"wave_map: one pool row per session, distinct and >= 0, got {rws} for {n} sessions")
+    new_tls = []
+    for i in range(n):
+        have = tls[i] + ms[i]
+        real = frs[i] if nrs[i] < 0 else max(0, min(frs[i], nrs[i] - ffs[i]))
+        if real > 0 and real * shift + (win - shift) > have:
+            raise ValueError(f"wave_map: session {i} asks for {real} frames of {win} samples every {shift}, its tail and hop hold {have} samples")
+        keep = have - min(frs[i] * shift, have)
+        if keep >= cap:
+            raise ValueError(f"wave_map: session {i} would be left with {keep} samples, a tail row holds fewer than {cap}")
+        new_tls.append(keep)
+    cu_s, cu_f = [0], [0]
+    for m, f in zip(ms, frs):
+        cu_s.append(cu_s[-1] + m)
+        cu_f.append(cu_f[-1] + f)
+    if cu_s[-1] + cu_f[-1] >= 1 << 31:
+        raise ValueError("wave_map: too many samples")
+    host = torch.tensor(cu_s + cu_f + list(tls) + list(ffs) + list(nrs) + (list(rws) if rows is not None else []), dtype=torch.int32)
+    device = torch.device(device)
+    if device.type == "cuda":
+        host = host.pin_memory()
+    buf = host.to(device, non_blocking=True)
+    o = [0, n + 1, 2 * n + 2, 3 * n + 2, 4 * n + 2, 5 * n + 2]
+    return WaveMap(ms, tls, frs, ffs, nrs, rws, tuple(new_tls), cap, cu_s[-1], cu_f[-1], buf[o[0]:o[1]], buf[o[1]:o[2]], buf[o[2]:o[3]],
+                   buf[o[3]:o[4]], buf[o[4]:o[5]], buf[o[5]:] if rows is not None else None)
+
+
+def fbank_stream_supported(wave, tails, tables):
+    """the limits of aum_fbank_stream_fwd (include/aum_hip.h): the padded == 512 tables (16 kHz / 25 ms), packed fp32 samples (total,),
+    an fp32 contiguous (nrows >= 1, win + 15 shift <= 2816) pool of tails on the samples' device"""
+    cap = tables["win"] + 15 * tables["shift"]
+    return (tables["padded"] == 512 and wave.dim() == 1 and wave.dtype == torch.float32 and wave.is_contiguous()
+            and tails.dim() == 2 and tails.dtype == torch.float32 and tails.is_contiguous() and tails.shape[0] >= 1
+            and tails.shape[1] == cap <= FBANK_STREAM_MAX_CAP and tails.device == wave.device)
+
+
+def fbank_stream(wave, wmap, tails, tables, norm_mean, norm_std, preemph=0.97, aug=None, noise=None, lib=None):
+    """The new log-mel frames of several sessions from raw audio that arrives in hops of any size (aum_fbank_stream_fwd): wave
+    (total_samples,) fp32, the sessions' new samples behind one another; wmap from wave_map; tails (nrows, win + 15 shift) fp32, the pool
+    of carried samples -- the rows wmap names are rewritten IN PLACE (the last wmap.new_tail_lens[i] samples of [tail ; hop]), the
+    others are not touched.  Returns (wmap.total_frames, num_mel) fp32: every frame is bit-identical to the same row of fbank_fwd on
+    the whole waveform, however the stream was cut.  aug / noise: not in streams (refused)."""
+    lib = lib or get()
+    for t in (wave, tails):
+        lib.check_tensor(t)
+    if aug is not None or noise is not None or not fbank_stream_supported(wave, tails, tables):
+        raise RuntimeError(f"fbank_stream: unsupported operands wave {tuple(wave.shape)} {wave.dtype}, tails {tuple(tails.shape)} {tails.dtype}, "
+                           f"padded {tables['padded']}, aug {'set' if aug is not None else None}, noise {'set' if noise is not None else None} "
+                           "(need (total,) fp32 samples, an fp32 contiguous (nrows, win + 15 shift <= 2816) pool on their device, the padded == 512 "
+                           "tables, no aug, no noise)")
+    if not isinstance(wmap, WaveMap):
+        raise TypeError("fbank_stream: wmap must come from aum_hip.wave_map()")
+    if wmap.total_samples != wave.shape[0] or wmap.cap != tails.shape[1]:
+        raise ValueError(f"fbank_stream: wave_map describes {wmap.total_samples} samples and tails of {wmap.cap}, the call has {wave.shape[0]} and {tails.shape[1]}")
+    if max(wmap.rows) >= tails.shape[0]:
+        raise ValueError(f"fbank_stream: wave_map names pool row {max(wmap.rows)}, the pool has {tails.shape[0]} rows")
+    if wmap.cu_samples.device != wave.device:
+        raise RuntimeError(f"fbank_stream: wave_map lives on {wmap.cu_samples.device}, the samples on {wave.device}")
+    num_mel, stride = tables["mel_w"].shape
+    out = torch.empty((wmap.total_frames, num_mel), dtype=torch.float32, device=wave.device)
+    if wmap.total_samples == 0 and wmap.total_frames == 0:          # nothing arrives, nothing is due: the tails stay as they are
+        return out
+    a = FbankStreamArgs()
+    f = a.fbank
+    f.wave, f.out = _ptr(wave) if wave.shape[0] else None, _ptr(out) if wmap.total_frames else None
+    f.window, f.twiddle = _ptr(tables["window"]), _ptr(tables["twiddle"])
+    f.mel_start_f, f.mel_count_f, f.mel_w = _ptr(tables["mel_start_f"]), _ptr(tables["mel_count_f"]), _ptr(tables["mel_w"])
+    f.win, f.shift, f.padded, f.num_mel, f.mel_wstride = tables["win"], tables["shift"], tables["padded"], num_mel, stride
+    f.preemph, f.norm_mean, f.norm_inv2std, f.log_floor = preemph, norm_mean, 1.0 / (2.0 * norm_std), 1.1920928955078125e-07
+    a.cu_samples, a.cu_frames, a.tail_len = _ptr(wmap.cu_samples), _ptr(wmap.cu_frames), _ptr(wmap.tail_len)
+    a.first_frame, a.n_real, a.idx, a.tails = _ptr(wmap.first_frame), _ptr(wmap.n_real_t), _ptr(wmap.idx), _ptr(tails)
+    a.total_samples, a.total_frames, a.nseq, a.nrows, a.cap = wmap.total_samples, wmap.total_frames, len(wmap.samples), tails.shape[0], wmap.cap
+    _launch(lib.c.aum_fbank_stream_fwd, a, tails, lib, "fbank_stream", (len(wmap.samples), wmap.total_samples, wmap.total_frames))
+    return out
 
 
 TIME_WARP_COLS = 8     # columns of the per-clip time-warp table (include/aum_hip.h AUM_TIME_WARP_COLS)

@@ -939,4 +939,38 @@ AUM_API int aum_scan_tm_fwd_state_var(const AumScanTmFwdStateVarArgs* a, void* s
     if (r != AUM_OK) return r;
     return run(&sg, 0);
 }
+
+// ---- streaming log-mel (fbank_kernels.h): the new frames of many sessions from [carried tail ; hop], then the new tails ----
+#ifndef AUM_EMU
+__global__ __launch_bounds__(FBANK_THREADS) void k_fbank_stream(AumFbankStreamArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[FbankWLds::n];
+    fbank_stream_frames_wg(a, (int)blockIdx.x, lds);
+}
+__global__ __launch_bounds__(FBANK_THREADS) void k_fbank_stream_tail(AumFbankStreamArgs a) { fbank_stream_tail_wg(a, (int)blockIdx.x); }
+#endif
+AUM_API int aum_fbank_stream_fwd(const AumFbankStreamArgs* a, void* stream) {
+    if (!a) return AUM_E_NULL;
+    const AumFbankArgs& f = a->fbank;
+    if (!f.window || !f.twiddle || !f.mel_start_f || !f.mel_count_f || !f.mel_w || !a->cu_frames || !a->tail_len || !a->first_frame || !a->n_real || !a->tails)
+        return AUM_E_NULL;
+    if ((a->total_samples > 0 && !f.wave) || (a->total_frames > 0 && !f.out)) return AUM_E_NULL;
+    const int64_t work = (int64_t)a->total_samples + a->total_frames;
+    if (a->total_samples < 0 || a->total_frames < 0 || work > 0x7fffffff) return AUM_E_SHAPE;
+    // the packed map: the samples and the frames of a call are its rows (a call with neither has nothing to do and is refused)
+    const StreamVar var = {a->cu_samples, a->idx, (int)work, a->nseq, a->nrows};
+    if (const int rc = stream_var_check(&var)) return rc;
+    if (f.win <= 0 || f.shift <= 0 || f.num_mel <= 0 || f.mel_wstride <= 0 || a->cap <= 0) return AUM_E_SHAPE;
+    if (f.aug || f.noise || f.padded != FBW_N || f.win > FBW_N) return AUM_E_UNSUPPORTED;
+    if ((int64_t)a->cap != (int64_t)f.win + 15 * (int64_t)f.shift || a->cap > FBS_MAX_CAP) return AUM_E_UNSUPPORTED;
+    const uintptr_t maps = (uintptr_t)a->cu_frames | (uintptr_t)a->tail_len | (uintptr_t)a->first_frame | (uintptr_t)a->n_real;
+    if ((maps & 3) || (((uintptr_t)a->tails | (uintptr_t)f.wave | (uintptr_t)f.out) & 3)) return AUM_E_UNSUPPORTED;
+    aum_stream_t s = (aum_stream_t)stream;
+    if (a->total_frames > 0) {
+        const int rc = AUM_LAUNCH((a->total_frames + FBW_WG_FRAMES - 1) / FBW_WG_FRAMES, FBANK_THREADS, s, (FbankWLds{}), k_fbank_stream,
+                                  (fbank_stream_frames_wg(*a, wg, lds)), *a);
+        if (rc != AUM_OK) return rc;
+    }
+    // behind the frames on the same stream: the frame waves have read the old tails before any of them is rewritten
+    return AUM_LAUNCH(a->nseq, FBANK_THREADS, s, (NoLds{}), k_fbank_stream_tail, (fbank_stream_tail_wg(*a, wg)), *a);
+}
 #endif

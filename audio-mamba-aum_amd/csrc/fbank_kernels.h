@@ -211,9 +211,10 @@ AUM_DEV void dft8(vf (&re)[8], vf (&im)[8]) {
     }
 }
 
-// one frame on one wave; wl = this wave's FBW_WAVE_FLOATS strip
-template <class EMIT>
-AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const FbankAug& ag, const FbwTw& tw, float* wl, EMIT emit) {
+// one frame on one wave; wl = this wave's FBW_WAVE_FLOATS strip.  load(i, in) fetches sample i of the frame (0 <= i < win on the lanes of
+// `in`, 0 elsewhere): where a frame's samples live is the caller's, the arithmetic on them is this function's alone.
+template <class LOAD, class EMIT>
+AUM_DEV void fbank_frame_wave_from(const AumFbankArgs& p, int b, int frame, const FbankAug& ag, const FbwTw& tw, float* wl, LOAD load, EMIT emit) {
     const float pad_value = (0.f - p.norm_mean) * p.norm_inv2std;
     const float amp = ag.amp;
     const float* nz = (p.noise && amp != 0.f) ? p.noise + ((int64_t)b * p.target_length + frame) * p.num_mel : nullptr;
@@ -228,7 +229,6 @@ AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const Fba
         }
         return;
     }
-    const float* x = p.wave + (int64_t)b * p.wave_bs + (int64_t)frame * p.shift;
     float* xr = wl;
     float* xi = wl + FBW_XCH;
     vf re[8], im[8];
@@ -237,7 +237,7 @@ AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const Fba
     AUM_UNROLL
     for (int r = 0; r < 8; ++r) {
         const vi i = lane + 64 * r;
-        re[r] = gload(x, i, i < p.win);
+        re[r] = load(i, i < p.win);
         s = s + re[r];
     }
     const float mean = wave_sum(s) / (float)p.win;
@@ -246,7 +246,7 @@ AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const Fba
         const vi i = lane + 64 * r;
         const vm in = i < p.win;
         const vf cur = re[r] - mean;
-        const vf prv = gload(x, vmax_i(i - 1, 0), in) - mean;                 // i = 0: replicate (x[0] - c*x[0])
+        const vf prv = load(vmax_i(i - 1, 0), in) - mean;                     // i = 0: replicate (x[0] - c*x[0])
         const vf v = (cur - p.preemph * prv) * gload(p.window, i, in);
         re[r] = vsel(in, v, splat(0.f));
         im[r] = splat(0.f);
@@ -316,6 +316,13 @@ AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const Fba
     }
 }
 
+// the frame `frame` of clip b of a (batch, n_samples) waveform: samples [frame * shift, frame * shift + win) of its row
+template <class EMIT>
+AUM_DEV void fbank_frame_wave(const AumFbankArgs& p, int b, int frame, const FbankAug& ag, const FbwTw& tw, float* wl, EMIT emit) {
+    const float* x = p.wave + (int64_t)b * p.wave_bs + (int64_t)frame * p.shift;
+    fbank_frame_wave_from(p, b, frame, ag, tw, wl, [&](vi i, vm in) { return gload(x, i, in); }, emit);
+}
+
 // stand-alone log-mel kernel, wave-per-frame form: FBANK_NW waves x FBW_FPW consecutive frames each
 constexpr int FBW_FPW = 4;
 constexpr int FBW_WG_FRAMES = FBANK_NW * FBW_FPW;
@@ -345,6 +352,94 @@ AUM_DEV void fbank_frame(const AumFbankArgs& p, int wg, float* lds) {
     if (frame_out < 0) frame_out += p.target_length;
     float* out = p.out + (int64_t)b * p.out_bs + (int64_t)frame_out * p.num_mel;
     fbank_frame_core(p, b, frame, ag, lds, [&](vi m, vf v, vm ok) { gstore(out, m, v, ok); });
+}
+
+// =================================================================================================
+// Streaming log-mel (aum_fbank_stream_fwd): the new frames of several sessions, each from its virtual stream [carried tail ; hop].
+// Frame launch: one wavefront per frame, FBANK_NW x FBW_FPW consecutive rows of the packed output per workgroup, the twiddles loaded once
+// per wave, a frame's session found from cu_frames; the arithmetic is fbank_frame_wave_from's, only the sample fetch is this file's.
+// Tail launch (behind the frame launch on the same stream): one workgroup per session reads its new tail -- the last
+// tail_len + m - consumed samples of the virtual stream -- into registers, passes a workgroup barrier, then writes it to the row:
+// source and destination overlap, and no store is issued before every load of the workgroup has returned.
+// =================================================================================================
+constexpr int FBS_TAIL_R = 11;                                  // samples per thread of the tail launch
+constexpr int FBS_MAX_CAP = FBS_TAIL_R * FBANK_THREADS;         // 2816 >= win + 15 shift = 2800 at 16 kHz
+
+// session i of a call: its pool row and hop, their lengths, its frames.  false: an operand is out of range and nothing of the session
+// may be touched (aum_hip.wave_map refuses such maps on the host)
+struct FbsSeq { const float *tail, *hop; int tl, m, f0, frames; };
+AUM_DEV bool fbs_seq(const AumFbankStreamArgs& a, int i, FbsSeq& q) {
+    const int s0 = a.cu_samples[i], s1 = a.cu_samples[i + 1];
+    const int row = a.idx ? a.idx[i] : i;
+    q.f0 = a.cu_frames[i];
+    q.frames = a.cu_frames[i + 1] - q.f0;
+    q.tl = a.tail_len[i];
+    q.m = s1 - s0;
+    if (s0 < 0 || q.m < 0 || s1 > a.total_samples || q.tl < 0 || q.tl >= a.cap || row < 0 || row >= a.nrows) return false;
+    if (q.f0 < 0 || q.frames < 0 || q.f0 + q.frames > a.total_frames) return false;
+    q.tail = a.tails + (int64_t)row * a.cap;
+    q.hop = a.fbank.wave + s0;          // not dereferenced when m == 0
+    return true;
+}
+// sample v of the virtual stream [tail[0:tl] ; hop[0:m]] on the lanes of `in`; v is clamped into [0, tl + m) and each half into its own range
+AUM_DEV vf fbs_load(const FbsSeq& q, vi v, vm in) {
+    const int n = q.tl + q.m;
+    v = vmax_i(vmin_i(v, n - 1), 0);
+    const vm live = in && (n > 0);
+    const vf t = gload(q.tail, vmax_i(vmin_i(v, q.tl - 1), 0), live && (v < q.tl));
+    const vf h = gload(q.hop, vmax_i(vmin_i(v - q.tl, q.m - 1), 0), live && (v >= q.tl));
+    return vsel(v < q.tl, t, h);
+}
+
+AUM_DEV void fbank_stream_frames_wg(const AumFbankStreamArgs& a, int wg, float* lds) {
+    const AumFbankArgs& p = a.fbank;
+    AUM_FOR_EACH_WAVE(w, FBANK_NW) {
+        FbwTw tw;
+        fbw_twiddles(p, tw);
+        int i = 0;
+        for (int q = 0; q < FBW_FPW; ++q) {
+            const int g = wg * FBW_WG_FRAMES + w * FBW_FPW + q;
+            if (g >= a.total_frames) break;
+            while (i < a.nseq && g >= a.cu_frames[i + 1]) ++i;          // rows are in session order: the search goes on where it stopped
+            if (i >= a.nseq) break;
+            FbsSeq sq;
+            if (g < a.cu_frames[i] || !fbs_seq(a, i, sq)) continue;
+            const int j = g - sq.f0, lim = a.n_real[i];
+            const int off = j * p.shift;
+            FbankAug ag{lim < 0 ? 0x7fffffff : lim, 0, 0, 0, 0, 0, 0.f};
+            if ((int64_t)off + p.win > (int64_t)sq.tl + sq.m) ag.n_frames = 0;      // a frame the samples do not cover is a padding row
+            float* out = p.out + (int64_t)g * p.num_mel;
+            fbank_frame_wave_from(p, 0, a.first_frame[i] + j, ag, tw, lds + w * FBW_WAVE_FLOATS,
+                                  [&](vi s, vm in) { return fbs_load(sq, s + off, in); }, [&](vi m, vf v, vm ok) { gstore(out, m, v, ok); });
+        }
+    }
+}
+
+AUM_DEV void fbank_stream_tail_wg(const AumFbankStreamArgs& a, int i) {
+    FbsSeq q;
+    if (!fbs_seq(a, i, q)) return;
+    const int n = q.tl + q.m;
+    const int64_t used = (int64_t)q.frames * a.fbank.shift;
+    const int consumed = used < n ? (int)used : n;
+    const int keep = n - consumed;
+    if (keep > a.cap) return;
+    float* row = const_cast<float*>(q.tail);
+    vf held[AUM_PER_WAVE(FBANK_NW)][FBS_TAIL_R];
+    AUM_FOR_EACH_WAVE(w, FBANK_NW) {
+        AUM_UNROLL
+        for (int r = 0; r < FBS_TAIL_R; ++r) {
+            const vi k = lane_id() + (r * FBANK_NW + w) * WAVE;
+            held[AUM_W(w)][r] = fbs_load(q, k + consumed, k < keep);
+        }
+    }
+    AUM_WG_BARRIER();
+    AUM_FOR_EACH_WAVE(w, FBANK_NW) {
+        AUM_UNROLL
+        for (int r = 0; r < FBS_TAIL_R; ++r) {
+            const vi k = lane_id() + (r * FBANK_NW + w) * WAVE;
+            gstore(row, k, held[AUM_W(w)][r], k < keep);
+        }
+    }
 }
 
 }  // namespace aum

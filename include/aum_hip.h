@@ -273,6 +273,40 @@ typedef struct AumFrontendArgs {
 int aum_frontend_tokens_fwd(const AumFrontendArgs* args, void* stream);
 
 /*
+ * Streaming log-mel (no version step: an addition): the NEW frames of several sessions whose PCM arrives in hops of any size.  A Kaldi
+ * snip_edges frame t depends on samples [t * shift, t * shift + win) and nothing else, so every frame is computed by the arithmetic of
+ * aum_fbank_fwd's wave-per-frame kernel on the session's virtual stream [its carried tail ; its hop] and is bit-identical to the same row
+ * of aum_fbank_fwd on the whole clip, however the sample stream was cut.
+ *   fbank       : the table, normalisation and pre-emphasis fields of AumFbankArgs (window .. mel_w, win, shift, padded, num_mel, mel_wstride,
+ *                 preemph, norm_mean, norm_inv2std, log_floor).  aug and noise must be NULL and padded must be 512 (AUM_E_UNSUPPORTED).
+ *                 .wave = (total_samples) fp32, the sessions' new samples behind one another (may be NULL when total_samples == 0);
+ *                 .out = (total_frames, num_mel) fp32, the sessions' new frames behind one another (may be NULL when total_frames == 0);
+ *                 batch, n_samples, num_frames, target_length, wave_bs, out_bs are not read.
+ *   cu_samples  : (nseq + 1) int32, session i's hop is wave[cu_samples[i] .. cu_samples[i + 1])
+ *   cu_frames   : (nseq + 1) int32, session i's frames are rows [cu_frames[i], cu_frames[i + 1]) of out; a session with no new frame is legal
+ *   tail_len    : (nseq) int32, samples session i holds in its pool row, 0 <= tail_len < cap
+ *   idx         : (nseq) int32 pool row of session i, distinct; NULL: session i owns row i
+ *   first_frame : (nseq) int32 clip index of session i's first new frame; n_real : (nseq) int32, frames with clip index >= n_real[i] are
+ *                 written as the normalised zero-padding row (the end of a clip); a negative entry means no limit
+ *   tails       : (nrows, cap) fp32 pool of carried samples, cap == win + 15 * shift (what a session holds at most before a whole column of
+ *                 16 frames is covered; 2800 at 16 kHz) and cap <= 2816
+ * Frame j of session i reads the virtual stream at [j * shift, j * shift + win), every load masked and clamped to [0, tail_len + m_i).
+ * Tail rule: behind the frames, row idx[i] holds the last tail_len + m_i - consumed_i samples of the virtual stream, where
+ * consumed_i = min(shift * frames_i, tail_len + m_i) (0 when no frame was produced: the hop is appended).  The update is a SECOND launch
+ * enqueued on the same stream behind the frame launch (one workgroup per session reads its whole new tail into registers, a workgroup
+ * barrier, then writes it), so it cannot race with the frame waves that read the old tail, nor with itself.  Rows of sessions that are
+ * not in the call are not touched.  A session whose operands are out of range (row outside the pool, lengths outside the buffers) is
+ * skipped by both launches.  The caller keeps tail_len on the host (aum_hip.wave_map checks frames_i against the samples there are).
+ */
+typedef struct AumFbankStreamArgs {
+    AumFbankArgs fbank;
+    const int32_t *cu_samples, *cu_frames, *tail_len, *idx, *first_frame, *n_real;
+    float *tails;
+    int32_t total_samples, total_frames, nseq, nrows, cap, reserved;
+} AumFbankStreamArgs;
+int aum_fbank_stream_fwd(const AumFbankStreamArgs* args, void* stream);
+
+/*
  * The skinny projections around the scan on CHANNEL-MAJOR activations (token t = b*len + l contiguous):
  *   conv_out / delta / ddelta / dconv : [dim][ntok]     x_dbl / dx_dbl : [dt_rank + 2*dstate][ntok], rows = dt | B | C
  * 16-bit activations only (AUM_BF16 / AUM_F16, fp32 accumulation on the MFMA units); weights in the same dtype.

@@ -266,6 +266,54 @@ def timeline_ab(model, args, dev):
         print(json.dumps(out), flush=True)
 
 
+def wave_ab(model, args, dev):
+    """--wave: 8 sessions, one hop of 2560 samples (one column) each per call -- by hand (a: per session the carried 240 samples and the hop
+    concatenated on the host side, fbank_fwd on the assembled buffer, then stream_push_many) against one stream_push_wave_many (b)"""
+    import aum_hip
+    from aum.frontend import FbankTables, WaveInput
+    S, hop = 8, 2560
+    fe = WaveInput(FbankTables(dev), target_length=16 * model.patch_grid_size[1])
+    pools = [model.allocate_stream_pool(S), model.allocate_stream_pool(S)]
+    ws = model.allocate_wave_stream(S, fe)
+    pcm = [torch.randn(hop, device=dev) * 0.1 for _ in range(S)]
+    held = [torch.zeros(240, device=dev) for _ in range(S)]
+    model.stream_push_wave_many(held, pools[1], ws, range(S))                 # both arms start with the 240 samples frames share
+
+    def by_hand():
+        if pools[0]["columns"][0] >= model.patch_grid_size[1]:
+            pools[0]["columns"] = [0] * S             # new clips: the caches' values do not matter for timing
+        specs = []
+        for i in range(S):
+            buf = torch.cat((held[i], pcm[i]))
+            specs.append(aum_hip.fbank_fwd(buf[None], fe.tables.tables, 16, fe.norm_mean, fe.norm_std)[0].to(torch.bfloat16))
+            held[i] = buf[-240:]
+        model.stream_push_many(specs, pools[0], range(S))
+
+    def one_call():
+        if pools[1]["columns"][0] >= model.patch_grid_size[1]:
+            pools[1]["columns"] = [0] * S
+            ws.reset(range(S))
+            model.stream_push_wave_many([h[:240] for h in pcm], pools[1], ws, range(S))
+        model.stream_push_wave_many(pcm, pools[1], ws, range(S))
+
+    arms = (("by_hand", by_hand), ("push_wave_many", one_call))
+    for _ in range(args.warm):
+        for _, fn in arms:
+            timed_call(fn)
+    times = [[] for _ in arms]
+    for _ in range(args.hops):
+        for t, (_, fn) in zip(times, arms):
+            t.append(timed_call(fn))
+    g = max(args.hops // args.groups, 1)
+    out = {"model": f"aum-{args.size} causal depth {args.depth} bf16", "sessions": S, "hop_samples": hop, "hops": args.hops, "warm": args.warm}
+    for (name, _), t in zip(arms, times):
+        out[name + "_ms_median"] = round(statistics.median(t), 4)
+        out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+        out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+    out["ratio_by_hand_over_push_wave_many"] = round(out["by_hand_ms_median"] / out["push_wave_many_ms_median"], 3)
+    print(json.dumps(out), flush=True)
+
+
 def prefill_pool_ab(model, args, dev):
     """--prefill-pool S --prefill COLS: S ragged backlogs into empty pool rows, the host loop (a) against one packed pass (b)"""
     S = args.prefill_pool
@@ -444,9 +492,15 @@ def main():
                     help="with --prefill COLS: S sessions with backlogs of COLS, COLS / 2, ... columns, stream_prefill_many as a host loop vs packed")
     ap.add_argument("--timeline", type=int, default=0, metavar="COLS",
                     help="the logits after every one of COLS columns: COLS stream_push(read=True) calls vs one stream_timeline")
+    ap.add_argument("--wave", action="store_true",
+                    help="raw audio: 8 sessions by hand (tail + hop on the host side, fbank_fwd, stream_push_many) vs one stream_push_wave_many")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill, 16 * args.timeline))
+    if args.wave:
+        with torch.no_grad():
+            wave_ab(model, args, dev)
+        return
     if args.timeline:
         with torch.no_grad():
             timeline_ab(model, args, dev)
