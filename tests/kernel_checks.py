@@ -146,9 +146,7 @@ def check_conv_tm(lib, dev, case, dtype=torch.float32, reverse=False, silu=True,
     """aum_conv1d_tm_fwd / _bwd against the same oracle as the channel-major conv, on (batch, len, dim) operands; xz_layout: x and dx
     are the first halves of (batch, len, 2 dim) tensors, as in the block."""
     name = case[0]
-    d = cases.conv_inputs(*case)
-    tol = 1e-5 if dtype == torch.float32 else TOL_BF16
-    q = {k: rq(d[k], dtype) for k in ("x", "dout")}
+    d, ry, rg = conv_tm_reference(case, dtype, reverse, silu)
     tm = lambda a: T(np.ascontiguousarray(a.transpose(0, 2, 1)), dev, dtype)
     x, dy = tm(d["x"]), tm(d["dout"])
     dim = x.shape[2]
@@ -162,15 +160,29 @@ def check_conv_tm(lib, dev, case, dtype=torch.float32, reverse=False, silu=True,
     assert aum_hip.conv1d_tm_supported(x, d["weight"].shape[1])
     w, b = T(d["weight"], dev), T(d["bias"], dev)
     y = aum_hip.conv1d_tm_fwd(x, w, b, silu, reverse, lib=lib)
-    ry = O.conv1d_fwd(q["x"], d["weight"], d["bias"], silu, reverse, "f64")
     dx, dw, db = aum_hip.conv1d_tm_bwd(x, w, b, dy, silu, reverse, dx_out=dx_out, lib=lib)
-    rg = O.conv1d_bwd(q["x"], d["weight"], d["bias"], q["dout"], silu, reverse, "f64")
-    untm = lambda t: N(t).transpose(0, 2, 1)
-    errs = {"y": rel_err(untm(y), ry), "dx": rel_err(untm(dx), rg["dx"]), "dw": rel_err(N(dw), rg["dweight"])}
-    if b is not None:
-        errs["db"] = rel_err(N(db), rg["dbias"])
     if xz_layout:
         assert float(dxz[:, :, dim:].abs().max()) == 0.0, (name, "dx wrote outside its half")
+    return conv_tm_assert(name, dtype, y, dx, dw, db, ry, rg)
+
+
+def conv_tm_reference(case, dtype, reverse, silu):
+    """the seeded inputs of a conv case and the fp64 oracle's y and gradients on them as rounded to `dtype`: what check_conv_tm (and the
+    poison checks of poison_checks.py) hold the token-major conv to -> (inputs, y, gradients)"""
+    d = cases.conv_inputs(*case)
+    q = {k: rq(d[k], dtype) for k in ("x", "dout")}
+    ry = O.conv1d_fwd(q["x"], d["weight"], d["bias"], silu, reverse, "f64")
+    rg = O.conv1d_bwd(q["x"], d["weight"], d["bias"], q["dout"], silu, reverse, "f64")
+    return d, ry, rg
+
+
+def conv_tm_assert(name, dtype, y, dx, dw, db, ry, rg):
+    """the bars of check_conv_tm on token-major (batch, len, dim) y / dx and fp32 dweight / dbias (db None: no bias)"""
+    tol = 1e-5 if dtype == torch.float32 else TOL_BF16
+    untm = lambda t: N(t).transpose(0, 2, 1)
+    errs = {"y": rel_err(untm(y), ry), "dx": rel_err(untm(dx), rg["dx"]), "dw": rel_err(N(dw), rg["dweight"])}
+    if db is not None:
+        errs["db"] = rel_err(N(db), rg["dbias"])
     bad = {k: v for k, v in errs.items() if not v < tol * (4 if k != "y" else 1)}
     assert not bad, (name, bad)
     return errs
@@ -567,11 +579,8 @@ def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=Fals
     halves of one (batch, len, 2 dim) tensor (row stride 2 dim), as in_proj leaves them.  segments > 1: the time-segmented launches
     (aum_scan_tm_seg_fwd / _bwd), held to the same oracle and the same tolerances."""
     name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
-    d = cases.scan_inputs(*case)
-    tol = tol or (TOL_F32 if dtype == torch.float32 else TOL_BF16)
-    q = {k: rq(d[k], dtype) for k in ("u", "delta", "z", "B", "C", "dout")}
-    rng = np.random.default_rng(7)
-    A_b = (d["A"] * np.exp(rng.normal(0, 0.1, d["A"].shape))).astype(np.float32) if bidir else None
+    ref = scan_tm_reference(case, dtype, reverse, bidir, backward)
+    d, A_b = ref["inputs"], ref["A_b"]
     tm = lambda a: None if a is None else T(a, dev, dtype).transpose(1, 2).contiguous()      # (batch, len, X)
     u, delta, z, dout = tm(d["u"]), tm(d["delta"]), tm(d["z"]), tm(d["dout"])
     if xz_layout and z is not None:
@@ -586,21 +595,33 @@ def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=Fals
         ck.fill_(float("nan"))
     out, out_pre = aum_hip.scan_tm_fwd(u, delta, A, Bm, Cm, D, z, bias, softplus, reverse, T(A_b, dev), want_out_pre=True, ckpt=ck,
                                        lib=lib, segments=segments)
-    ref = O.scan_fwd(q["u"], q["delta"], d["A"], q["B"], q["C"], d["D"], q["z"], d["delta_bias"], softplus, reverse, "f64")
-    ref_out, ref_pre = ref["out"], ref["y_pre"]
-    if bidir:
-        rb = O.scan_fwd(q["u"], q["delta"], A_b, q["B"], q["C"], d["D"], q["z"], d["delta_bias"], softplus, True, "f64")
-        ref_out, ref_pre = ref_out + rb["out"], ref_pre + rb["y_pre"]
-    cm = lambda t: N(t).transpose(0, 2, 1)
-    pairs = {"out": (cm(out), ref_out), "out_pre": (cm(out_pre), ref_pre)}
     out2, none = aum_hip.scan_tm_fwd(u, delta, A, Bm, Cm, D, z, bias, softplus, reverse, T(A_b, dev), lib=lib, segments=segments)    # inference form
     assert none is None
-    pairs["out_nopre"] = (cm(out2), ref_out)
+    g = None
     if backward:
         g = aum_hip.scan_tm_bwd(u, delta, A, Bm, Cm, D, z, bias, dout, out_pre if has_z else None, ck, softplus, reverse, T(A_b, dev), lib=lib,
                                 segments=segments, want_dA_xA=True)
         # the optional products d A .* A (the gradient of A_log) come out of the same partial-sum launch: exactly dA * A in fp32
         assert torch.equal(g["dA_xA"], g["dA"] * A) and (not bidir or torch.equal(g["dA_b_xA"], g["dA_b"] * T(A_b, dev)))
+    return scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out2, g)
+
+
+def scan_tm_reference(case, dtype, reverse, bidir, backward=True):
+    """the seeded inputs of a scan case (A_b: the second direction's A of a Fo-Bi pair) and the fp64 oracle's forward and gradients on them
+    as rounded to `dtype`, both directions summed for a pair: what check_scan_tm (and the poison checks of poison_checks.py) hold the
+    token-major scans to -> dict(inputs, A_b, out, out_pre, grads | None), channel-major like the oracle"""
+    name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
+    d = cases.scan_inputs(*case)
+    q = {k: rq(d[k], dtype) for k in ("u", "delta", "z", "B", "C", "dout")}
+    rng = np.random.default_rng(7)
+    A_b = (d["A"] * np.exp(rng.normal(0, 0.1, d["A"].shape))).astype(np.float32) if bidir else None
+    ref = O.scan_fwd(q["u"], q["delta"], d["A"], q["B"], q["C"], d["D"], q["z"], d["delta_bias"], softplus, reverse, "f64")
+    ref_out, ref_pre = ref["out"], ref["y_pre"]
+    if bidir:
+        rb = O.scan_fwd(q["u"], q["delta"], A_b, q["B"], q["C"], d["D"], q["z"], d["delta_bias"], softplus, True, "f64")
+        ref_out, ref_pre = ref_out + rb["out"], ref_pre + rb["y_pre"]
+    gr = None
+    if backward:
         gr = O.scan_bwd(q["u"], q["delta"], d["A"], q["B"], q["C"], d["D"], q["z"], d["delta_bias"], q["dout"], softplus, reverse, "f64")
         if bidir:
             gb = O.scan_bwd(q["u"], q["delta"], A_b, q["B"], q["C"], d["D"], q["z"], d["delta_bias"], q["dout"], softplus, True, "f64")
@@ -608,6 +629,18 @@ def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=Fals
                 if gr[k] is not None:
                     gr[k] = gr[k] + gb[k]
             gr["dA_b"] = gb["dA"]
+    return dict(inputs=d, A_b=A_b, out=ref_out, out_pre=ref_pre, grads=gr)
+
+
+def scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out_nopre, g):
+    """the bars of check_scan_tm: token-major (batch, len, dim) out / out_pre / the inference form's out and the dict of gradients as
+    scan_tm_bwd returns it (None: forward only) against scan_tm_reference's values"""
+    name, dstate = case[0], case[4]
+    tol = tol or (TOL_F32 if dtype == torch.float32 else TOL_BF16)
+    cm = lambda t: N(t).transpose(0, 2, 1)
+    pairs = {"out": (cm(out), ref["out"]), "out_pre": (cm(out_pre), ref["out_pre"]), "out_nopre": (cm(out_nopre), ref["out"])}
+    if g is not None:
+        gr = ref["grads"]
         got = dict(du=cm(g["du"]), ddelta=cm(g["ddelta"]), dz=None if g["dz"] is None else cm(g["dz"]), dA=N(g["dA"]),
                    dA_b=N(g["dA_b"]), dB=N(g["dBC"])[:, :, :dstate].transpose(0, 2, 1), dC=N(g["dBC"])[:, :, dstate:].transpose(0, 2, 1),
                    dD=N(g["dD"]), ddelta_bias=N(g["ddelta_bias"]))
@@ -752,12 +785,17 @@ def check_gemm(lib, dev, case, dtype, flags=0):
     c_full = c_buf[:m]
     out = aum_hip.gemm_tn(a, b, out=c_full[:, pad_c:], lib=lib, flags=flags)
     assert torch.all(c_buf[m:] == 7.0), "rows behind the result were written"
+    gemm_assert(name, out, a, b, dtype)
+    if pad_c:
+        assert torch.all(c_full[:, :pad_c] == 7.0), "columns outside the result were written"
+
+
+def gemm_assert(name, out, a, b, dtype):
+    """the bar of check_gemm: out (m, n) against the fp64 product of the 16-bit operands a (m, k), b (n, k)"""
     ref = a.double().cpu() @ b.double().cpu().t()
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     err = (out.double().cpu() - ref).abs().max().item()
     assert err <= 1.01 * ulp * ref.abs().max().item() + 1e-30, (name, err, ref.abs().max().item())
-    if pad_c:
-        assert torch.all(c_full[:, :pad_c] == 7.0), "columns outside the result were written"
 
 
 def check_gemm_wgrad(lib, dev, t, n, k, splits, dtype, pad_y=0, pad_x=0):
@@ -769,6 +807,15 @@ def check_gemm_wgrad(lib, dev, t, n, k, splits, dtype, pad_y=0, pad_x=0):
     y, x = y_full[:, pad_y:], x_full[:, :k]
     part = aum_hip.gemm_wgrad(y, x, splits=splits, lib=lib, partials=True)
     assert part.shape == (splits, n, k) and part.dtype == torch.float32
+    total = aum_hip.gemm_wgrad(y, x, splits=splits, lib=lib)
+    gemm_wgrad_assert(part, total, y, x, splits)
+    assert torch.equal(total, aum_hip.gemm_wgrad(y, x, splits=splits, lib=lib))
+
+
+def gemm_wgrad_assert(part, total, y, x, splits):
+    """the bars of check_gemm_wgrad: every split's partial tile part[s] (n, k) against the fp64 product over its token range (an empty
+    split: zeros) and the summed result against the whole product, of the 16-bit operands y (t, n), x (t, k)"""
+    t, n, k = y.shape[0], y.shape[1], x.shape[1]
     chunk = (((t + splits - 1) // splits) + 63) // 64 * 64
     yd, xd = y.double().cpu(), x.double().cpu()
     scale = float((yd.t() @ xd).abs().max()) + 1e-30
@@ -777,9 +824,7 @@ def check_gemm_wgrad(lib, dev, t, n, k, splits, dtype, pad_y=0, pad_x=0):
         ref = yd[t0:t1].t() @ xd[t0:t1]
         err = (part[s_].double().cpu() - ref).abs().max().item()
         assert err <= 2e-6 * scale * max(1.0, (t1 - t0) ** 0.5 / 8), (t, n, k, splits, s_, err, scale)      # fp32 accumulation of exact 16-bit products
-    total = aum_hip.gemm_wgrad(y, x, splits=splits, lib=lib)
     assert rel_err(N(total), (yd.t() @ xd).numpy()) < 1e-5
-    assert torch.equal(total, aum_hip.gemm_wgrad(y, x, splits=splits, lib=lib))
 
 
 def check_decode_kernels(lib, dev, dtype, batch=3, dim=70, dstate=16, width=4):
@@ -845,6 +890,12 @@ def check_dtproj(lib, dev, ntok, dim, rank, ncols, dtype):
     x = torch.randn(ntok, ncols, generator=g).to(dtype).to(dev)
     w = (torch.randn(dim, rank, generator=g) / rank ** 0.5).to(dtype).to(dev)
     out = aum_hip.dtproj_tm_fwd(x, rank, w, lib=lib)
+    dtproj_assert(out, x, w, rank, dtype)
+
+
+def dtproj_assert(out, x, w, rank, dtype):
+    """the bar of check_dtproj: out (ntok, dim) against the fp64 product of the first `rank` columns of the 16-bit x rows and w (dim, rank)"""
+    ntok, dim = x.shape[0], w.shape[0]
     ref = x[:, :rank].double().cpu() @ w.double().cpu().t()
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     err = (out.double().cpu() - ref).abs().max().item()
@@ -866,6 +917,15 @@ def check_xdt_bwd(lib, dev, ntok, dim, dtype, pad=0):
     du_in = du.double().cpu()
     tail_in = duf[:, dim:].clone()
     dx = aum_hip.xdt_tm_bwd(ddelta, dbc, wdt_t, wx_t, du, lib=lib)
+    xdt_bwd_assert(dx, du, du_in, ddelta, dbc, wdt_t, wx_t, dtype)
+    assert torch.equal(duf[:, dim:], tail_in), "columns behind the du rows were written"
+
+
+def xdt_bwd_assert(dx, du, du_in, ddelta, dbc, wdt_t, wx_t, dtype):
+    """the bars of check_xdt_bwd: dx_dbl (ntok, ncols) and the updated du (ntok, dim) against fp64 products of the 16-bit operands;
+    du_in: du before the call, in fp64 on the host"""
+    ntok, dim = ddelta.shape
+    R, C = wdt_t.shape[0], wx_t.shape[1]
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     ref_r = ddelta.double().cpu() @ wdt_t.double().cpu().t()
     er = (dx[:, :R].double().cpu() - ref_r).abs().max().item()
@@ -874,7 +934,6 @@ def check_xdt_bwd(lib, dev, ntok, dim, dtype, pad=0):
     ref_u = du_in + dx.double().cpu() @ wx_t.double().cpu().t()
     eu = (du.double().cpu() - ref_u).abs().max().item()
     assert eu <= 1.01 * ulp * ref_u.abs().max().item(), ("du", ntok, dim, eu)
-    assert torch.equal(duf[:, dim:], tail_in), "columns behind the du rows were written"
 
 
 def check_xdt(lib, dev, ntok, dim, rank, dtype, ncols=80):
@@ -885,6 +944,14 @@ def check_xdt(lib, dev, ntok, dim, rank, dtype, ncols=80):
     wx = (torch.randn(ncols, dim, generator=g) / dim ** 0.5).to(dtype).to(dev)
     wdt = (torch.randn(dim, rank, generator=g) / rank ** 0.5).to(dtype).to(dev)
     x_dbl, delta = aum_hip.xdt_tm_fwd(u, wx, wdt, lib=lib)
+    xdt_assert(x_dbl, delta, u, wx, wdt, dtype)
+
+
+def xdt_assert(x_dbl, delta, u, wx, wdt, dtype):
+    """the bars of check_xdt: x_dbl (ntok, ncols) against the fp64 product of the 16-bit operands, delta (ntok, dim) against the fp64
+    product of the kernel's own rounded dt block"""
+    ntok, dim = u.shape
+    ncols, rank = wx.shape[0], wdt.shape[1]
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     ref_x = u.double().cpu() @ wx.double().cpu().t()
     ex = (x_dbl.double().cpu() - ref_x).abs().max().item()

@@ -51,6 +51,13 @@ def check_xdt_fwd(lib, device, ntok, dt, softplus):
     bias = (torch.randn(DIM, generator=g) * 0.5 - 1.0).to(device) if softplus else None
     assert aum_hip.xdt_tm_supported(u, wx, wdt)
     x_dbl, delta = aum_hip.xdt_tm_fwd(u, wx, wdt, lib=lib, delta_bias=bias, delta_softplus=softplus)
+    assert_xdt_fwd(x_dbl, delta, u, wx44, wdt12, bias, dt, softplus)
+    return x_dbl, delta
+
+
+def assert_xdt_fwd(x_dbl, delta, u, wx44, wdt12, bias, dt, softplus):
+    """the bars of check_xdt_fwd on the outputs of one call (also what tests/poison_checks.py holds the padded width to)"""
+    ntok = u.shape[0]
     f = lambda t: t.detach().double().cpu().numpy()
     ref_x = f(u) @ f(wx44).T                                        # (ntok, 44)
     ref_d = ref_x[:, :R] @ f(wdt12).T
@@ -62,7 +69,6 @@ def check_xdt_fwd(lib, device, ntok, dt, softplus):
     assert e_dt < OUT_BAR[dt] and e_bc < OUT_BAR[dt]
     assert e_d < OUT_BAR[dt]
     assert _is_pos_zero(x_dbl[:, R:RP]), "the pad columns of x_dbl are not exactly +0"
-    return x_dbl, delta
 
 
 def check_pad_columns_unread(lib, device, ntok, dt, softplus):
