@@ -451,7 +451,9 @@ def train(model, train_loader, val_loader, args, D):
         net = nn.parallel.DistributedDataParallel(model, device_ids=[D.dev_index] if D.cuda else None,
                                                   gradient_as_bucket_view=True, static_graph=bool(args.if_nan2num))
         # (torch's default buckets -- 25 MB behind a first one of 1 MB: with a custom cap the odd-sized head.bias sits at the front of a big
-        # bucket and leaves every view behind it off a 16-byte boundary, which the in-bucket gradient writes of ssi.grad_home need)
+        # bucket and leaves every view behind it off a 16-byte boundary.  The in-bucket gradient writes of ssi.grad_home take such a view -- a
+        # destination is any 4-byte aligned float address (aum_hip._sum_out, aum_sum_rows) -- but their 16-byte stores and the fused Adam's
+        # loads then straddle: the default layout is kept for speed, not for correctness)
         homes = compress_gradients(net, args.grad_compress)
     scaler = torch.amp.GradScaler("cuda", enabled=(args.mixed_precision == "fp16" and D.cuda))
     epic = args.dataset == "epic_sounds"

@@ -2335,10 +2335,11 @@ def selftest_wave_sum32(values, lib=None):
 
 
 def _sum_out(out, shape, device):
-    """the destination of a sum: `out` (a contiguous fp32 tensor of that many elements on that device -- e.g. the bucket view a parameter's
-    gradient lives in under DistributedDataParallel) or a new tensor"""
-    if out is not None and out.dtype == torch.float32 and out.is_contiguous() and out.device == device and out.numel() == math.prod(shape):
-        return out.view(shape)          # (4-byte aligned is enough: a view in a bucket behind an odd-sized parameter)
+    """the destination of a sum: `out` -- a contiguous fp32 tensor of exactly that shape on that device, at any float address (4-byte aligned is
+    enough: the bucket view a parameter's gradient lives in under DistributedDataParallel may sit behind an odd-sized parameter, and every
+    kernel that takes a destination stores to it with 4-byte aligned stores) -- or a new tensor.  Anything else passed as `out` is left alone"""
+    if out is not None and out.dtype == torch.float32 and out.is_contiguous() and out.device == device and tuple(out.shape) == tuple(shape):
+        return out
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
@@ -2351,9 +2352,7 @@ def sum_rows(t, lib=None, out=None):
     inner = t[0].numel() if t.shape[0] > 0 else 0
     if debug.torch_sums or t.dtype not in _DT or not t.is_contiguous() or inner % 8 or inner == 0 or t.data_ptr() % 16:
         r = t.sum(0, dtype=torch.float32)
-        if out is not None and out.shape == r.shape and out.dtype == r.dtype:
-            return out.copy_(r)
-        return r
+        return _sum_out(out, r.shape, r.device).copy_(r) if out is not None else r
     lib.check_tensor(t)
     outer, shape = t.shape[0], t.shape[1:]
     stream = lib.stream(t)
@@ -2387,7 +2386,7 @@ def sum_rows_multi(parts, tr_cols=None, lib=None, outs=None):
         for t, tc, o in zip(parts, tr_cols, outs):
             if tc:
                 r = sum_rows(t, lib=lib).t()
-                res.append(o.copy_(r) if o is not None and o.shape == r.shape else r.contiguous())
+                res.append(_sum_out(o, r.shape, r.device).copy_(r) if o is not None else r.contiguous())
             else:
                 res.append(sum_rows(t, lib=lib, out=o))
         return res

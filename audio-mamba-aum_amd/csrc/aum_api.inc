@@ -873,7 +873,7 @@ template <class T> static int sum_rows_t(const void* src, float* dst, int64_t ba
 AUM_API int aum_sum_rows(const void* src, float* dst, int64_t batch, int64_t outer, int64_t inner, int32_t src_dtype, void* stream) {
     if (!src || !dst) return AUM_E_NULL;
     if (batch <= 0 || batch > 65535 || outer <= 0 || inner <= 0 || (inner & 7)) return AUM_E_SHAPE;
-    if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 3)) return AUM_E_SHAPE;          // dst: any float address (a gradient's view in a bucket)
+    if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 3)) return AUM_E_SHAPE;          // dst: any 4-byte aligned float address (a gradient's view in a bucket; aum_hip._sum_out)
     if (src_dtype < 0 || src_dtype > 2) return AUM_E_DTYPE;
     return AUM_BY_DTYPE_T(src_dtype, sum_rows_t, src, dst, batch, outer, inner, (aum_stream_t)stream);
 }

@@ -60,14 +60,48 @@ def _autocast_dtype():
 # weight sum -- and what the autograd function returns is a fresh alias of that view: the accumulator keeps it without a copy, the reducer's
 # hook finds a gradient that already aliases its bucket and copies nothing.  A stale home (buckets rebuilt, another wrapper) only costs the
 # copy it was meant to save: the reducer then copies as before.
+#
+# A home is written by ONE node of a backward pass.  A parameter used twice in one graph (two forwards of a model summed into one loss, a
+# shared layer) has two nodes that finish a gradient for it, and autograd adds what they return only after both ran: the first node that
+# asks claims the home for the pass (_HOME_CLAIMS), every later one gets None and returns a tensor of its own.  Claims are keyed by the
+# engine's number of the pass, so one left behind by a pass that raised never matches a later pass; a pass that ends drops its own (the
+# engine's queue_callback, as _da_xa_put).  Outside a backward pass (a backward helper called directly) nothing is recorded.
+_HOME_CLAIMS = {}       # (backward pass, id(parameter)) -> (parameter, the home handed out to the first node that asked)
+_HOME_PASSES = set()    # passes that have a release queued
+
+
+def _release_homes(task):
+    _HOME_PASSES.discard(task)
+    for k in [k for k in _HOME_CLAIMS if k[0] == task]:
+        del _HOME_CLAIMS[k]
+
+
 def grad_home(p):
-    """where parameter p's gradient is wanted, or None.  Only while p.grad is None: a backward that ACCUMULATES (gradient accumulation,
-    no_sync) must not overwrite what it is added to."""
+    """where parameter p's gradient is wanted, or None.  Only for a parameter that takes a gradient, only while p.grad is None -- a backward
+    that ACCUMULATES (gradient accumulation, no_sync) must not overwrite what it is added to -- and only once per backward pass."""
     h = getattr(p, "_aum_grad_home", None) if p is not None else None
-    if h is None or p.grad is not None or h.dtype != torch.float32 or p.dtype != torch.float32 or h.device != p.device or h.shape != p.shape \
-            or not h.is_contiguous():
+    if h is None or not p.requires_grad or p.grad is not None or h.dtype != torch.float32 or p.dtype != torch.float32 or h.device != p.device \
+            or h.shape != p.shape or not h.is_contiguous():
         return None
+    task = torch._C._current_graph_task_id()
+    if task < 0:
+        return h                 # not inside a backward pass: no second node to keep apart
+    if (task, id(p)) in _HOME_CLAIMS:
+        return None
+    if task not in _HOME_PASSES:
+        if len(_HOME_CLAIMS) > 4096:            # (what passes that raised left behind)
+            _HOME_CLAIMS.clear()
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: _release_homes(task))
+        _HOME_PASSES.add(task)
+    _HOME_CLAIMS[task, id(p)] = (p, h)
     return h
+
+
+def claimed_home(p):
+    """the home grad_home handed out for p earlier in the running backward pass (a later node of the SAME gradient's chain hands it over:
+    _NegExpFn behind the scan backward), or None"""
+    ent = _HOME_CLAIMS.get((torch._C._current_graph_task_id(), id(p))) if p is not None else None
+    return ent[1] if ent is not None and ent[0] is p else None
 
 
 def _homed(t, home):
@@ -228,7 +262,7 @@ class _NegExpFn(torch.autograd.Function):
         ent = _DA_XA.pop(g.data_ptr(), None)
         if ent is not None and ent[0].data_ptr() == g.data_ptr() and ent[0].shape == g.shape and ent[0].dtype == g.dtype \
                 and ent[2].data_ptr() == ctx.saved_tensors[0].data_ptr():
-            return _homed(ent[1], grad_home(ctx.A_log)), None
+            return _homed(ent[1], claimed_home(ctx.A_log)), None       # (the scan backward of this chain asked for the home and wrote there)
         return g * ctx.saved_tensors[0], None
 
 
@@ -834,7 +868,8 @@ def _inner_backward_tm(ctx, dout):
         w_x_t, w_dt_t, R, pend, H["x_proj"], H["dt_proj"])
     # conv
     _, dconv_w, dconv_b = aum_hip.conv1d_tm_bwd(x, conv_w, conv1d_bias, g["du"], True, ctx.reverse, dx_out=dx, partials=True)   # SSI:594
-    dconv_w, dconv_b = pend.add(dconv_w, out=H["conv_w"]), (None if dconv_b is None else pend.add(dconv_b, out=H["conv_b"]))
+    home_w = None if H["conv_w"] is None else H["conv_w"].view(E, -1)          # the parameter is (E, 1, W), the sum (E, W): a destination has the sum's shape
+    dconv_w, dconv_b = pend.add(dconv_w, out=home_w), (None if dconv_b is None else pend.add(dconv_b, out=H["conv_b"]))
     # the partial sets of the whole function in one launch
     sums = pend.run()
     dout_proj_weight, ddelta_proj_weight, dx_proj_weight, dconv_w, dconv_b = (
