@@ -625,6 +625,31 @@ class AudioMamba(nn.Module):
         pick = lambda t: t.reshape(-1, nf + 1, t.shape[-1])[:, nf]
         return self._head_rows(pick(hidden), pick(residual), return_features)
 
+    def forward_timeline(self, spec, return_features=False, frontend=None):
+        """The differentiable counterpart of stream_timeline from column 0 -- TRAINING for the per-column logits: spec (batch, 16 K,
+        n_mels) frames of the first K time columns of a clip (1 <= K <= the grid's column count) -> logits (batch, K, classes);
+        logits[:, j] is the model's output "if the clip ended behind column j", the last of a full clip is model(spec).  One pass over
+        the rows [column 0's n_f tokens | cls | column 1's tokens | cls | ...]: every block runs Mamba.forward(peek_every=n_f), whose cls
+        rows read the conv window and the state and enter neither (HIP kernels both ways).  Causal models only (_check_streamable).
+        frontend=aum.frontend.WaveInput: spec is the (batch, n_samples) waveform; it goes through the log-mel kernel first (the fused
+        waveform -> tokens kernel writes the offline token layout, cls once).
+        The path is deterministic, as the offline forward is: this model has no drop-path and no token dropout to apply."""
+        self._check_streamable()
+        if frontend is not None:
+            spec = frontend.spectrogram(spec)
+        nf, nt = self.patch_grid_size
+        if spec.dim() != 3 or spec.shape[1] < 16 or spec.shape[1] % 16 or spec.shape[1] > 16 * nt or spec.shape[2] != 16 * nf:
+            raise ValueError(f"forward_timeline: spec must be (batch, 16 K, {16 * nf}) frames of K = 1 .. {nt} time columns, not {tuple(spec.shape)}")
+        K = spec.shape[1] // 16
+        hidden = self._with_cls_rows(self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(0, K)))
+        residual = None
+        for layer in self.layers:
+            hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
+                                           residual_in_fp32=True, eps=layer.norm.eps)
+            hidden = layer.mixer(hidden, peek_every=nf)
+        out = self._timeline_rows(hidden, residual, return_features)
+        return out.reshape(spec.shape[0], K, -1)
+
     @torch.no_grad()
     def stream_timeline(self, spec, cache, return_features=False):
         """The logits "if the clip ended now" after EVERY one of the next k time columns, in one pass: spec (batch, 16 k, n_mels) as
@@ -680,8 +705,11 @@ class AudioMamba(nn.Module):
             hidden, residual = self._stream_layers(cls, copies)
         return self._head_rows(hidden[:, 0], residual[:, 0], return_features)
 
-    def forward(self, x, return_features=False, frontend=None):
-        """x: (B, T, F) normalised log-mel spectrogram, or -- with frontend=aum.frontend.WaveInput -- (B, n_samples) waveform"""
+    def forward(self, x, return_features=False, frontend=None, timeline=False):
+        """x: (B, T, F) normalised log-mel spectrogram, or -- with frontend=aum.frontend.WaveInput -- (B, n_samples) waveform.
+        timeline=True: forward_timeline on the same arguments, (B, K, classes) (so that a DistributedDataParallel wrapper reaches it)"""
+        if timeline:
+            return self.forward_timeline(x, return_features, frontend)
         f = self.forward_features(x, frontend)
         return f if return_features else self.head(f)
 

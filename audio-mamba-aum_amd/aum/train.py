@@ -107,6 +107,9 @@ def build_parser():
     a("--depth", type=int, default=24, help="(new) number of blocks; every published AuM size uses 24 (RUN:227-237)")
     a("--grad_compress", type=str, default="no", choices=["no", "bf16", "fp16"],
       help="(new) exchange the gradient buckets in 16 bits (DDP communication hook): 368 -> 184 MB per step for AuM-Base")
+    a("--timeline_loss", type=_lit, default="False",
+      help="(new) train the per-column logits of a streaming (causal) model: the loss is the mean over the time columns of the --loss "
+           "between AudioMamba.forward_timeline's logits behind each column and the clip's target; validation uses the last column")
     a("--max-steps", type=int, default=0, help="(new) stop each epoch after this many steps (smoke runs)")
     a("--epic_config", type=str, default=None,
       help="(new) the reference's epic_sounds config yaml: ANNOTATIONS_DIR, AUDIO_DATA_FILE and the split lists are read from it")
@@ -135,6 +138,10 @@ def check_scope(args):
         raise ValueError("--imagenet_pretrain True needs --imagenet_pretrain_path")
     if not args.if_cls_token or args.use_double_cls_token or args.if_random_cls_token_position or args.if_random_token_rank:
         raise NotImplementedError("no / double / randomly placed cls tokens are off the accelerated path")
+    if args.timeline_loss and not (args.aum_type == "Fo-Fo" and not args.use_middle_cls_token and args.use_end_cls_token
+                                   and args.transpose_token_sequence):
+        raise ValueError("--timeline_loss True trains a streaming model: it needs --aum_type Fo-Fo --use_middle_cls_token False "
+                         "--use_end_cls_token True --transpose_token_sequence True (causal blocks, time-major tokens, the cls token last)")
 
 
 
@@ -365,6 +372,12 @@ def _loss(loss_fn, out, labels):
     return loss_fn(out, labels)
 
 
+def _timeline_loss(loss_fn, logits, labels):
+    """--timeline_loss: logits (batch, K, classes), the model's output behind each of the K time columns -> the mean over the columns of
+    the configured loss against the clip's target"""
+    return torch.stack([_loss(loss_fn, logits[:, j], labels) for j in range(logits.shape[1])]).mean()
+
+
 def _gather_order(n_steps, batch_size, per_rank, world):
     """Sampler position (0 .. world*per_rank-1, positions >= len(dataset) are padding) of every row of the concatenated
     per-step gathers: step s, rank r, row j holds sample number (s*batch_size + j) of rank r, i.e. position (.)*world + r."""
@@ -499,8 +512,8 @@ def train(model, train_loader, val_loader, args, D):
             with torch.no_grad():
                 x, fe = fe_train(wave, n_valid.to(D.device))
             with _autocast(args, D):
-                out = net(x, frontend=fe)
-            loss = _loss(loss_fn, out.float(), labels)
+                out = net(x, frontend=fe, timeline=True) if args.timeline_loss else net(x, frontend=fe)
+            loss = _timeline_loss(loss_fn, out.float(), labels) if args.timeline_loss else _loss(loss_fn, out.float(), labels)
             if args.if_nan2num:
                 loss = torch.nan_to_num(loss)
             else:

@@ -232,6 +232,21 @@ class ScanTmChunkPeeksArgs(C.Structure):
     _fields_ = [("base", ScanTmChunkVarArgs), ("peek_every", _i32), ("reserved", _i32)]
 
 
+class ScanTmPeeksFwdArgs(C.Structure):
+    _fields_ = [("base", ScanTmChunkVarArgs), ("ckpt", _vp), ("ckpt_bytes", _i64), ("peek_every", _i32), ("reserved", _i32)]
+
+
+class ScanTmPeeksBwdArgs(C.Structure):
+    _fields_ = ([("base", ScanTmChunkVarArgs)] + [(n, _vp) for n in ("ckpt", "du", "ddelta", "dz", "workspace")]
+                + [(n, _i64) for n in ("ckpt_bytes", "workspace_bytes", "du_ts", "ddelta_ts", "dz_ts")] + [("peek_every", _i32), ("reserved", _i32)])
+
+
+class ConvTmPeeksBwdArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("x", "dy", "weight", "bias", "dx", "workspace", "cu_seqlens")]
+                + [(n, _i64) for n in ("workspace_bytes", "x_ts", "dy_ts", "dx_ts")]
+                + [(n, _i32) for n in ("total", "nseq", "dim", "width", "dtype")] + [("flags", _u32), ("peek_every", _i32), ("reserved", _i32)])
+
+
 class ConvTmPrefillVarArgs(C.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "conv_state", "weight", "bias", "y", "cu_seqlens", "state_indices")] + [(n, _i64) for n in ("x_ts", "y_ts")]
                 + [(n, _i32) for n in ("total", "nseq", "nrows", "dim", "width", "dtype")] + [("flags", _u32), ("max_len", _i32)])
@@ -270,7 +285,8 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_proj_bwd_weight", "aum_scan_tm_fwd", "aum_scan_tm_bwd", "aum_scan_tm_seg_fwd", "aum_scan_tm_seg_bwd", "aum_conv1d_tm_fwd",
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
-    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd")}
+    "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd",
+    "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -284,6 +300,8 @@ _SIGNATURES.update({
     "aum_cast_bank": ([_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp], C.c_int),
     "aum_stream_block_scratch_bytes": ([_i32] * 3, _i64), "aum_stream_block_max_len": ([], _i32),
     "aum_scan_tm_fwd_state_var_carry_bytes": ([_i32] * 4, _i64),
+    "aum_scan_tm_peeks_ckpt_bytes": ([_i32] * 4, _i64), "aum_scan_tm_peeks_bwd_workspace_bytes": ([_i32] * 4, _i64),
+    "aum_conv1d_tm_peeks_bwd_workspace_bytes": ([_i32] * 3, _i64),
 })
 EXPORTS = list(_SIGNATURES)
 
@@ -1294,6 +1312,158 @@ def scan_tm_chunk_peeks(state, u, delta, A, B, C, D=None, z=None, delta_bias=Non
                            "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
     check_seq_map("scan_tm_chunk_peeks", seq_map, u.shape[0], state.shape[0], u.device)
     return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, False, peek_every)
+
+
+# ---- timeline training: the peek-row operators from the start of a clip, differentiable (aum_scan_tm_peeks_fwd_ckpt / _bwd, aum_conv1d_tm_peeks_bwd)
+def peeks_rows(t, smap, name="peeks"):
+    """Token-major operands of the peek-row training functions: packed (total, X) rows with a map from seq_map(), or (batch, T, X) with every batch
+    entry one sequence -> ((rows, X) rows, the map, the leading shape to give the result back in or None)"""
+    if smap is not None:
+        if t.dim() != 2:
+            raise ValueError(f"{name}: with seq_map the operands are packed (total, X) rows")
+        return t, smap, None
+    if t.dim() != 3:
+        raise ValueError(f"{name}: operands are token-major (batch, T, X), or packed (total, X) with seq_map")
+    return t.reshape(-1, t.shape[-1]), seq_map([t.shape[1]] * t.shape[0], device=t.device), t.shape[:2]
+
+
+def _peeks_train_check(name, lib, u, seq_map, width=None):
+    """operands of the training entry points: packed (total >= 1, dim) rows as the *_chunk_var kernels take them (width None: the scan's,
+    dim % 64 == 0; else the conv's at that window width, 16-byte rows), and a map of this stream"""
+    ok = u.dim() == 2 and u.shape[0] >= 1 and u.dtype in _DT
+    if ok and width is None:
+        ok = scan_tm_supported(u.shape[1], 16)
+    elif ok:
+        ok = 1 <= width <= 4 and conv1d_tm_chunk_var_supported(u, torch.empty((1, u.shape[1], width), dtype=torch.float32, device=u.device))
+    if not ok:
+        raise RuntimeError(f"{name}: unsupported operands {tuple(u.shape)} {u.dtype} strides {u.stride()} (need packed (total >= 1, dim) rows"
+                           + (", dim % 64 == 0)" if width is None else f", 16-byte rows, window width {width} <= 4)"))
+    check_seq_map(name, seq_map, u.shape[0], len(seq_map.lens) if isinstance(seq_map, SeqMap) else 0, u.device)
+
+
+def _scan_peeks_base(a, name, lib, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out, m):
+    total, dim = u.shape
+    state = u.new_empty((0, dim, 16), dtype=torch.float32)         # no pool: the shape alone is read
+    out, held = _scan_chunk_operands(a, name, lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
+    a.state = None
+    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
+    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
+    a.B_ts, a.C_ts = _tm2(B, "B", 16), _tm2(C, "C", 16)
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), None
+    a.total, a.nseq, a.nrows = total, len(m.lens), len(m.lens)
+    return out, held
+
+
+def scan_tm_peeks_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None, peek_every=None,
+                      lib=None):
+    """The training forward of the peek-row scan (aum_scan_tm_peeks_fwd_ckpt): packed sequences, each from a zero state, a peek row behind
+    every peek_every committed rows.  Returns (out, ckpt): out (total, dim) bit for bit scan_tm_chunk_peeks on a zeroed pool; ckpt the
+    fp32 states in front of every 8 rows, which scan_tm_peeks_bwd reads."""
+    lib = lib or get()
+    peek_every = _peek_period("scan_tm_peeks_fwd", peek_every)
+    for t in (u, delta, z, B, C):
+        lib.check_tensor(t)
+    _peeks_train_check("scan_tm_peeks_fwd", lib, u, seq_map)
+    pa = ScanTmPeeksFwdArgs()
+    out, _held = _scan_peeks_base(pa.base, "scan_tm_peeks_fwd", lib, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, None, seq_map)
+    total, dim = u.shape
+    nbytes = int(lib.c.aum_scan_tm_peeks_ckpt_bytes(total, len(seq_map.lens), dim, 16))
+    ckpt = torch.empty(nbytes // 4, dtype=torch.float32, device=u.device)
+    pa.ckpt, pa.ckpt_bytes, pa.peek_every = _ptr(ckpt), nbytes, peek_every
+    _launch(lib.c.aum_scan_tm_peeks_fwd_ckpt, pa, u, lib, "scan_tm_peeks_fwd", (len(seq_map.lens), dim, total, 16, u.element_size()))
+    return out, ckpt
+
+
+def scan_tm_peeks_bwd_parts(dout, ckpt, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
+                            peek_every=None, lib=None, fill=None):
+    """aum_scan_tm_peeks_bwd as it is: (du, ddelta, dz or None) in u's dtype and the fp32 partial rows (dBC_part (dim / 64, total, 32),
+    dA_part (nseq, dim, 16), dD_part (nseq, dim), dbias_part (nseq, dim)) still to be added over their first axis.  fill: what the
+    buffers hold before the launch (tests: a sentinel); None: the per-sequence parts are zeroed, the rest is left uninitialised."""
+    lib = lib or get()
+    peek_every = _peek_period("scan_tm_peeks_bwd", peek_every)
+    for t in (dout, ckpt, u, delta, z, B, C):
+        lib.check_tensor(t)
+    _peeks_train_check("scan_tm_peeks_bwd", lib, u, seq_map)
+    if dout.dtype != u.dtype or dout.shape != u.shape:
+        raise RuntimeError("scan_tm_peeks_bwd: dout must have u's shape and dtype")
+    total, dim = u.shape
+    nseq, ngrp = len(seq_map.lens), dim // 64
+    pa = ScanTmPeeksBwdArgs()
+    _, _held = _scan_peeks_base(pa.base, "scan_tm_peeks_bwd", lib, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, dout, seq_map)
+    new = (lambda shape, dt: torch.empty(shape, dtype=dt, device=u.device)) if fill is None else (
+        lambda shape, dt: torch.full(shape, fill, dtype=dt, device=u.device))
+    du, ddelta = new(u.shape, u.dtype), new(u.shape, u.dtype)
+    dz = None if z is None else new(u.shape, u.dtype)
+    nbytes = int(lib.c.aum_scan_tm_peeks_bwd_workspace_bytes(total, nseq, dim, 16))
+    ws = new((nbytes // 4,), torch.float32)
+    n_bc = ngrp * total * 32
+    if fill is None:
+        ws[n_bc:].zero_()
+    pa.ckpt, pa.ckpt_bytes = _ptr(ckpt), ckpt.numel() * 4
+    pa.du, pa.ddelta, pa.dz, pa.workspace, pa.workspace_bytes = _ptr(du), _ptr(ddelta), _ptr(dz), _ptr(ws), nbytes
+    pa.du_ts, pa.ddelta_ts, pa.dz_ts, pa.peek_every = dim, dim, dim, peek_every
+    _launch(lib.c.aum_scan_tm_peeks_bwd, pa, u, lib, "scan_tm_peeks_bwd", (nseq, dim, total, 16, u.element_size()))
+    n_a = nseq * dim * 16
+    parts = (ws[:n_bc].view(ngrp, total, 32), ws[n_bc:n_bc + n_a].view(nseq, dim, 16), ws[n_bc + n_a:n_bc + n_a + nseq * dim].view(nseq, dim),
+             ws[n_bc + n_a + nseq * dim:].view(nseq, dim))
+    return du, ddelta, dz, parts
+
+
+def scan_tm_peeks_bwd(dout, ckpt, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
+                      peek_every=None, lib=None):
+    """The adjoint of scan_tm_peeks_fwd.  Returns (du, ddelta, dz or None, dA (dim, 16), dB (total, 16), dC (total, 16), dD (dim) or None,
+    ddelta_bias (dim)): the first three in u's dtype, ddelta in raw space, the rest fp32 -- the kernel's partial rows added in a fixed
+    order by aum_sum_rows (bitwise repeatable)."""
+    lib = lib or get()
+    du, ddelta, dz, (p_bc, p_a, p_d, p_b) = scan_tm_peeks_bwd_parts(dout, ckpt, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated,
+                                                                    seq_map, peek_every, lib)
+    dbc = sum_rows(p_bc, lib=lib)
+    return (du, ddelta, dz, sum_rows(p_a, lib=lib), dbc[:, :16], dbc[:, 16:], None if D is None else sum_rows(p_d, lib=lib), sum_rows(p_b, lib=lib))
+
+
+def conv1d_tm_peeks_fwd(x, weight, bias=None, silu=True, seq_map=None, peek_every=None, lib=None):
+    """The training forward of the peek-row conv: conv1d_tm_chunk_peeks itself on a zeroed pool (every sequence starts a clip)."""
+    lib = lib or get()
+    pool = torch.zeros((len(seq_map.lens), x.shape[1], weight.reshape(x.shape[1], -1).shape[1]), dtype=torch.float32, device=x.device)
+    return conv1d_tm_chunk_peeks(x, pool, weight, bias, silu, seq_map=seq_map, lib=lib, peek_every=peek_every)
+
+
+def conv1d_tm_peeks_bwd_parts(dy, x, weight, bias=None, silu=True, seq_map=None, peek_every=None, lib=None, fill=None):
+    """aum_conv1d_tm_peeks_bwd as it is: dx in x's dtype and the fp32 partial rows dw_part (nseq, dim, width), db_part (nseq, dim) (fill: see
+    scan_tm_peeks_bwd_parts)"""
+    lib = lib or get()
+    peek_every = _peek_period("conv1d_tm_peeks_bwd", peek_every)
+    for t in (dy, x):
+        lib.check_tensor(t)
+    _peeks_train_check("conv1d_tm_peeks_bwd", lib, x, seq_map, weight.reshape(x.shape[-1], -1).shape[1] if x.dim() == 2 else 0)
+    if dy.dtype != x.dtype or dy.shape != x.shape:
+        raise RuntimeError("conv1d_tm_peeks_bwd: dy must have x's shape and dtype")
+    total, dim = x.shape
+    nseq = len(seq_map.lens)
+    weight = _al16(_f32c(weight.reshape(dim, -1)))
+    bias = _al16(_f32c(bias))
+    for t in (weight, bias):
+        lib.check_tensor(t)
+    width = weight.shape[1]
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if fill is None else torch.full(x.shape, fill, dtype=x.dtype, device=x.device)
+    nbytes = int(lib.c.aum_conv1d_tm_peeks_bwd_workspace_bytes(nseq, dim, width))
+    ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=x.device) if fill is None else torch.full((nbytes // 4,), fill, dtype=torch.float32,
+                                                                                                        device=x.device)
+    a = ConvTmPeeksBwdArgs()
+    a.x, a.dy, a.weight, a.bias, a.dx, a.workspace, a.cu_seqlens = _ptr(x), _ptr(dy), _ptr(weight), _ptr(bias), _ptr(dx), _ptr(ws), _ptr(seq_map.cu)
+    a.workspace_bytes, a.x_ts, a.dy_ts, a.dx_ts = nbytes, _tm2(x, "x", dim), _tm2(dy, "dy", dim), dim
+    a.total, a.nseq, a.dim, a.width, a.dtype, a.flags, a.peek_every = total, nseq, dim, width, _DT[x.dtype], (CONV_SILU if silu else 0), peek_every
+    _launch(lib.c.aum_conv1d_tm_peeks_bwd, a, x, lib, "conv1d_tm_peeks_bwd", (nseq, dim, total, x.element_size()))
+    n_w = nseq * dim * width
+    return dx, (ws[:n_w].view(nseq, dim, width), ws[n_w:].view(nseq, dim))
+
+
+def conv1d_tm_peeks_bwd(dy, x, weight, bias=None, silu=True, seq_map=None, peek_every=None, lib=None):
+    """The adjoint of the peek-row conv from a zero window.  Returns (dx in x's dtype, dw (dim, width) fp32, db (dim) fp32 or None): the
+    kernel's per-sequence partial rows added in a fixed order by aum_sum_rows."""
+    lib = lib or get()
+    dx, (p_w, p_b) = conv1d_tm_peeks_bwd_parts(dy, x, weight, bias, silu, seq_map, peek_every, lib)
+    return dx, sum_rows(p_w, lib=lib), None if bias is None else sum_rows(p_b, lib=lib)
 
 
 # ---- packed prefill: the backlogs of many sessions in one launch per operator (aum_conv1d_tm_prefill_var, aum_scan_tm_fwd_state_var)

@@ -32,6 +32,58 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
     return CausalConv1dFn.apply(x, weight, bias, activation)
 
 
+class CausalConv1dPeeksFn(torch.autograd.Function):
+    """aum_hip.conv1d_tm_peeks_fwd / conv1d_tm_peeks_bwd on (rows, dim) rows.  The parameter gradients are returned the ordinary way (no
+    grad_home bucket destinations)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, silu, peek_every, seq_map):
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        ctx.silu, ctx.peek_every, ctx.seq_map = silu, peek_every, seq_map
+        ctx.save_for_backward(x, weight, bias)
+        return aum_hip.conv1d_tm_peeks_fwd(x, weight, bias, silu, seq_map, peek_every)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, bias = ctx.saved_tensors
+        dx, dw, db = aum_hip.conv1d_tm_peeks_bwd(dout.to(x.dtype).contiguous(), x, weight, bias, ctx.silu, ctx.seq_map, ctx.peek_every)
+        return dx, dw.to(weight.dtype).reshape(weight.shape), (None if bias is None else db.to(bias.dtype)), None, None, None
+
+
+def causal_conv1d_peeks_fn(x, weight, bias=None, activation=None, peek_every=None, seq_map=None):
+    """The causal conv over rows [column 0's tokens | cls | column 1's tokens | cls | ...]: row j of a sequence is a peek row iff
+    (j + 1) % (peek_every + 1) == 0 -- it sees the last width - 1 committed rows and itself and does not enter the window of later rows;
+    every sequence starts from a zero window.  Differentiable (HIP both ways).  x: token-major (batch, T, dim), or packed (total, dim)
+    rows with seq_map; weight (dim, width <= 4) or (dim, 1, width).  Returns y in x's shape and dtype."""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish")
+    x2, m, shape = aum_hip.peeks_rows(x, seq_map, "causal_conv1d_peeks_fn")
+    y = CausalConv1dPeeksFn.apply(x2, weight, bias, activation is not None, peek_every, m)
+    return y if shape is None else y.reshape(*shape, y.shape[-1])
+
+
+def causal_conv1d_peeks_ref(x, weight, bias=None, activation=None, peek_every=None, seq_map=None):
+    """causal_conv1d_peeks_fn as a differentiable Python loop over the rows, in the dtype it is given (run it in float64 for an oracle)."""
+    x2, m, shape = aum_hip.peeks_rows(x, seq_map, "causal_conv1d_peeks_ref")
+    dim = x2.shape[1]
+    w = weight.reshape(dim, -1).to(x2.dtype)
+    outs, at = [], 0
+    for n in m.lens:
+        win = [torch.zeros(dim, dtype=x2.dtype, device=x2.device) for _ in range(w.shape[1] - 1)]
+        for j in range(n):
+            full = win + [x2[at + j]]
+            pre = sum(w[:, k] * full[k] for k in range(w.shape[1]))
+            if bias is not None:
+                pre = pre + bias.to(pre.dtype)
+            outs.append(torch.nn.functional.silu(pre) if activation is not None else pre)
+            if (j + 1) % (peek_every + 1) != 0:
+                win = full[1:]
+        at += n
+    y = torch.stack(outs) if outs else x2.new_zeros(x2.shape)
+    return y if shape is None else y.reshape(*shape, y.shape[-1])
+
+
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, *, seq_map=None):
     """Streaming inference (the wheel's function of the same name, call site MS:328-334).  x (batch, dim): one token; conv_state (batch, dim,
     width) is shifted left and extended by x IN PLACE; returns act(sum(conv_state * weight, -1) + bias) in x's dtype (aum_causal_conv1d_update;

@@ -6,6 +6,7 @@
 #include "scan_tm_kernels.h"
 #include "conv_tm_kernels.h"
 #include "stream_tm_kernels.h"
+#include "stream_train_kernels.h"
 #include "stream_block_kernels.h"
 #include "stream_prefill_kernels.h"
 
@@ -779,6 +780,121 @@ AUM_API int aum_scan_tm_chunk_peeks(const AumScanTmChunkPeeksArgs* pa, void* str
     const AumScanTmChunkVarArgs k = scan_tm_fwd_resolve(*a);
     aum_stream_t s = (aum_stream_t)stream;
     return AUM_BY_DTYPE_T(k.dtype, scancp_dispatch_t, k, (int)pa->peek_every, s);
+}
+
+// ---- timeline training (stream_train_kernels.h): the peek-row scan forward with state checkpoints, and the adjoints of both operators.
+// No pool: for the shared operand checks the cache pointer is the checkpoint / workspace buffer (non-NULL, aligned alike) ----
+#ifndef AUM_EMU
+template <class T, bool SP, bool HAS_Z> AUM_GLOBAL void k_scanp_fwd_ckpt(AumScanTmChunkVarArgs a, float* ckpt, int pe) {
+    scanp_fwd_wave<T, SP, HAS_Z>(a, ckpt, (int)blockIdx.x, pe);
+}
+template <class T, int SPM, bool HAS_Z> AUM_GLOBAL void k_scanp_bwd(AumScanTmChunkVarArgs a, const float* ckpt, ScanpBwdOuts w, int pe) {
+    scanp_bwd_wave<T, SPM, HAS_Z>(a, ckpt, w, (int)blockIdx.x, pe);
+}
+template <class T, bool SILU> AUM_GLOBAL void k_convp_bwd(ConvpBwdArgs a) { convp_bwd_wave<T, SILU>(a, (int)blockIdx.x); }
+#endif
+static bool scanp_dims_ok(int64_t total, int64_t nseq, int64_t dim, int64_t dstate) { return total > 0 && nseq > 0 && dim > 0 && dstate > 0; }
+AUM_API int64_t aum_scan_tm_peeks_ckpt_bytes(int32_t total, int32_t nseq, int32_t dim, int32_t dstate) {
+    return scanp_dims_ok(total, nseq, dim, dstate) ? scanp_ck_slots(total, nseq) * dim * dstate * (int64_t)sizeof(float) : 0;
+}
+AUM_API int64_t aum_scan_tm_peeks_bwd_workspace_bytes(int32_t total, int32_t nseq, int32_t dim, int32_t dstate) {
+    if (!scanp_dims_ok(total, nseq, dim, dstate)) return 0;
+    return ((int64_t)(dim / WAVE) * total * 2 * dstate + (int64_t)nseq * dim * (dstate + 2)) * (int64_t)sizeof(float);
+}
+AUM_API int64_t aum_conv1d_tm_peeks_bwd_workspace_bytes(int32_t nseq, int32_t dim, int32_t width) {
+    return nseq > 0 && dim > 0 && width > 0 ? (int64_t)nseq * dim * (width + 1) * (int64_t)sizeof(float) : 0;
+}
+// what the forward and the backward share behind scan_stream_check: the 32-bit cursors of a sequence's checkpoints and of the dB | dC rows
+static bool scanp_cursors_ok(const AumScanTmChunkVarArgs& a) {
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    return ((int64_t)a.total / STREAM_UB + 1) * a.dim * a.dstate * 4 <= lim && ((int64_t)a.total + 1) * 2 * a.dstate * 4 <= lim;
+}
+template <class T, bool SP, bool HAS_Z> static int scanp_fwd_launch(const AumScanTmChunkVarArgs& a, float* ckpt, int pe, aum_stream_t s) {
+    const int grid = a.nseq * (a.dim / WAVE);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_scanp_fwd_ckpt<T, SP, HAS_Z>), (scanp_fwd_wave<T, SP, HAS_Z>(a, ckpt, wg, pe)), a, ckpt, pe);
+}
+template <class T> static int scanp_fwd_dispatch_t(const AumScanTmChunkVarArgs& a, float* ckpt, int pe, aum_stream_t s) {
+    return with_bool((a.flags & AUM_SCAN_SOFTPLUS) != 0, [&](auto sp) {
+        return with_bool(a.z != nullptr, [&](auto hz) { return scanp_fwd_launch<T, sp, hz>(a, ckpt, pe, s); }); });
+}
+AUM_API int aum_scan_tm_peeks_fwd_ckpt(const AumScanTmPeeksFwdArgs* pa, void* stream) {
+    if (!pa) return AUM_E_NULL;
+    if (!pa->ckpt) return AUM_E_NULL;
+    AumScanTmChunkVarArgs a = pa->base;
+    a.state = pa->ckpt;
+    a.state_indices = nullptr;
+    a.nrows = a.nseq;
+    const StreamVar var = {a.cu_seqlens, nullptr, a.total, a.nseq, a.nrows};
+    if (const int rc = scan_stream_check(a, &var, pa->peek_every >= 1, a.total, AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED, scanp_cursors_ok(a), a.nseq, false)) return rc;
+    if (pa->ckpt_bytes < aum_scan_tm_peeks_ckpt_bytes(a.total, a.nseq, a.dim, a.dstate)) return AUM_E_WORKSPACE;
+    const AumScanTmChunkVarArgs k = scan_tm_fwd_resolve(a);
+    aum_stream_t s = (aum_stream_t)stream;
+    return AUM_BY_DTYPE_T(k.dtype, scanp_fwd_dispatch_t, k, pa->ckpt, (int)pa->peek_every, s);
+}
+template <class T, int SPM, bool HAS_Z> static int scanp_bwd_launch(const AumScanTmChunkVarArgs& a, const float* ckpt, const ScanpBwdOuts& w, int pe, aum_stream_t s) {
+    const int grid = a.nseq * (a.dim / WAVE);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_scanp_bwd<T, SPM, HAS_Z>), (scanp_bwd_wave<T, SPM, HAS_Z>(a, ckpt, w, wg, pe)), a, ckpt, w, pe);
+}
+template <class T> static int scanp_bwd_dispatch_t(const AumScanTmChunkVarArgs& a, const float* ckpt, const ScanpBwdOuts& w, int pe, aum_stream_t s) {
+    const int spm = (a.flags & AUM_SCAN_DELTA_ACTIVATED) ? SCANP_ACTIVATED : (a.flags & AUM_SCAN_SOFTPLUS) ? SCANP_SOFTPLUS : SCANP_RAW;
+    return with_int<SCANP_RAW, SCANP_SOFTPLUS, SCANP_ACTIVATED>(spm, [&](auto m) {
+        return with_bool(a.z != nullptr, [&](auto hz) { return scanp_bwd_launch<T, m, hz>(a, ckpt, w, pe, s); }); });
+}
+AUM_API int aum_scan_tm_peeks_bwd(const AumScanTmPeeksBwdArgs* pa, void* stream) {
+    if (!pa) return AUM_E_NULL;
+    if (!pa->ckpt || !pa->du || !pa->ddelta || !pa->workspace || (pa->base.z && !pa->dz)) return AUM_E_NULL;
+    AumScanTmChunkVarArgs a = pa->base;
+    a.state = const_cast<float*>(pa->ckpt);
+    a.state_indices = nullptr;
+    a.nrows = a.nseq;
+    const StreamVar var = {a.cu_seqlens, nullptr, a.total, a.nseq, a.nrows};
+    const uint32_t allowed = AUM_SCAN_SOFTPLUS | AUM_SCAN_DELTA_ACTIVATED;
+    if (const int rc = scan_stream_check(a, &var, pa->peek_every >= 1, a.total, allowed, scanp_cursors_ok(a), a.nseq, false)) return rc;
+    AumScanTmChunkVarArgs g = a;            // the gradients of the rows under the same rules as the rows
+    g.u = pa->du; g.delta = pa->ddelta; g.z = a.z ? pa->dz : nullptr; g.state = pa->workspace;
+    g.u_ts = pa->du_ts; g.delta_ts = pa->ddelta_ts; g.z_ts = a.z ? pa->dz_ts : 0;
+    if (const int rc = scan_stream_check(g, &var, true, a.total, allowed, true, a.nseq, false)) return rc;
+    if (pa->ckpt_bytes < aum_scan_tm_peeks_ckpt_bytes(a.total, a.nseq, a.dim, a.dstate)) return AUM_E_WORKSPACE;
+    if (pa->workspace_bytes < aum_scan_tm_peeks_bwd_workspace_bytes(a.total, a.nseq, a.dim, a.dstate)) return AUM_E_WORKSPACE;
+    ScanpBwdOuts w;
+    w.du = pa->du; w.ddelta = pa->ddelta; w.dz = pa->dz;
+    w.du_ts = pa->du_ts; w.ddelta_ts = pa->ddelta_ts; w.dz_ts = pa->dz_ts;
+    w.dbc_part = pa->workspace;
+    w.dA_part = w.dbc_part + (int64_t)(a.dim / WAVE) * a.total * 2 * a.dstate;
+    w.dD_part = w.dA_part + (int64_t)a.nseq * a.dim * a.dstate;
+    w.dbias_part = w.dD_part + (int64_t)a.nseq * a.dim;
+    aum_stream_t s = (aum_stream_t)stream;
+    return AUM_BY_DTYPE_T(a.dtype, scanp_bwd_dispatch_t, a, pa->ckpt, w, (int)pa->peek_every, s);
+}
+template <class T, bool SILU> static int convp_bwd_launch(const ConvpBwdArgs& a, int nseq, aum_stream_t s) {
+    const int grid = nseq * convt_cblocks<T, true>(a.dim);
+    return AUM_LAUNCH(grid, 64, s, (NoLds{}), (k_convp_bwd<T, SILU>), (convp_bwd_wave<T, SILU>(a, wg)), a);
+}
+template <class T> static int convp_bwd_dispatch_t(const ConvpBwdArgs& a, int nseq, bool silu, aum_stream_t s) {
+    return with_bool(silu, [&](auto sl) { return convp_bwd_launch<T, sl>(a, nseq, s); });
+}
+AUM_API int aum_conv1d_tm_peeks_bwd(const AumConvTmPeeksBwdArgs* pa, void* stream) {
+    if (!pa) return AUM_E_NULL;
+    if (!pa->dy || !pa->workspace) return AUM_E_NULL;
+    AumConvTmChunkVarArgs c = {};           // (x, dx) and (dy, dx) under the rules of the forward's (x, y)
+    c.x = pa->x; c.conv_state = pa->workspace; c.weight = pa->weight; c.bias = pa->bias; c.y = pa->dx;
+    c.cu_seqlens = pa->cu_seqlens; c.x_ts = pa->x_ts; c.y_ts = pa->dx_ts;
+    c.total = pa->total; c.nseq = pa->nseq; c.nrows = pa->nseq; c.dim = pa->dim; c.width = pa->width; c.dtype = pa->dtype; c.flags = pa->flags;
+    const StreamVar var = {c.cu_seqlens, nullptr, c.total, c.nseq, c.nrows};
+    const uint32_t allowed = AUM_CONV_SILU;
+    if (const int rc = conv_stream_check(c, &var, pa->peek_every >= 1, c.total, 0, allowed, ((uintptr_t)pa->workspace & 15) == 0, 2 * (int64_t)c.nseq)) return rc;
+    c.x = pa->dy; c.x_ts = pa->dy_ts;
+    if (const int rc = conv_stream_check(c, &var, true, c.total, 0, allowed, true, 0)) return rc;
+    if (pa->workspace_bytes < aum_conv1d_tm_peeks_bwd_workspace_bytes(c.nseq, c.dim, c.width)) return AUM_E_WORKSPACE;
+    ConvpBwdArgs k;
+    k.x = pa->x; k.dy = pa->dy; k.weight = pa->weight; k.bias = pa->bias; k.dx = pa->dx;
+    k.dw_part = pa->workspace;
+    k.db_part = pa->bias ? pa->workspace + (int64_t)c.nseq * c.dim * c.width : nullptr;
+    k.cu_seqlens = pa->cu_seqlens;
+    k.x_ts = pa->x_ts; k.dy_ts = pa->dy_ts; k.dx_ts = pa->dx_ts;
+    k.total = c.total; k.dim = c.dim; k.width = c.width; k.pe = pa->peek_every;
+    aum_stream_t s = (aum_stream_t)stream;
+    return AUM_BY_DTYPE_T(c.dtype, convp_bwd_dispatch_t, k, (int)c.nseq, (pa->flags & AUM_CONV_SILU) != 0, s);
 }
 
 // ---- conv -> x/dt projections -> scan of packed sessions in one launch (stream_block_kernels.h) ----

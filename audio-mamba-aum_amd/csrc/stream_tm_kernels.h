@@ -225,9 +225,12 @@ template <class T> struct ScancSeq {
 // with bias == NULL: the launcher drops it).  commit == false: the state row is read and not written (the exit stores are skipped).
 // PEEK: row L - 1 is a peek row -- LC = L - 1 rows go through the loop and into the state, the last one is stepped behind the exit stores
 // PEEKS: every (pe + 1)-th row is a peek row -- all L rows go through the loop, a peek row's step does not take its result into the state
-template <class T, bool SP, bool HAS_Z, bool PEEK = false, bool PEEKS = false>
-AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true, int pe = 0) {
+// CKPT (aum_scan_tm_peeks_fwd_ckpt, the training forward; with PEEKS): the sequence enters with a ZERO state (q.state is not read), and the
+// fp32 state in front of rows 0, 8, 16, ... is stored to ck + (row / 8) * ck_sb bytes in the (dim, 16) layout of a cache row; commit is false
+template <class T, bool SP, bool HAS_Z, bool PEEK = false, bool PEEKS = false, bool CKPT = false>
+AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool commit = true, int pe = 0, const float* ck = nullptr, int ck_sb = 0) {
     static_assert(!(PEEK && PEEKS), "one peek row behind the rows, or one every pe rows");
+    static_assert(!CKPT || PEEKS, "the checkpointing form is the training forward of the PEEKS rows");
     constexpr int N = SCANT_N, ES = (int)sizeof(T);
     const int L = q.len;
     const int LC = PEEK ? L - 1 : L;             // the rows the state takes in
@@ -244,7 +247,7 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
     const gbuf<T> obuf = make_gbuf(q.out);
     const gbuf<T> Bbuf = make_gbuf(q.B);
     const gbuf<T> Cbuf = make_gbuf(q.C);
-    const gbuf<float> sbuf = make_gbuf(q.state);
+    const gbuf<float> sbuf = make_gbuf(CKPT ? ck : q.state);
     const int u_tb = (int)p.u_ts * ES, d_tb = (int)p.delta_ts * ES, z_tb = HAS_Z ? (int)p.z_ts * ES : 0, o_tb = (int)p.out_ts * ES,
               B_tb = (int)p.B_ts * ES, C_tb = (int)p.C_ts * ES;
     const vi el_off = ec * ES;                   // this lane's channel inside a token row
@@ -255,7 +258,8 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
     AUM_UNROLL
     for (int i = 0; i < N / 4; ++i) {
         vf t[4];
-        vq_unpack<float>(gbuf_load16(sbuf, st_off + 16 * i, 0), t);
+        if (CKPT) t[0] = t[1] = t[2] = t[3] = splat(0.f);
+        else vq_unpack<float>(gbuf_load16(sbuf, st_off + 16 * i, 0), t);
         x[2 * i] = mk2(t[0], t[1]);
         x[2 * i + 1] = mk2(t[2], t[3]);
     }
@@ -319,6 +323,13 @@ AUM_DEV void scanc_unit(const ScancOps& p, const ScancSeq<T>& q, int e0, bool co
     };
     int next_peek = pe;                         // PEEKS: the index of the next peek row
     auto comp_blk = [&](int itb, const ScancRaw (&raw)[STREAM_UB]) {
+        if (CKPT && itb < LC) {                 // the state in front of the block (itb is a multiple of STREAM_UB)
+            AUM_UNROLL
+            for (int i = 0; i < N / 4; ++i) {
+                const vf t[4] = {lo2(x[2 * i]), hi2(x[2 * i]), lo2(x[2 * i + 1]), hi2(x[2 * i + 1])};
+                gbuf_store16(sbuf, st_off + 16 * i, (itb / STREAM_UB) * ck_sb, vq_pack<float>(t));
+            }
+        }
         AUM_UNROLL
         for (int j = 0; j < STREAM_UB; ++j) {
             if (itb + j < LC) {

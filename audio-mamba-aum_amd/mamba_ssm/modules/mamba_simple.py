@@ -94,10 +94,15 @@ class Mamba(nn.Module):
         return p
 
     # ---- forward (MS:169-311) ---------------------------------------------------------------------
-    def forward(self, hidden_states, inference_params=None, *, time_reversed=False):
+    def forward(self, hidden_states, inference_params=None, *, time_reversed=False, peek_every=None):
         """MS:169.  `time_reversed` (extension, keyword only): the block applied to the time-reversed sequence and reversed
         back, flip(forward(flip(h))), without the copies -- the odd layers of an `if_bidirectional` model (MM:623-638): every stage but
-        the conv and the scan is token-wise, and those two take a direction flag."""
+        the conv and the scan is token-wise, and those two take a direction flag.
+        `peek_every`=P (extension, keyword only; causal block, no caches): timeline training -- see forward_peeks."""
+        if peek_every is not None:
+            if inference_params is not None or time_reversed:
+                raise ValueError("forward(peek_every=) takes neither inference_params nor time_reversed")
+            return self.forward_peeks(hidden_states, peek_every)
         conv_state = ssm_state = None
         if time_reversed and (inference_params is not None or not self.use_fast_path):
             return self.forward(hidden_states.flip([1]), inference_params).flip([1])
@@ -204,6 +209,30 @@ class Mamba(nn.Module):
         if self.init_layer_scale is not None:
             out = out * self.gamma
         return out
+
+    def forward_peeks(self, hidden_states, peek_every):
+        """The causal block on (batch, T, d_model) rows [P tokens | peek row | P tokens | peek row | ...] from the start of a clip,
+        differentiable: what step_chunk(peek_every=P) computes from zeroed caches, with gradients.  Row j is a peek row iff
+        (j + 1) % (P + 1) == 0: it sees the conv window and the state of the committed rows in front of it and enters neither.
+            in_proj -> causal_conv1d_peeks_fn -> x_proj / dt_proj -> selective_scan_peeks_fn -> out_proj
+        The projections are ordinary differentiable products (the fused x/dt kernels are written for the offline block's operand
+        layout and are not used here); the conv and the scan are HIP both ways.  ssi.peeks_on_ref(): the two on their pure-torch twins."""
+        if self.bimamba_type != "none":
+            raise NotImplementedError("forward(peek_every=) needs the causal (bimamba_type='none') block")
+        if isinstance(peek_every, bool) or not isinstance(peek_every, int) or peek_every < 1:
+            raise ValueError(f"forward: peek_every is the number of committed rows before each peek row, an int >= 1, not {peek_every!r}")
+        if hidden_states.dim() != 3 or hidden_states.shape[1] < 1:
+            raise ValueError("forward(peek_every=): hidden_states must be (batch, T >= 1, d_model)")
+        E, N, R = self.d_inner, self.d_state, self.dt_rank
+        xz = self.in_proj(hidden_states)                                            # (batch, T, 2E): rows [x | z]
+        x, z = xz[..., :E], xz[..., E:]
+        xc = ssi.conv_peeks(x, self.conv1d.weight.reshape(E, self.d_conv), self.conv1d.bias, self.activation, peek_every)
+        x_dbl = self.x_proj(xc)
+        dt = F.linear(x_dbl[..., :R], self.dt_proj.weight)                          # the bias and the softplus are the scan's
+        y = ssi.scan_peeks(xc, dt.to(xc.dtype), neg_exp(self.A_log), x_dbl[..., R:R + N].to(xc.dtype), x_dbl[..., R + N:R + 2 * N].to(xc.dtype),
+                           self.D.float(), z.to(xc.dtype), self.dt_proj.bias.float(), True, peek_every)
+        out = self.out_proj(y)
+        return out if self.init_layer_scale is None else out * self.gamma
 
     def step(self, hidden_states, conv_state, ssm_state):
         """One token of streaming inference for the causal block (MS:313-358): (batch, 1, d_model) in, (batch, 1, d_model) out, the caches

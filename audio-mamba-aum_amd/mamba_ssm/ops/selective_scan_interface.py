@@ -361,6 +361,108 @@ def selective_scan_ref(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     return (out, h) if return_last_state else out
 
 
+# ---- timeline training: the scan with an uncommitted (peek) row behind every `peek_every` committed rows, from a zero state ----
+peeks_rows = aum_hip.peeks_rows
+
+
+def _rows2(t):
+    return None if t is None else t.reshape(-1, t.shape[-1])
+
+
+class SelectiveScanPeeksFn(torch.autograd.Function):
+    """aum_hip.scan_tm_peeks_fwd / scan_tm_peeks_bwd on (rows, dim) operands.  The parameter gradients are returned the ordinary way (no
+    grad_home bucket destinations)."""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, delta_softplus, peek_every, seq_map):
+        fix = lambda t: t if t is None or t.stride(-1) == 1 else t.contiguous()
+        u, delta, B, C, z = fix(u), fix(delta).to(u.dtype), fix(B).to(u.dtype), fix(C).to(u.dtype), fix(z)
+        z = None if z is None else z.to(u.dtype)
+        out, ckpt = aum_hip.scan_tm_peeks_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, False, seq_map, peek_every)
+        ctx.delta_softplus, ctx.peek_every, ctx.seq_map = delta_softplus, peek_every, seq_map
+        ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, ckpt)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        u, delta, A, B, C, D, z, delta_bias, ckpt = ctx.saved_tensors
+        dout = dout.to(u.dtype).contiguous()
+        du, ddelta, dz, dA, dB, dC, dD, dbias = aum_hip.scan_tm_peeks_bwd(dout, ckpt, u, delta, A, B, C, D, z, delta_bias, ctx.delta_softplus, False,
+                                                                         ctx.seq_map, ctx.peek_every)
+        return (du, ddelta, dA.to(A.dtype), dB.to(B.dtype), dC.to(C.dtype), None if D is None else dD.to(D.dtype), dz,
+                None if delta_bias is None else dbias.to(delta_bias.dtype), None, None, None)
+
+
+def selective_scan_peeks_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, peek_every=None, seq_map=None):
+    """The selective scan over rows [column 0's tokens | cls | column 1's tokens | cls | ...]: row j of a sequence is a peek row iff
+    (j + 1) % (peek_every + 1) == 0 -- it is computed from the state in front of it and does not update it; every sequence starts from a
+    zero state.  Differentiable (HIP forward with state checkpoints, HIP adjoint).  Token-major operands: u, delta, z (batch, T, dim) and
+    B, C (batch, T, dstate), or packed (total, .) rows with seq_map (aum_hip.seq_map).  Returns out in u's shape and dtype."""
+    u2, m, shape = peeks_rows(u, seq_map, "selective_scan_peeks_fn")
+    out = SelectiveScanPeeksFn.apply(u2, _rows2(delta), A, _rows2(B), _rows2(C), D, _rows2(z), delta_bias, delta_softplus, peek_every, m)
+    return out if shape is None else out.reshape(*shape, out.shape[-1])
+
+
+def selective_scan_peeks_ref(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, peek_every=None, seq_map=None):
+    """selective_scan_peeks_fn as a differentiable Python loop over the rows, in the dtype it is given (run it in float64 for an oracle)."""
+    u2, m, shape = peeks_rows(u, seq_map, "selective_scan_peeks_ref")
+    delta, B, C, z = _rows2(delta), _rows2(B), _rows2(C), _rows2(z)
+    dl = delta if delta_bias is None else delta + delta_bias.to(delta.dtype)
+    if delta_softplus:
+        dl = F.softplus(dl)
+    A = A.to(u2.dtype)
+    outs, at = [], 0
+    for n in m.lens:
+        h = torch.zeros(u2.shape[1], A.shape[1], dtype=u2.dtype, device=u2.device)
+        for j in range(n):
+            t = at + j
+            hn = torch.exp(dl[t][:, None] * A) * h + (dl[t] * u2[t])[:, None] * B[t][None, :]
+            y = hn @ C[t]
+            if D is not None:
+                y = y + D.to(y.dtype) * u2[t]
+            if z is not None:
+                y = y * F.silu(z[t])
+            outs.append(y)
+            if (j + 1) % (peek_every + 1) != 0:
+                h = hn
+        at += n
+    out = torch.stack(outs) if outs else u2.new_zeros(u2.shape)
+    return out if shape is None else out.reshape(*shape, out.shape[-1])
+
+
+_PEEKS_ON_REF = False
+
+
+@contextlib.contextmanager
+def peeks_on_ref():
+    """Inside: Mamba.forward(peek_every=) runs its conv and scan on the pure-torch twins (fp32 arithmetic on the operands as the kernels
+    get them, the result rounded to their dtype) -- the oracle the kernel path is tested against, and a way to train where no library is."""
+    global _PEEKS_ON_REF
+    old, _PEEKS_ON_REF = _PEEKS_ON_REF, True
+    try:
+        yield
+    finally:
+        _PEEKS_ON_REF = old
+
+
+def conv_peeks(x, weight, bias, activation, peek_every):
+    """the peek-row conv of the timeline block: the HIP function, or its twin under peeks_on_ref()"""
+    from causal_conv1d import causal_conv1d_peeks_fn, causal_conv1d_peeks_ref
+    if not _PEEKS_ON_REF:
+        return causal_conv1d_peeks_fn(x, weight, bias, activation, peek_every)
+    with torch.autocast(device_type=x.device.type, enabled=False):
+        return causal_conv1d_peeks_ref(x.float(), weight.float(), None if bias is None else bias.float(), activation, peek_every).to(x.dtype)
+
+
+def scan_peeks(u, delta, A, B, C, D, z, delta_bias, delta_softplus, peek_every):
+    """the peek-row scan of the timeline block: the HIP function, or its twin under peeks_on_ref()"""
+    if not _PEEKS_ON_REF:
+        return selective_scan_peeks_fn(u, delta, A, B, C, D, z, delta_bias, delta_softplus, peek_every)
+    with torch.autocast(device_type=u.device.type, enabled=False):
+        f = lambda t: None if t is None else t.float()
+        return selective_scan_peeks_ref(f(u), f(delta), f(A), f(B), f(C), f(D), f(z), f(delta_bias), delta_softplus, peek_every).to(u.dtype)
+
+
 # =================================================================================================
 # fused inner blocks  (SSI:155-633)
 # =================================================================================================

@@ -736,6 +736,81 @@ int aum_conv1d_tm_chunk_peeks(const AumConvTmChunkPeeksArgs* args, void* stream)
 int aum_scan_tm_chunk_peeks(const AumScanTmChunkPeeksArgs* args, void* stream);
 
 /*
+ * TIMELINE TRAINING (additive to ABI 13; `Mamba.forward(..., peek_every=)`, `AudioMamba.forward_timeline`): the two peek-row operators
+ * above as differentiable operations on packed sequences that START A CLIP -- every sequence enters with a zero conv window and a zero
+ * state, nothing is carried out, and there is no pool (base.state / base.conv_state, base.state_indices and base.nrows are not read).
+ * Row rule as above: row j of a sequence (0-based) is a peek row iff (j + 1) % (P + 1) == 0, P = peek_every >= 1, else a committed row.
+ * Gradients into an entry state are not provided.  `base` keeps every other field, dtype, stride rule and limit of the *_chunk_var entry
+ * points (cu_seqlens, total, nseq, the 32-bit cursor limit on `total`); an empty sequence is a no-op, and so is a cu_seqlens pair outside
+ * [0, total]: none of its rows and none of its partial rows is touched.  No atomics: every result is bitwise repeatable and a sequence's
+ * results do not depend on its neighbours or on its place in the pack.  The conv's training forward is aum_conv1d_tm_chunk_peeks itself on
+ * a zeroed pool.
+ *
+ * Scan, per channel e and state n, h the state in front of row t (zero in front of row 0):
+ *     dl = delta_t + delta_bias, through softplus with AUM_SCAN_SOFTPLUS (with AUM_SCAN_DELTA_ACTIVATED delta_t is taken as it is);
+ *     a = exp(dl A[e,n]);  hn = a h + dl u_t B_t[n];  y_t = sum_n hn C_t[n] + D[e] u_t;  out_t = y_t z_t sigmoid(z_t) (y_t without z);
+ *     h <- hn behind a committed row; h stays behind a peek row.
+ *   aum_scan_tm_peeks_fwd_ckpt -- the forward.  `out` is BIT FOR BIT that of aum_scan_tm_chunk_peeks on a zeroed pool (the same step
+ *     routine); in addition the fp32 state in front of rows 0, 8, 16, ... of every sequence is stored to `ckpt`, which the backward reads:
+ *     aum_scan_tm_peeks_ckpt_bytes(total, nseq, dim, dstate) bytes = (total / 8 + nseq) slots of (dim, dstate) fp32, 16-byte aligned.
+ *   aum_scan_tm_peeks_bwd -- the adjoint.  base.out is dout (read).  Rows walked downward, g = dL/dh behind row t, zero behind the last row:
+ *     dy = dout_t z sigmoid(z);  dz_t = dout_t y_t d/dz[z sigmoid(z)];  dhn[n] = C_t[n] dy + (committed ? g[n] : 0);
+ *     dC_t[n] = sum_e hn dy;  dB_t[n] = sum_e dhn dl u_t;  du_t = D dy + dl sum_n dhn B_t[n];  ddl = sum_n dhn (A a h + u_t B_t[n]);
+ *     dA[e,n] += dhn dl a h;  dD[e] += dy u_t;  g[n] <- a dhn[n] + (committed ? 0 : g[n]).
+ *     ddelta_t is ddl in RAW space as aum_scan_tm_bwd returns it: times 1 - exp(-dl) (the softplus derivative) with AUM_SCAN_SOFTPLUS or
+ *     AUM_SCAN_DELTA_ACTIVATED; ddelta_bias[e] += ddelta_t.  du, ddelta, dz: (total, dim) in `dtype`, row strides du_ts / ddelta_ts / dz_ts
+ *     (dz NULL without z).  The sums over channels and sequences are left as fp32 PARTIAL ROWS in `workspace`
+ *     (aum_scan_tm_peeks_bwd_workspace_bytes(total, nseq, dim, dstate) bytes, 16-byte aligned), in this order:
+ *         dBC_part [dim / 64][total][2 dstate]   (dB | dC of a token, one row per 64-channel group)
+ *         dA_part  [nseq][dim][dstate],  dD_part [nseq][dim],  dbias_part [nseq][dim]   (one row per sequence)
+ *     which the caller adds over the first axis with aum_sum_rows (a fixed order).  The rows of an empty sequence are not written: the
+ *     caller zeroes the per-sequence parts first.
+ *
+ * Conv (width <= 4, weight (dim, width) and bias (dim) fp32, AUM_CONV_SILU):  pre_j = bias + sum_k w[k] win_j[k], win_j = the last
+ * width - 1 COMMITTED inputs in front of row j (zeros in front of the sequence) followed by x_j;  y_j = silu?(pre_j).
+ *   aum_conv1d_tm_peeks_bwd -- dpre_j = dy_j act'(pre_j) (pre_j recomputed, as aum_conv1d_tm_bwd does); dx of each row in win_j gains
+ *     w[k] dpre_j; dw[e,k] += dpre_j win_j[k]; db[e] += dpre_j.  dx (total, dim) in `dtype`, dx != x, dx != dy; the sums over sequences are
+ *     left in `workspace` (aum_conv1d_tm_peeks_bwd_workspace_bytes(nseq, dim, width) bytes, 16-byte aligned) as dw_part [nseq][dim][width],
+ *     db_part [nseq][dim], to be added with aum_sum_rows; the caller zeroes them first.
+ *
+ * Refused with nothing touched: peek_every < 1 (AUM_E_SHAPE); AUM_SCAN_PEEK_LAST / AUM_CONV_PEEK_LAST or any flag the forward entry points
+ * do not take (AUM_E_UNSUPPORTED); ckpt_bytes / workspace_bytes below the sizes above (AUM_E_WORKSPACE); the 32-bit cursor limit, which
+ * here also covers a sequence's checkpoints and the partial rows (AUM_E_UNSUPPORTED).  reserved: 0.
+ */
+typedef struct AumScanTmPeeksFwdArgs {
+    AumScanTmChunkVarArgs base;
+    float* ckpt;
+    int64_t ckpt_bytes;
+    int32_t peek_every, reserved;
+} AumScanTmPeeksFwdArgs;
+typedef struct AumScanTmPeeksBwdArgs {
+    AumScanTmChunkVarArgs base;         /* base.out: dout */
+    const float* ckpt;
+    void *du, *ddelta, *dz;
+    float* workspace;
+    int64_t ckpt_bytes, workspace_bytes, du_ts, ddelta_ts, dz_ts;
+    int32_t peek_every, reserved;
+} AumScanTmPeeksBwdArgs;
+typedef struct AumConvTmPeeksBwdArgs {
+    const void *x, *dy;
+    const float *weight, *bias;
+    void* dx;
+    float* workspace;
+    const int32_t* cu_seqlens;
+    int64_t workspace_bytes, x_ts, dy_ts, dx_ts;
+    int32_t total, nseq, dim, width;
+    int32_t dtype;
+    uint32_t flags;
+    int32_t peek_every, reserved;
+} AumConvTmPeeksBwdArgs;
+int64_t aum_scan_tm_peeks_ckpt_bytes(int32_t total, int32_t nseq, int32_t dim, int32_t dstate);
+int64_t aum_scan_tm_peeks_bwd_workspace_bytes(int32_t total, int32_t nseq, int32_t dim, int32_t dstate);
+int64_t aum_conv1d_tm_peeks_bwd_workspace_bytes(int32_t nseq, int32_t dim, int32_t width);
+int aum_scan_tm_peeks_fwd_ckpt(const AumScanTmPeeksFwdArgs* args, void* stream);
+int aum_scan_tm_peeks_bwd(const AumScanTmPeeksBwdArgs* args, void* stream);
+int aum_conv1d_tm_peeks_bwd(const AumConvTmPeeksBwdArgs* args, void* stream);
+
+/*
  * The recurrent middle of the causal block on packed sessions in ONE launch (additive to ABI 13; `Mamba.step_chunk` through
  * aum_hip.stream_block): from the x half of the in_proj rows to the gated scan output,
  *     xc = silu(conv(x) from conv_state);  x_dbl = xc . wx^T;  delta = softplus(x_dbl[:, :rank] . wdt^T + delta_bias);
