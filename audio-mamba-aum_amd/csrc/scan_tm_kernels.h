@@ -1278,7 +1278,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
         if constexpr (FULL) {
             // two steps per packed instruction; the two running sums (dD, dbias) keep their step order (one fma / add per step): bit-equal to the
             // step-by-step form below
-            const vf2 Dv2 = spl2(Dv), one2 = spl2(splat(1.f));
+            const vf2 Dv2 = spl2(Dv);
             AUM_UNROLL
             for (int i = 0; i < SCANT_CK / 2; ++i) {
                 const int s0 = 2 * i, s1 = 2 * i + 1;
@@ -1296,7 +1296,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
                         du = du + mk2(raw_to_f32<T>(rpu[s0]), raw_to_f32<T>(rpu[s1]));
                         dd = dd + mk2(raw_to_f32<T>(rpd[s0]), raw_to_f32<T>(rpd[s1]));
                     }
-                    if (SP != SCANT_SP_NONE) dd = dd * (one2 - vexp2_2(dls * spl2(splat(-LOG2E))));      // sigmoid(raw) = 1 - exp(-softplus(raw))
+                    if (SP != SCANT_SP_NONE) dd = dd * vsigmoid_of_softplus2(dls);      // sigmoid(raw) = 1 - exp(-softplus(raw))
                     dbacc = dbacc + lo2(dd);
                     dbacc = dbacc + hi2(dd);
                 }
@@ -1322,7 +1322,7 @@ AUM_DEV void scant_bwd_run(const AumScanTmBwdArgs& p, const ScanTBwdOut& wo, int
                             du = du + raw_to_f32<T>(rpu[s]);
                             dd = dd + raw_to_f32<T>(rpd[s]);
                         }
-                        if (SP != SCANT_SP_NONE) dd = dd * (splat(1.f) - vexp2(dls * (-LOG2E)));      // sigmoid(raw) = 1 - exp(-softplus(raw))
+                        if (SP != SCANT_SP_NONE) dd = dd * vsigmoid_of_softplus(dls);      // sigmoid(raw) = 1 - exp(-softplus(raw))
                         dbacc = dbacc + dd;
                     }
                     lds_write_elem<T>(t_du, off, du);

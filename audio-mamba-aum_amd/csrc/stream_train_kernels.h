@@ -219,7 +219,7 @@ AUM_DEV void scanp_bwd_wave(const AumScanTmChunkVarArgs& p, const float* ckpt, c
                 const vf s1 = lo2(S1[s]) + hi2(S1[s]), s2 = lo2(S2[s]) + hi2(S2[s]);
                 const vf duo = vfma(Dv, dy[s], dl[s] * s1);
                 vf dd = vfma(uu[s], s1, s2);
-                if (SPM != SCANP_RAW) dd = dd * (splat(1.f) - vexp2(dl[s] * (-LOG2E)));       // sigmoid(raw) = 1 - exp(-softplus(raw))
+                if (SPM != SCANP_RAW) dd = dd * vsigmoid_of_softplus(dl[s]);       // sigmoid(raw) = 1 - exp(-softplus(raw))
                 dDacc = vfma(dy[s], uu[s], dDacc);
                 dbacc = dbacc + dd;
                 gbuf_store(dubuf, el_off, (tb + s) * du_tb, duo);

@@ -1017,6 +1017,20 @@ AUM_DEV vf2 vsoftplus2(vf2 x) {
     return mk2(vsel(lo2(x) > 20.0f, lo2(x), vsel(z0, lo2(e), lo2(v))), vsel(hi2(x) > 20.0f, hi2(x), vsel(z1, hi2(e), hi2(v))));
 }
 
+// sigmoid(raw) from delta = softplus(raw): 1 - exp(-delta), for the backward passes that keep delta and not raw.  The difference
+// cancels for small delta (its error is 2^-25 / delta of the result: 1.3 % at delta = 2.3e-6), so below 2^-6 the series
+// delta (1 - delta/2 + delta^2/6) stands in: truncated at 1.6e-7 of the result there, where the difference is good to 1.9e-6.  Two
+// fmas and one live temporary: k_scant_bwd has no register to spare.  The packed form is the same arithmetic on both halves (bit-equal).
+AUM_DEV vf vsigmoid_of_softplus(vf d) {
+    const vf s = d * vfma(d, vfma(d, splat(1.f / 6.f), splat(-0.5f)), splat(1.f));
+    return vsel(d < 0.015625f, s, splat(1.f) - vexp2(d * (-LOG2E)));
+}
+AUM_DEV vf2 vsigmoid_of_softplus2(vf2 d) {
+    const vf2 s = d * vfma2(d, vfma2(d, spl2(splat(1.f / 6.f)), spl2(splat(-0.5f))), spl2(splat(1.f)));
+    const vf2 e = spl2(splat(1.f)) - vexp2_2(d * spl2(splat(-LOG2E)));
+    return mk2(vsel(lo2(d) < 0.015625f, lo2(s), lo2(e)), vsel(hi2(d) < 0.015625f, hi2(s), hi2(e)));
+}
+
 // Sum over each 16-lane row, result in every lane of the row: 4 DPP rotate-and-add steps.
 AUM_DEV vf row_sum16(vf x) {
     x = x + dpp_row_ror<8>(x);

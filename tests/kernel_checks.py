@@ -60,13 +60,25 @@ def _scan_errors(pairs):
 
 
 def check_scan(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, tol=None, strided=False, generic=False,
-               rowpair=False, ckpt=False, lane_ckpt=False):
+               rowpair=False, ckpt=False, lane_ckpt=False, inputs=None):
     """lane_ckpt: L = 513 rows -- let the forward fill the lane-entry checkpoint and hand it to the backward (the row kernels of
     scan_row_kernels.h; without it the backward runs the previous-generation kernels).
-    ckpt: hand the forward's chunk-entry-state checkpoint to the backward (long rows; the backward then skips its pre-pass)"""
-    name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
-    d = cases.scan_inputs(*case)
+    ckpt: hand the forward's chunk-entry-state checkpoint to the backward (long rows; the backward then skips its pre-pass).
+    inputs: a dict with the keys of cases.scan_inputs to run on instead of the seeded values of `case` (scan_domain_checks.py)"""
+    name = case[0]
     tol = tol or (TOL_F32 if dtype == torch.float32 else TOL_BF16)
+    pairs = scan_pairs(lib, dev, case, dtype, reverse, bidir, strided, generic, rowpair, ckpt, lane_ckpt, inputs)
+    errs = _scan_errors(pairs)
+    bad = {k: v for k, v in errs.items() if not (v < tol * (4 if k.split(":")[-1].startswith("d") else 1))}
+    assert not bad, (name, str(dtype), "rev" if reverse else "fwd", "bidir" if bidir else "uni", bad, errs)
+    return errs
+
+
+def scan_pairs(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, strided=False, generic=False, rowpair=False, ckpt=False,
+               lane_ckpt=False, inputs=None):
+    """the launches and the fp64 oracle of check_scan -> {name: (got, reference)}, channel-major like the oracle"""
+    name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
+    d = cases.scan_inputs(*case) if inputs is None else inputs
     act = lambda a: T(a, dev, dtype)
     q = {k: rq(d[k], dtype) for k in ("u", "delta", "z", "B", "C", "dout")}
     rng = np.random.default_rng(7)
@@ -113,10 +125,7 @@ def check_scan(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, 
             assert g.get(k) is None, k
             continue
         pairs[k] = (N(g[k]), gr[k])
-    errs = _scan_errors(pairs)
-    bad = {k: v for k, v in errs.items() if not (v < tol * (4 if k.split(":")[-1].startswith("d") else 1))}
-    assert not bad, (name, str(dtype), "rev" if reverse else "fwd", "bidir" if bidir else "uni", bad, errs)
-    return errs
+    return pairs
 
 
 def check_conv(lib, dev, case, dtype=torch.float32, reverse=False, silu=True, generic=False):
@@ -573,13 +582,21 @@ def check_scan_accumulate(lib, dev, case, dtype=torch.float32, tol=None):
 
 
 
-def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, tol=None, xz_layout=False, backward=True, segments=1):
+def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, tol=None, xz_layout=False, backward=True, segments=1,
+                  inputs=None):
     """aum_scan_tm_fwd / _bwd (time-serial scan on token-major activations) against the fp64 oracle on the same seeded inputs as the
     channel-major kernels.  xz_layout: u and z are the two
     halves of one (batch, len, 2 dim) tensor (row stride 2 dim), as in_proj leaves them.  segments > 1: the time-segmented launches
-    (aum_scan_tm_seg_fwd / _bwd), held to the same oracle and the same tolerances."""
+    (aum_scan_tm_seg_fwd / _bwd), held to the same oracle and the same tolerances.
+    inputs: a dict with the keys of cases.scan_inputs to run on instead of the seeded values of `case` (scan_domain_checks.py)"""
+    ref, out, out_pre, out2, g = scan_tm_launch(lib, dev, case, dtype, reverse, bidir, xz_layout, backward, segments, inputs)
+    return scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out2, g)
+
+
+def scan_tm_launch(lib, dev, case, dtype=torch.float32, reverse=False, bidir=False, xz_layout=False, backward=True, segments=1, inputs=None):
+    """the launches of check_scan_tm -> (scan_tm_reference's dict, out, out_pre, the inference form's out, the gradients | None)"""
     name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
-    ref = scan_tm_reference(case, dtype, reverse, bidir, backward)
+    ref = scan_tm_reference(case, dtype, reverse, bidir, backward, inputs)
     d, A_b = ref["inputs"], ref["A_b"]
     tm = lambda a: None if a is None else T(a, dev, dtype).transpose(1, 2).contiguous()      # (batch, len, X)
     u, delta, z, dout = tm(d["u"]), tm(d["delta"]), tm(d["z"]), tm(d["dout"])
@@ -603,15 +620,16 @@ def check_scan_tm(lib, dev, case, dtype=torch.float32, reverse=False, bidir=Fals
                                 segments=segments, want_dA_xA=True)
         # the optional products d A .* A (the gradient of A_log) come out of the same partial-sum launch: exactly dA * A in fp32
         assert torch.equal(g["dA_xA"], g["dA"] * A) and (not bidir or torch.equal(g["dA_b_xA"], g["dA_b"] * T(A_b, dev)))
-    return scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out2, g)
+    return ref, out, out_pre, out2, g
 
 
-def scan_tm_reference(case, dtype, reverse, bidir, backward=True):
+def scan_tm_reference(case, dtype, reverse, bidir, backward=True, inputs=None):
     """the seeded inputs of a scan case (A_b: the second direction's A of a Fo-Bi pair) and the fp64 oracle's forward and gradients on them
     as rounded to `dtype`, both directions summed for a pair: what check_scan_tm (and the poison checks of poison_checks.py) hold the
-    token-major scans to -> dict(inputs, A_b, out, out_pre, grads | None), channel-major like the oracle"""
+    token-major scans to -> dict(inputs, A_b, out, out_pre, grads | None), channel-major like the oracle.
+    inputs: a dict with the keys of cases.scan_inputs in place of the seeded values of `case`"""
     name, batch, dim, length, dstate, has_z, has_D, has_bias, softplus = case
-    d = cases.scan_inputs(*case)
+    d = cases.scan_inputs(*case) if inputs is None else inputs
     q = {k: rq(d[k], dtype) for k in ("u", "delta", "z", "B", "C", "dout")}
     rng = np.random.default_rng(7)
     A_b = (d["A"] * np.exp(rng.normal(0, 0.1, d["A"].shape))).astype(np.float32) if bidir else None
@@ -635,8 +653,17 @@ def scan_tm_reference(case, dtype, reverse, bidir, backward=True):
 def scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out_nopre, g):
     """the bars of check_scan_tm: token-major (batch, len, dim) out / out_pre / the inference form's out and the dict of gradients as
     scan_tm_bwd returns it (None: forward only) against scan_tm_reference's values"""
-    name, dstate = case[0], case[4]
+    name = case[0]
     tol = tol or (TOL_F32 if dtype == torch.float32 else TOL_BF16)
+    errs = _scan_errors(scan_tm_pairs(case, ref, out, out_pre, out_nopre, g))
+    bad = {k: v for k, v in errs.items() if not (v < tol * (4 if k.split(":")[-1].startswith("d") else 1))}
+    assert not bad, (name, str(dtype), "rev" if reverse else "fwd", "bidir" if bidir else "uni", bad, errs)
+    return errs
+
+
+def scan_tm_pairs(case, ref, out, out_pre, out_nopre, g):
+    """what scan_tm_assert compares -> {name: (got, reference)}, channel-major like the oracle"""
+    dstate = case[4]
     cm = lambda t: N(t).transpose(0, 2, 1)
     pairs = {"out": (cm(out), ref["out"]), "out_pre": (cm(out_pre), ref["out_pre"]), "out_nopre": (cm(out_nopre), ref["out"])}
     if g is not None:
@@ -649,10 +676,7 @@ def scan_tm_assert(case, dtype, reverse, bidir, tol, ref, out, out_pre, out_nopr
                 assert got.get(k) is None, k
                 continue
             pairs[k] = (got[k], gr[k])
-    errs = _scan_errors(pairs)
-    bad = {k: v for k, v in errs.items() if not (v < tol * (4 if k.split(":")[-1].startswith("d") else 1))}
-    assert not bad, (name, str(dtype), "rev" if reverse else "fwd", "bidir" if bidir else "uni", bad, errs)
-    return errs
+    return pairs
 
 
 def _tm_rows_vs_oracle(O, b, es, u, dl, z, Bm, Cm, A, A_b, D, bias, dout, softplus=True):

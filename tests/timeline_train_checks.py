@@ -40,8 +40,19 @@ class Scan:
     TOKEN, PARAM = ("du", "ddelta", "dz", "dB", "dC"), ("dA", "dD", "ddelta_bias")
 
     @staticmethod
-    def operands(dt, dim, total, device, kind, seed):
-        return ScanOp.operands(dt, dim, total, 1, (), device, kind=kind, seed=seed)
+    def operands(dt, dim, total, device, kind, seed, inputs=None):
+        """inputs: a dict with the keys of cases.scan_inputs, batch 1 and `total` steps, to pack instead of the seeded values (and
+        "softplus" / "activated": the form delta is in; scan_domain_checks.py)"""
+        if inputs is None:
+            return ScanOp.operands(dt, dim, total, 1, (), device, kind=kind, seed=seed)
+        tm = lambda k, t=None: None if inputs[k] is None else torch.tensor(np.ascontiguousarray(inputs[k][0].T)).to(t or DT[dt]).to(device)
+        par = lambda k: None if inputs[k] is None else torch.tensor(inputs[k], dtype=torch.float32).to(device)
+        assert inputs["u"].shape == (1, dim, total)
+        xz = torch.cat((tm("u"), tm("z") if inputs["z"] is not None else tm("u")), dim=1)      # u, z as the halves of one xz row
+        bcm = torch.cat((tm("B"), tm("C")), dim=1)
+        return {"dt": dt, "dim": dim, "u": xz[:, :dim], "z": xz[:, dim:] if inputs["z"] is not None else None, "delta": tm("delta"),
+                "B": bcm[:, :16], "C": bcm[:, 16:], "A": par("A"), "D": par("D"), "bias": par("delta_bias"),
+                "sp": bool(inputs.get("softplus", True)), "act": bool(inputs.get("activated", False)), "pool": None}
 
     @staticmethod
     def rows(o):
