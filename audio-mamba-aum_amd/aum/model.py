@@ -111,6 +111,39 @@ class Block(nn.Module):
         return self.mixer(hidden_states, inference_params=inference_params), residual
 
 
+class ParkedSessions:
+    """Streaming sessions off their pool (AudioMamba.stream_park makes it, stream_resume takes it):
+      blob       (n, record) uint8, on the pool's device or in pinned host memory -- session i's rows of every pool tensor behind one
+                 another (aum_hip.stream_park_layout: per layer conv window and scan state, then the sample tail), as the bytes they were
+      columns    [n] time columns pushed so far
+      wave       None, or with a WaveStream {tail_len, samples, frames, ended}: [n] each, the host counters of the sample tail
+      signature  (depth, d_inner, d_conv, d_state, cache dtype, tail width; 0: no tail): what the record's layout depends on --
+                 stream_resume refuses caches with another one
+    len(state) sessions; state[i] one of them, state.select(idx) several, in that order (an index may repeat)."""
+    WAVE_KEYS = ("tail_len", "samples", "frames", "ended")
+
+    def __init__(self, blob, columns, wave, signature):
+        self.blob, self.columns, self.wave, self.signature = blob, list(columns), wave, tuple(signature)
+
+    def __len__(self):
+        return len(self.columns)
+
+    def select(self, idx):
+        idx = [int(i) for i in idx]
+        if not idx or min(idx) < -len(self) or max(idx) >= len(self):
+            raise IndexError(f"ParkedSessions.select: {idx} of {len(self)} sessions")
+        idx = [i % len(self) for i in idx]
+        if len(set(idx)) == 1:                     # one record for all: a view, no copy (stream_resume reads it len(idx) times)
+            blob = self.blob[idx[0]:idx[0] + 1].expand(len(idx), -1)
+        else:
+            blob = self.blob.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.blob.device))
+        wave = None if self.wave is None else {k: [v[i] for i in idx] for k, v in self.wave.items()}
+        return ParkedSessions(blob, [self.columns[i] for i in idx], wave, self.signature)
+
+    def __getitem__(self, i):
+        return self.select([i])
+
+
 class AudioMamba(nn.Module):
     def __init__(self, spectrogram_size=(128, 1024), patch_size=(16, 16), strides=(16, 16), depth=24, embed_dim=768,
                  channels=1, num_classes=527, norm_epsilon=1e-5, bimamba_type="v1", if_devide_out=True,
@@ -611,6 +644,152 @@ class AudioMamba(nn.Module):
         if ks[0] >= 1:
             return self.stream_push(frames.reshape(wave.shape[0], wmap.frames[0], -1), cache, read=read, return_features=return_features)
         return (cache["columns"], self.stream_read(cache, return_features)) if read else cache["columns"]
+
+    # ---- parking sessions: a session's rows off a pool and back, into any free rows of any pool of the same model --------
+    def _park_tensors(self, cache, wave_stream):
+        """the pool tensors a session has a row in, in record order: per layer (conv_state, ssm_state), then the sample tails"""
+        ts = [t for i in sorted(cache["layers"]) for t in cache["layers"][i]]
+        return ts + ([wave_stream.tails] if wave_stream is not None else [])
+
+    def _park_signature(self, what, cache, wave_stream):
+        """(depth, d_inner, d_conv, d_state, cache dtype, tail width) of a cache (and its wave stream): what a record's layout depends on"""
+        from .frontend import WaveStream
+        if not cache["layers"]:
+            raise ValueError(f"{what}: the cache has no layers")
+        c, s = cache["layers"][min(cache["layers"])]
+        if any(cc.shape[1:] != c.shape[1:] or ss.shape[1:] != s.shape[1:] or cc.dtype != c.dtype or ss.dtype != s.dtype or s.dtype != c.dtype
+               for cc, ss in cache["layers"].values()):
+            raise ValueError(f"{what}: the layers' caches differ in shape or dtype")
+        if wave_stream is not None:
+            if not isinstance(wave_stream, WaveStream):
+                raise TypeError(f"{what}: wave_stream must come from allocate_wave_stream")
+            if wave_stream.sessions != cache["batch"] or wave_stream.tails.device != c.device:
+                raise ValueError(f"{what}: the wave stream was built for {wave_stream.sessions} sessions on {wave_stream.tails.device}, the cache "
+                                 f"has {cache['batch']} rows on {c.device}")
+        return (len(cache["layers"]), c.shape[1], c.shape[2], s.shape[2], c.dtype, 0 if wave_stream is None else wave_stream.cap)
+
+    def _check_park_rows(self, what, cache, sessions):
+        """_check_sessions for a park / resume / fork: a pool or a fixed-batch cache (its rows are sessions too), at least one row, distinct"""
+        rows = self._check_sessions(what, cache, sessions, writes=self._is_pool(cache))
+        if not rows:
+            raise ValueError(f"{what}: at least one session")
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"{what}: the sessions {rows} are not distinct")
+        return rows
+
+    @staticmethod
+    def _park_kernel(tensors):
+        """the library whose aum_stream_park moves the rows, or None: plain indexed copies (CPU tensors without a host-pointer library).
+        Device tensors always take the kernel: a missing library is an error there, as everywhere."""
+        import aum_hip
+        if tensors[0].device.type == "cuda":
+            return aum_hip.get()
+        lib = aum_hip._product
+        return lib if lib is not None and lib.host else None
+
+    @staticmethod
+    def _park_copies(tensors, rows, blob, restore):
+        """The un-fused twin of aum_hip.stream_park, one indexed copy per pool tensor: the same records byte for byte."""
+        import aum_hip
+        lay = aum_hip.stream_park_layout(tensors)
+        n = len(rows)
+        if blob is None:
+            blob = torch.zeros((n, lay.record), dtype=torch.uint8, device=tensors[0].device)
+        idx = torch.tensor(rows, dtype=torch.int64).to(tensors[0].device)
+        for t, off, nb in zip(tensors, lay.offsets, lay.row_bytes):
+            if restore:
+                t.index_copy_(0, idx, blob[:, off:off + nb].contiguous().view(t.dtype).reshape((n,) + tuple(t.shape[1:])))
+            else:
+                blob[:, off:off + nb] = t.index_select(0, idx).reshape(n, -1).view(torch.uint8)
+        return blob
+
+    def _park_move(self, tensors, rows, blob, restore):
+        import aum_hip
+        lib = self._park_kernel(tensors)
+        if lib is None:
+            return self._park_copies(tensors, rows, blob, restore)
+        return aum_hip.stream_park(tensors, rows, blob, restore=restore, lib=lib)
+
+    @torch.no_grad()
+    def stream_park(self, cache, sessions, wave_stream=None, to_host=False):
+        """Take sessions off a pool: everything the rows `sessions` of `cache` (a pool from allocate_stream_pool, or a fixed-batch cache
+        from allocate_inference_cache, whose rows are sessions too) carry -- per layer the conv window and the scan state, the column
+        counts and, with wave_stream= (the WaveStream carried next to the cache), the sample tails and their counters -- as one
+        ParkedSessions, in the order of `sessions`.  ONE launch (aum_hip.stream_park) whatever the depth; to_host=True: plus one copy
+        of the blob into pinned host memory (the call then waits for the stream).  Parking is a read: the pool keeps the rows, the caller
+        decides when to stream_reset them.  The kernels that advance a session give the same bits under any pool row, so a session
+        resumed from its record continues bit for bit.  Every argument is checked first: a refused call changes nothing."""
+        self._check_streamable()
+        rows = self._check_park_rows("stream_park", cache, sessions)
+        sig = self._park_signature("stream_park", cache, wave_stream)
+        pool_cols = cache["columns"]
+        columns = [pool_cols[r] for r in rows] if self._is_pool(cache) else [pool_cols] * len(rows)
+        wave = None
+        if wave_stream is not None:
+            ws, pw = wave_stream, self.patch_embed.proj.kernel_size[1]
+            for r, c in zip(rows, columns):
+                if c * pw != ws.frames[r]:
+                    raise ValueError(f"stream_park: session {r} has {c} columns in the cache and {ws.frames[r]} frames in the wave stream: they "
+                                     "do not belong together")
+            wave = {k: [getattr(ws, k)[r] for r in rows] for k in ParkedSessions.WAVE_KEYS}
+        blob = self._park_move(self._park_tensors(cache, wave_stream), rows, None, False)
+        if to_host and blob.device.type == "cuda":
+            host = torch.empty(blob.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(blob)
+            blob = host
+        return ParkedSessions(blob, columns, wave, sig)
+
+    @torch.no_grad()
+    def stream_resume(self, state, cache, sessions, wave_stream=None):
+        """Bring parked sessions back: state[i] into row sessions[i] of `cache` -- any cache of the same layout (depth, d_inner, d_conv,
+        d_state, cache dtype; with a sample tail, wave_stream= and the same tail width), any distinct rows, whatever they hold -- with
+        its column count and, with wave_stream=, its tail and counters.  ONE launch; a host blob is uploaded with one copy first.
+        Refused before anything is written: another layout, a blob of another record size, rows that are not distinct or not rows of
+        the cache, a session count other than len(state), a wave stream missing or unexpected.  A fixed-batch cache keeps ONE column
+        count for all rows: it takes sessions that are at its own count, or all of its rows at once at one count."""
+        import aum_hip
+        self._check_streamable()
+        if not isinstance(state, ParkedSessions):
+            raise TypeError("stream_resume: state must come from stream_park")
+        rows = self._check_park_rows("stream_resume", cache, sessions)
+        sig = self._park_signature("stream_resume", cache, wave_stream)
+        if sig != state.signature:
+            raise ValueError(f"stream_resume: the sessions were parked from caches of layout {state.signature}, these are {sig} "
+                             "(depth, d_inner, d_conv, d_state, cache dtype, tail width)")
+        if len(rows) != len(state):
+            raise ValueError(f"stream_resume: {len(state)} parked sessions for the rows {rows}")
+        tensors = self._park_tensors(cache, wave_stream)
+        record = aum_hip.stream_park_layout(tensors).record
+        if state.blob.dim() != 2 or state.blob.dtype != torch.uint8 or tuple(state.blob.shape) != (len(rows), record):
+            raise ValueError(f"stream_resume: the blob is {tuple(state.blob.shape)} {state.blob.dtype}, these caches take ({len(rows)}, {record}) uint8")
+        if not self._is_pool(cache) and any(c != cache["columns"] for c in state.columns) and not (
+                len(rows) == cache["batch"] and len(set(state.columns)) == 1):
+            raise ValueError(f"stream_resume: a cache from allocate_inference_cache keeps one column count ({cache['columns']}) for all rows; "
+                             f"the sessions are at {state.columns}")
+        dev = tensors[0].device
+        blob = state.blob if state.blob.device == dev else state.blob.to(dev, non_blocking=True)
+        self._park_move(tensors, rows, blob, True)
+        if self._is_pool(cache):
+            for r, c in zip(rows, state.columns):
+                cache["columns"][r] = c
+        else:
+            cache["columns"] = state.columns[0]
+        if wave_stream is not None:
+            for k in ParkedSessions.WAVE_KEYS:
+                for r, v in zip(rows, state.wave[k]):
+                    getattr(wave_stream, k)[r] = v
+
+    @torch.no_grad()
+    def stream_fork(self, cache, src, dst, wave_stream=None):
+        """Copy session `src` of a cache into the rows `dst` of the same cache (distinct, not src): a park of one session and a resume
+        of every dst row from that one record, two launches on the device, src untouched.  The forks continue bit for bit as src
+        would -- to score several continuations of one prefix."""
+        rows = self._check_park_rows("stream_fork", cache, list(dst))
+        (s,) = self._check_park_rows("stream_fork", cache, [src])
+        if s in rows:
+            raise ValueError(f"stream_fork: the source session {s} is among the destinations {rows}")
+        state = self.stream_park(cache, [s], wave_stream=wave_stream)
+        self.stream_resume(state.select([0] * len(rows)), cache, rows, wave_stream=wave_stream)
 
     def _with_cls_rows(self, x):
         """(B, K n_f, Dm) time-major tokens of K columns -> (B, K (n_f + 1), Dm): the cls row behind every column's n_f tokens"""

@@ -277,6 +277,15 @@ class XdtArgs(C.Structure):
                 + [("delta_bias", _vp), ("flags", _u32)])
 
 
+PARK_MAX_TENSORS = 64       # AUM_PARK_MAX_TENSORS
+PARK_RESTORE = 1            # AUM_PARK_RESTORE: blob -> pool
+
+
+class ParkArgs(C.Structure):
+    _fields_ = ([("base", _vp * PARK_MAX_TENSORS)] + [(n, _i64 * PARK_MAX_TENSORS) for n in ("row_stride", "row_bytes", "blob_off")]
+                + [("rows", _vp), ("blob", _vp), ("blob_stride", _i64), ("n_tensors", _i32), ("n_sessions", _i32), ("flags", _u32)])
+
+
 # Every entry point of include/aum_hip.h: name -> (argtypes, restype).  The launches take (const Args*, void* stream) and return an AUM_E_*
 # code; only the other forms are spelled out.  Lib sets these on load; EXPORTS (what tests/test_abi.py holds against the header) is the keys.
 _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
@@ -286,7 +295,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
     "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd",
-    "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd")}
+    "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd", "aum_stream_park")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -1829,6 +1838,122 @@ def stream_block(xz_x, z, conv_state, state, plan, seq_map=None, commit=True, ou
     a.flags = (0 if commit else STREAM_NO_COMMIT) | (STREAM_PEEK_LAST if peek else 0)
     _launch(lib.c.aum_stream_block_tm, a, x2, lib, "stream_block", (len(seq_map.lens), dim, total))
     return y.view(shape)
+
+
+# ---- parking sessions: the pool rows of many sessions to one record each of a byte blob, and back (aum_stream_park) ----
+PARK_RECORD_ALIGN = 256     # a record is rounded up to this many bytes
+PARK_CHUNK = 4096           # PARK_CHUNK of csrc/stream_park_kernels.h: the bytes of a row one workgroup moves
+
+
+class ParkLayout(typing.NamedTuple):
+    """Where the rows of a list of pool tensors sit inside a session's record (stream_park_layout): tensor t's row is the row_bytes[t]
+    bytes at offsets[t]; `record` is the size of a record, the end of the last row rounded up to PARK_RECORD_ALIGN."""
+    offsets: tuple
+    row_bytes: tuple
+    record: int
+
+
+class RowMap(typing.NamedTuple):
+    """the pool rows of the sessions of one park / resume call: host tuple (checked there) and the same as an int32 device tensor"""
+    rows: tuple
+    idx: torch.Tensor
+
+
+def row_map(rows, *, device):
+    """Built once per call (stream_park takes a list as well and builds it): distinct rows >= 0, sent to `device` in one pinned,
+    non-blocking upload as seq_map does.  That the rows exist is checked where the pool is known (stream_park)."""
+    rows = tuple(int(r) for r in rows)
+    if not rows or min(rows) < 0 or len(set(rows)) != len(rows) or max(rows) >= 1 << 31:
+        raise ValueError(f"row_map: at least one pool row, distinct and >= 0, got {rows}")
+    host = torch.tensor(rows, dtype=torch.int32)
+    device = torch.device(device)
+    if device.type == "cuda":
+        host = host.pin_memory()
+    return RowMap(rows, host.to(device, non_blocking=True))
+
+
+def stream_park_layout(tensors):
+    """The record of a session over these pool tensors (each (nrows, ...), a session's row t[r]): the rows behind one another in the
+    order given, every offset a multiple of 16, the record rounded up to 256 bytes -> ParkLayout(offsets, row_bytes, record)."""
+    offs, sizes, at = [], [], 0
+    for t in tensors:
+        n = t[0].numel() * t.element_size()
+        offs.append(at)
+        sizes.append(n)
+        at = (at + n + 15) // 16 * 16
+    return ParkLayout(tuple(offs), tuple(sizes), (at + PARK_RECORD_ALIGN - 1) // PARK_RECORD_ALIGN * PARK_RECORD_ALIGN)
+
+
+def stream_park_args_ok(a):
+    """park_check of csrc/stream_park_kernels.h on a filled ParkArgs, rule for rule: what aum_stream_park takes (AUM_OK) and what it
+    refuses (AUM_E_NULL / AUM_E_UNSUPPORTED)"""
+    if not a.rows or not a.blob:
+        return False
+    if not 1 <= a.n_tensors <= PARK_MAX_TENSORS or a.n_sessions < 1 or (a.flags & ~PARK_RESTORE):
+        return False
+    if any(not a.base[t] for t in range(a.n_tensors)):
+        return False
+    restore = bool(a.flags & PARK_RESTORE)
+    if (a.rows & 3) or (a.blob & 15) or (a.blob_stride & 15) or a.blob_stride < 0:
+        return False
+    end = chunks = 0
+    for t in range(a.n_tensors):
+        if (a.base[t] | a.row_stride[t] | a.row_bytes[t] | a.blob_off[t]) & 15:
+            return False
+        if a.row_bytes[t] < 16 or a.row_stride[t] < a.row_bytes[t] or a.blob_off[t] < end:
+            return False
+        if a.row_bytes[t] > 1 << 40:
+            return False
+        end = a.blob_off[t] + a.row_bytes[t]
+        chunks += (a.row_bytes[t] + PARK_CHUNK - 1) // PARK_CHUNK
+    if not (restore and a.blob_stride == 0) and end > a.blob_stride:
+        return False
+    return chunks * a.n_sessions <= 0x7fffffff
+
+
+def stream_park(tensors, rows, blob=None, restore=False, lib=None):
+    """ONE launch (aum_stream_park) for the rows `rows` of every pool tensor: restore=False copies them into one record per session of
+    `blob` ((len(rows), record) uint8 on the tensors' device; None: allocated, zero-filled) and leaves the pools as they are;
+    restore=True copies the records of `blob` into those rows (a blob expanded from one record -- row stride 0 -- restores every
+    session from it).  tensors: at most 64, each (nrows, ...) with contiguous rows, all with the same nrows and device; the record is
+    stream_park_layout(tensors).  rows: a list of distinct rows of the pools, or a row_map().  Returns the blob.
+    Every operand is checked on the host before the launch, by the rules of the C side (stream_park_args_ok) and against the pools'
+    row count, which the kernel does not know: a refused call raises and changes nothing.  No device synchronisation."""
+    lib = lib or get()
+    tensors = list(tensors)
+    if not tensors or any(not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] < 1 for t in tensors):
+        raise RuntimeError("stream_park: at least one pool tensor, each (nrows >= 1, ...)")
+    dev, nrows = tensors[0].device, tensors[0].shape[0]
+    m = rows if isinstance(rows, RowMap) else row_map(rows, device=dev)
+    if max(m.rows) >= nrows:
+        raise ValueError(f"stream_park: pool row {max(m.rows)} named, the pools have {nrows} rows")
+    if m.idx.device != dev or m.idx.dtype != torch.int32 or m.idx.numel() != len(m.rows):
+        raise RuntimeError(f"stream_park: the row map lives on {m.idx.device}, the pools on {dev}")
+    n, lay = len(m.rows), stream_park_layout(tensors)
+    bad = [i for i, t in enumerate(tensors) if t.device != dev or t.shape[0] != nrows or t.numel() == 0 or not t[0].is_contiguous()]
+    if bad or len(tensors) > PARK_MAX_TENSORS:
+        raise RuntimeError(f"stream_park: unsupported operands: {len(tensors)} pool tensors (at most {PARK_MAX_TENSORS}), tensors {bad} are not "
+                           f"({nrows}, ...) on {dev} with contiguous rows")
+    if blob is None:
+        if restore:
+            raise RuntimeError("stream_park: restore=True needs the blob to restore from")
+        blob = torch.zeros((n, lay.record), dtype=torch.uint8, device=dev)
+    if (not torch.is_tensor(blob) or blob.dtype != torch.uint8 or blob.device != dev or tuple(blob.shape) != (n, lay.record)
+            or blob.stride(1) != 1):
+        got = f"{tuple(blob.shape)} {blob.dtype} on {blob.device}" if torch.is_tensor(blob) else type(blob).__name__
+        raise RuntimeError(f"stream_park: unsupported operands: the blob must be ({n}, {lay.record}) uint8 on {dev}, got {got}")
+    for t in tensors + [blob]:
+        lib.check_tensor(t)
+    a = ParkArgs()
+    for i, t in enumerate(tensors):
+        a.base[i], a.row_stride[i], a.row_bytes[i], a.blob_off[i] = t.data_ptr(), t.stride(0) * t.element_size(), lay.row_bytes[i], lay.offsets[i]
+    a.rows, a.blob, a.blob_stride = m.idx.data_ptr(), blob.data_ptr(), blob.stride(0) if n > 1 or restore else lay.record
+    a.n_tensors, a.n_sessions, a.flags = len(tensors), n, PARK_RESTORE if restore else 0
+    if not stream_park_args_ok(a):
+        raise RuntimeError(f"stream_park: unsupported operands: rows of {lay.row_bytes} bytes at strides {[int(a.row_stride[i]) for i in range(len(tensors))]}, "
+                           f"blob row stride {blob.stride(0)} (16-byte multiples, rows inside their strides, records inside the blob's)")
+    _launch(lib.c.aum_stream_park, a, blob, lib, "stream_park", (n, len(tensors), lay.record))
+    return blob
 
 
 def dtproj_tm_supported(x_dbl, rank, w):

@@ -1089,4 +1089,14 @@ AUM_API int aum_fbank_stream_fwd(const AumFbankStreamArgs* a, void* stream) {
     // behind the frames on the same stream: the frame waves have read the old tails before any of them is rewritten
     return AUM_LAUNCH(a->nseq, FBANK_THREADS, s, (NoLds{}), k_fbank_stream_tail, (fbank_stream_tail_wg(*a, wg)), *a);
 }
+
+// ---- park / resume (stream_park_kernels.h): the pool rows of many sessions to one record each of a blob, or back, in one launch ----
+// park_check is this family's one operand check; the grid is (session, tensor, 4 KiB chunk) flattened, per_session chunks per session
+#include "stream_park_kernels.h"
+AUM_API int aum_stream_park(const AumParkArgs* a, void* stream) {
+    int64_t per_session = 0;
+    if (const int rc = park_check(a, &per_session)) return rc;
+    return AUM_LAUNCH(per_session * a->n_sessions, PARK_THREADS, (aum_stream_t)stream, (NoLds{}), k_stream_park, (park_wg(*a, per_session, wg)), *a,
+                      per_session);
+}
 #endif

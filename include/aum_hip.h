@@ -47,7 +47,8 @@ extern "C" {
                                    additions without a version step (no existing struct or entry point changes): aum_stft_logmel_fwd, aum_spec_time_warp
                                    (the EPIC-Sounds frontend); AUM_SCAN_DELTA_ACTIVATED (token-major scans) and, appended to AumXdtArgs, delta_bias /
                                    flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour; aum_xdt_tm_bwd also takes
-                                   (ncols, rank) = (56, 24) and aum_gemm_wgrad k in {24, 56} (AuM-Small: shapes that were AUM_E_UNSUPPORTED) */
+                                   (ncols, rank) = (56, 24) and aum_gemm_wgrad k in {24, 56} (AuM-Small: shapes that were AUM_E_UNSUPPORTED);
+                                   aum_stream_park / AumParkArgs (streaming sessions to a blob and back in one launch) */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -966,6 +967,41 @@ int aum_sum_rows_multi(const AumSumJob* jobs, int32_t njobs, void* stream);
  *   bank_t  (n, cols, rows): the transposes, or NULL
  * rows % 8 == 0, cols % 4 == 0; bank / bank_t 16-byte aligned. */
 int aum_cast_bank(const uint64_t* src, int32_t n, int32_t rows, int32_t cols, void* bank, void* bank_t, int32_t dtype, void* stream);
+
+/*
+ * Parking streaming sessions (no version step: an addition).  A session of a pool is one row of every pool tensor -- per layer the conv
+ * window and the scan state, and the sample tail of a raw-audio stream.  ONE launch copies those rows of n_sessions sessions into one
+ * record per session of a byte blob (flags 0), or the records back into rows of a pool (AUM_PARK_RESTORE): the same pool or another one
+ * of the same layout, any rows.  The bytes are moved as they are; nothing is converted.
+ *   base[t], row_stride[t], row_bytes[t]   pool tensor t < n_tensors: row r is the row_bytes[t] bytes at base[t] + r * row_stride[t]
+ *   blob_off[t]                            where tensor t's row sits inside a record; the ranges [blob_off[t], blob_off[t] + row_bytes[t])
+ *                                          ascend with t, do not overlap and end inside blob_stride
+ *   rows                                   (n_sessions) int32 in DEVICE memory: the pool row of session i, >= 0 and distinct.  That the rows
+ *                                          exist in every pool tensor is the caller's check (aum_hip.stream_park makes it on the host); a
+ *                                          negative entry is skipped
+ *   blob, blob_stride                      record i is the blob_stride bytes at blob + i * blob_stride.  AUM_PARK_RESTORE also takes
+ *                                          blob_stride == 0: every session is restored from the one record at `blob`
+ * Workgroups of 256 lanes over (session, tensor, 4 KiB chunk of the row), 16 bytes per lane; the tail of a row is guarded by row_bytes.
+ * Only the named rows' row_bytes and the records' [blob_off, blob_off + row_bytes) ranges are read or written: the bytes between the rows
+ * of a strided pool tensor and between or behind the ranges of a record keep what they hold.
+ * AUM_E_NULL: args, rows, blob or a base is NULL.  AUM_E_UNSUPPORTED: n_tensors outside [1, AUM_PARK_MAX_TENSORS], n_sessions < 1, an
+ * unknown flag, a base, blob, stride, row size or offset that is not a multiple of 16 (rows: of 4), row_bytes < 16, row_stride < row_bytes,
+ * ranges of a record that overlap, descend or pass blob_stride, or more than 2^31 - 1 workgroups.
+ */
+#define AUM_PARK_MAX_TENSORS 64
+#define AUM_PARK_RESTORE 1u
+typedef struct AumParkArgs {
+    void*   base[AUM_PARK_MAX_TENSORS];
+    int64_t row_stride[AUM_PARK_MAX_TENSORS]; /* bytes */
+    int64_t row_bytes[AUM_PARK_MAX_TENSORS];  /* bytes copied per row, multiple of 16 */
+    int64_t blob_off[AUM_PARK_MAX_TENSORS];   /* byte offset of tensor t's row inside a session's record, multiple of 16 */
+    const int32_t* rows;    /* (n_sessions) pool rows, device memory */
+    void*   blob;           /* (n_sessions, blob_stride) bytes */
+    int64_t blob_stride;
+    int32_t n_tensors, n_sessions;
+    uint32_t flags;         /* AUM_PARK_RESTORE: blob -> pool; 0: pool -> blob */
+} AumParkArgs;
+int aum_stream_park(const AumParkArgs* args, void* stream);
 
 /*
  * EPIC-Sounds log-mel frontend (an addition to ABI 13; replaces librosa.stft + filters.mel + log on the CPU DataLoader workers of the reference,

@@ -48,6 +48,14 @@ columns (one pass over COLS x 9 rows, the cls row behind every column as a peek 
 arms.  Same method: HIP events around each call, warm calls discarded, medians of all calls and of the groups, min / max.
 
     python tools/stream_hop_bench.py --timeline 64 [--batch 1]       (--count-only a: the per-column loop, b: stream_timeline)
+
+--park N: N sessions of a pool of 2 N rows taken off the pool and brought back into other rows, with their sample tails, two ways
+alternating in one process: (a) by hand -- per layer an index_select of conv_state and of ssm_state and one of the WaveStream tails
+into held copies, then as many index_copy_ back: 2 (2 depth + 1) indexed copies; (b) one stream_park and one stream_resume (one launch
+each).  One timed call is park + resume.  Same method: HIP events around each call, warm calls discarded, medians of all calls and of
+the groups, min / max.
+
+    python tools/stream_hop_bench.py --park 8 --hops 100             (--count-only a: by hand, b: stream_park + stream_resume)
 """
 import argparse
 import contextlib
@@ -314,6 +322,53 @@ def wave_ab(model, args, dev):
     print(json.dumps(out), flush=True)
 
 
+def park_ab(model, args, dev):
+    """--park N: park + resume of N sessions (with sample tails) as 2 (2 depth + 1) indexed copies (a) against one launch each way (b)"""
+    from aum.frontend import FbankTables, WaveInput
+    N = args.park
+    fe = WaveInput(FbankTables(dev), target_length=16 * model.patch_grid_size[1])
+    pool, ws = model.allocate_stream_pool(2 * N), model.allocate_wave_stream(2 * N, fe)
+    for c, s in pool["layers"].values():
+        c.normal_(), s.normal_()
+    src, dst = list(range(0, 2 * N, 2)), list(range(1, 2 * N, 2))
+    i_src, i_dst = torch.tensor(src, device=dev), torch.tensor(dst, device=dev)
+    tensors = model._park_tensors(pool, ws)
+
+    def by_hand():
+        held = [t.index_select(0, i_src) for t in tensors]
+        for t, h in zip(tensors, held):
+            t.index_copy_(0, i_dst, h)
+
+    def one_launch_each():
+        model.stream_resume(model.stream_park(pool, src, wave_stream=ws), pool, dst, wave_stream=ws)
+
+    arms = (("by_hand", by_hand), ("park_resume", one_launch_each))
+    if args.count_only:
+        i = 0 if args.count_only == "a" else 1
+        for _ in range(args.count_hops):
+            arms[i][1]()
+        torch.cuda.synchronize()
+        print(json.dumps({"path": "park " + arms[i][0], "sessions": N, "hops": args.count_hops}))
+        return
+    for _ in range(args.warm):
+        for _, fn in arms:
+            timed_call(fn)
+    times = [[] for _ in arms]
+    for _ in range(args.hops):
+        for t, (_, fn) in zip(times, arms):
+            t.append(timed_call(fn))
+    g = max(args.hops // args.groups, 1)
+    import aum_hip
+    out = {"model": f"aum-{args.size} causal depth {args.depth}", "sessions": N, "pool_rows": 2 * N, "pool_tensors": len(tensors),
+           "record_bytes": aum_hip.stream_park_layout(tensors).record, "indexed_copies_by_hand": 2 * len(tensors), "hops": args.hops, "warm": args.warm}
+    for (name, _), t in zip(arms, times):
+        out[name + "_ms_median"] = round(statistics.median(t), 4)
+        out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+        out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+    out["ratio_by_hand_over_park_resume"] = round(out["by_hand_ms_median"] / out["park_resume_ms_median"], 3)
+    print(json.dumps(out), flush=True)
+
+
 def prefill_pool_ab(model, args, dev):
     """--prefill-pool S --prefill COLS: S ragged backlogs into empty pool rows, the host loop (a) against one packed pass (b)"""
     S = args.prefill_pool
@@ -494,9 +549,15 @@ def main():
                     help="the logits after every one of COLS columns: COLS stream_push(read=True) calls vs one stream_timeline")
     ap.add_argument("--wave", action="store_true",
                     help="raw audio: 8 sessions by hand (tail + hop on the host side, fbank_fwd, stream_push_many) vs one stream_push_wave_many")
+    ap.add_argument("--park", type=int, default=0, metavar="N",
+                    help="N sessions off a pool and back into other rows: 2 (2 depth + 1) indexed copies vs one stream_park + one stream_resume")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill, 16 * args.timeline))
+    if args.park:
+        with torch.no_grad():
+            park_ab(model, args, dev)
+        return
     if args.wave:
         with torch.no_grad():
             wave_ab(model, args, dev)
