@@ -144,6 +144,81 @@ class ParkedSessions:
         return self.select([i])
 
 
+class StreamStack:
+    """What aum_hip.stream_layers reads of a streamable AudioMamba, converted once (AudioMamba.stream_stack makes and caches it): per block
+    Mamba.stream_params(dtype), the 16-bit in_proj / out_proj weights, the fp32 norm weight, and the HOST table of device pointers the C loop
+    walks -- only its two pool pointers per block are written per call.  With it a hop through all blocks is ONE library call that
+    enqueues 3 * depth launches (add + norm + in_proj, the one-launch middle, out_proj), no Python or torch dispatch between them.
+    takes(total, max_len): which calls go that way -- sessions of at most 128 rows (the middle kernel's limit) and at most MAX_TOTAL rows
+    in all; the others take the loop over the layers as without a stack.
+    MAX_TOTAL = 512: the projection kernels accept any row count, but every workgroup recomputes the norm of ALL rows of the call for its
+    32 output columns; at a few hundred rows that prologue is the size of the workgroup's weight slab, beyond it the prologue is the
+    kernel and the library GEMMs of the loop are the better tool.  512 is four sessions at the middle kernel's limit and leaves room
+    above the 288 rows of 32 sessions pushing one column with a peek row each.  The tensors are shared between calls: do not write to them.
+    The workspace is ONE tensor, shared by every call through this stack: calls on different torch streams at the same time would
+    overwrite one another's rows -- serve one stream per model, or give every stream a model (and so a stack) of its own.
+    fresh(): whether the model still is what the stack was built from -- per source parameter one dict lookup for its identity and its
+    _version, dtype and device, and per block the generation Mamba.invalidate_stream_params() moves: the only per-hop host work of the cache."""
+    MAX_TOTAL = 512
+
+    def __init__(self, model, dtype):
+        import aum_hip
+        self.dtype, self.depth = dtype, len(model.layers)
+        self.sources = [(d, n, p, None if p is None else (p._version, p.dtype, p.device)) for d, n, p in model._stack_sources()]
+        self.gens = [(layer.mixer.__dict__, layer.mixer.__dict__.get("_stream_gen", 0)) for layer in model.layers]
+        m0 = model.layers[0].mixer
+        self.d_model, self.dim, self.eps = m0.d_model, m0.d_inner, model.layers[0].norm.eps
+        self.plans, self.keep, recs = [], [], []
+        for layer in model.layers:
+            mx = layer.mixer
+            plan = mx.stream_params(dtype)
+            w_in = aum_hip._al16(mx.in_proj.weight.detach().to(dtype).contiguous())
+            w_out = aum_hip._al16(mx.out_proj.weight.detach().to(dtype).contiguous())
+            nw = aum_hip._al16(aum_hip._f32c(layer.norm.weight))
+            self.plans.append(plan)
+            self.keep.append((w_in, w_out, nw))
+            recs.append({"norm_weight": nw, "w_in": w_in, "conv_weight": plan.conv_w, "conv_bias": plan.conv_b, "wx": plan.w_x, "wdt": plan.w_dt,
+                         "A": plan.A, "D": plan.D, "delta_bias": plan.dt_bias, "w_out": w_out, "conv_state": None, "state": None})
+        p0 = self.plans[0]
+        self.rank, self.ncols, self.ldwx, self.ldwdt = p0.w_dt.shape[1], p0.w_x.shape[0], p0.w_x.stride(0), p0.w_dt.stride(0)
+        self.table = aum_hip.stream_layers_table(recs)
+        self.records_ok = aum_hip.stream_layers_records_ok(self.table, self.depth)       # the parameter pointers: checked once, here
+        self.workspace = None
+
+    def fresh(self):
+        for d, n, p, sig in self.sources:
+            q = d.get(n)
+            if q is not p or (p is not None and (p._version, p.dtype, p.device) != sig):
+                return False
+        return all(d.get("_stream_gen", 0) == g for d, g in self.gens)
+
+    def takes(self, total, max_len):
+        import aum_hip
+        return 1 <= max_len <= aum_hip.STREAM_BLOCK_MAX_T and 1 <= total <= self.MAX_TOTAL
+
+    def pools_ok(self, layer_caches):
+        """the pools as the middle kernel takes them: fp32, contiguous, 16-byte aligned, (nrows, dim, 4) / (nrows, dim, 16), one size"""
+        if len(layer_caches) != self.depth:
+            return False
+        n = layer_caches[0][0].shape[0]
+        return all(c.dtype == torch.float32 and s.dtype == torch.float32 and c.is_contiguous() and s.is_contiguous()
+                   and tuple(c.shape) == (n, self.dim, 4) and tuple(s.shape) == (n, self.dim, 16) and c.data_ptr() % 16 == 0 and s.data_ptr() % 16 == 0
+                   for c, s in (layer_caches[i] for i in range(self.depth)))
+
+    def run(self, rows, layer_caches, smap, commit=True, peek=False):
+        """rows (total, d_model) -> (hidden, residual fp32) of the last block; the pools of layer_caches advance in place"""
+        import aum_hip
+        rows = rows.to(self.dtype).contiguous()
+        for i in range(self.depth):
+            self.table[i].conv_state, self.table[i].state = layer_caches[i][0].data_ptr(), layer_caches[i][1].data_ptr()
+        need = aum_hip.stream_layers_scratch_layout(rows.shape[0], self.d_model, self.dim, self.ncols)[2]
+        if self.workspace is None or self.workspace.numel() < need or self.workspace.device != rows.device:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+        return aum_hip.stream_layers(rows, self.table, self.depth, layer_caches[0][0], smap, dim=self.dim, rank=self.rank, ncols=self.ncols,
+                                     ldwx=self.ldwx, ldwdt=self.ldwdt, eps=self.eps, commit=commit, peek=peek, workspace=self.workspace,
+                                     records_ok=self.records_ok)
+
+
 class AudioMamba(nn.Module):
     def __init__(self, spectrogram_size=(128, 1024), patch_size=(16, 16), strides=(16, 16), depth=24, embed_dim=768,
                  channels=1, num_classes=527, norm_epsilon=1e-5, bimamba_type="v1", if_devide_out=True,
@@ -276,12 +351,75 @@ class AudioMamba(nn.Module):
                            for i, layer in enumerate(self.layers)},
                 "columns": 0, "batch": batch_size}
 
-    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False, prefill=False, peek_every=None):
+    def _stack_sources(self):
+        """(the module's parameter dict, name, parameter or None) of everything a StreamStack is converted from"""
+        out = []
+        for layer in self.layers:
+            mx = layer.mixer
+            for mod, names in ((mx, ("A_log", "D")), (mx.conv1d, ("weight", "bias")), (mx.x_proj, ("weight",)), (mx.dt_proj, ("weight", "bias")),
+                               (mx.in_proj, ("weight", "bias")), (mx.out_proj, ("weight", "bias")), (layer.norm, ("weight", "bias"))):
+                out += [(mod._parameters, n, mod._parameters.get(n)) for n in names]
+        return out
+
+    @torch.no_grad()
+    def stream_stack(self, dtype=None):
+        """The StreamStack of this model for stream_push / stream_push_many / stream_read (..., stack=): every block's parameters as the
+        one-call path reads them.  dtype: the working 16-bit dtype (default: the parameters').  Cached and keyed as Mamba.stream_params()
+        is, on every source parameter's identity, _version, dtype and device: an optimizer step, load_state_dict or .to() rebuild it (a
+        write through `p.data` does not: write under torch.no_grad(), or call Mamba.invalidate_stream_params() on the block behind it,
+        which drops this cache as well).  A hit costs StreamStack.fresh() and nothing else; the model is examined on a miss.  Raises ValueError, with the reason, for a model the kernels do
+        not take: not streamable, projection or norm biases, d_conv != 4, d_state != 16, widths other than (192, 384), (384, 768),
+        (768, 1536), or a dtype that is not bf16 / fp16."""
+        import aum_hip
+        hit = self.__dict__.get("_stream_stack")
+        if hit is not None and (dtype is None or dtype == hit.dtype) and hit.fresh() and (
+                dtype is not None or hit.dtype == self.layers[0].mixer.in_proj.weight.dtype):
+            return hit
+        self._check_streamable()
+        if not len(self.layers):
+            raise ValueError("stream_stack: the model has no blocks")
+        dtype = self.layers[0].mixer.in_proj.weight.dtype if dtype is None else dtype
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"stream_stack: the projection kernels run in bf16 or fp16, not {dtype}")
+        for i, layer in enumerate(self.layers):
+            mx = layer.mixer
+            if mx.in_proj.bias is not None or mx.out_proj.bias is not None:
+                raise ValueError(f"stream_stack: block {i} has projection biases (bias=True); the projection kernels add none")
+            if getattr(layer.norm, "bias", None) is not None:
+                raise ValueError(f"stream_stack: block {i}'s norm has a bias")
+            if mx.d_conv != 4 or mx.d_state != 16:
+                raise ValueError(f"stream_stack: block {i} has d_conv {mx.d_conv}, d_state {mx.d_state}; the middle kernel is built for 4 and 16")
+            if (mx.d_model, mx.d_inner) not in aum_hip.STREAM_STACK_WIDTHS:
+                raise ValueError(f"stream_stack: block {i} has widths ({mx.d_model}, {mx.d_inner}); the kernels are built for {aum_hip.STREAM_STACK_WIDTHS}")
+            if layer.norm.eps != self.layers[0].norm.eps:
+                raise ValueError("stream_stack: the blocks' norms differ in eps")
+        stack = StreamStack(self, dtype)
+        if not aum_hip.xdt_fwd_shape_ok(stack.ncols, stack.dim) or stack.rank % 8 or stack.rank + 32 > stack.ncols:
+            raise ValueError(f"stream_stack: dt_rank {self.layers[0].mixer.dt_rank} gives x/dt rows of {stack.ncols} columns, which the middle kernel does not take")
+        self.__dict__["_stream_stack"] = stack
+        return stack
+
+    def _stack_for(self, stack, hidden, layer_caches, seq_map, prefill, peek_every):
+        """the stack a pass goes through, or None: the loop over the layers"""
+        if stack is None or prefill or peek_every is not None:
+            return None
+        if not isinstance(stack, StreamStack):
+            raise TypeError("stack= takes what AudioMamba.stream_stack() returns")
+        stack = self.stream_stack(stack.dtype)                          # the cached one, or rebuilt where the parameters have moved on
+        total = hidden.shape[0] * hidden.shape[1]
+        max_len = hidden.shape[1] if seq_map is None else max(seq_map.lens)
+        return stack if stack.takes(total, max_len) and stack.pools_ok(layer_caches) else None
+
+    def _stream_layers(self, hidden, layer_caches, seq_map=None, commit=True, peek=False, prefill=False, peek_every=None, stack=None):
         """Block.forward (MM:58-99) for every layer on T new tokens, the mixers advancing `layer_caches` in place.  seq_map: hidden is
         (1, total, Dm), the packed tokens of several sessions, and the caches are pools (Mamba.step_chunk).  commit=False: the caches
         are read and not written.  peek=True: the last row of every session is computed and the caches advance by the rows before it.
         prefill=True (no peek row): the mixers take the tokens as a backlog (Mamba.prefill_chunk; with seq_map the packed backlogs of
-        several sessions over pools).  peek_every=P (not with the others): a peek row behind every P committed rows of every session."""
+        several sessions over pools).  peek_every=P (not with the others): a peek row behind every P committed rows of every session.
+        stack (AudioMamba.stream_stack()): the whole loop as ONE aum_hip.stream_layers call where StreamStack.takes() the pass."""
+        st = self._stack_for(stack, hidden, layer_caches, seq_map, prefill, peek_every)
+        if st is not None:
+            return self._run_stack(st, hidden, layer_caches, seq_map, commit, peek)
         residual = None
         for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
@@ -294,6 +432,17 @@ class AudioMamba(nn.Module):
                 hidden, _, _ = layer.mixer.step_chunk(hidden, conv_state, ssm_state, seq_map=seq_map, commit=commit, peek=peek,
                                                       **({} if peek_every is None else {"peek_every": peek_every}))
         return hidden, residual
+
+    @staticmethod
+    def _run_stack(st, hidden, layer_caches, seq_map, commit, peek):
+        """the pass of _stream_layers through a StreamStack that _stack_for has chosen"""
+        import aum_hip
+        batch, T, Dm = hidden.shape
+        if seq_map is not None:
+            aum_hip.check_seq_map("stream_layers", seq_map, T, layer_caches[0][0].shape[0], hidden.device)
+        smap = seq_map if seq_map is not None else aum_hip.fixed_seq_map(batch, T, hidden.device)
+        h, r = st.run(hidden.reshape(batch * T, Dm), layer_caches, smap, commit=commit, peek=peek)
+        return h.view(batch, T, Dm), r.view(batch, T, Dm)
 
     def _read_in_place(self, cls, cache, rows):
         """stream_read without copies: the cls row of each session through the blocks ON the caches themselves, as one-token sessions on
@@ -356,7 +505,7 @@ class AudioMamba(nn.Module):
         return f if return_features else self.head(f)
 
     @torch.no_grad()
-    def stream_push_many(self, specs, pool, sessions, read=False, return_features=False):
+    def stream_push_many(self, specs, pool, sessions, read=False, return_features=False, stack=None):
         """specs[i]: (16 k_i, n_mels), k_i >= 1 -- the next k_i time columns of the clip of session sessions[i] (distinct rows of a pool from
         allocate_stream_pool), every session at its own column offset and with its own hop size.  One patch-embed GEMM over the frames
         concatenated in time, each session's position rows gathered from its own offset, tokens time-major within a session, then ONE pass
@@ -364,7 +513,8 @@ class AudioMamba(nn.Module):
         Returns the per-session column counts.  Every argument is checked before any cache is touched: a refused call changes nothing.
         read=True: the logits "if the clip ended now" of every session with the same pass -- the cls row rides behind each session's new
         tokens as a peek row (Mamba.step_chunk(peek=True): it sees the state the tokens produced, the caches do not take it in).
-        Returns (column counts, logits (len(sessions), classes) in the order of `sessions`; features with return_features)."""
+        Returns (column counts, logits (len(sessions), classes) in the order of `sessions`; features with return_features).
+        stack (stream_stack()): the pass through the blocks as one library call (StreamStack); the patch embedding and the head stay."""
         import aum_hip
         ks, c0s, rows, specs = self._check_push("stream_push_many", specs, pool, sessions)
         nf, dev = self.patch_grid_size[0], specs[0].device
@@ -381,10 +531,10 @@ class AudioMamba(nn.Module):
             if dev.type == "cuda":
                 last = last.pin_memory()
             last = last.to(dev, non_blocking=True)
-            hidden, residual = self._stream_layers(torch.cat(pieces, dim=0).unsqueeze(0), pool["layers"], smap, peek=True)
+            hidden, residual = self._stream_layers(torch.cat(pieces, dim=0).unsqueeze(0), pool["layers"], smap, peek=True, stack=stack)
             out = self._head_rows(hidden[0].index_select(0, last), residual[0].index_select(0, last), return_features)
         else:
-            self._stream_layers(x, pool["layers"], smap)
+            self._stream_layers(x, pool["layers"], smap, stack=stack)
         counts = self._commit_columns(pool, ks, rows)
         return (counts, out) if read else counts
 
@@ -507,7 +657,7 @@ class AudioMamba(nn.Module):
         return [pool["columns"][r] for r in rows]
 
     @torch.no_grad()
-    def stream_push(self, spec, cache, read=False, return_features=False):
+    def stream_push(self, spec, cache, read=False, return_features=False, stack=None):
         """spec: (batch, 16 k, n_mels) -- the next k time columns of the clip's normalised log-mel spectrogram.  Embeds their
         k x n_f tokens (time-major, each with the position row of its (f, t) cell), runs them through all blocks from the carried caches
         and advances the caches.  Returns the number of columns pushed so far.
@@ -516,14 +666,15 @@ class AudioMamba(nn.Module):
         arguments and leaves the same caches.
         read=True: what stream_read would say behind this push, from the same pass -- the cls row rides behind the new tokens as a peek
         row (Mamba.step_chunk(peek=True)), goes through the final norm and the head, and the caches advance by the tokens only.
-        Returns (columns, logits (batch, classes); features with return_features)."""
+        Returns (columns, logits (batch, classes); features with return_features).
+        stack (stream_stack()): the pass through the blocks as one library call (StreamStack), opt-in; the default path is unchanged."""
         (k,), (c0,), _, _ = self._check_push("stream_push", spec, cache)
         x = self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(c0, c0 + k))
         if not read:
-            self._stream_layers(x, cache["layers"])
+            self._stream_layers(x, cache["layers"], stack=stack)
             return self._commit_columns(cache, [k], None)
         x = torch.cat((x, self._cls_row().to(x.dtype).expand(x.shape[0], -1, -1)), dim=1)
-        hidden, residual = self._stream_layers(x, cache["layers"], peek=True)
+        hidden, residual = self._stream_layers(x, cache["layers"], peek=True, stack=stack)
         return self._commit_columns(cache, [k], None), self._head_rows(hidden[:, -1], residual[:, -1], return_features)
 
     # ---- streaming from raw audio: PCM hops of any size, the log-mel stage carried by a WaveStream ----
@@ -586,7 +737,7 @@ class AudioMamba(nn.Module):
         return frames.to(self.patch_embed.proj.weight.dtype)        # a model held in 16 bits takes its frames in 16 bits (no-op in fp32)
 
     @torch.no_grad()
-    def stream_push_wave_many(self, waves, pool, wave_stream, sessions, read=False, end=False, return_features=False):
+    def stream_push_wave_many(self, waves, pool, wave_stream, sessions, read=False, end=False, return_features=False, stack=None):
         """stream_push_many from RAW AUDIO: waves[i] (m_i,) fp32 on the device, m_i >= 0 -- the next samples of the clip of session
         sessions[i] (distinct rows of a pool from allocate_stream_pool), in hops of any size.  wave_stream (allocate_wave_stream) holds
         what the hops leave over: the 240 samples neighbouring frames share and the samples of a column that is not whole yet.  The host
@@ -612,21 +763,21 @@ class AudioMamba(nn.Module):
         go = [i for i, k in enumerate(ks) if k >= 1]
         out = None
         if go:
-            out = self.stream_push_many([pieces[i] for i in go], pool, [rows[i] for i in go], read=read, return_features=return_features)
+            out = self.stream_push_many([pieces[i] for i in go], pool, [rows[i] for i in go], read=read, return_features=return_features, stack=stack)
         counts = [pool["columns"][r] for r in rows]
         if not read:
             return counts
         if len(go) == len(rows):
             return counts, out[1]
         stay = [i for i, k in enumerate(ks) if k < 1]
-        quiet = self.stream_read(pool, return_features, sessions=[rows[i] for i in stay])
+        quiet = self.stream_read(pool, return_features, sessions=[rows[i] for i in stay], stack=stack)
         if not go:
             return counts, quiet
         order = torch.tensor(go + stay, dtype=torch.int64).argsort().to(quiet.device)
         return counts, torch.cat((out[1].to(quiet.dtype), quiet), dim=0).index_select(0, order)
 
     @torch.no_grad()
-    def stream_push_wave(self, wave, cache, wave_stream, read=False, end=False, return_features=False):
+    def stream_push_wave(self, wave, cache, wave_stream, read=False, end=False, return_features=False, stack=None):
         """stream_push from raw audio, the fixed-batch, lockstep form: wave (batch, m) fp32, the next m >= 0 samples of every row of a
         cache from allocate_inference_cache; the same kernel as stream_push_wave_many under a map in which session b owns row b.  Whole
         new columns go through stream_push; returns the columns pushed so far, with read=True (columns, logits) -- stream_read where no
@@ -642,8 +793,8 @@ class AudioMamba(nn.Module):
         wmap, ks, ends = self._plan_wave("stream_push_wave", list(wave), cache, wave_stream, None, end)
         frames = self._wave_frames(wave.reshape(-1), wmap, wave_stream, range(wave.shape[0]), ends)
         if ks[0] >= 1:
-            return self.stream_push(frames.reshape(wave.shape[0], wmap.frames[0], -1), cache, read=read, return_features=return_features)
-        return (cache["columns"], self.stream_read(cache, return_features)) if read else cache["columns"]
+            return self.stream_push(frames.reshape(wave.shape[0], wmap.frames[0], -1), cache, read=read, return_features=return_features, stack=stack)
+        return (cache["columns"], self.stream_read(cache, return_features, stack=stack)) if read else cache["columns"]
 
     # ---- parking sessions: a session's rows off a pool and back, into any free rows of any pool of the same model --------
     def _park_tensors(self, cache, wave_stream):
@@ -860,11 +1011,12 @@ class AudioMamba(nn.Module):
         return self._commit_columns(pool, ks, rows), list(out.split(ks, dim=0))
 
     @torch.no_grad()
-    def stream_read(self, cache, return_features=False, sessions=None):
+    def stream_read(self, cache, return_features=False, sessions=None, stack=None):
         """Logits if the clip ended now: the cls row run through the blocks from the caches, which are NOT advanced (read in place where
         every block takes the one-launch path, Mamba.step_chunk(commit=False); otherwise from a copy -- also where a row is named
         twice), then the final norm and the head.  After all columns of a clip have been pushed this is model(spec).  sessions: read
-        those rows only, (len(sessions), ...) in that order; None: every row (of a pool too)."""
+        those rows only, (len(sessions), ...) in that order; None: every row (of a pool too).
+        stack (stream_stack()): the uncommitted in-place pass as one library call where the stack takes it (distinct rows)."""
         self._check_streamable()
         rows = None
         if sessions is not None:
@@ -872,7 +1024,17 @@ class AudioMamba(nn.Module):
             if not rows:
                 raise ValueError("stream_read: at least one session")
         cls = self._cls_row().expand(cache["batch"] if rows is None else len(rows), -1, -1)
-        done = self._read_in_place(cls, cache, rows) if rows is None or len(set(rows)) == len(rows) else None
+        done = None
+        if stack is not None and (rows is None or len(set(rows)) == len(rows)):
+            import aum_hip
+            n = cls.shape[0]
+            smap = aum_hip.fixed_seq_map(n, 1, cls.device) if rows is None else aum_hip.seq_map((1,) * n, rows, device=cls.device)
+            st = self._stack_for(stack, cls.reshape(1, n, -1), cache["layers"], smap, False, None)
+            if st is not None:
+                hidden, residual = self._run_stack(st, cls.reshape(1, n, -1), cache["layers"], smap, False, False)
+                done = hidden.reshape(n, 1, -1), residual.reshape(n, 1, -1)
+        if done is None:
+            done = self._read_in_place(cls, cache, rows) if rows is None or len(set(rows)) == len(rows) else None
         if done is not None:
             hidden, residual = done
         else:

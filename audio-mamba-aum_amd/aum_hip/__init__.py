@@ -286,6 +286,30 @@ class ParkArgs(C.Structure):
                 + [("rows", _vp), ("blob", _vp), ("blob_stride", _i64), ("n_tensors", _i32), ("n_sessions", _i32), ("flags", _u32)])
 
 
+class StreamInArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("hidden", "residual_in", "norm_weight", "w_in", "residual_out", "xz")] + [("hidden_ts", _i64), ("xz_ts", _i64)]
+                + [(n, _i32) for n in ("total", "d_model", "dim", "ldw", "dtype")] + [("eps", C.c_float)])
+
+
+class StreamOutArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("y", "w_out", "out")] + [("y_ts", _i64), ("out_ts", _i64)]
+                + [(n, _i32) for n in ("total", "d_model", "dim", "ldw", "dtype", "reserved")])
+
+
+STREAM_LAYER_POINTERS = ("norm_weight", "w_in", "conv_weight", "conv_bias", "wx", "wdt", "A", "D", "delta_bias", "w_out", "conv_state", "state")
+
+
+class StreamLayer(C.Structure):
+    _fields_ = [(n, _vp) for n in STREAM_LAYER_POINTERS]
+
+
+class StreamLayersArgs(C.Structure):
+    _fields_ = ([(n, _vp) for n in ("layers", "hidden", "residual_in", "hidden_out", "residual_out", "workspace", "cu_seqlens", "state_indices")]
+                + [("hidden_ts", _i64), ("workspace_bytes", _i64)]
+                + [(n, _i32) for n in ("depth", "total", "nseq", "nrows", "max_len", "d_model", "dim", "rank", "ncols", "ldwx", "ldwdt", "dtype")]
+                + [("flags", _u32), ("eps", C.c_float)])
+
+
 # Every entry point of include/aum_hip.h: name -> (argtypes, restype).  The launches take (const Args*, void* stream) and return an AUM_E_*
 # code; only the other forms are spelled out.  Lib sets these on load; EXPORTS (what tests/test_abi.py holds against the header) is the keys.
 _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
@@ -295,7 +319,8 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_conv1d_tm_bwd", "aum_gemm_tn", "aum_gemm_wgrad", "aum_dtproj_tm_fwd", "aum_xdt_tm_fwd", "aum_xdt_tm_bwd", "aum_causal_conv1d_update",
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
     "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd",
-    "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd", "aum_stream_park")}
+    "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd", "aum_stream_park", "aum_stream_in_tm", "aum_stream_out_tm",
+    "aum_stream_layers")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -311,6 +336,7 @@ _SIGNATURES.update({
     "aum_scan_tm_fwd_state_var_carry_bytes": ([_i32] * 4, _i64),
     "aum_scan_tm_peeks_ckpt_bytes": ([_i32] * 4, _i64), "aum_scan_tm_peeks_bwd_workspace_bytes": ([_i32] * 4, _i64),
     "aum_conv1d_tm_peeks_bwd_workspace_bytes": ([_i32] * 3, _i64),
+    "aum_stream_layers_scratch_bytes": ([_i32] * 4, _i64),
 })
 EXPORTS = list(_SIGNATURES)
 
@@ -1954,6 +1980,216 @@ def stream_park(tensors, rows, blob=None, restore=False, lib=None):
                            f"blob row stride {blob.stride(0)} (16-byte multiples, rows inside their strides, records inside the blob's)")
     _launch(lib.c.aum_stream_park, a, blob, lib, "stream_park", (n, len(tensors), lay.record))
     return blob
+
+
+# ---- a hop through all blocks in one library call (aum_stream_in_tm, aum_stream_out_tm, aum_stream_layers) ----
+STREAM_STACK_WIDTHS = ((192, 384), (384, 768), (768, 1536))     # (d_model, d_inner) the two projection kernels are built for
+
+
+def _al16p(*ptrs):
+    return all(p is None or p % 16 == 0 for p in ptrs)
+
+
+def stream_in_args_ok(a):
+    """ss_in_check of csrc/stream_stack_kernels.h on a filled StreamInArgs, rule for rule"""
+    if not (a.hidden and a.norm_weight and a.w_in and a.residual_out and a.xz):
+        return False
+    if a.total <= 0 or a.d_model <= 0 or a.dim <= 0:
+        return False
+    if a.dtype not in (AUM_BF16, AUM_F16):
+        return False
+    if (a.d_model, a.dim) not in STREAM_STACK_WIDTHS:
+        return False
+    if a.hidden_ts < a.d_model or a.xz_ts < 2 * a.dim or a.ldw < a.d_model or ((a.hidden_ts | a.xz_ts | a.ldw) & 7):
+        return False
+    if not _al16p(a.hidden, a.residual_in, a.norm_weight, a.w_in, a.residual_out, a.xz):
+        return False
+    if a.residual_in == a.residual_out:
+        return False
+    return a.total * max(a.hidden_ts, a.xz_ts) * 2 <= (1 << 31) - 1
+
+
+def stream_out_args_ok(a):
+    """ss_out_check of csrc/stream_stack_kernels.h on a filled StreamOutArgs, rule for rule"""
+    if not (a.y and a.w_out and a.out):
+        return False
+    if a.total <= 0 or a.d_model <= 0 or a.dim <= 0:
+        return False
+    if a.dtype not in (AUM_BF16, AUM_F16):
+        return False
+    if (a.d_model, a.dim) not in STREAM_STACK_WIDTHS:
+        return False
+    if a.y_ts < a.dim or a.out_ts < a.d_model or a.ldw < a.dim or ((a.y_ts | a.out_ts | a.ldw) & 7):
+        return False
+    if not _al16p(a.y, a.w_out, a.out) or a.y == a.out:
+        return False
+    return a.total * max(a.y_ts, a.out_ts) * 2 <= (1 << 31) - 1
+
+
+def _rows16(name, t, last, lib):
+    lib.check_tensor(t)
+    if t.dim() != 2 or t.shape[1] != last or t.stride(1) != 1 or t.dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError(f"{name}: expected 16-bit (total, {last}) rows with the last axis contiguous, got {tuple(t.shape)} {t.dtype}")
+    return t.stride(0) if t.shape[0] > 1 else last
+
+
+def stream_in(hidden, norm_weight, w_in, residual=None, eps=1e-5, lib=None):
+    """Fused add + RMSNorm + in_proj of a streaming hop in ONE launch (aum_stream_in_tm): hidden (total, d_model) 16-bit rows, residual fp32
+    (total, d_model) contiguous or None, norm_weight (d_model) fp32, w_in (2 dim, d_model) in hidden's dtype -> (xz (total, 2 dim),
+    residual_out fp32 (total, d_model), a new tensor).  residual_out and the normed row behind xz are rmsnorm_fwd's bits; every xz element
+    is one rounding of an fp32 sum of exact products; a row's bits do not depend on the other rows of the call."""
+    lib = lib or get()
+    d_model = hidden.shape[-1]
+    a = StreamInArgs()
+    a.hidden_ts = _rows16("stream_in", hidden, d_model, lib)
+    for t in (norm_weight, w_in, residual):
+        lib.check_tensor(t)
+    total, n2 = hidden.shape[0], w_in.shape[0]
+    if (w_in.dim() != 2 or w_in.dtype != hidden.dtype or w_in.shape[1] != d_model or w_in.stride(1) != 1 or norm_weight.dtype != torch.float32
+            or norm_weight.shape != (d_model,) or not norm_weight.is_contiguous()
+            or (residual is not None and (residual.dtype != torch.float32 or residual.shape != hidden.shape or not residual.is_contiguous()))):
+        raise RuntimeError("stream_in: unsupported operands: w_in (2 dim, d_model) in hidden's dtype, norm_weight fp32 (d_model), residual fp32 contiguous")
+    xz = torch.empty((total, n2), dtype=hidden.dtype, device=hidden.device)
+    res_out = torch.empty((total, d_model), dtype=torch.float32, device=hidden.device)
+    a.hidden, a.residual_in, a.norm_weight, a.w_in, a.residual_out, a.xz = _ptr(hidden), _ptr(residual), _ptr(norm_weight), _ptr(w_in), _ptr(res_out), _ptr(xz)
+    a.xz_ts, a.total, a.d_model, a.dim, a.ldw, a.dtype, a.eps = n2, total, d_model, n2 // 2, w_in.stride(0), _DT[hidden.dtype], eps
+    if n2 % 2 or not stream_in_args_ok(a):
+        raise RuntimeError(f"stream_in: unsupported operands hidden {tuple(hidden.shape)} {hidden.dtype} strides {hidden.stride()}, w_in {tuple(w_in.shape)}")
+    _launch(lib.c.aum_stream_in_tm, a, hidden, lib, "stream_in", (total, d_model, n2))
+    return xz, res_out
+
+
+def stream_out(y, w_out, lib=None):
+    """out_proj of a streaming hop (aum_stream_out_tm): y (total, dim) 16-bit rows, w_out (d_model, dim) in y's dtype -> (total, d_model);
+    the numeric contract of stream_in's projection."""
+    lib = lib or get()
+    dim = y.shape[-1]
+    a = StreamOutArgs()
+    a.y_ts = _rows16("stream_out", y, dim, lib)
+    lib.check_tensor(w_out)
+    if w_out.dim() != 2 or w_out.dtype != y.dtype or w_out.shape[1] != dim or w_out.stride(1) != 1:
+        raise RuntimeError("stream_out: unsupported operands: w_out (d_model, dim) in y's dtype, rows contiguous")
+    total, d_model = y.shape[0], w_out.shape[0]
+    out = torch.empty((total, d_model), dtype=y.dtype, device=y.device)
+    a.y, a.w_out, a.out = _ptr(y), _ptr(w_out), _ptr(out)
+    a.out_ts, a.total, a.d_model, a.dim, a.ldw, a.dtype = d_model, total, d_model, dim, w_out.stride(0), _DT[y.dtype]
+    if not stream_out_args_ok(a):
+        raise RuntimeError(f"stream_out: unsupported operands y {tuple(y.shape)} {y.dtype} strides {y.stride()}, w_out {tuple(w_out.shape)}")
+    _launch(lib.c.aum_stream_out_tm, a, y, lib, "stream_out", (total, dim, d_model))
+    return out
+
+
+def stream_layers_scratch_layout(total, d_model, dim, ncols):
+    """ss_ws of csrc/stream_stack_kernels.h: byte offsets (xz, y, hid0, hid1, res0, res1, block), the block scratch's size and the total"""
+    up = lambda n: (n + 15) // 16 * 16
+    block_bytes = 2 * (2 * total * dim + total * ncols)         # aum_stream_block_scratch_bytes
+    offs, at = [], 0
+    for n in (total * 2 * dim * 2, total * dim * 2, total * d_model * 2, total * d_model * 2, total * d_model * 4, total * d_model * 4, block_bytes):
+        offs.append(at)
+        at += up(n)
+    return offs, block_bytes, at
+
+
+def stream_layers_table(layers):
+    """the HOST table of aum_stream_layers: one StreamLayer record per block from dicts / objects naming STREAM_LAYER_POINTERS as tensors
+    (None: NULL).  The caller keeps the tensors alive; the pool pointers may be rewritten per call."""
+    table = (StreamLayer * len(layers))()
+    for rec, L in zip(table, layers):
+        for n in STREAM_LAYER_POINTERS:
+            setattr(rec, n, _ptr(L[n]))
+    return table
+
+
+_STREAM_LAYER_PARAMS = tuple(n for n in STREAM_LAYER_POINTERS if n not in ("conv_state", "state"))
+
+
+def stream_layers_records_ok(table, depth):
+    """the rules of stream_layers_check for the PARAMETER pointers of the records (everything but the two pools): the required ones are
+    there, all are 16-byte aligned.  They do not change between the calls of a StreamStack, which asks once and passes records_ok=True"""
+    recs = [table[l] for l in range(depth)]
+    return (all(getattr(L, n) for L in recs for n in _STREAM_LAYER_PARAMS if n not in ("conv_bias", "D", "delta_bias"))
+            and all(_al16p(*(getattr(L, n) or None for n in _STREAM_LAYER_PARAMS)) for L in recs))
+
+
+def stream_layers_supported(a, table=None, records_ok=False):
+    """stream_layers_check of csrc/aum_api_tm.inc on a filled StreamLayersArgs (table: its StreamLayer array; None: read through a.layers),
+    rule for rule and in its order: what aum_stream_layers takes, and what it refuses before its first launch.  records_ok=True: the
+    parameter pointers of this table have passed stream_layers_records_ok; only the pool pointers are looked at"""
+    if not (a.layers and a.hidden and a.hidden_out and a.residual_out and a.workspace and a.cu_seqlens):
+        return False
+    if min(a.depth, a.total, a.nseq, a.nrows, a.d_model, a.dim, a.ncols, a.rank) <= 0:
+        return False
+    if table is None:
+        table = C.cast(a.layers, C.POINTER(StreamLayer))
+    recs = [table[l] for l in range(a.depth)]
+    names = ("conv_state", "state") if records_ok else STREAM_LAYER_POINTERS
+    if any(not getattr(L, n) for L in recs for n in names if n not in ("conv_bias", "D", "delta_bias")):
+        return False
+    if a.dtype not in (AUM_BF16, AUM_F16):
+        return False
+    if (a.d_model, a.dim) not in STREAM_STACK_WIDTHS:
+        return False
+    if not _al16p(a.workspace, a.hidden_out, a.residual_out) or a.residual_in == a.residual_out:
+        return False
+    offs, block_bytes, need = stream_layers_scratch_layout(a.total, a.d_model, a.dim, a.ncols)
+    if a.workspace_bytes < need:
+        return False
+    lim = (1 << 31) - 1
+    # what ss_in_check / stream_block_check / ss_out_check see of layer l: the workspace offsets are multiples of 16, the pitches the widths
+    if (a.cu_seqlens | (a.state_indices or 0)) & 3:
+        return False
+    if a.flags & ~(STREAM_NO_COMMIT | STREAM_PEEK_LAST) or not 1 <= a.max_len <= STREAM_BLOCK_MAX_T:
+        return False
+    if (not xdt_fwd_shape_ok(a.ncols, a.dim) or a.rank % 8 or a.rank > 64 or a.rank + 32 > a.ncols or a.ldwx < a.dim or a.ldwdt < a.rank
+            or a.ldwx % 8 or a.ldwdt % 8):
+        return False
+    if a.hidden_ts < a.d_model or a.hidden_ts & 7 or not _al16p(a.hidden, a.residual_in):
+        return False
+    if a.total * max(a.hidden_ts, 2 * a.dim) * 2 > lim or (2 * a.dim + a.dim) * 2 * a.total > lim:
+        return False
+    return all(_al16p(*(getattr(L, n) or None for n in names)) for L in recs)
+
+
+def stream_layers_args(hidden, table, depth, conv_state0, seq_map, workspace, hidden_out, residual_out, *, dim, rank, ncols, ldwx, ldwdt, eps,
+                       commit=True, peek=False, residual=None):
+    """the filled StreamLayersArgs of one hop (stream_layers makes it; tests alter it): hidden (total, d_model) rows, table from
+    stream_layers_table, conv_state0 any layer's conv pool (for the row count)"""
+    a = StreamLayersArgs()
+    total, d_model = hidden.shape
+    a.layers = C.cast(table, C.c_void_p)
+    a.hidden, a.residual_in, a.hidden_out, a.residual_out, a.workspace = _ptr(hidden), _ptr(residual), _ptr(hidden_out), _ptr(residual_out), _ptr(workspace)
+    a.cu_seqlens, a.state_indices = _ptr(seq_map.cu), _ptr(seq_map.idx)
+    a.hidden_ts, a.workspace_bytes = (hidden.stride(0) if total > 1 else d_model), workspace.numel() * workspace.element_size()
+    a.depth, a.total, a.nseq, a.nrows, a.max_len = depth, total, len(seq_map.lens), conv_state0.shape[0], max(seq_map.lens)
+    a.d_model, a.dim, a.rank, a.ncols, a.ldwx, a.ldwdt, a.dtype = d_model, dim, rank, ncols, ldwx, ldwdt, _DT.get(hidden.dtype, -1)
+    a.flags, a.eps = (0 if commit else STREAM_NO_COMMIT) | (STREAM_PEEK_LAST if peek else 0), eps
+    return a
+
+
+def stream_layers(hidden, table, depth, conv_state0, seq_map, *, dim, rank, ncols, ldwx, ldwdt, eps, commit=True, peek=False, residual=None,
+                  workspace=None, lib=None, records_ok=False):
+    """ALL blocks of a streaming hop in ONE library call (aum_stream_layers): per block stream_in -> stream_block -> stream_out, 3 * depth
+    launches enqueued from a C loop.  hidden (total, d_model) 16-bit packed rows with seq_map (trusted: check_seq_map is the caller's);
+    table: stream_layers_table of the blocks' parameters and pools (the pools advance in place; commit / peek as stream_block).
+    workspace: a uint8 tensor of at least stream_layers_scratch_layout(...)[2] bytes, or None: allocated.
+    Returns (hidden_out (total, d_model), residual_out fp32) of the last block.  Bit for bit the loop of the three calls."""
+    lib = lib or get()
+    for t in (hidden, conv_state0, workspace, residual):
+        lib.check_tensor(t)
+    if hidden.dim() != 2 or hidden.stride(1) != 1:
+        raise RuntimeError("stream_layers: hidden must be (total, d_model) packed rows")
+    total, d_model = hidden.shape
+    if workspace is None:
+        workspace = torch.empty(stream_layers_scratch_layout(total, d_model, dim, ncols)[2], dtype=torch.uint8, device=hidden.device)
+    hidden_out = torch.empty((total, d_model), dtype=hidden.dtype, device=hidden.device)
+    residual_out = torch.empty((total, d_model), dtype=torch.float32, device=hidden.device)
+    a = stream_layers_args(hidden, table, depth, conv_state0, seq_map, workspace, hidden_out, residual_out, dim=dim, rank=rank, ncols=ncols,
+                           ldwx=ldwx, ldwdt=ldwdt, eps=eps, commit=commit, peek=peek, residual=residual)
+    if not stream_layers_supported(a, table, records_ok):
+        raise RuntimeError(f"stream_layers: unsupported operands hidden {tuple(hidden.shape)} {hidden.dtype}, widths ({d_model}, {dim}), x_dbl "
+                           f"{ncols} columns, rank {rank}, longest session {a.max_len}, workspace {a.workspace_bytes} bytes")
+    _launch(lib.c.aum_stream_layers, a, hidden, lib, "stream_layers", (depth, total, d_model))
+    return hidden_out, residual_out
 
 
 def dtproj_tm_supported(x_dbl, rank, w):

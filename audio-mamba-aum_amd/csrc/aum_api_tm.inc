@@ -940,7 +940,8 @@ AUM_API int64_t aum_stream_block_scratch_bytes(int32_t total, int32_t dim, int32
     if (total <= 0 || dim <= 0 || ncols <= 0) return 0;
     return sb_scratch(total, dim, ncols).total * 2;
 }
-AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
+// the operand check of aum_stream_block_tm (and of every block of aum_stream_layers, before its first launch)
+static int stream_block_check(const AumStreamBlockArgs* a) {
     if (!a || !a->x || !a->z || !a->conv_state || !a->state || !a->conv_weight || !a->wx || !a->wdt || !a->A || !a->y || !a->scratch) return AUM_E_NULL;
     const StreamVar var = {a->cu_seqlens, a->state_indices, a->total, a->nseq, a->nrows};
     if (const int rc = stream_var_check(&var)) return rc;
@@ -965,6 +966,10 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
         if ((ts + a->dim) * 2 * a->total > lim || (int64_t)a->nseq > lim) return AUM_E_UNSUPPORTED;
     }
     if (a->scratch_bytes < aum_stream_block_scratch_bytes(a->total, a->dim, a->ncols)) return AUM_E_WORKSPACE;
+    return AUM_OK;
+}
+// the launch behind the check (aum_stream_layers has checked every block before its first launch and calls this alone)
+static int stream_block_run(const AumStreamBlockArgs* a, void* stream) {
 #ifdef AUM_EMU
     // the lane-array build has no matrix pipe: the three host entry points behind one another on the same operands.
     // AUM_STREAM_NO_COMMIT: the pools are advanced in copies.
@@ -988,6 +993,10 @@ AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
     return with_bool((a->flags & AUM_STREAM_PEEK_LAST) != 0, [&](auto peek) {
         return a->dtype == AUM_BF16 ? sb_launch<bf16_t, true, peek>(*a, s) : sb_launch<f16_t, false, peek>(*a, s); });
 #endif
+}
+AUM_API int aum_stream_block_tm(const AumStreamBlockArgs* a, void* stream) {
+    if (const int rc = stream_block_check(a)) return rc;
+    return stream_block_run(a, stream);
 }
 
 // ---- packed prefill (stream_prefill_kernels.h): the backlogs of many sessions, time-parallel conv and state in / state out scan ----
@@ -1098,5 +1107,89 @@ AUM_API int aum_stream_park(const AumParkArgs* a, void* stream) {
     if (const int rc = park_check(a, &per_session)) return rc;
     return AUM_LAUNCH(per_session * a->n_sessions, PARK_THREADS, (aum_stream_t)stream, (NoLds{}), k_stream_park, (park_wg(*a, per_session, wg)), *a,
                       per_session);
+}
+
+// ---- a hop through all blocks in one call (stream_stack_kernels.h): add + norm + in_proj, the block above, out_proj, per layer ----
+#include "stream_stack_kernels.h"
+AUM_API int aum_stream_in_tm(const AumStreamInArgs* a, void* stream) {
+    if (const int rc = ss_in_check(a)) return rc;
+    return ss_in_run(*a, (aum_stream_t)stream);
+}
+AUM_API int aum_stream_out_tm(const AumStreamOutArgs* a, void* stream) {
+    if (const int rc = ss_out_check(a)) return rc;
+    return ss_out_run(*a, (aum_stream_t)stream);
+}
+AUM_API int64_t aum_stream_layers_scratch_bytes(int32_t total, int32_t d_model, int32_t dim, int32_t ncols) {
+    if (total <= 0 || d_model <= 0 || dim <= 0 || ncols <= 0) return 0;
+    return ss_ws(total, d_model, dim, aum_stream_block_scratch_bytes(total, dim, ncols)).total;
+}
+// the three argument structs of layer l as the loop hands them on: block l reads hidden / residual l - 1 and writes l (two buffers each,
+// taken in turn; the call's own operands at both ends)
+static void ss_layer_args(const AumStreamLayersArgs& a, const SsWs& w, int l, AumStreamInArgs& in, AumStreamBlockArgs& b, AumStreamOutArgs& out) {
+    const AumStreamLayer& L = a.layers[l];
+    char* ws = static_cast<char*>(a.workspace);
+    const bool first = l == 0, last = l == a.depth - 1;
+    in = {};
+    in.hidden = first ? a.hidden : ws + w.hid[(l - 1) & 1];
+    in.residual_in = first ? a.residual_in : reinterpret_cast<const float*>(ws + w.res[(l - 1) & 1]);
+    in.norm_weight = L.norm_weight; in.w_in = L.w_in;
+    in.residual_out = last ? a.residual_out : reinterpret_cast<float*>(ws + w.res[l & 1]);
+    in.xz = ws + w.xz;
+    in.hidden_ts = first ? a.hidden_ts : a.d_model; in.xz_ts = 2 * (int64_t)a.dim;
+    in.total = a.total; in.d_model = a.d_model; in.dim = a.dim; in.ldw = a.d_model; in.dtype = a.dtype; in.eps = a.eps;
+    b = {};
+    b.x = ws + w.xz; b.z = ws + w.xz + (int64_t)a.dim * 2;
+    b.conv_state = L.conv_state; b.state = L.state; b.conv_weight = L.conv_weight; b.conv_bias = L.conv_bias;
+    b.wx = L.wx; b.wdt = L.wdt; b.A = L.A; b.D = L.D; b.delta_bias = L.delta_bias;
+    b.y = ws + w.y; b.scratch = ws + w.block;
+    b.cu_seqlens = a.cu_seqlens; b.state_indices = a.state_indices;
+    b.x_ts = b.z_ts = 2 * (int64_t)a.dim; b.y_ts = a.dim; b.scratch_bytes = w.block_bytes;
+    b.total = a.total; b.nseq = a.nseq; b.nrows = a.nrows; b.max_len = a.max_len;
+    b.dim = a.dim; b.width = CONVT_W; b.dstate = SCANT_N; b.rank = a.rank; b.ncols = a.ncols; b.ldwx = a.ldwx; b.ldwdt = a.ldwdt;
+    b.dtype = a.dtype; b.flags = a.flags;
+    out = {};
+    out.y = ws + w.y; out.w_out = L.w_out; out.out = last ? a.hidden_out : ws + w.hid[l & 1];
+    out.y_ts = a.dim; out.out_ts = a.d_model;
+    out.total = a.total; out.d_model = a.d_model; out.dim = a.dim; out.ldw = a.dim; out.dtype = a.dtype;
+}
+// aum_hip.stream_layers_supported states the same rules in the same order
+static int stream_layers_check(const AumStreamLayersArgs* a, SsWs* wo) {
+    if (!a || !a->layers || !a->hidden || !a->hidden_out || !a->residual_out || !a->workspace || !a->cu_seqlens) return AUM_E_NULL;
+    if (a->depth <= 0 || a->total <= 0 || a->nseq <= 0 || a->nrows <= 0 || a->d_model <= 0 || a->dim <= 0 || a->ncols <= 0 || a->rank <= 0) return AUM_E_SHAPE;
+    for (int l = 0; l < a->depth; ++l) {
+        const AumStreamLayer& L = a->layers[l];
+        if (!L.norm_weight || !L.w_in || !L.conv_weight || !L.wx || !L.wdt || !L.A || !L.w_out || !L.conv_state || !L.state) return AUM_E_NULL;
+    }
+    if (a->dtype < 0 || a->dtype > 2 || a->dtype == AUM_F32) return AUM_E_DTYPE;
+    if (!ss_widths_ok(a->d_model, a->dim)) return AUM_E_UNSUPPORTED;
+    if (((uintptr_t)a->workspace | (uintptr_t)a->hidden_out | (uintptr_t)a->residual_out) & 15) return AUM_E_UNSUPPORTED;
+    if (a->residual_in == a->residual_out) return AUM_E_UNSUPPORTED;
+    const SsWs w = ss_ws(a->total, a->d_model, a->dim, aum_stream_block_scratch_bytes(a->total, a->dim, a->ncols));
+    if (a->workspace_bytes < w.total) return AUM_E_WORKSPACE;
+    for (int l = 0; l < a->depth; ++l) {
+        AumStreamInArgs in;
+        AumStreamBlockArgs b;
+        AumStreamOutArgs out;
+        ss_layer_args(*a, w, l, in, b, out);
+        if (const int rc = ss_in_check(&in)) return rc;
+        if (const int rc = stream_block_check(&b)) return rc;
+        if (const int rc = ss_out_check(&out)) return rc;
+    }
+    *wo = w;
+    return AUM_OK;
+}
+AUM_API int aum_stream_layers(const AumStreamLayersArgs* a, void* stream) {
+    SsWs w;
+    if (const int rc = stream_layers_check(a, &w)) return rc;
+    for (int l = 0; l < a->depth; ++l) {
+        AumStreamInArgs in;
+        AumStreamBlockArgs b;
+        AumStreamOutArgs out;
+        ss_layer_args(*a, w, l, in, b, out);
+        if (const int rc = ss_in_run(in, (aum_stream_t)stream)) return rc;
+        if (const int rc = stream_block_run(&b, stream)) return rc;
+        if (const int rc = ss_out_run(out, (aum_stream_t)stream)) return rc;
+    }
+    return AUM_OK;
 }
 #endif

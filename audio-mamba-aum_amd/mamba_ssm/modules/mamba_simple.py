@@ -286,8 +286,10 @@ class Mamba(nn.Module):
         return plan
 
     def invalidate_stream_params(self):
-        """drop the cached stream_params(): the next call converts the parameters again (behind a write the key cannot see: `p.data`)"""
+        """drop the cached stream_params(): the next call converts the parameters again (behind a write the key cannot see: `p.data`).
+        Moves this block's generation, which a cached AudioMamba.stream_stack() compares: it is rebuilt as well."""
         self.__dict__.pop("_stream_params", None)
+        self.__dict__["_stream_gen"] = self.__dict__.get("_stream_gen", 0) + 1
 
     @staticmethod
     def _check_packed(what, hidden_states, conv_state, ssm_state, seq_map):

@@ -1004,6 +1004,88 @@ typedef struct AumParkArgs {
 int aum_stream_park(const AumParkArgs* args, void* stream);
 
 /*
+ * A HOP THROUGH ALL BLOCKS IN ONE CALL (no version step: an addition; `AudioMamba.stream_stack`, aum_hip.stream_layers).  What is left of
+ * a streaming hop around aum_stream_block_tm is the add + RMSNorm, the two skinny projections and the host between them; here a block is
+ * three launches that a C loop enqueues back to back:
+ *     aum_stream_in_tm   residual_out = hidden (+ residual_in)   fp32
+ *                        normed       = rmsnorm(residual_out) * norm_weight, rounded to `dtype`   (bit for bit aum_rmsnorm_fwd: its row routine)
+ *                        xz           = normed . w_in^T
+ *     aum_stream_block_tm on xz's halves (the existing kernel, the existing arguments)
+ *     aum_stream_out_tm  out = y . w_out^T
+ * Both projections: every output element is ONE round-to-nearest-even of an fp32 accumulation of exact 16-bit products, on the matrix
+ * pipe (v_mfma_f32_16x16x32), the weights as the A operand and 16 token rows as the B operand: an MFMA column is one token, and the
+ * order of the K loop (four waves take the K-steps of 32 round robin, their four partial sums are added in wave order) depends on
+ * nothing but K.  A row's bits therefore do not depend on total, on the row's place in the pack or on its neighbours.
+ * A workgroup owns 32 (in) / 16 (out) output columns, keeps their weights in registers and walks the rows in tiles of 16; the norm
+ * prologue is recomputed by every workgroup (the rows come from L2), workgroup 0 alone writes residual_out.  No workgroup waits for
+ * another: no grid sync, no flags, no atomics, no partial sums through memory.
+ *   hidden (total, d_model) pitch hidden_ts, xz (total, 2 dim) pitch xz_ts, y (total, dim) pitch y_ts, out (total, d_model) pitch out_ts,
+ *   w_in (2 dim, d_model) pitch ldw, w_out (d_model, dim) pitch ldw: `dtype` AUM_BF16 / AUM_F16 (AUM_F32: AUM_E_DTYPE), K contiguous.
+ *   residual_in (total, d_model) fp32 contiguous or NULL; residual_out the same, never NULL and NOT residual_in (other workgroups still
+ *   read residual_in while it is written: AUM_E_UNSUPPORTED).  norm_weight (d_model) fp32.
+ *   Built for (d_model, dim) = (192, 384), (384, 768), (768, 1536), any total >= 1; pointers 16-byte aligned, pitches % 8 == 0 and not
+ *   below the row, total * pitch * 2 < 2^31; anything else AUM_E_UNSUPPORTED.
+ */
+typedef struct AumStreamInArgs {
+    const void* hidden;
+    const float *residual_in, *norm_weight;
+    const void* w_in;
+    float* residual_out;
+    void* xz;
+    int64_t hidden_ts, xz_ts;
+    int32_t total, d_model, dim, ldw, dtype;
+    float eps;
+} AumStreamInArgs;
+typedef struct AumStreamOutArgs {
+    const void *y, *w_out;
+    void* out;
+    int64_t y_ts, out_ts;
+    int32_t total, d_model, dim, ldw, dtype, reserved;
+} AumStreamOutArgs;
+int aum_stream_in_tm(const AumStreamInArgs* args, void* stream);
+int aum_stream_out_tm(const AumStreamOutArgs* args, void* stream);
+/*
+ * aum_stream_layers: `depth` blocks on the packed rows of a hop, 3 * depth launches on the one stream.
+ *   layers      HOST array of depth records of DEVICE pointers (read during the call only): norm_weight (d_model) fp32, w_in, w_out as
+ *               above (pitches d_model / dim), conv_weight .. delta_bias and the pools conv_state (nrows, dim, 4) / state (nrows, dim, 16)
+ *               as AumStreamBlockArgs names them (conv_bias, D, delta_bias may be NULL), wx pitch ldwx, wdt pitch ldwdt
+ *   hidden      (total, d_model) pitch hidden_ts: the rows that enter block 0;  residual_in: fp32 (total, d_model) or NULL
+ *   hidden_out  (total, d_model) contiguous, residual_out fp32 the same: what the last block leaves (residual_out != residual_in)
+ *   cu_seqlens, state_indices, total, nseq, nrows, max_len, flags (AUM_STREAM_NO_COMMIT, AUM_STREAM_PEEK_LAST): aum_stream_block_tm's
+ *   workspace   aum_stream_layers_scratch_bytes(total, d_model, dim, ncols) bytes, 16-byte aligned: xz, y, two hidden buffers, two fp32
+ *               residual buffers (a block reads one and writes the other) and aum_stream_block_tm's scratch, every offset a multiple of 16
+ * EVERY operand of EVERY layer is checked before the first launch (the checks of the three entry points on the arguments the loop will
+ * hand them): a refused call returns its code and has written nothing.  Given the same xz the middle launch's y and pool rows are bit for
+ * bit aum_stream_block_tm's, and the whole call is bit for bit the loop of the three entry points.
+ */
+typedef struct AumStreamLayer {
+    const float* norm_weight;
+    const void* w_in;
+    const float *conv_weight, *conv_bias;
+    const void *wx, *wdt;
+    const float *A, *D, *delta_bias;
+    const void* w_out;
+    float *conv_state, *state;
+} AumStreamLayer;
+typedef struct AumStreamLayersArgs {
+    const AumStreamLayer* layers;
+    const void* hidden;
+    const float* residual_in;
+    void* hidden_out;
+    float* residual_out;
+    void* workspace;
+    const int32_t *cu_seqlens, *state_indices;
+    int64_t hidden_ts, workspace_bytes;
+    int32_t depth, total, nseq, nrows, max_len;
+    int32_t d_model, dim, rank, ncols, ldwx, ldwdt;
+    int32_t dtype;
+    uint32_t flags;
+    float eps;
+} AumStreamLayersArgs;
+int aum_stream_layers(const AumStreamLayersArgs* args, void* stream);
+int64_t aum_stream_layers_scratch_bytes(int32_t total, int32_t d_model, int32_t dim, int32_t ncols);
+
+/*
  * EPIC-Sounds log-mel frontend (an addition to ABI 13; replaces librosa.stft + filters.mel + log on the CPU DataLoader workers of the reference,
  * src/epic_sounds/epic_data/audio_loader_epicsounds.py:94-156).  Per clip b and output frame t < target_length:
  *   frames  = 1 + n_valid[b] / hop   (librosa center=True: the clip is zero-padded by n_fft / 2 on both sides);  frame t >= frames is a copy of

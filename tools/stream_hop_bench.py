@@ -56,6 +56,15 @@ each).  One timed call is park + resume.  Same method: HIP events around each ca
 the groups, min / max.
 
     python tools/stream_hop_bench.py --park 8 --hops 100             (--count-only a: by hand, b: stream_park + stream_resume)
+
+--stack: stream_push (with --pool S: stream_push_many, staggered, one column each) without and with stack=model.stream_stack() -- the loop
+over the layers against ONE aum_stream_layers call -- alternating in one process, each arm on caches of its own.  Same method: HIP events
+around each call, warm hops discarded, medians of all hops and of the groups.  Next to each arm's time its HOST time: the wall clock from
+entering the call to its return, before any synchronisation -- the Python, the checks and the enqueueing of the launches; a hop whose
+host time is its whole time is bound by the host, one whose host time is a fraction of it waits for the kernels.
+
+    python tools/stream_hop_bench.py --stack [--batch 1 8]           (--count-only a: the loop, b: stack=)
+    python tools/stream_hop_bench.py --stack --pool 8                (--count-only a | b)
 """
 import argparse
 import contextlib
@@ -63,6 +72,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -152,6 +162,76 @@ def fused_ab(model, args, dev):
                           "three_launch_ms_median": round(statistics.median(ta), 4), "three_launch_ms_group_medians": med(ta),
                           "fused_ms_median": round(statistics.median(tb), 4), "fused_ms_group_medians": med(tb),
                           "ratio_three_over_fused": round(statistics.median(ta) / statistics.median(tb), 3)}), flush=True)
+
+
+def stack_ab(model, args, dev):
+    """--stack: one hop through the loop over the layers (a) against one aum_stream_layers call (b), the arms alternating"""
+    stack = model.stream_stack()
+    nt = model.patch_grid_size[1]
+    cases = []
+    if args.pool:
+        S = args.pool
+        specs = [torch.randn(16, 128, device=dev, dtype=torch.bfloat16) for _ in range(S)]
+        pools = [model.allocate_stream_pool(S) for _ in range(2)]
+        for p in pools:
+            p["columns"] = [(7 * i) % (nt - 8) for i in range(S)]
+
+        def many(i, st):
+            def run():
+                for j in range(S):
+                    if pools[i]["columns"][j] + 1 > nt:
+                        pools[i]["columns"][j] = 0        # a new clip: the caches' values do not matter for timing
+                model.stream_push_many(specs, pools[i], range(S), stack=st)
+            return run
+        cases.append(({"sessions": S}, (("loop", many(0, None)), ("stack", many(1, stack)))))
+    else:
+        for B in args.batch:
+            spec = torch.randn(B, 16, 128, device=dev, dtype=torch.bfloat16)
+            caches = [model.allocate_inference_cache(B) for _ in range(2)]
+
+            def push(i, st, spec=spec, caches=caches):
+                def run():
+                    if caches[i]["columns"] + 1 > nt:
+                        caches[i]["columns"] = 0
+                    model.stream_push(spec, caches[i], stack=st)
+                return run
+            cases.append(({"batch": B}, (("loop", push(0, None)), ("stack", push(1, stack)))))
+    for tag, arms in cases:
+        if args.count_only:
+            name, fn = arms[0 if args.count_only == "a" else 1]
+            for _ in range(args.count_hops):
+                fn()
+            torch.cuda.synchronize()
+            print(json.dumps(dict(tag, path="stack " + name, hops=args.count_hops)))
+            continue
+        def timed_host(fn):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            t0 = time.perf_counter()
+            fn()
+            t1 = time.perf_counter()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b), (t1 - t0) * 1e3
+
+        for _ in range(args.warm):
+            for _, fn in arms:
+                timed_call(fn)
+        times, host = [[] for _ in arms], [[] for _ in arms]
+        for _ in range(args.hops):
+            for t, h, (_, fn) in zip(times, host, arms):
+                ms, hms = timed_host(fn)
+                t.append(ms)
+                h.append(hms)
+        g = max(args.hops // args.groups, 1)
+        out = dict(tag, model=f"aum-{args.size} causal depth {args.depth} bf16", hop_tokens=8, hops=args.hops, warm=args.warm)
+        for (name, _), t, h in zip(arms, times, host):
+            out[name + "_host_ms_median"] = round(statistics.median(h), 4)
+            out[name + "_ms_median"] = round(statistics.median(t), 4)
+            out[name + "_ms_group_medians"] = [round(statistics.median(t[i:i + g]), 4) for i in range(0, g * args.groups, g)]
+            out[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+        out["ratio_loop_over_stack"] = round(out["loop_ms_median"] / out["stack_ms_median"], 3)
+        print(json.dumps(out), flush=True)
 
 
 def hop_push_then_read(model, spec, cache):
@@ -551,9 +631,14 @@ def main():
                     help="raw audio: 8 sessions by hand (tail + hop on the host side, fbank_fwd, stream_push_many) vs one stream_push_wave_many")
     ap.add_argument("--park", type=int, default=0, metavar="N",
                     help="N sessions off a pool and back into other rows: 2 (2 depth + 1) indexed copies vs one stream_park + one stream_resume")
+    ap.add_argument("--stack", action="store_true", help="stream_push / stream_push_many without and with stack=model.stream_stack()")
     args = ap.parse_args()
     dev = "cuda:0"
     model = make(args.size, args.depth, dev, max(1024, 16 * args.prefill, 16 * args.timeline))
+    if args.stack:
+        with torch.no_grad():
+            stack_ab(model, args, dev)
+        return
     if args.park:
         with torch.no_grad():
             park_ab(model, args, dev)
