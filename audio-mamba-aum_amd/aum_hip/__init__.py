@@ -452,7 +452,10 @@ def _unit(t, name):
 
 
 def _f32c(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
+    if t is None:
+        return None
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()    # what .to().contiguous() return then
 
 
 def _bc3(t):
@@ -650,13 +653,110 @@ def _tm3(t, name, last):
     return bs, ts
 
 
+def _tm2(t, name, last):
+    """(total, X) packed rows with unit stride along X -> row stride in elements"""
+    if t.dim() != 2 or t.shape[1] != last or (t.stride(1) != 1 and last != 1):
+        raise RuntimeError(f"{name}: expected (total, {last}) with the last axis contiguous (packed token-major rows)")
+    return t.stride(0) if t.shape[0] > 1 else last
+
+
+# the row operands of a token-major scan as _scan_rows took them: ops (u, delta, z, B, C); lead (batch, len), or (total,) for packed rows; es bytes
+# per element; strides per operand in elements, (batch stride, row stride) or for packed rows the row stride alone, 0s for an absent z
+_ScanRows = typing.NamedTuple("_ScanRows", [("ops", tuple), ("lead", tuple), ("dim", int), ("dstate", int), ("es", int), ("strides", list)])
+
+
+def _scan_rows(u, delta, z, B, C, dstate, strict=False, pad=0, activated=False):
+    """THE operand rule of the token-major scans, for (batch, len, X) and packed (total, X) rows -> (_ScanRows, None), or (None, (clause,
+    operand, message)) where it refuses; callers raise the message, or one of their own for the clause.  Every binding: u of a dtype the
+    kernels have, delta / z / B / C of that dtype ("dtype"); every operand of u's rank, dim (u, delta, z) or dstate (B, C) columns of unit
+    stride ("shape").  strict (the kernels that move rows as 16-byte chunks; the chunk kernels read element by element and take the rest):
+    u's leading shape ("shape"); dim-wide rows at 16-byte addresses and strides, 16-bit B / C rows at 4-byte addresses and even strides
+    ("align"); (row stride + pad) * es * rows < 2^31 with rows = len at pad 0 (the C check of fixed rows) or total at pad dim (that of
+    packed rows) ("bound"); an activated delta only with 16-bit rows and z ("activated")."""
+    packed = u.dim() == 2
+    dim, dt = u.shape[-1], u.dtype
+    ops = (("u", u, dim), ("delta", delta, dim), ("z", z, dim), ("B", B, dstate), ("C", C, dstate))
+    if dt not in _DT:
+        return None, ("dtype", "u", "u must be fp32, bf16 or fp16")
+    if delta.dtype != dt or B.dtype != dt or C.dtype != dt or (z is not None and z.dtype != dt):
+        name, t, _ = next(o for o in ops if o[1] is not None and o[1].dtype != dt)
+        return None, ("dtype", name, f"{name} must have u's dtype ({dt}), got {t.dtype}")
+    es = 4 if dt == torch.float32 else 2
+    tm, none = (_tm2, 0) if packed else (_tm3, (0, 0))
+    try:                                # every streaming call of a host loop over the blocks comes through here: the plain path is kept short
+        strides = [none if t is None else tm(t, name, last) for name, t, last in ops]
+    except RuntimeError as e:           # _tm2 / _tm3: not token-major rows of this rank and width; their message begins with the operand's name
+        return None, ("shape", str(e).split(":")[0], str(e))
+    if strict:
+        for (name, t, last), st in zip(ops, strides):
+            if t is None:
+                continue
+            bs, ts = (0, st) if packed else st
+            if t.shape[:-1] != u.shape[:-1]:
+                return None, ("shape", name, f"{name}: expected {tuple(u.shape[:-1]) + (last,)}, got {tuple(t.shape)}")
+            if last == dim and (t.data_ptr() % 16 or (ts * es) % 16 or (bs * es) % 16):
+                return None, ("align", name, f"{name}: rows are moved as 16-byte chunks")
+            if last != dim and es == 2 and (t.data_ptr() % 4 or ts % 2 or bs % 2):
+                return None, ("align", name, f"{name}: 16-bit B / C rows are read as dwords")
+            if ts < 0 or (ts + pad) * es * u.shape[-2] >= 2 ** 31:
+                return None, ("bound", name, f"{name}: row offsets are 32-bit byte cursors")
+    if strict and activated and (es == 4 or z is None):
+        return None, ("activated", "delta", "an activated delta is taken with 16-bit rows and z only")
+    return _ScanRows((u, delta, z, B, C), (u.shape[0],) if packed else (u.shape[0], u.shape[1]), dim, dstate, es, strides), None
+
+
+def _scan_flags(softplus, reverse, activated):
+    return (SCAN_SOFTPLUS if softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_DELTA_ACTIVATED if activated else 0)
+
+
+def _fill_scan(a, rows, A, A_b, D, delta_bias, out, flags):
+    """Writes what the token-major scan Args structs share into `a` (a struct, or the `base` of one): the row operands' pointers and strides
+    (batch strides and batch / len where the rows have them, else total), the parameters as fp32 contiguous tensors, out (None: the struct
+    has none), dim / dstate / dtype / flags.  Returns the converted parameters: the caller holds them until its launch is enqueued."""
+    u, delta, z, B, C = rows.ops
+    held = A, A_b, D, delta_bias = _f32c(A), _f32c(A_b), _f32c(D), _f32c(delta_bias)
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.D, a.delta_bias = _ptr(A), _ptr(D), _ptr(delta_bias)
+    if A_b is not None:
+        a.A_b = _ptr(A_b)
+    if len(rows.lead) == 1:
+        a.u_ts, a.delta_ts, a.z_ts, a.B_ts, a.C_ts = rows.strides
+        a.total, = rows.lead
+        if out is not None:
+            a.out, a.out_ts = _ptr(out), _tm2(out, "out", rows.dim)
+    else:
+        (a.u_bs, a.u_ts), (a.delta_bs, a.delta_ts), (a.z_bs, a.z_ts), (a.B_bs, a.B_ts), (a.C_bs, a.C_ts) = rows.strides
+        a.batch, a.len = rows.lead
+        if out is not None:
+            (a.out_bs, a.out_ts), a.out = _tm3(out, "out", rows.dim), _ptr(out)
+    a.dim, a.dstate, a.dtype, a.flags = rows.dim, rows.dstate, _DT[u.dtype], flags
+    return held
+
+
+def _fill_map(a, m, nrows, pooled=True):
+    """the sessions of a packed call: where they are in the stream, and (pooled) which of the `nrows` cache rows each owns"""
+    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx) if pooled else None
+    a.nseq, a.nrows = len(m.lens), nrows
+
+
+def _scan_tm_ckpt_shape(lib, batch, length, dim, dstate, bidir, dtype):
+    """THE size of the state checkpoint of scan_tm_fwd / _bwd: (directions, batch, nck, rows, dim) dwords -- fp32 states (rows = dstate)
+    for fp32 activations, pairs of states in the activations' own type (rows = dstate / 2) for 16-bit ones"""
+    rows = int(lib.c.aum_scan_tm_ckpt_rows(_DT[dtype])) if dstate == 16 else dstate
+    return (2 if bidir else 1, batch, max(int(lib.c.aum_scan_tm_nck(length)), 1), rows, dim)
+
+
+def _check_scan_tm_ckpt(lib, ckpt, *launch):
+    if ckpt is None or ckpt.dtype != torch.float32 or not ckpt.is_contiguous():
+        raise RuntimeError("ckpt: the contiguous fp32 tensor scan_tm_fwd filled")
+    if ckpt.numel() < math.prod(_scan_tm_ckpt_shape(lib, *launch)):
+        raise RuntimeError("ckpt too small for this launch")
+
+
 def scan_tm_ckpt(batch, length, dim, dstate, bidir, device, lib=None, dtype=torch.float32):
     """empty state checkpoint (directions, batch, nck, rows, dim) dwords for scan_tm_fwd to fill and scan_tm_bwd to read; dtype = the
     activations' dtype: fp32 states (rows = dstate) for fp32, pairs of states in the activations' own type (rows = dstate / 2) for 16-bit activations"""
-    lib = lib or get()
-    nck = int(lib.c.aum_scan_tm_nck(length))
-    rows = int(lib.c.aum_scan_tm_ckpt_rows(_DT[dtype])) if dstate == 16 else dstate
-    return torch.empty((2 if bidir else 1, batch, max(nck, 1), rows, dim), dtype=torch.float32, device=device)
+    return torch.empty(_scan_tm_ckpt_shape(lib or get(), batch, length, dim, dstate, bidir, dtype), dtype=torch.float32, device=device)
 
 
 SCAN_TM_MAX_SEGMENTS = 32
@@ -688,43 +788,27 @@ def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softpl
     delta_activated: delta already holds softplus(raw + delta_bias) (AUM_SCAN_DELTA_ACTIVATED; 16-bit with z only): used as it is.
     Returns (out, out_pre|None), both (batch, len, dim) contiguous."""
     lib = lib or get()
-    batch, length, dim = u.shape
-    dstate = A.shape[1]
+    (batch, length, dim), dstate = u.shape, A.shape[1]
     for t in (u, delta, z, B, C):
         lib.check_tensor(t)
-    if u.dtype not in _DT or delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype):
-        raise RuntimeError("u, delta, z must share one dtype in {fp32, bf16, fp16}")
-    if B.dtype != u.dtype or C.dtype != u.dtype:
-        raise RuntimeError("B, C must have u's dtype")
-    A, A_b, D, delta_bias = _f32c(A), _f32c(A_b), _f32c(D), _f32c(delta_bias)
-    a = ScanTmFwdArgs()
-    a.u_bs, a.u_ts = _tm3(u, "u", dim)
-    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
-    if z is not None:
-        a.z_bs, a.z_ts = _tm3(z, "z", dim)
-    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
-    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
+    rows, why = _scan_rows(u, delta, z, B, C, dstate)
+    if why:
+        raise RuntimeError(why[2] if why[0] != "dtype" else "B, C must have u's dtype" if why[1] in "BC" else
+                           "u, delta, z must share one dtype in {fp32, bf16, fp16}")
     if out is None:
         out = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device)
     out_pre = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device) if want_out_pre else None
-    a.out_bs, a.out_ts = _tm3(out, "out", dim)
+    a = ScanTmFwdArgs()
+    _held = _fill_scan(a, rows, A, A_b, D, delta_bias, out, _scan_flags(delta_softplus, reverse, delta_activated))
     if out_pre is not None:
-        a.pre_bs, a.pre_ts = _tm3(out_pre, "out_pre", dim)
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.A_b, a.D, a.delta_bias = _ptr(A), _ptr(A_b), _ptr(D), _ptr(delta_bias)
-    a.out, a.out_pre = _ptr(out), _ptr(out_pre)
+        (a.pre_bs, a.pre_ts), a.out_pre = _tm3(out_pre, "out_pre", dim), _ptr(out_pre)
     if ckpt is not None:
-        assert ckpt.dtype == torch.float32 and ckpt.is_contiguous()
-        rows = int(lib.c.aum_scan_tm_ckpt_rows(_DT[u.dtype])) if dstate == 16 else dstate
-        assert ckpt.numel() >= (2 if A_b is not None else 1) * batch * max(int(lib.c.aum_scan_tm_nck(length)), 1) * rows * dim, "ckpt too small"
+        _check_scan_tm_ckpt(lib, ckpt, batch, length, dim, dstate, A_b is not None, u.dtype)
         lib.check_tensor(ckpt)
         a.ckpt = _ptr(ckpt)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
     if segments > 1:
         sa = ScanTmSegFwdArgs()
-        sa.base = a
-        sa.segments = int(segments)
+        sa.base, sa.segments = a, int(segments)
         sa.carry_bytes = int(lib.c.aum_scan_tm_seg_carry_bytes(batch, dim, length, dstate, int(A_b is not None), int(segments)))
         if sa.carry_bytes <= 0:
             raise RuntimeError(f"scan_tm_fwd: segments={segments} not supported for this shape")
@@ -732,9 +816,9 @@ def scan_tm_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softpl
         sa.carry = _ptr(carry)
         _launch(lib.c.aum_scan_tm_seg_fwd, sa, u, lib, "scan_tm_seg_fwd_bidir" if A_b is not None else "scan_tm_seg_fwd",
                 (batch, dim, length, dstate, u.element_size(), want_out_pre, int(segments)))
-        return out, out_pre
-    _launch(lib.c.aum_scan_tm_fwd, a, u, lib, "scan_tm_fwd_bidir" if A_b is not None else "scan_tm_fwd",
-            (batch, dim, length, dstate, u.element_size(), want_out_pre))
+    else:
+        _launch(lib.c.aum_scan_tm_fwd, a, u, lib, "scan_tm_fwd_bidir" if A_b is not None else "scan_tm_fwd",
+                (batch, dim, length, dstate, u.element_size(), want_out_pre))
     return out, out_pre
 
 
@@ -751,23 +835,9 @@ def scan_tm_fwd_state_supported(u, delta, A, B, C, D=None, z=None, delta_bias=No
     for 16-bit rows with z -- and the states fp32 contiguous (batch, dim, 16), 16-byte aligned.  Outside them callers use scan_stream."""
     if u.dim() != 3 or A.dim() != 2 or u.shape[1] < 1 or not scan_tm_supported(u.shape[2], A.shape[1]) or u.dtype not in _DT:
         return False
-    batch, length, dim = u.shape
-    dstate, es = A.shape[1], u.element_size()
-    if not (1 <= int(segments) <= SCAN_TM_MAX_SEGMENTS) or A.shape[0] != dim:
-        return False
-    for t, last in ((u, dim), (delta, dim), (z, dim), (B, dstate), (C, dstate)):
-        if t is None:
-            continue
-        if t.dtype != u.dtype or t.dim() != 3 or tuple(t.shape) != (batch, length, last) or (t.stride(2) != 1 and last != 1):
-            return False
-        bs, ts = _tm3(t, "operand", last)
-        if last == dim and (t.data_ptr() % 16 or (ts * es) % 16 or (bs * es) % 16):
-            return False
-        if last == dstate and es == 2 and (t.data_ptr() % 4 or ts % 2 or bs % 2):
-            return False
-        if ts < 0 or ts * es * length >= 2 ** 31:
-            return False
-    if delta_activated and (es == 4 or z is None):
+    (batch, length, dim), dstate = u.shape, A.shape[1]
+    if (not (1 <= int(segments) <= SCAN_TM_MAX_SEGMENTS) or A.shape[0] != dim
+            or _scan_rows(u, delta, z, B, C, dstate, strict=True, activated=delta_activated)[0] is None):
         return False
     return scan_state_supported(state_in, batch, dim, dstate) and scan_state_supported(state_out, batch, dim, dstate)
 
@@ -788,30 +858,16 @@ def scan_tm_fwd_state(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
                            f"{None if state_in is None else (tuple(state_in.shape), state_in.dtype)}, state_out "
                            f"{None if state_out is None else (tuple(state_out.shape), state_out.dtype)}, segments {segments} "
                            "(need token-major 16-byte rows of one dtype, dim % 64 == 0, dstate 16, fp32 contiguous (batch, dim, 16) states)")
-    batch, length, dim = u.shape
-    dstate = A.shape[1]
-    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
-    for t in (A, D, delta_bias):
-        lib.check_tensor(t)
+    (batch, length, dim), dstate = u.shape, A.shape[1]
     if out is None:
         out = torch.empty((batch, length, dim), dtype=u.dtype, device=u.device)
     if out.dtype != u.dtype or tuple(out.shape) != (batch, length, dim):
         raise RuntimeError("scan_tm_fwd_state: out must have u's shape and dtype")
     sa = ScanTmFwdStateArgs()
-    a = sa.base
-    a.u_bs, a.u_ts = _tm3(u, "u", dim)
-    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
-    if z is not None:
-        a.z_bs, a.z_ts = _tm3(z, "z", dim)
-    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
-    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
-    a.out_bs, a.out_ts = _tm3(out, "out", dim)
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.D, a.delta_bias, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(out)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    _held = _fill_scan(sa.base, _scan_rows(u, delta, z, B, C, dstate)[0], A, None, D, delta_bias, out, _scan_flags(delta_softplus, False, delta_activated))
+    for t in _held:
+        lib.check_tensor(t)
     sa.state_in, sa.state_out, sa.segments = _ptr(state_in), _ptr(state_out), int(segments)
-    carry = None
     if segments > 1:
         sa.carry_bytes = int(lib.c.aum_scan_tm_seg_carry_bytes(batch, dim, length, dstate, 0, int(segments)))
         carry = torch.empty((sa.carry_bytes // 4,), dtype=torch.float32, device=u.device)
@@ -827,15 +883,15 @@ def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_
     delta_activated: delta holds softplus(raw + delta_bias); ddelta and ddelta_bias are still the gradients with respect to raw and the
     bias (ddelta_bias whenever delta_bias is given)."""
     lib = lib or get()
-    batch, length, dim = u.shape
-    dstate = A.shape[1]
+    (batch, length, dim), dstate = u.shape, A.shape[1]
     dev = u.device
     for t in (u, delta, z, B, C, dout, out_pre, ckpt):
         lib.check_tensor(t)
     # the kernel is told ONE element type: a tensor of another one would be read past its end (e.g. a 16-bit dout under fp32 rows)
-    if u.dtype not in _DT:
-        raise RuntimeError("u must be fp32, bf16 or fp16")
-    for name, t in (("delta", delta), ("z", z), ("B", B), ("C", C), ("dout", dout), ("out_pre", out_pre), ("dz_out", dz_out)):
+    rows, why = _scan_rows(u, delta, z, B, C, dstate)
+    if why and why[0] == "dtype":
+        raise RuntimeError(why[2])
+    for name, t in (("dout", dout), ("out_pre", out_pre), ("dz_out", dz_out)):
         if t is not None and t.dtype != u.dtype:
             raise RuntimeError(f"{name} must have u's dtype ({u.dtype}), got {t.dtype}")
     for name, t in (("delta", delta), ("z", z), ("dout", dout), ("out_pre", out_pre), ("dz_out", dz_out)):
@@ -843,18 +899,13 @@ def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_
             raise RuntimeError(f"{name}: expected shape {(batch, length, dim)}, got {tuple(t.shape)}")
     if z is not None and out_pre is None:
         raise RuntimeError("out_pre (the forward's pre-gate sum) is required when z is given")
-    A, A_b, D, delta_bias = _f32c(A), _f32c(A_b), _f32c(D), _f32c(delta_bias)
     bidir = A_b is not None
-    if ckpt is None or ckpt.dtype != torch.float32 or not ckpt.is_contiguous():
-        raise RuntimeError("ckpt: the contiguous fp32 tensor scan_tm_fwd filled")
-    rows_ = int(lib.c.aum_scan_tm_ckpt_rows(_DT[u.dtype])) if dstate == 16 else dstate
-    if ckpt.numel() < (2 if bidir else 1) * batch * max(int(lib.c.aum_scan_tm_nck(length)), 1) * rows_ * dim:
-        raise RuntimeError("ckpt too small for this launch")
-    du = torch.empty((batch, length, dim), dtype=u.dtype, device=dev)
-    ddelta = torch.empty((batch, length, dim), dtype=u.dtype, device=dev)
-    dz = None
-    if z is not None:
-        dz = dz_out if dz_out is not None else torch.empty((batch, length, dim), dtype=u.dtype, device=dev)
+    _check_scan_tm_ckpt(lib, ckpt, batch, length, dim, dstate, bidir, u.dtype)
+    if why:
+        raise RuntimeError(why[2])
+    new = lambda: torch.empty((batch, length, dim), dtype=u.dtype, device=dev)
+    du, ddelta = new(), new()
+    dz = None if z is None else dz_out if dz_out is not None else new()
     f32 = dict(dtype=torch.float32, device=dev)
     dBC = torch.empty((batch, length, 2 * dstate), **f32)
     # param_out: {"dD" | "ddelta_bias" | "dA_xA" | "dA_b_xA": destination} -- where a parameter's gradient is wanted (its bucket view under
@@ -875,29 +926,19 @@ def scan_tm_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, ckpt, delta_
         ws_bytes = int(lib.c.aum_scan_tm_workspace_bytes(batch, dim, length, dstate, int(bidir)))
     ws = torch.empty((max(ws_bytes, 4) // 4,), **f32)
     a = ScanTmBwdArgs()
-    a.u, a.delta, a.z, a.B, a.C, a.dout, a.out_pre = map(_ptr, (u, delta, z, B, C, dout, out_pre))
-    a.A, a.A_b, a.D, a.delta_bias, a.ckpt = _ptr(A), _ptr(A_b), _ptr(D), _ptr(delta_bias), _ptr(ckpt)
-    a.du, a.ddelta, a.dz = _ptr(du), _ptr(ddelta), _ptr(dz)
-    a.dA, a.dA_b, a.dBC, a.dD, a.ddelta_bias = map(_ptr, (dA, dA_b, dBC, dD, dbias))
-    a.dA_xA, a.dA_b_xA = _ptr(dA_xA), _ptr(dA_b_xA)
+    _held = _fill_scan(a, rows, A, A_b, D, delta_bias, None, _scan_flags(delta_softplus, reverse, delta_activated))
+    a.dout, a.out_pre, a.ckpt, a.du, a.ddelta, a.dz = map(_ptr, (dout, out_pre, ckpt, du, ddelta, dz))
+    a.dA, a.dA_b, a.dBC, a.dD, a.ddelta_bias, a.dA_xA, a.dA_b_xA = map(_ptr, (dA, dA_b, dBC, dD, dbias, dA_xA, dA_b_xA))
     a.workspace, a.workspace_bytes = _ptr(ws), ws_bytes
-    a.u_bs, a.u_ts = _tm3(u, "u", dim)
-    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
-    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
-    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
     a.dout_bs, a.dout_ts = _tm3(dout, "dout", dim)
     a.du_bs, a.du_ts = _tm3(du, "du", dim)
     a.ddelta_bs, a.ddelta_ts = _tm3(ddelta, "ddelta", dim)
     if z is not None:
-        a.z_bs, a.z_ts = _tm3(z, "z", dim)
         a.pre_bs, a.pre_ts = _tm3(out_pre, "out_pre", dim)
         a.dz_bs, a.dz_ts = _tm3(dz, "dz", dim)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
     if segments > 1:
         sa = ScanTmSegBwdArgs()
-        sa.base = a
-        sa.segments = int(segments)
+        sa.base, sa.segments = a, int(segments)
         _launch(lib.c.aum_scan_tm_seg_bwd, sa, u, lib, "scan_tm_seg_bwd_bidir" if bidir else "scan_tm_seg_bwd",
                 (batch, dim, length, dstate, u.element_size(), True, int(segments)))
     else:
@@ -1053,7 +1094,8 @@ def state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplu
     return out
 
 
-# ---- streaming inference, T tokens per launch: fixed batch (aum_*_tm_chunk) or packed sessions (aum_*_tm_chunk_var), which differ in addressing only
+# ---- streaming inference, T tokens per launch: fixed batch (aum_*_tm_chunk) or packed sessions (aum_*_tm_chunk_var), which differ in addressing
+# only: one filler per operator (_fill_conv, _fill_scan) writes either struct, the packed forms add their map (_fill_map)
 def _stream_ok(cache, x, scan):
     """x a token-major (batch, T >= 1, dim) view, cache fp32 contiguous (., dim, .), of a dim / dstate / width the operator's kernels take"""
     if not (cache.dim() == 3 and cache.dtype == torch.float32 and cache.is_contiguous() and x.dim() == 3 and x.shape[1] >= 1
@@ -1089,40 +1131,54 @@ def scan_tm_chunk_var_supported(state, u):
 
 
 def _conv_chunk_operands(a, name, lib, x, conv_state, weight, bias, silu, out):
-    """Fills what ConvTmChunkArgs and ConvTmChunkVarArgs share (operand pointers, dim, width, dtype, flags); returns y (out, or allocated)."""
-    dim = x.shape[-1]
-    weight = _al16(_f32c(weight.reshape(dim, -1)))
-    bias = _al16(_f32c(bias))
-    if weight.shape[1] != conv_state.shape[2]:
-        raise RuntimeError(f"{name}: weight (dim, width) and conv_state (rows, dim, width) disagree on the width")
-    for t in (weight, bias):
-        lib.check_tensor(t)
+    """Fills what the conv's streaming Args structs share -- ConvTmChunkArgs (batch, T, dim) rows, the packed ConvTmChunkVarArgs and
+    ConvTmPrefillVarArgs (total, dim) rows -- through _fill_conv; returns y (out, or allocated) and the converted operands."""
     y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
     if y.dtype != x.dtype or y.shape != x.shape:
         raise RuntimeError(f"{name}: out must have x's shape and dtype")
+    held = _fill_conv(a, x, conv_state, weight, bias, y, CONV_SILU if silu else 0)
+    if a.width != conv_state.shape[2]:
+        raise RuntimeError(f"{name}: weight (dim, width) and conv_state (rows, dim, width) disagree on the width")
+    for t in held:
+        lib.check_tensor(t)
+    return y, held                       # the converted operands: the caller holds them until its launch is enqueued
+
+
+def _fill_conv(a, x, conv_state, weight, bias, y, flags):
+    """The conv counterpart of _fill_scan: x / y pointers and strides (batch strides and batch / len, or total for packed rows), the cache,
+    weight (dim, width) and bias as fp32 16-byte aligned tensors, dim / width / dtype / flags.  Returns the converted weight and bias."""
+    dim = x.shape[-1]
+    held = weight, bias = _al16(_f32c(weight.reshape(dim, -1))), _al16(_f32c(bias))
     a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
-    a.dim, a.width, a.dtype, a.flags = dim, weight.shape[1], _DT[x.dtype], (CONV_SILU if silu else 0)
-    return y, (weight, bias)             # the converted operands: the caller holds them until its launch is enqueued
+    if x.dim() == 2:
+        a.x_ts, a.y_ts, a.total = _tm2(x, "x", dim), _tm2(y, "out", dim), x.shape[0]
+    else:
+        a.x_bs, a.x_ts = _tm3(x, "x", dim)
+        a.y_bs, a.y_ts = _tm3(y, "y", dim)
+        a.batch, a.len = x.shape[0], x.shape[1]
+    a.dim, a.width, a.dtype, a.flags = dim, weight.shape[1], _DT[x.dtype], flags
+    return held
 
 
 def _scan_chunk_operands(a, name, lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out):
-    """Fills what ScanTmChunkArgs and ScanTmChunkVarArgs share (operand pointers, dim, dstate, dtype, flags); returns out (given, or allocated)."""
+    """Fills what the scan's streaming Args structs share -- ScanTmChunkArgs (batch, T, dim) rows, the packed ScanTmChunkVarArgs and
+    ScanTmFwdStateVarArgs (total, dim) rows -- through _scan_rows and _fill_scan; returns out (given, or allocated) and the converted operands."""
     dim, dstate = u.shape[-1], state.shape[2]
-    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype) or B.dtype != u.dtype or C.dtype != u.dtype:
+    rows, why = _scan_rows(u, delta, z, B, C, dstate)
+    if why and why[0] == "dtype":
         raise RuntimeError(f"{name}: u, delta, z, B, C must share one dtype")
-    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
-    for t in (A, D, delta_bias):
-        lib.check_tensor(t)
     if A.shape != (dim, dstate):
         raise RuntimeError(f"{name}: A must be (dim, dstate)")
     if out is None:
         out = torch.empty(u.shape, dtype=u.dtype, device=u.device)
     if out.dtype != u.dtype or out.shape != u.shape:
         raise RuntimeError(f"{name}: out must have u's shape and dtype")
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.D, a.delta_bias, a.state, a.out = _ptr(A), _ptr(D), _ptr(delta_bias), _ptr(state), _ptr(out)
-    a.dim, a.dstate, a.dtype = dim, dstate, _DT[u.dtype]
-    a.flags = (SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_DELTA_ACTIVATED if delta_activated else 0)
+    if why:
+        raise RuntimeError(why[2])
+    A, _, D, delta_bias = _fill_scan(a, rows, A, None, D, delta_bias, out, _scan_flags(delta_softplus, False, delta_activated))
+    for t in (A, D, delta_bias):
+        lib.check_tensor(t)
+    a.state = _ptr(state)
     return out, (A, D, delta_bias)       # the converted operands: the caller holds them until its launch is enqueued
 
 
@@ -1139,9 +1195,6 @@ def conv1d_tm_chunk(x, conv_state, weight, bias=None, silu=True, lib=None):
     batch, length, dim = x.shape
     a = ConvTmChunkArgs()
     y, _held = _conv_chunk_operands(a, "conv1d_tm_chunk", lib, x, conv_state, weight, bias, silu, None)
-    a.x_bs, a.x_ts = _tm3(x, "x", dim)
-    a.y_bs, a.y_ts = _tm3(y, "y", dim)
-    a.batch, a.len = batch, length
     _launch(lib.c.aum_conv1d_tm_chunk, a, x, lib, "conv_tm_chunk", (batch, dim, length, x.element_size()))
     return y
 
@@ -1159,17 +1212,9 @@ def scan_tm_chunk(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, del
         raise RuntimeError(f"scan_tm_chunk: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
                            "(need fp32 contiguous (batch, dim, 16), dim % 64 == 0, u (batch, T, dim))")
     batch, length, dim = u.shape
-    dstate = state.shape[2]
     a = ScanTmChunkArgs()
     out, _held = _scan_chunk_operands(a, "scan_tm_chunk", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
-    a.u_bs, a.u_ts = _tm3(u, "u", dim)
-    a.delta_bs, a.delta_ts = _tm3(delta, "delta", dim)
-    a.z_bs, a.z_ts = (0, 0) if z is None else _tm3(z, "z", dim)
-    a.B_bs, a.B_ts = _tm3(B, "B", dstate)
-    a.C_bs, a.C_ts = _tm3(C, "C", dstate)
-    a.out_bs, a.out_ts = _tm3(out, "out", dim)
-    a.batch, a.len = batch, length
-    _launch(lib.c.aum_scan_tm_chunk, a, u, lib, "scan_tm_chunk", (batch, dim, length, dstate, u.element_size()))
+    _launch(lib.c.aum_scan_tm_chunk, a, u, lib, "scan_tm_chunk", (batch, dim, length, state.shape[2], u.element_size()))
     return out
 
 
@@ -1222,11 +1267,27 @@ def check_seq_map(name, m, total, nrows, device):
         raise RuntimeError(f"{name}: seq_map lives on {m.cu.device}, the packed stream on {device}")
 
 
-def _tm2(t, name, last):
-    """(total, X) packed rows with unit stride along X -> row stride in elements"""
-    if t.dim() != 2 or t.shape[1] != last or (t.stride(1) != 1 and last != 1):
-        raise RuntimeError(f"{name}: expected (total, {last}) with the last axis contiguous (packed token-major rows)")
-    return t.stride(0) if t.shape[0] > 1 else last
+def _packed_call(name, lib, tensors, lead, pool, seq_map, out, supported, refusal, run):
+    """The front door of every public packed entry point, in this order: tensors of the library's kind; a pack of nothing but empty sessions is
+    answered at once; `supported()` or the entry point's own `refusal()` text; the call's one check_seq_map; `run()`, the underscore form."""
+    for t in tensors:
+        lib.check_tensor(t)
+    if lead.dim() == 2 and lead.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
+        return lead.new_empty(lead.shape) if out is None else out
+    if not supported():
+        raise RuntimeError(refusal())
+    check_seq_map(name, seq_map, lead.shape[0], pool.shape[0], lead.device)
+    return run()
+
+
+def _conv_var_refusal(name, x, conv_state, rows="total"):
+    return (f"{name}: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
+            f"{tuple(conv_state.shape)} {conv_state.dtype} (need ({rows}, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
+
+
+def _scan_var_refusal(name, state, u):
+    return (f"{name}: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
+            "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
 
 
 def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=None, out=None, lib=None, peek=False):
@@ -1235,15 +1296,9 @@ def conv1d_tm_chunk_var(x, conv_state, weight, bias=None, silu=True, seq_map=Non
     PLACE, the others are not touched.  Per session bit for bit conv1d_tm_chunk at batch 1.  Returns y (total, dim) in x's dtype.  No
     device synchronisation.  peek (AUM_CONV_PEEK_LAST): every session's last row is computed and the caches close one row early."""
     lib = lib or get()
-    for t in (x, conv_state, out):
-        lib.check_tensor(t)
-    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return x.new_empty(x.shape) if out is None else out
-    if not conv1d_tm_chunk_var_supported(x, conv_state):
-        raise RuntimeError(f"conv1d_tm_chunk_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
-                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
-    check_seq_map("conv1d_tm_chunk_var", seq_map, x.shape[0], conv_state.shape[0], x.device)
-    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, peek)
+    return _packed_call("conv1d_tm_chunk_var", lib, (x, conv_state, out), x, conv_state, seq_map, out,
+                        lambda: conv1d_tm_chunk_var_supported(x, conv_state), lambda: _conv_var_refusal("conv1d_tm_chunk_var", x, conv_state),
+                        lambda: _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, peek))
 
 
 def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib, peek=False, peek_every=None):
@@ -1253,9 +1308,7 @@ def _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, m, out, lib, peek=Fa
     pa = ConvTmChunkPeeksArgs()
     a = pa.base                         # a view of pa's first field
     y, _held = _conv_chunk_operands(a, "conv1d_tm_chunk_var", lib, x, conv_state, weight, bias, silu, out)
-    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
-    a.x_ts, a.y_ts = _tm2(x, "x", dim), _tm2(y, "out", dim)
-    a.total, a.nseq, a.nrows = total, len(m.lens), conv_state.shape[0]
+    _fill_map(a, m, conv_state.shape[0])
     if peek_every is not None:
         pa.peek_every = peek_every
         _launch(lib.c.aum_conv1d_tm_chunk_peeks, pa, x, lib, "conv1d_tm_chunk_peeks", (len(m.lens), dim, total, x.element_size()))
@@ -1278,15 +1331,9 @@ def conv1d_tm_chunk_peeks(x, conv_state, weight, bias=None, silu=True, seq_map=N
     bit for bit conv1d_tm_chunk_var(peek=True) on one group of peek_every + 1 rows after the other, then a plain call on the rest."""
     lib = lib or get()
     peek_every = _peek_period("conv1d_tm_chunk_peeks", peek_every)
-    for t in (x, conv_state, out):
-        lib.check_tensor(t)
-    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return x.new_empty(x.shape) if out is None else out
-    if not conv1d_tm_chunk_var_supported(x, conv_state):
-        raise RuntimeError(f"conv1d_tm_chunk_peeks: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
-                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
-    check_seq_map("conv1d_tm_chunk_peeks", seq_map, x.shape[0], conv_state.shape[0], x.device)
-    return _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, False, peek_every)
+    return _packed_call("conv1d_tm_chunk_peeks", lib, (x, conv_state, out), x, conv_state, seq_map, out,
+                        lambda: conv1d_tm_chunk_var_supported(x, conv_state), lambda: _conv_var_refusal("conv1d_tm_chunk_peeks", x, conv_state),
+                        lambda: _conv1d_tm_chunk_var(x, conv_state, weight, bias, silu, seq_map, out, lib, False, peek_every))
 
 
 def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, delta_activated=False, seq_map=None,
@@ -1296,30 +1343,19 @@ def scan_tm_chunk_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=None,
     rows in one dtype (row strides free).  Per session bit for bit scan_tm_chunk at batch 1.  Returns (total, dim) in u's dtype.  No
     device synchronisation.  peek (AUM_SCAN_PEEK_LAST): every session's last row is computed and the caches close one row early."""
     lib = lib or get()
-    for t in (state, u, delta, z, B, C, out):
-        lib.check_tensor(t)
-    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return u.new_empty(u.shape) if out is None else out
-    if not scan_tm_chunk_var_supported(state, u):
-        raise RuntimeError(f"scan_tm_chunk_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
-                           "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
-    check_seq_map("scan_tm_chunk_var", seq_map, u.shape[0], state.shape[0], u.device)
-    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, peek)
+    return _packed_call("scan_tm_chunk_var", lib, (state, u, delta, z, B, C, out), u, state, seq_map, out,
+                        lambda: scan_tm_chunk_var_supported(state, u), lambda: _scan_var_refusal("scan_tm_chunk_var", state, u),
+                        lambda: _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, peek))
 
 
 def _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, out, lib, peek=False, peek_every=None):
     """scan_tm_chunk_var behind its checks: operands scan_tm_chunk_var_supported takes, a map check_seq_map passed, total >= 1.
     peek_every: the same operands through aum_scan_tm_chunk_peeks"""
-    total, dim = u.shape
-    dstate = state.shape[2]
+    (total, dim), dstate = u.shape, state.shape[2]
     pa = ScanTmChunkPeeksArgs()
     a = pa.base                         # a view of pa's first field
     out, _held = _scan_chunk_operands(a, "scan_tm_chunk_var", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
-    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
-    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
-    a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
-    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
-    a.total, a.nseq, a.nrows = total, len(m.lens), state.shape[0]
+    _fill_map(a, m, state.shape[0])
     if peek_every is not None:
         pa.peek_every = peek_every
         _launch(lib.c.aum_scan_tm_chunk_peeks, pa, u, lib, "scan_tm_chunk_peeks", (len(m.lens), dim, total, dstate, u.element_size()))
@@ -1338,15 +1374,10 @@ def scan_tm_chunk_peeks(state, u, delta, A, B, C, D=None, z=None, delta_bias=Non
     other, then a plain call on the rest."""
     lib = lib or get()
     peek_every = _peek_period("scan_tm_chunk_peeks", peek_every)
-    for t in (state, u, delta, z, B, C, out):
-        lib.check_tensor(t)
-    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return u.new_empty(u.shape) if out is None else out
-    if not scan_tm_chunk_var_supported(state, u):
-        raise RuntimeError(f"scan_tm_chunk_peeks: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} "
-                           "(need fp32 contiguous (nrows, dim, 16), dim % 64 == 0, u (total, dim))")
-    check_seq_map("scan_tm_chunk_peeks", seq_map, u.shape[0], state.shape[0], u.device)
-    return _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, False, peek_every)
+    return _packed_call("scan_tm_chunk_peeks", lib, (state, u, delta, z, B, C, out), u, state, seq_map, out,
+                        lambda: scan_tm_chunk_var_supported(state, u), lambda: _scan_var_refusal("scan_tm_chunk_peeks", state, u),
+                        lambda: _scan_tm_chunk_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, out, lib, False,
+                                                   peek_every))
 
 
 # ---- timeline training: the peek-row operators from the start of a clip, differentiable (aum_scan_tm_peeks_fwd_ckpt / _bwd, aum_conv1d_tm_peeks_bwd)
@@ -1377,15 +1408,10 @@ def _peeks_train_check(name, lib, u, seq_map, width=None):
 
 
 def _scan_peeks_base(a, name, lib, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out, m):
-    total, dim = u.shape
-    state = u.new_empty((0, dim, 16), dtype=torch.float32)         # no pool: the shape alone is read
+    state = u.new_empty((0, u.shape[1], 16), dtype=torch.float32)         # no pool: the shape alone is read
     out, held = _scan_chunk_operands(a, name, lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
     a.state = None
-    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), _tm2(out, "out", dim)
-    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
-    a.B_ts, a.C_ts = _tm2(B, "B", 16), _tm2(C, "C", 16)
-    a.cu_seqlens, a.state_indices = _ptr(m.cu), None
-    a.total, a.nseq, a.nrows = total, len(m.lens), len(m.lens)
+    _fill_map(a, m, len(m.lens), pooled=False)
     return out, held
 
 
@@ -1517,15 +1543,10 @@ def conv1d_tm_prefill_var(x, conv_state, weight, bias=None, silu=True, seq_map=N
     conv1d_tm_prefill's at batch 1 when the window's values are exact in x's dtype.  Returns y (total, dim) contiguous in x's dtype
     (out: written there).  Raises where the kernel does not take the operands.  No device synchronisation."""
     lib = lib or get()
-    for t in (x, conv_state, out):
-        lib.check_tensor(t)
-    if x.dim() == 2 and x.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return x.new_empty(x.shape) if out is None else out
-    if not (x.dim() == 2 and x.shape[0] >= 1 and conv1d_tm_prefill_var_supported(x, conv_state)):
-        raise RuntimeError(f"conv1d_tm_prefill_var: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, conv_state "
-                           f"{tuple(conv_state.shape)} {conv_state.dtype} (need (total >= 1, dim) packed rows, 16-byte rows; fp32 contiguous (nrows, dim, width <= 4))")
-    check_seq_map("conv1d_tm_prefill_var", seq_map, x.shape[0], conv_state.shape[0], x.device)
-    return _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, seq_map, out, lib)
+    return _packed_call("conv1d_tm_prefill_var", lib, (x, conv_state, out), x, conv_state, seq_map, out,
+                        lambda: x.dim() == 2 and x.shape[0] >= 1 and conv1d_tm_prefill_var_supported(x, conv_state),
+                        lambda: _conv_var_refusal("conv1d_tm_prefill_var", x, conv_state, "total >= 1"),
+                        lambda: _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, seq_map, out, lib))
 
 
 def _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, m, out, lib):
@@ -1535,9 +1556,8 @@ def _conv1d_tm_prefill_var(x, conv_state, weight, bias, silu, m, out, lib):
     y, _held = _conv_chunk_operands(a, "conv1d_tm_prefill_var", lib, x, conv_state, weight, bias, silu, out)
     if not y.is_contiguous():
         raise RuntimeError("conv1d_tm_prefill_var: out must be contiguous")
-    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
-    a.x_ts, a.y_ts = _tm2(x, "x", dim), dim
-    a.total, a.nseq, a.nrows, a.max_len = total, len(m.lens), conv_state.shape[0], max(m.lens)
+    _fill_map(a, m, conv_state.shape[0])
+    a.max_len = max(m.lens)
     _launch(lib.c.aum_conv1d_tm_prefill_var, a, x, lib, "conv_tm_prefill_var", (len(m.lens), dim, total, x.element_size()))
     return y
 
@@ -1565,23 +1585,8 @@ def scan_tm_fwd_state_var_supported(state, u, delta, A, B, C, D=None, z=None, de
     session (max_len; None: not known here) into at most SCAN_TM_MAX_SEGMENTS ranges."""
     if u.dim() != 2 or A.dim() != 2 or u.shape[0] < 1 or not scan_tm_supported(u.shape[1], A.shape[1]) or u.dtype not in _DT:
         return False
-    total, dim = u.shape
-    dstate, es = A.shape[1], u.element_size()
-    if A.shape[0] != dim:
-        return False
-    for t, last in ((u, dim), (delta, dim), (z, dim), (B, dstate), (C, dstate)):
-        if t is None:
-            continue
-        if t.dtype != u.dtype or t.dim() != 2 or tuple(t.shape) != (total, last) or (t.stride(1) != 1 and last != 1):
-            return False
-        ts = _tm2(t, "operand", last)
-        if last == dim and (t.data_ptr() % 16 or (ts * es) % 16):
-            return False
-        if last == dstate and es == 2 and (t.data_ptr() % 4 or ts % 2):
-            return False
-        if ts < 0 or (ts + dim) * es * total >= 2 ** 31:
-            return False
-    if delta_activated and (es == 4 or z is None):
+    dim, dstate = u.shape[1], A.shape[1]
+    if A.shape[0] != dim or _scan_rows(u, delta, z, B, C, dstate, strict=True, pad=dim, activated=delta_activated)[0] is None:
         return False
     range_len = int(range_len)
     if range_len < 0 or range_len % SCAN_TM_CK:
@@ -1607,34 +1612,26 @@ def scan_tm_fwd_state_var(state, u, delta, A, B, C, D=None, z=None, delta_bias=N
     A session's results do not depend on the other sessions of the call, on its place in the pack or on its pool row (bitwise).
     Returns out (total, dim) contiguous in u's dtype.  Raises where the kernel does not take the operands.  No device synchronisation."""
     lib = lib or get()
-    for t in (state, u, delta, z, B, C, out):
-        lib.check_tensor(t)
-    if u.dim() == 2 and u.shape[0] == 0 and isinstance(seq_map, SeqMap) and seq_map.total == 0:       # nothing but empty sessions
-        return u.new_empty(u.shape) if out is None else out
     max_len = max(seq_map.lens) if isinstance(seq_map, SeqMap) else None
-    if not scan_tm_fwd_state_var_supported(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, range_len, max_len):
-        raise RuntimeError(f"scan_tm_fwd_state_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} strides "
-                           f"{u.stride()}, A {tuple(A.shape)}, range_len {range_len} for a longest session of {max_len} (need packed 16-byte "
-                           "rows of one dtype, dim % 64 == 0, dstate 16, an fp32 contiguous 16-byte aligned (nrows, dim, 16) pool, range_len a "
-                           f"multiple of {SCAN_TM_CK} giving at most {SCAN_TM_MAX_SEGMENTS} ranges)")
-    check_seq_map("scan_tm_fwd_state_var", seq_map, u.shape[0], state.shape[0], u.device)
-    return _scan_tm_fwd_state_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, int(range_len), out, lib)
+    return _packed_call(
+        "scan_tm_fwd_state_var", lib, (state, u, delta, z, B, C, out), u, state, seq_map, out,
+        lambda: scan_tm_fwd_state_var_supported(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, range_len, max_len),
+        lambda: (f"scan_tm_fwd_state_var: unsupported operands state {tuple(state.shape)} {state.dtype}, u {tuple(u.shape)} {u.dtype} strides "
+                 f"{u.stride()}, A {tuple(A.shape)}, range_len {range_len} for a longest session of {max_len} (need packed 16-byte "
+                 "rows of one dtype, dim % 64 == 0, dstate 16, an fp32 contiguous 16-byte aligned (nrows, dim, 16) pool, range_len a "
+                 f"multiple of {SCAN_TM_CK} giving at most {SCAN_TM_MAX_SEGMENTS} ranges)"),
+        lambda: _scan_tm_fwd_state_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, seq_map, int(range_len), out, lib))
 
 
 def _scan_tm_fwd_state_var(state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, m, range_len, out, lib):
     """scan_tm_fwd_state_var behind its checks: operands scan_tm_fwd_state_var_supported takes, a map check_seq_map passed"""
-    total, dim = u.shape
-    dstate = state.shape[2]
+    (total, dim), dstate = u.shape, state.shape[2]
     a = ScanTmFwdStateVarArgs()
     out, _held = _scan_chunk_operands(a, "scan_tm_fwd_state_var", lib, state, u, delta, A, B, C, D, z, delta_bias, delta_softplus, delta_activated, out)
     if not out.is_contiguous():
         raise RuntimeError("scan_tm_fwd_state_var: out must be contiguous")
-    a.u_ts, a.delta_ts, a.out_ts = _tm2(u, "u", dim), _tm2(delta, "delta", dim), dim
-    a.z_ts = 0 if z is None else _tm2(z, "z", dim)
-    a.B_ts, a.C_ts = _tm2(B, "B", dstate), _tm2(C, "C", dstate)
-    a.cu_seqlens, a.state_indices = _ptr(m.cu), _ptr(m.idx)
-    a.total, a.nseq, a.nrows, a.max_len, a.range_len = total, len(m.lens), state.shape[0], max(m.lens), range_len
-    carry = None
+    _fill_map(a, m, state.shape[0])
+    a.max_len, a.range_len = max(m.lens), range_len
     if range_len:
         nranges = -(-max(m.lens) // range_len)
         a.carry_bytes = int(lib.c.aum_scan_tm_fwd_state_var_carry_bytes(len(m.lens), dim, dstate, nranges))

@@ -74,9 +74,7 @@ class ConvOp:
         pa = aum_hip.ConvTmChunkPeeksArgs()
         a = pa.base
         _, held = aum_hip._conv_chunk_operands(a, "test", lib, o["x"], pool, o["w"], o["b"], o["silu"], y)
-        a.cu_seqlens, a.state_indices = smap.cu.data_ptr(), None if smap.idx is None else smap.idx.data_ptr()
-        a.x_ts, a.y_ts = o["x"].stride(0), y.stride(0)
-        a.total, a.nseq, a.nrows = o["x"].shape[0], len(smap.lens), pool.shape[0]
+        aum_hip._fill_map(a, smap, pool.shape[0])
         return pa, lib.c.aum_conv1d_tm_chunk_peeks, aum_hip.CONV_PEEK_LAST, held
 
     @staticmethod
@@ -143,11 +141,7 @@ class ScanOp:
         a = pa.base
         _, held = aum_hip._scan_chunk_operands(a, "test", lib, pool, o["u"], o["delta"], o["A"], o["B"], o["C"], o["D"], o["z"], o["bias"],
                                                o["sp"], o["act"], y)
-        a.u_ts, a.delta_ts, a.out_ts = o["u"].stride(0), o["delta"].stride(0), y.stride(0)
-        a.z_ts = 0 if o["z"] is None else o["z"].stride(0)
-        a.B_ts, a.C_ts = o["B"].stride(0), o["C"].stride(0)
-        a.cu_seqlens, a.state_indices = smap.cu.data_ptr(), None if smap.idx is None else smap.idx.data_ptr()
-        a.total, a.nseq, a.nrows = o["u"].shape[0], len(smap.lens), pool.shape[0]
+        aum_hip._fill_map(a, smap, pool.shape[0])
         return pa, lib.c.aum_scan_tm_chunk_peeks, aum_hip.SCAN_PEEK_LAST, held
 
     @staticmethod

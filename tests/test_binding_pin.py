@@ -1,0 +1,32 @@
+"""CPU: what the token-major scan / conv bindings tell the library -- every launch's name and Args struct, field for field -- on the
+lane-array build of the kernel sources (tests/emu) with host tensors, against tests/golden/binding_args.json
+(tests/binding_pin_checks.py).  The device library is held to the same record in tests/test_gpu_binding_pin.py."""
+import os
+import sys
+
+import pytest
+
+import aum_hip
+import binding_pin_checks as bp
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import build_emu
+    return aum_hip.Lib(build_emu.build(), host=True)
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return bp.load_fixture()
+
+
+def test_the_fixture_holds_exactly_the_cases(fixture):
+    assert sorted(fixture) == sorted(bp.CASES)
+
+
+@pytest.mark.parametrize("group", bp.GROUPS)
+def test_bindings_tell_the_library_what_the_fixture_holds(group, lib, fixture):
+    bp.check_group(group, lib, "cpu", fixture)

@@ -71,7 +71,6 @@ def test_fixed_batch_entry_points_refuse_the_flags(lib):
     x, cs = torch.randn(1, 3, 64), torch.randn(1, 64, 4)
     a = aum_hip.ConvTmChunkArgs()
     y, held = aum_hip._conv_chunk_operands(a, "t", lib, x, cs, torch.randn(64, 4), None, True, None)
-    a.x_bs, a.x_ts, a.y_bs, a.y_ts, a.batch, a.len = 192, 64, 192, 64, 1, 3
     snap = cs.clone()
     assert lib.c.aum_conv1d_tm_chunk(aum_hip.C_byref(a), None) == 0 and not torch.equal(cs, snap)
     a.flags |= aum_hip.CONV_PEEK_LAST
