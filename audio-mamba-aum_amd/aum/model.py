@@ -7,7 +7,7 @@ forward_features MM:509-667, Block.forward MM:58-99, defaults MM:191-242) and pr
 head.*) so published checkpoints load.  Also mirrored: the cls-token placements of RUN's flags (middle / end / head,
 MM:528-535), `transpose_token_sequence` (time-major token order, MM:545-566) and `if_bidirectional` layer pairing
 (MM:623-638), and ImageNet Vim initialisation (`imagenet_pretrain`, MM:348-395; aum.checkpoint.load_imagenet_checkpoint).
-Options off that surface (rope, double cls, flexible patch sizes, drop-path > 0) are rejected.
+Options off that surface (rope, double cls, flexible patch sizes, token dropout) are rejected.
 """
 import math
 
@@ -92,20 +92,44 @@ class PosEmbed(nn.Module):
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
 
 
-class Block(nn.Module):
-    """MM:30-99 with fused_add_norm=True, residual_in_fp32=True, drop_path=0."""
+def drop_rates(drop_path_rate, depth):
+    """depth + 1 rates.  Entry i < depth is block i's: inter_dpr[i] of MM:290-292, inter_dpr = [0.0] + linspace(0, rate, depth) (block 0
+    never drops, block i >= 1 has rate (i - 1) / (depth - 1); at depth 1 the linspace is [0]).  The last entry is the rate itself, at
+    every depth: that of the add in front of norm_f, DropPath(drop_path_rate) (MM:293, 650)."""
+    inter_dpr = [0.0] + torch.linspace(0, drop_path_rate, depth, device="cpu").tolist()      # (on the host also under a device context)
+    return inter_dpr[:depth] + [float(drop_path_rate)]
 
-    def __init__(self, dim, mixer, eps):
+
+def drop_factors(keep):
+    """timm's DropPath factors (training, scale_by_keep): one Bernoulli(keep) draw per element of the fp32 tensor `keep` (keep > 0) in
+    ONE launch, from the default generator of its device; a kept element is 1 / keep, a dropped one 0."""
+    return torch.bernoulli(keep) / keep
+
+
+class Block(nn.Module):
+    """MM:30-99 with fused_add_norm=True, residual_in_fp32=True.  drop_path (MM:51): the rate of stochastic depth on the incoming
+    hidden_states -- the previous mixer's output -- in training; the factor is applied inside the add + norm kernels."""
+
+    def __init__(self, dim, mixer, eps, drop_path=0.0):
         super().__init__()
+        if not 0.0 <= drop_path < 1.0:
+            raise ValueError(f"drop_path must be in [0, 1), not {drop_path}")
         self.mixer = mixer
         self.norm = RMSNorm(dim, eps=eps)
+        self.drop_path = float(drop_path)
 
-    def forward(self, hidden_states, residual=None, inference_params=None, *, time_reversed=False):
+    def forward(self, hidden_states, residual=None, inference_params=None, *, time_reversed=False, row_scale=None):
         """MM:58-99 (the third positional slot is the reference's inference_params).  time_reversed (keyword only): the block on the
         time-reversed sequence, reversed back (the odd layers of `if_bidirectional`) -- add + norm is token-wise, the mixer takes the
-        flag: no flipped copies of hidden_states / residual."""
+        flag: no flipped copies of hidden_states / residual.  row_scale (keyword only): this forward's (batch,) fp32 stochastic-depth
+        factors of the block (AudioMamba draws all blocks' at once); a block called on its own in training draws them itself.  No
+        residual (the first block): no drop, MM:78-87."""
+        if residual is None:
+            row_scale = None
+        elif row_scale is None and self.training and self.drop_path > 0:
+            row_scale = drop_factors(torch.full((hidden_states.shape[0],), 1.0 - self.drop_path, device=hidden_states.device))
         hidden_states, residual = rms_norm_fn(hidden_states, self.norm.weight, self.norm.bias, residual=residual,
-                                              prenorm=True, residual_in_fp32=True, eps=self.norm.eps)
+                                              prenorm=True, residual_in_fp32=True, eps=self.norm.eps, row_scale=row_scale)
         if time_reversed:
             return self.mixer(hidden_states, inference_params=inference_params, time_reversed=True), residual
         return self.mixer(hidden_states, inference_params=inference_params), residual
@@ -225,7 +249,7 @@ class AudioMamba(nn.Module):
                  use_middle_cls_token=True, use_end_cls_token=False, transpose_token_sequence=False,
                  if_bidirectional=False, ssm_cfg=None, device=None, dtype=None, imagenet_pretrain=False,
                  imagenet_pretrain_path=None, imagenet_pretrain_modelkey="model", imagenet_load_middle_cls_token=True,
-                 imagenet_load_double_cls_token=False, **unsupported):
+                 imagenet_load_double_cls_token=False, drop_path_rate=0.0, **unsupported):
         super().__init__()
         on = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0.0, -1.0)
               and k not in ("if_cls_token", "rms_norm", "fused_add_norm", "residual_in_fp32", "if_abs_pos_embed", "final_pool_type",
@@ -244,6 +268,11 @@ class AudioMamba(nn.Module):
         self.if_bidirectional = if_bidirectional
         if if_bidirectional and depth % 2:
             raise ValueError("if_bidirectional pairs the layers: depth must be even")
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1), not {drop_path_rate}")
+        self.drop_path_rate = float(drop_path_rate)
+        self._drop_rates = drop_rates(self.drop_path_rate, depth)      # [block 0 .. block depth - 1, the add in front of norm_f]
+        self._drop_keep = {}                                            # device -> (depth + 1, 1) fp32 keep probabilities
         fdim = (spectrogram_size[0] - patch_size[0]) // strides[0] + 1
         tdim = (spectrogram_size[1] - patch_size[1]) // strides[1] + 1
         self.patch_grid_size = (fdim, tdim)
@@ -253,7 +282,7 @@ class AudioMamba(nn.Module):
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         self.layers = nn.ModuleList([
             Block(embed_dim, Mamba(embed_dim, layer_idx=i, bimamba_type=bimamba_type, if_devide_out=if_devide_out,
-                                   **(ssm_cfg or {})), norm_epsilon)
+                                   **(ssm_cfg or {})), norm_epsilon, drop_path=self._drop_rates[i])
             for i in range(depth)])
         self.norm_f = RMSNorm(embed_dim, eps=norm_epsilon)
         if isinstance(self.head, nn.Linear):                       # segm_init_weights, MM:179-184
@@ -303,26 +332,45 @@ class AudioMamba(nn.Module):
                                      self.transpose_token_sequence)
         return tok, pos
 
+    def drop_scales(self, batch, device):
+        """The stochastic-depth factors of ONE forward, (depth + 1, batch) fp32 on `device`: row i is block i's (row 0: ones, block 0
+        never drops), row `depth` the add's in front of norm_f; an entry is 0 (the sample skips that block's input) or 1 / keep.  All
+        rows are one Bernoulli launch from the device's default generator (reproducible under torch.manual_seed; every rank of a
+        data-parallel run draws its own, as the reference's DropPath modules do)."""
+        device = torch.device(device)
+        keep = self._drop_keep.get(device)
+        if keep is None:
+            keep = self._drop_keep[device] = (1.0 - torch.tensor(self._drop_rates, dtype=torch.float64)).to(torch.float32)[:, None].to(device)
+        return drop_factors(keep.expand(-1, batch))
+
+    def _drop(self, hidden):
+        """this forward's drop_scales, or None (eval, rate 0): then no factor exists and the unscaled add + norm kernels run"""
+        return self.drop_scales(hidden.shape[0], hidden.device) if self.training and self.drop_path_rate > 0 else None
+
     def forward_features(self, x, frontend=None):
         hidden, pos = self.tokens(x) if frontend is None else self.tokens_from_wave(x, frontend)
+        scales = self._drop(hidden)
         with step_cache([layer.mixer for layer in self.layers], _autocast_dtype()):     # all blocks' 16-bit weights and A in a few launches
-            hidden, residual = self._run_layers(hidden)
+            hidden, residual = self._run_layers(hidden, scales)
         # MM:646-657, then the cls row (MM:660-680).  add + RMSNorm is row-wise and only the cls row is read: the final norm runs on
         # those `batch` rows instead of on all 513 per clip (same values, same gradients; 0.1 ms per step at the bench shape)
         return rms_norm_fn(hidden[:, pos], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps,
-                           residual=None if residual is None else residual[:, pos], prenorm=False, residual_in_fp32=True)
+                           residual=None if residual is None else residual[:, pos], prenorm=False, residual_in_fp32=True,
+                           row_scale=None if scales is None or residual is None else scales[-1])
 
-    def _run_layers(self, hidden):
+    def _run_layers(self, hidden, scales=None):
+        """scales: drop_scales() of this forward or None; block i takes row i (each layer of an `if_bidirectional` pair its own)"""
         residual = None
+        row = (lambda i: None) if scales is None else (lambda i: scales[i])
         if not self.if_bidirectional:
-            for layer in self.layers:
-                hidden, residual = layer(hidden, residual)
+            for i, layer in enumerate(self.layers):
+                hidden, residual = layer(hidden, residual, row_scale=row(i))
         else:                                                      # MM:623-638: layer 2i forward, layer 2i+1 on the flipped sequence
             for i in range(len(self.layers) // 2):
                 # flip(layer(flip(h), flip(r))) == layer(h, r, time_reversed=True): the four flipped copies per pair are direction
-                # flags on the conv and scan kernels
-                hf, rf = self.layers[2 * i](hidden, residual)
-                hb, rb = self.layers[2 * i + 1](hidden, residual, time_reversed=True)
+                # flags on the conv and scan kernels (a per-sample factor commutes with the flip)
+                hf, rf = self.layers[2 * i](hidden, residual, row_scale=row(2 * i))
+                hb, rb = self.layers[2 * i + 1](hidden, residual, time_reversed=True, row_scale=row(2 * i + 1))
                 hidden, residual = hf + hb, rf + rb
         return hidden, residual
 
@@ -498,10 +546,15 @@ class AudioMamba(nn.Module):
     def _cls_row(self):
         return self.cls_token + self.pos_embed.pos_embed[:, :1]                  # (1, 1, Dm)
 
-    def _head_rows(self, hidden, residual, return_features):
-        """final norm and head on (n, Dm) rows of the last block's output and residual"""
+    def _head_rows(self, hidden, residual, return_features, row_scale=None):
+        """final norm and head on (n, Dm) rows of the last block's output and residual.  row_scale (batch,): the stochastic-depth
+        factors of the add (training); the n rows are then batch runs of n / batch rows, sample by sample"""
+        if row_scale is not None:
+            hidden, residual = (t.reshape(row_scale.shape[0], -1, t.shape[-1]) for t in (hidden, residual))
         f = rms_norm_fn(hidden, self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=residual, prenorm=False,
-                        residual_in_fp32=True)
+                        residual_in_fp32=True, row_scale=row_scale)
+        if row_scale is not None:
+            f = f.reshape(-1, f.shape[-1])
         return f if return_features else self.head(f)
 
     @torch.no_grad()
@@ -949,11 +1002,11 @@ class AudioMamba(nn.Module):
         cls = self._cls_row().to(x.dtype).reshape(1, 1, 1, -1).expand(Bsz, K, 1, -1)
         return torch.cat((x.reshape(Bsz, K, nf, -1), cls), dim=2).reshape(Bsz, K * (nf + 1), -1)
 
-    def _timeline_rows(self, hidden, residual, return_features):
+    def _timeline_rows(self, hidden, residual, return_features, row_scale=None):
         """the cls rows of _with_cls_rows' layout out of the last block's output and residual -> (B K, classes): final norm and head"""
         nf = self.patch_grid_size[0]
         pick = lambda t: t.reshape(-1, nf + 1, t.shape[-1])[:, nf]
-        return self._head_rows(pick(hidden), pick(residual), return_features)
+        return self._head_rows(pick(hidden), pick(residual), return_features, row_scale)
 
     def forward_timeline(self, spec, return_features=False, frontend=None):
         """The differentiable counterpart of stream_timeline from column 0 -- TRAINING for the per-column logits: spec (batch, 16 K,
@@ -963,7 +1016,8 @@ class AudioMamba(nn.Module):
         rows read the conv window and the state and enter neither (HIP kernels both ways).  Causal models only (_check_streamable).
         frontend=aum.frontend.WaveInput: spec is the (batch, n_samples) waveform; it goes through the log-mel kernel first (the fused
         waveform -> tokens kernel writes the offline token layout, cls once).
-        The path is deterministic, as the offline forward is: this model has no drop-path and no token dropout to apply."""
+        In eval mode and at drop_path_rate 0 the path is deterministic, as the offline forward is; in training with a rate it draws
+        drop_scales once, as the offline forward does (a dropped sample skips a block's input at all of its rows)."""
         self._check_streamable()
         if frontend is not None:
             spec = frontend.spectrogram(spec)
@@ -972,12 +1026,14 @@ class AudioMamba(nn.Module):
             raise ValueError(f"forward_timeline: spec must be (batch, 16 K, {16 * nf}) frames of K = 1 .. {nt} time columns, not {tuple(spec.shape)}")
         K = spec.shape[1] // 16
         hidden = self._with_cls_rows(self._embed_columns(spec.unsqueeze(1).transpose(2, 3), slice(0, K)))
+        scales = self._drop(hidden)
         residual = None
-        for layer in self.layers:
+        for i, layer in enumerate(self.layers):
             hidden, residual = rms_norm_fn(hidden, layer.norm.weight, layer.norm.bias, residual=residual, prenorm=True,
-                                           residual_in_fp32=True, eps=layer.norm.eps)
+                                           residual_in_fp32=True, eps=layer.norm.eps,
+                                           row_scale=None if scales is None or residual is None else scales[i])
             hidden = layer.mixer(hidden, peek_every=nf)
-        out = self._timeline_rows(hidden, residual, return_features)
+        out = self._timeline_rows(hidden, residual, return_features, None if scales is None else scales[-1])
         return out.reshape(spec.shape[0], K, -1)
 
     @torch.no_grad()

@@ -124,8 +124,13 @@ def build_parser():
 def check_scope(args):
     if args.model != "aum":
         raise NotImplementedError("--model ast (the transformer baseline) is outside the accelerated path")
-    if args.flexible_training or args.aum_drop_path:
-        raise NotImplementedError("flexible training / drop-path are out of scope")
+    if args.flexible_training:
+        raise NotImplementedError("flexible training is out of scope")
+    if args.aum_drop_path and args.dataset == "epic_sounds":
+        raise NotImplementedError("--aum_drop_path (stochastic depth) is implemented for the AudioSet-style datasets; together with "
+                                  "--dataset epic_sounds it is not")
+    if not 0.0 <= args.aum_drop_path < 1.0:
+        raise ValueError("--aum_drop_path is a drop probability: it must be in [0, 1)")
     if args.dataset == "epic_sounds" and not (args.epic_config or (args.epic_annotations_dir and args.epic_audio)):
         # run.py:139-141 falls back to the config_default.yaml of its own source tree, whose paths name the authors' storage; that
         # implicit configuration is not implemented here: the data source is always given
@@ -210,7 +215,8 @@ def build_model(args):
     model = AudioMamba(spectrogram_size=(args.melbins, args.audio_length), patch_size=(args.fpatch_size, args.tpatch_size),
                        strides=(args.fstride, args.tstride), depth=args.depth, embed_dim=AUM_SIZES[size], num_classes=args.n_class,
                        bimamba_type=bimamba, use_middle_cls_token=args.use_middle_cls_token,
-                       use_end_cls_token=args.use_end_cls_token, transpose_token_sequence=args.transpose_token_sequence)
+                       use_end_cls_token=args.use_end_cls_token, transpose_token_sequence=args.transpose_token_sequence,
+                       drop_path_rate=args.aum_drop_path)
     if args.imagenet_pretrain:                   # ImageNet first, AuM second: the AuM checkpoint's values win (MM:348-446)
         from .checkpoint import load_imagenet_checkpoint
         print(load_imagenet_checkpoint(model, args.imagenet_pretrain_path, args.imagenet_pretrain_modelkey,

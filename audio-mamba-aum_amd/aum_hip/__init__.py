@@ -8,6 +8,7 @@ The functions mirror the reference's extension modules:
   scan_fwd / scan_bwd          <- selective_scan_cuda.fwd / .bwd   (SSI:37, 62-65, 499-505, 541-552)
   conv1d_fwd / conv1d_bwd      <- causal_conv1d_cuda.causal_conv1d_fwd / _bwd (SSI:463, 594-596)
   rmsnorm_fwd / rmsnorm_bwd    <- _layer_norm_fwd / _layer_norm_bwd (LN:123-177, 293-377)
+  rmsnorm_drop_fwd / _bwd      <- the same behind timm's DropPath on x (MM:90, MM:650): the per-sample factor inside the kernels
 """
 import ctypes as C
 import math
@@ -126,6 +127,10 @@ class NormArgs(C.Structure):
                                        "row_stride_dy", "row_stride_dres_out", "row_stride_dx", "row_stride_dres_in")]
                 + [("eps", C.c_float)] + [(n, _i32) for n in ("rows", "cols", "x_dtype", "res_dtype", "y_dtype")]
                 + [("flags", _u32)])
+
+
+class NormDropArgs(C.Structure):
+    _fields_ = [("base", NormArgs), ("row_scale", _vp), ("rows_per_scale", _i32), ("reserved", _i32)]
 
 
 class FbankArgs(C.Structure):
@@ -320,7 +325,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
     "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd",
     "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd", "aum_stream_park", "aum_stream_in_tm", "aum_stream_out_tm",
-    "aum_stream_layers")}
+    "aum_stream_layers", "aum_rmsnorm_drop_fwd", "aum_rmsnorm_drop_bwd")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -2514,6 +2519,77 @@ def rmsnorm_bwd(dy, x_saved, weight, rstd, dresidual=None, has_residual=False, x
     if has_residual and dres_in is None:
         dres_in = dx
     return dx, dw, dres_in
+
+
+def _row_scale(row_scale, rows_per_scale, rows, like, lib):
+    """the (rows / rows_per_scale,) fp32 per-sample factors of the scaled add + norm, checked against the row count"""
+    lib.check_tensor(row_scale)
+    if rows_per_scale < 1 or rows % rows_per_scale:
+        raise ValueError(f"rmsnorm_drop: {rows} rows are not whole samples of {rows_per_scale} rows")
+    if row_scale.dtype != torch.float32 or row_scale.dim() != 1 or row_scale.numel() != rows // rows_per_scale or row_scale.device != like.device:
+        raise ValueError(f"rmsnorm_drop: row_scale must be ({rows // rows_per_scale},) fp32 on {like.device}, not "
+                         f"{tuple(row_scale.shape)} {row_scale.dtype} on {row_scale.device}")
+    return row_scale.detach().contiguous()
+
+
+def rmsnorm_drop_fwd(x, weight, residual, row_scale, rows_per_scale, eps=1e-5, generic=False, lib=None):
+    """rmsnorm_fwd behind stochastic depth on x (aum_rmsnorm_drop_fwd): residual_out = fma(s, x, residual) in fp32 with
+    s = row_scale[row // rows_per_scale]; a sample with s == 0 has its x rows not read.  x, residual: (rows, cols); the residual is
+    required.  Returns (y, rstd, residual_out), residual_out a new tensor in the residual's dtype."""
+    lib = lib or get()
+    lib.check_tensor(x)
+    rows, cols = x.shape
+    if residual is None:
+        raise ValueError("rmsnorm_drop_fwd: the factor multiplies x on its way into the add: a residual is required")
+    assert x.stride(1) == 1 and residual.stride(1) == 1 and residual.shape == x.shape
+    row_scale = _row_scale(row_scale, rows_per_scale, rows, x, lib)
+    weight = _f32c(weight)
+    y = torch.empty_like(x, memory_format=torch.contiguous_format)
+    res_out = torch.empty((rows, cols), dtype=residual.dtype, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    d = NormDropArgs()
+    a = d.base
+    a.x, a.residual, a.weight, a.y, a.residual_out, a.rstd_out = map(_ptr, (x, residual, weight, y, res_out, rstd))
+    a.row_stride_x, a.row_stride_y, a.row_stride_res, a.row_stride_res_out = x.stride(0), y.stride(0), residual.stride(0), res_out.stride(0)
+    a.eps, a.rows, a.cols = eps, rows, cols
+    a.x_dtype = a.y_dtype = _DT[x.dtype]
+    a.res_dtype = _DT[residual.dtype]
+    a.flags = 2 if generic else 0
+    d.row_scale, d.rows_per_scale = _ptr(row_scale), rows_per_scale
+    _launch(lib.c.aum_rmsnorm_drop_fwd, d, x, lib, "rmsnorm_drop_fwd", (rows, cols, x.element_size()))
+    return y, rstd, res_out
+
+
+def rmsnorm_drop_bwd(dy, x_saved, weight, rstd, row_scale, rows_per_scale, dresidual=None, x_dtype=None, generic=False, lib=None,
+                     dw_out=None):
+    """rmsnorm_bwd of rmsnorm_drop_fwd (aum_rmsnorm_drop_bwd).  x_saved = residual_out of the forward.  Returns (dx [x_dtype] = s * g
+    rounded once, +0 where s == 0; dweight fp32 (into dw_out where given); dresidual_in = g in x_saved's dtype) -- always two buffers."""
+    lib = lib or get()
+    lib.check_tensor(dy)
+    rows, cols = x_saved.shape
+    x_dtype = x_dtype or x_saved.dtype
+    assert dy.stride(1) == 1 and x_saved.stride(1) == 1 and dy.dtype == x_dtype
+    row_scale = _row_scale(row_scale, rows_per_scale, rows, dy, lib)
+    weight = _f32c(weight)
+    dx = torch.empty((rows, cols), dtype=x_dtype, device=dy.device)
+    dres_in = torch.empty_like(x_saved, memory_format=torch.contiguous_format)
+    n_part = int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, 2 if generic else 0))     # rows the kernel leaves sums in
+    dwp = torch.empty((n_part, cols), dtype=torch.float32, device=dy.device)
+    d = NormDropArgs()
+    a = d.base
+    a.x, a.dy, a.dresidual_out, a.weight, a.rstd_in = map(_ptr, (x_saved, dy, dresidual, weight, rstd))
+    a.dx, a.dresidual_in, a.dweight_partial = _ptr(dx), _ptr(dres_in), _ptr(dwp)
+    a.row_stride_x, a.row_stride_dy, a.row_stride_dx, a.row_stride_dres_in = x_saved.stride(0), dy.stride(0), dx.stride(0), dres_in.stride(0)
+    if dresidual is not None:
+        assert dresidual.dtype == x_saved.dtype and dresidual.stride(1) == 1
+        a.row_stride_dres_out = dresidual.stride(0)
+    a.rows, a.cols = rows, cols
+    a.x_dtype = a.y_dtype = _DT[x_dtype]
+    a.res_dtype = _DT[x_saved.dtype]
+    a.flags = 2 if generic else 0
+    d.row_scale, d.rows_per_scale = _ptr(row_scale), rows_per_scale
+    _launch(lib.c.aum_rmsnorm_drop_bwd, d, dy, lib, "rmsnorm_drop_bwd", (rows, cols, dy.element_size()))
+    return dx, sum_rows(dwp, lib, out=dw_out), dres_in
 
 
 FBANK_AUG = 8     # columns of the per-clip augmentation table (include/aum_hip.h AUM_FBANK_AUG)

@@ -101,6 +101,17 @@ template <class TX, class TR> AUM_GLOBAL void k_norm_bwd(AumNormArgs a, int n_pa
     extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
     rmsnorm_bwd_wave<TX, TR>(a, (int)blockIdx.x, n_partials, dyn_lds);
 }
+// the same four with a per-sample factor on x (aum_rmsnorm_drop_fwd / _bwd)
+template <class TX, class TR, int NCH> AUM_GLOBAL void k_norm_drop_fwd_vec(AumNormArgs a, RowScale sc) { rmsnorm_fwd_vec<TX, TR, NCH>(a, (int)blockIdx.x, sc); }
+template <class TX, class TR, int NCH> __global__ __launch_bounds__(NORM_BWD_NW * 64) void k_norm_drop_bwd_vec(AumNormArgs a, int n_waves, RowScale sc) {
+    __shared__ __attribute__((aligned(16))) float lds[NormBwdVecLds<NCH>::n];
+    rmsnorm_bwd_vec<TX, TR, NCH>(a, (int)blockIdx.x, n_waves, lds, sc);
+}
+template <class TX, class TR> AUM_GLOBAL void k_norm_drop_fwd(AumNormArgs a, RowScale sc) { rmsnorm_fwd_wave<TX, TR>(a, (int)blockIdx.x, sc); }
+template <class TX, class TR> AUM_GLOBAL void k_norm_drop_bwd(AumNormArgs a, int n_partials, RowScale sc) {
+    extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
+    rmsnorm_bwd_wave<TX, TR>(a, (int)blockIdx.x, n_partials, dyn_lds, sc);
+}
 #if AUM_API_PART == 3 || AUM_API_PART == 0
 AUM_GLOBAL void k_selftest_sum32(const float* in, float* out) {
     vf v[32], w[16];
@@ -646,23 +657,35 @@ AUM_API int aum_rmsnorm_bwd_partial_rows(int32_t rows, int32_t cols, uint32_t fl
     return norm_is_vec(cols, flags) ? (np + NORM_BWD_NW - 1) / NORM_BWD_NW : np;
 }
 
-template <class TX, class TR, int NCH> static int norm_vec_launch(const AumNormArgs& a, bool bwd, aum_stream_t s) {
+// S: NoRowScale (aum_rmsnorm_fwd / _bwd) or RowScale (aum_rmsnorm_drop_fwd / _bwd): the same routines, grids and partial rows
+template <class TX, class TR, int NCH, class S> static int norm_vec_launch(const AumNormArgs& a, bool bwd, aum_stream_t s, const S& sc) {
     const int np = aum_rmsnorm_bwd_partials(a.rows);
-    if (bwd) return AUM_LAUNCH((np + NORM_BWD_NW - 1) / NORM_BWD_NW, NORM_BWD_NW * 64, s, (NormBwdVecLds<NCH>{}), (k_norm_bwd_vec<TX, TR, NCH>),
-                               (rmsnorm_bwd_vec<TX, TR, NCH>(a, wg, np, lds)), a, np);
-    return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd_vec<TX, TR, NCH>), (rmsnorm_fwd_vec<TX, TR, NCH>(a, wg)), a);
+    if constexpr (S::on) {
+        if (bwd) return AUM_LAUNCH((np + NORM_BWD_NW - 1) / NORM_BWD_NW, NORM_BWD_NW * 64, s, (NormBwdVecLds<NCH>{}), (k_norm_drop_bwd_vec<TX, TR, NCH>),
+                                   (rmsnorm_bwd_vec<TX, TR, NCH>(a, wg, np, lds, sc)), a, np, sc);
+        return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_drop_fwd_vec<TX, TR, NCH>), (rmsnorm_fwd_vec<TX, TR, NCH>(a, wg, sc)), a, sc);
+    } else {
+        if (bwd) return AUM_LAUNCH((np + NORM_BWD_NW - 1) / NORM_BWD_NW, NORM_BWD_NW * 64, s, (NormBwdVecLds<NCH>{}), (k_norm_bwd_vec<TX, TR, NCH>),
+                                   (rmsnorm_bwd_vec<TX, TR, NCH>(a, wg, np, lds)), a, np);
+        return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd_vec<TX, TR, NCH>), (rmsnorm_fwd_vec<TX, TR, NCH>(a, wg)), a);
+    }
 }
-template <class TX, class TR> static int norm_launch(const AumNormArgs& a, bool bwd, aum_stream_t s) {
+template <class TX, class TR, class S> static int norm_launch(const AumNormArgs& a, bool bwd, aum_stream_t s, const S& sc) {
     if (norm_is_vec(a.cols, a.flags)) {
         const int nch = (a.cols + 511) / 512;
-        return with_int<1, 2, 3, 4>(nch < 4 ? nch : 4, [&](auto n) { return norm_vec_launch<TX, TR, n>(a, bwd, s); });
+        return with_int<1, 2, 3, 4>(nch < 4 ? nch : 4, [&](auto n) { return norm_vec_launch<TX, TR, n>(a, bwd, s, sc); });
     }
     const int np = aum_rmsnorm_bwd_partials(a.rows);
     const DynLds row = {((a.cols + WAVE - 1) / WAVE) * WAVE};
-    if (bwd) return AUM_LAUNCH(np, 64, s, (row), (k_norm_bwd<TX, TR>), (rmsnorm_bwd_wave<TX, TR>(a, wg, np, lds)), a, np);
-    return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd<TX, TR>), (rmsnorm_fwd_wave<TX, TR>(a, wg)), a);
+    if constexpr (S::on) {
+        if (bwd) return AUM_LAUNCH(np, 64, s, (row), (k_norm_drop_bwd<TX, TR>), (rmsnorm_bwd_wave<TX, TR>(a, wg, np, lds, sc)), a, np, sc);
+        return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_drop_fwd<TX, TR>), (rmsnorm_fwd_wave<TX, TR>(a, wg, sc)), a, sc);
+    } else {
+        if (bwd) return AUM_LAUNCH(np, 64, s, (row), (k_norm_bwd<TX, TR>), (rmsnorm_bwd_wave<TX, TR>(a, wg, np, lds)), a, np);
+        return AUM_LAUNCH(a.rows, 64, s, (NoLds{}), (k_norm_fwd<TX, TR>), (rmsnorm_fwd_wave<TX, TR>(a, wg)), a);
+    }
 }
-static int norm_dispatch(const AumNormArgs* a, bool bwd, void* stream) {
+template <class S> static int norm_dispatch(const AumNormArgs* a, bool bwd, void* stream, const S& sc) {
     if (!a || !a->x || !a->weight) return AUM_E_NULL;
     if (bwd ? (!a->dy || !a->dx || !a->rstd_in || !a->dweight_partial) : !a->y) return AUM_E_NULL;
     if (a->rows <= 0 || a->cols <= 0) return AUM_E_SHAPE;
@@ -672,14 +695,27 @@ static int norm_dispatch(const AumNormArgs* a, bool bwd, void* stream) {
     aum_stream_t s = (aum_stream_t)stream;
     // residual stream is fp32 (residual_in_fp32) or shares the activation dtype
     if (a->res_dtype == AUM_F32) {
-        return by_dtype(a->x_dtype, norm_launch<float, float>, norm_launch<bf16_t, float>, norm_launch<f16_t, float>, *a, bwd, s);
+        return by_dtype(a->x_dtype, norm_launch<float, float, S>, norm_launch<bf16_t, float, S>, norm_launch<f16_t, float, S>, *a, bwd, s, sc);
     }
     if (a->res_dtype != a->x_dtype) return AUM_E_DTYPE;
-    if (a->x_dtype == AUM_BF16) return norm_launch<bf16_t, bf16_t>(*a, bwd, s);
-    return norm_launch<f16_t, f16_t>(*a, bwd, s);
+    if (a->x_dtype == AUM_BF16) return norm_launch<bf16_t, bf16_t>(*a, bwd, s, sc);
+    return norm_launch<f16_t, f16_t>(*a, bwd, s, sc);
 }
-AUM_API int aum_rmsnorm_fwd(const AumNormArgs* a, void* stream) { return norm_dispatch(a, false, stream); }
-AUM_API int aum_rmsnorm_bwd(const AumNormArgs* a, void* stream) { return norm_dispatch(a, true, stream); }
+AUM_API int aum_rmsnorm_fwd(const AumNormArgs* a, void* stream) { return norm_dispatch(a, false, stream, NoRowScale{}); }
+AUM_API int aum_rmsnorm_bwd(const AumNormArgs* a, void* stream) { return norm_dispatch(a, true, stream, NoRowScale{}); }
+
+// stochastic depth: the pair above with a per-sample factor on x.  The operands the scaled routines assume are checked here, every other
+// rule is norm_dispatch's.
+static int norm_drop_dispatch(const AumNormDropArgs* d, bool bwd, void* stream) {
+    if (!d || !d->row_scale) return AUM_E_NULL;
+    const AumNormArgs* a = &d->base;
+    if (bwd ? !a->dresidual_in : (!a->residual || !a->residual_out)) return AUM_E_NULL;
+    if (d->rows_per_scale < 1 || a->rows % d->rows_per_scale != 0) return AUM_E_SHAPE;
+    if (d->reserved != 0) return AUM_E_UNSUPPORTED;
+    return norm_dispatch(a, bwd, stream, RowScale{d->row_scale, d->rows_per_scale});
+}
+AUM_API int aum_rmsnorm_drop_fwd(const AumNormDropArgs* a, void* stream) { return norm_drop_dispatch(a, false, stream); }
+AUM_API int aum_rmsnorm_drop_bwd(const AumNormDropArgs* a, void* stream) { return norm_drop_dispatch(a, true, stream); }
 
 // ---- fbank frontend ----------------------------------------------------------------------------
 typedef Lds<float, FBANK_LDS_FLOATS> FbankLds;

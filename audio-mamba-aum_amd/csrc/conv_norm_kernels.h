@@ -116,8 +116,48 @@ template <class T> AUM_DEV void conv_bwd_wave(const AumConvArgs& p, int wg, floa
 // ------------------------------------------------------------------------------------------------
 // Fused residual-add + RMSNorm.  One wave per row (forward) / per block of rows (backward).
 // ------------------------------------------------------------------------------------------------
-template <class TX, class TR> AUM_DEV void rmsnorm_fwd_wave(const AumNormArgs& p, int wg) {
+// The per-sample factor on the x operand (stochastic depth, MM:90: drop_path(hidden_states) in front of the add).  Every RMSNorm routine
+// below takes one of the two as its last argument: NoRowScale is aum_rmsnorm_fwd / _bwd (its branches compile away: the same code as
+// before the argument existed), RowScale is aum_rmsnorm_drop_fwd / _bwd -- row r belongs to sample r / per:
+//   forward    pre = fma(s, x, residual) in fp32; s == 0: pre = residual and the row of x is not read (a dropped sample's NaN stays out)
+//   backward   g = the unscaled dx;  dresidual_in = g;  dx = s * g rounded once (s == 0: +0)
+// With a RowScale, residual / residual_out (forward) and dresidual_in (backward) exist: the entry points refuse anything else.
+struct NoRowScale {
+    static constexpr bool on = false;
+    AUM_DEV float at(int) const { return 1.f; }
+};
+struct RowScale {
+    static constexpr bool on = true;
+    const float* s;
+    int32_t per;
+    AUM_DEV float at(int row) const { return s[row / per]; }
+};
+
+// the norm's input at columns c: x (+ residual), or fma(s, x, residual)
+template <class S, class TX, class TR> AUM_DEV vf norm_pre(const TX* xp, const TR* rp, vi c, vm m, float s) {
+    if constexpr (S::on) {
+        const vf r = gload(rp, c, m);
+        if (s == 0.f) return r;
+        return vfma(splat(s), gload(xp, c, m), r);
+    } else {
+        vf v = gload(xp, c, m);
+        if (rp) v = v + gload(rp, c, m);
+        return v;
+    }
+}
+// the two gradients leaving the backward: dx = g (= dresidual_in where that exists), or dresidual_in = g and dx = s * g
+template <class S> AUM_DEV vf norm_dx(vf g, float s) {
+    if constexpr (S::on) {
+        if (s == 0.f) return splat(0.f);
+        return g * s;
+    } else {
+        return g;
+    }
+}
+
+template <class TX, class TR, class S = NoRowScale> AUM_DEV void rmsnorm_fwd_wave(const AumNormArgs& p, int wg, const S sc = S{}) {
     const int row = wg;
+    const float s = sc.at(row);
     const TX* xp = (const TX*)p.x + (int64_t)row * p.row_stride_x;
     const TR* rp = p.residual ? (const TR*)p.residual + (int64_t)row * p.row_stride_res : nullptr;
     TR* rop = p.residual_out ? (TR*)p.residual_out + (int64_t)row * p.row_stride_res_out : nullptr;
@@ -127,8 +167,7 @@ template <class TX, class TR> AUM_DEV void rmsnorm_fwd_wave(const AumNormArgs& p
     for (int c0 = 0; c0 < p.cols; c0 += WAVE) {
         const vi c = lane + c0;
         const vm m = c < p.cols;
-        vf v = gload(xp, c, m);
-        if (rp) v = v + gload(rp, c, m);
+        const vf v = norm_pre<S>(xp, rp, c, m, s);
         if (rop) gstore(rop, c, v, m);
         ss = vfma(v, v, ss);
     }
@@ -138,14 +177,13 @@ template <class TX, class TR> AUM_DEV void rmsnorm_fwd_wave(const AumNormArgs& p
     for (int c0 = 0; c0 < p.cols; c0 += WAVE) {
         const vi c = lane + c0;
         const vm m = c < p.cols;
-        vf v = gload(xp, c, m);
-        if (rp) v = v + gload(rp, c, m);
+        const vf v = norm_pre<S>(xp, rp, c, m, s);
         gstore(yp, c, v * rstd * gload(p.weight, c, m), m);
     }
 }
 
 // lds: cols floats of per-lane-owned dweight accumulators (column c is only ever touched by lane c%64)
-template <class TX, class TR> AUM_DEV void rmsnorm_bwd_wave(const AumNormArgs& p, int wg, int n_partials, float* lds) {
+template <class TX, class TR, class S = NoRowScale> AUM_DEV void rmsnorm_bwd_wave(const AumNormArgs& p, int wg, int n_partials, float* lds, const S sc = S{}) {
     const int rows_per = (p.rows + n_partials - 1) / n_partials;
     const int r0 = wg * rows_per;
     const int r1 = r0 + rows_per < p.rows ? r0 + rows_per : p.rows;
@@ -158,6 +196,7 @@ template <class TX, class TR> AUM_DEV void rmsnorm_bwd_wave(const AumNormArgs& p
         TX* dxp = (TX*)p.dx + (int64_t)row * p.row_stride_dx;
         TR* drip = p.dresidual_in ? (TR*)p.dresidual_in + (int64_t)row * p.row_stride_dres_in : nullptr;
         const float rstd = p.rstd_in[row];
+        const float s = sc.at(row);
         vf c1 = splat(0.f);
         for (int c0 = 0; c0 < p.cols; c0 += WAVE) {
             const vi c = lane + c0;
@@ -175,7 +214,7 @@ template <class TX, class TR> AUM_DEV void rmsnorm_bwd_wave(const AumNormArgs& p
             const vf xhat = gload(xp, c, m) * rstd;
             vf g = (gload(p.weight, c, m) * gload(gp, c, m) - xhat * cm) * rstd;
             if (drp) g = g + gload(drp, c, m);
-            gstore(dxp, c, g, m);
+            gstore(dxp, c, norm_dx<S>(g, s), m);
             if (drip) gstore(drip, c, g, m);
         }
     }
@@ -332,8 +371,23 @@ template <class T, bool REV> AUM_DEV void conv4_bwd_wave(const AumConvArgs& p, i
 // RMSNorm, vectorised: each lane owns 8 consecutive columns per 512-column chunk, rows cached in registers
 // (cols <= 512*NCH), one pass over memory.
 // ------------------------------------------------------------------------------------------------
-template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_fwd_vec(const AumNormArgs& p, int wg) {
+// norm_pre's scaled form for a lane's 8 consecutive columns from c0: with it the one place that states the rule of a zero factor (the
+// unscaled form stays written out in rmsnorm_fwd_vec, statement for statement as before the factor existed)
+template <class TX, class TR> AUM_DEV void norm_pre8_scaled(const TX* xp, const TR* rp, vi c0, int cols, float s, vf (&v)[8]) {
+    vf r[8];
+    row_load8(rp, c0, cols, r);
+    if (s == 0.f) {
+        AUM_UNROLL
+        for (int j = 0; j < 8; ++j) v[j] = r[j];
+    } else {
+        row_load8(xp, c0, cols, v);
+        AUM_UNROLL
+        for (int j = 0; j < 8; ++j) v[j] = vfma(splat(s), v[j], r[j]);
+    }
+}
+template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnorm_fwd_vec(const AumNormArgs& p, int wg, const S sc = S{}) {
     const int row = wg;
+    const float s = sc.at(row);
     const TX* xp = (const TX*)p.x + (int64_t)row * p.row_stride_x;
     const TR* rp = p.residual ? (const TR*)p.residual + (int64_t)row * p.row_stride_res : nullptr;
     TR* rop = p.residual_out ? (TR*)p.residual_out + (int64_t)row * p.row_stride_res_out : nullptr;
@@ -344,12 +398,16 @@ template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_fwd_vec(const AumNor
     AUM_UNROLL
     for (int c = 0; c < NCH; ++c) {
         const vi c0 = lane * 8 + c * 512;
-        row_load8(xp, c0, p.cols, v[c]);
-        if (rp) {
-            vf r[8];
-            row_load8(rp, c0, p.cols, r);
-            AUM_UNROLL
-            for (int j = 0; j < 8; ++j) v[c][j] = v[c][j] + r[j];
+        if constexpr (S::on) {
+            norm_pre8_scaled(xp, rp, c0, p.cols, s, v[c]);
+        } else {
+            row_load8(xp, c0, p.cols, v[c]);
+            if (rp) {
+                vf r[8];
+                row_load8(rp, c0, p.cols, r);
+                AUM_UNROLL
+                for (int j = 0; j < 8; ++j) v[c][j] = v[c][j] + r[j];
+            }
         }
         if (rop) row_store8(rop, c0, p.cols, v[c]);
         AUM_UNROLL
@@ -373,7 +431,7 @@ template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_fwd_vec(const AumNor
 // Round 6: NORM_BWD_NW waves form a workgroup and add their sums through LDS in wave order before one row of partials leaves -- 512 partial
 // rows instead of 4 096 for the caller to add (one launch of aum_sum_rows instead of two: 12 -> 4 us per layer).
 constexpr int NORM_BWD_NW = 8;
-template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_bwd_vec(const AumNormArgs& p, int wg, int n_waves, float* lds) {
+template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnorm_bwd_vec(const AumNormArgs& p, int wg, int n_waves, float* lds, const S sc = S{}) {
     // rows dealt evenly: 64 x 513 rows on 4 096 waves are 8 rows each and a ninth for the first 64 (ceil(rows / waves) = 9 rows each left
     // 448 of the 4 096 waves without any)
     const int base = p.rows / n_waves, rem = p.rows - base * n_waves;
@@ -397,6 +455,7 @@ template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_bwd_vec(const AumNor
         TX* dxp = (TX*)p.dx + (int64_t)row * p.row_stride_dx;
         TR* drip = p.dresidual_in ? (TR*)p.dresidual_in + (int64_t)row * p.row_stride_dres_in : nullptr;
         const float rstd = p.rstd_in[row];
+        const float s = sc.at(row);
         vf xh[NCH][8], wdy[NCH][8];
         vf c1 = splat(0.f);
         AUM_UNROLL
@@ -426,7 +485,14 @@ template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_bwd_vec(const AumNor
                 AUM_UNROLL
                 for (int j = 0; j < 8; ++j) g[j] = g[j] + dr[j];
             }
-            row_store8(dxp, c0, p.cols, g);
+            if constexpr (S::on) {
+                vf d[8];
+                AUM_UNROLL
+                for (int j = 0; j < 8; ++j) d[j] = norm_dx<S>(g[j], s);
+                row_store8(dxp, c0, p.cols, d);
+            } else {
+                row_store8(dxp, c0, p.cols, g);
+            }
             if (drip) row_store8(drip, c0, p.cols, g);
         }
     }

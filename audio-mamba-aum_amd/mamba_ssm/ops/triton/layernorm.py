@@ -10,26 +10,34 @@ import torch.nn.functional as F
 import aum_hip
 
 
-def layer_norm_ref(x, weight, bias, residual=None, eps=1e-6, prenorm=False, upcast=False):
+def _scaled(x, row_scale):
+    """x with sample b multiplied by row_scale[b] (stochastic depth on the mixer output, MM:90): the torch statement of the factor"""
+    return x if row_scale is None else x * row_scale.reshape((-1,) + (1,) * (x.dim() - 1)).to(x.dtype)
+
+
+def layer_norm_ref(x, weight, bias, residual=None, eps=1e-6, prenorm=False, upcast=False, row_scale=None):
     """Pure-PyTorch LayerNorm with optional residual add (contract of LN:19-32)."""
     dtype = x.dtype
     if upcast:
         x, weight = x.float(), weight.float()
         bias = bias.float() if bias is not None else None
         residual = residual.float() if residual is not None else None
+    x = _scaled(x, row_scale)
     if residual is not None:
         x = (x + residual).to(x.dtype)
     out = F.layer_norm(x.to(weight.dtype), x.shape[-1:], weight=weight, bias=bias, eps=eps).to(dtype)
     return (out, x) if prenorm else out
 
 
-def rms_norm_ref(x, weight, bias, residual=None, eps=1e-6, prenorm=False, upcast=False):
-    """Pure-PyTorch RMSNorm with optional residual add (contract of LN:35-48)."""
+def rms_norm_ref(x, weight, bias, residual=None, eps=1e-6, prenorm=False, upcast=False, row_scale=None):
+    """Pure-PyTorch RMSNorm with optional residual add (contract of LN:35-48).  row_scale: (batch,) factors on x, sample by sample, in
+    front of the add (what DropPath does to the mixer output in training); None: no factor."""
     dtype = x.dtype
     if upcast:
         x, weight = x.float(), weight.float()
         bias = bias.float() if bias is not None else None
         residual = residual.float() if residual is not None else None
+    x = _scaled(x, row_scale)
     if residual is not None:
         x = (x + residual).to(x.dtype)
     inv = torch.rsqrt(x.square().mean(dim=-1, keepdim=True) + eps)
@@ -42,13 +50,17 @@ def rms_norm_ref(x, weight, bias, residual=None, eps=1e-6, prenorm=False, upcast
 
 class LayerNormFn(torch.autograd.Function):
     """LN:380-461.  is_rms_norm=True is the HIP kernel pair; plain LayerNorm (never reached by AuM: rms_norm=True,
-    MM:206) is composed from torch ops so the public function keeps working."""
+    MM:206) is composed from torch ops so the public function keeps working.
+    row_scale (batch,) fp32: stochastic depth's per-sample factor on x, applied inside the kernels (aum_rmsnorm_drop_fwd / _bwd: a
+    dropped sample's x is not read, its dx is +0); it needs the residual and receives no gradient.  None: the unscaled pair."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual=None, eps=1e-6, prenorm=False, residual_in_fp32=False,
-                is_rms_norm=False):
+                is_rms_norm=False, row_scale=None):
         if not is_rms_norm or bias is not None:
             raise NotImplementedError("HIP fused add+norm implements RMSNorm without bias (what AuM uses, MM:77-97)")
+        if row_scale is not None and residual is None:
+            raise ValueError("row_scale multiplies x on its way into the residual add: it needs a residual")
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
         if x2.stride(-1) != 1:
@@ -60,8 +72,16 @@ class LayerNormFn(torch.autograd.Function):
             if r2.stride(-1) != 1:
                 r2 = r2.contiguous()
         res_dtype = r2.dtype if r2 is not None else (torch.float32 if residual_in_fp32 else None)
-        y, rstd, res_out = aum_hip.rmsnorm_fwd(x2, weight, r2, eps, residual_dtype=res_dtype)
-        ctx.save_for_backward(res_out, weight, rstd)
+        ctx.rows_per_scale = None
+        if row_scale is None:
+            y, rstd, res_out = aum_hip.rmsnorm_fwd(x2, weight, r2, eps, residual_dtype=res_dtype)
+            ctx.save_for_backward(res_out, weight, rstd)
+        else:
+            if x.dim() < 2 or row_scale.shape != shape[:1]:
+                raise ValueError(f"row_scale must be ({shape[0]},): one factor per sample of x {tuple(shape)}, not {tuple(row_scale.shape)}")
+            ctx.rows_per_scale = x2.shape[0] // shape[0]
+            y, rstd, res_out = aum_hip.rmsnorm_drop_fwd(x2, weight, r2, row_scale, ctx.rows_per_scale, eps)
+            ctx.save_for_backward(res_out, weight, rstd, row_scale)
         ctx.shape, ctx.has_residual, ctx.prenorm, ctx.x_dtype = shape, residual is not None, prenorm, x.dtype
         ctx.wparam = weight
         y = y.reshape(shape)
@@ -69,7 +89,7 @@ class LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, *args):
-        x, weight, rstd = ctx.saved_tensors
+        x, weight, rstd = ctx.saved_tensors[:3]
         dy2 = dy.reshape(-1, dy.shape[-1])
         if dy2.stride(-1) != 1:
             dy2 = dy2.contiguous()
@@ -81,16 +101,22 @@ class LayerNormFn(torch.autograd.Function):
             dres = dres.to(x.dtype)
         from mamba_ssm.ops.selective_scan_interface import _homed, grad_home
         home = grad_home(ctx.wparam)          # the weight gradient's place in a DistributedDataParallel bucket, if the parameter has one
-        dx, dw, dres_in = aum_hip.rmsnorm_bwd(dy2.to(ctx.x_dtype), x, weight, rstd, dres, ctx.has_residual,
-                                              x_dtype=ctx.x_dtype, dw_out=home)
+        if ctx.rows_per_scale is None:
+            dx, dw, dres_in = aum_hip.rmsnorm_bwd(dy2.to(ctx.x_dtype), x, weight, rstd, dres, ctx.has_residual,
+                                                  x_dtype=ctx.x_dtype, dw_out=home)
+        else:
+            dx, dw, dres_in = aum_hip.rmsnorm_drop_bwd(dy2.to(ctx.x_dtype), x, weight, rstd, ctx.saved_tensors[3], ctx.rows_per_scale, dres,
+                                                       x_dtype=ctx.x_dtype, dw_out=home)
         return (dx.reshape(ctx.shape), _homed(dw.to(weight.dtype), home), None,
-                dres_in.reshape(ctx.shape) if ctx.has_residual else None, None, None, None, None)
+                dres_in.reshape(ctx.shape) if ctx.has_residual else None, None, None, None, None, None)
 
 
 def layer_norm_fn(x, weight, bias, residual=None, eps=1e-6, prenorm=False, residual_in_fp32=False,
-                  is_rms_norm=False):
+                  is_rms_norm=False, row_scale=None):
     if is_rms_norm and bias is None:
-        return LayerNormFn.apply(x, weight, bias, residual, eps, prenorm, residual_in_fp32, True)
+        return LayerNormFn.apply(x, weight, bias, residual, eps, prenorm, residual_in_fp32, True, row_scale)
+    if row_scale is not None:
+        raise NotImplementedError("row_scale (stochastic depth inside the add + norm) exists for RMSNorm without bias, the HIP kernel pair")
     # plain LayerNorm / biased RMSNorm: off the AuM path; torch composition with the reference's return convention
     res_dtype = residual.dtype if residual is not None else (torch.float32 if residual_in_fp32 else x.dtype)
     pre = x.to(res_dtype) if residual is None else (x.float() + residual.float()).to(res_dtype)
@@ -99,8 +125,8 @@ def layer_norm_fn(x, weight, bias, residual=None, eps=1e-6, prenorm=False, resid
     return (out, pre) if prenorm else out
 
 
-def rms_norm_fn(x, weight, bias, residual=None, prenorm=False, residual_in_fp32=False, eps=1e-6):
-    return layer_norm_fn(x, weight, bias, residual, eps, prenorm, residual_in_fp32, True)
+def rms_norm_fn(x, weight, bias, residual=None, prenorm=False, residual_in_fp32=False, eps=1e-6, row_scale=None):
+    return layer_norm_fn(x, weight, bias, residual, eps, prenorm, residual_in_fp32, True, row_scale)
 
 
 class RMSNorm(torch.nn.Module):
@@ -116,6 +142,6 @@ class RMSNorm(torch.nn.Module):
     def reset_parameters(self):
         torch.nn.init.ones_(self.weight)
 
-    def forward(self, x, residual=None, prenorm=False, residual_in_fp32=False):
+    def forward(self, x, residual=None, prenorm=False, residual_in_fp32=False, row_scale=None):
         return rms_norm_fn(x, self.weight, self.bias, residual=residual, eps=self.eps, prenorm=prenorm,
-                           residual_in_fp32=residual_in_fp32)
+                           residual_in_fp32=residual_in_fp32, row_scale=row_scale)

@@ -48,7 +48,8 @@ extern "C" {
                                    (the EPIC-Sounds frontend); AUM_SCAN_DELTA_ACTIVATED (token-major scans) and, appended to AumXdtArgs, delta_bias /
                                    flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour; aum_xdt_tm_bwd also takes
                                    (ncols, rank) = (56, 24) and aum_gemm_wgrad k in {24, 56} (AuM-Small: shapes that were AUM_E_UNSUPPORTED);
-                                   aum_stream_park / AumParkArgs (streaming sessions to a blob and back in one launch) */
+                                   aum_stream_park / AumParkArgs (streaming sessions to a blob and back in one launch);
+                                   aum_rmsnorm_drop_fwd / _bwd / AumNormDropArgs (stochastic depth inside the add + RMSNorm) */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -219,6 +220,29 @@ int aum_rmsnorm_bwd_partials(int32_t rows);
 /* ABI 13: rows of dweight_partial that hold sums after aum_rmsnorm_bwd (<= aum_rmsnorm_bwd_partials(rows), which remains the size to
  * allocate): the vectorised kernels (cols <= 2048, no AUM_NORM_GENERIC) add eight waves' sums inside the workgroup, in wave order. */
 int aum_rmsnorm_bwd_partial_rows(int32_t rows, int32_t cols, uint32_t flags);
+
+/*
+ * Stochastic depth in the fused add + RMSNorm (timm DropPath on the x operand, MM:90 / MM:650): row r of x is multiplied by
+ * row_scale[r / rows_per_scale] -- 0 for a dropped sample, 1 / keep for a kept one -- on its way into the add.  The same kernels, limits
+ * and dweight_partial rows as aum_rmsnorm_fwd / _bwd (aum_rmsnorm_bwd_partials / _partial_rows); an all-ones row_scale gives their bits.
+ *   base                 the arguments of the unscaled pair, with these differences:
+ *   row_scale            (rows / rows_per_scale) fp32, one factor per sample; rows % rows_per_scale == 0 (else AUM_E_SHAPE)
+ *   forward              residual and residual_out are required.  residual_out = fma(s, x, residual) in fp32 (no 16-bit rounding of s or of
+ *                        s * x), rounded once to res_dtype; rstd and y follow from it.  s == 0: residual_out = residual and the row of x
+ *                        is NOT READ -- a NaN or inf in a dropped sample's x does not reach the residual stream
+ *   backward             dresidual_in is required and is always a buffer of its own: dresidual_in = g, dx = s * g rounded once to x_dtype
+ *                        (s == 0: +0), where g is what aum_rmsnorm_bwd writes as dx.  dweight_partial as in aum_rmsnorm_bwd
+ * AUM_E_NULL: row_scale, residual / residual_out (forward) or dresidual_in (backward) is NULL -- nothing is written.  reserved: 0 (anything else: AUM_E_UNSUPPORTED).
+ */
+typedef struct AumNormDropArgs {
+    AumNormArgs base;
+    const float* row_scale;
+    int32_t rows_per_scale;
+    int32_t reserved;
+} AumNormDropArgs;
+
+int aum_rmsnorm_drop_fwd(const AumNormDropArgs* args, void* stream);
+int aum_rmsnorm_drop_bwd(const AumNormDropArgs* args, void* stream);
 
 /*
  * Log-mel filterbank frontend (replaces torchaudio.compliance.kaldi.fbank + pad + normalise on the CPU DataLoader
