@@ -929,7 +929,7 @@ static void sb_split(const AumStreamBlockArgs& a, AumConvTmChunkVarArgs& c, AumX
 #else
 template <class T, bool BF16, bool PEEK> static int sb_launch(const AumStreamBlockArgs& a, aum_stream_t s) {
     return with_bool(a.rank <= 32, [&](auto one) {
-        return with_int<XDT_COLS, XDT_COLS_SMALL, XDT_COLS_TINY>(a.ncols, [&](auto nc) {
+        return with_int<XDT_FWD_WIDTHS>(a.ncols, [&](auto nc) {
             return AUM_LAUNCH(a.nseq, SB_NW * 64, s, (NoLds{}), (k_stream_block<T, BF16, one ? 1 : 2, nc, PEEK>), (0), a);
         });
     });

@@ -1,9 +1,12 @@
-// launch.h -- how the host code of aum_api.inc / aum_api_tm.inc starts a kernel and picks its instantiation.  Shared by the gfx950 build and
+// launch.h -- how the host code of aum_api.inc / aum_api_tm.inc and gemm.hip starts a kernel and picks its instantiation.  Shared by the gfx950 build and
 // the lane-array build (AUM_EMU), which has no kernels: there a launch is a loop of the kernel's workgroup body over the grid.
 //
 //   Lds<E, N>        the LDS array of a kernel, stated once: the __shared__ array of the k_* entry is E[L::n], and the lane-array build
 //                    allocates the same count for a launch -- a body that reaches past it is out of bounds in both builds.
 //   AUM_LAUNCH       the one launch: grid, workgroup size, stream, LDS, kernel, workgroup body, kernel arguments; ends in launch_status().
+//                    It does not clear the HIP error first, so an entry of aum_api.inc / aum_api_tm.inc reports whatever error is pending.
+//                    gemm.hip alone clears, in its launch() around AUM_LAUNCH: its entries have always promised that a stale error of an
+//                    earlier, unrelated launch is not reported as theirs.
 //   with_bool / with_int / by_dtype   runtime flags, small integers and the activation dtype into template parameters.
 #pragma once
 #include <type_traits>

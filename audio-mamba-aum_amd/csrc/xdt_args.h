@@ -3,6 +3,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <initializer_list>
+
 #include "../../include/aum_hip.h"
 
 #define XDT_COLS 80          // columns of x_dbl = dt_rank + 2 d_state the kernels are built for (AuM-Base: 48 + 32)
@@ -12,18 +15,27 @@
 #ifndef XDT_TOK_W
 #define XDT_TOK_W 16         // tokens per wave
 #endif
-#define XDT_WAVES_MIN 8      // waves (of XDT_TOK_W tokens) per workgroup: xdt_waves picks 8 .. 12 from the token count
-#define XDT_WAVES_MAX 12
 #define XDT_MAX_DIM 1536     // W_x passes through LDS in two K-halves of XDT_COLS rows: 80 x (768 x 2 + 16) bytes
+// THE lists of what the kernels are instantiated for, each stated here alone: the checks below walk them, the dispatches (gemm.hip,
+// aum_api_tm.inc) hand them to with_int, which refuses a value that is not listed
+#define XDT_FWD_WIDTHS XDT_COLS, XDT_COLS_SMALL, XDT_COLS_TINY   // ncols of k_xdt_tm_fwd and k_stream_block
+#define XDT_BWD_WIDTHS XDT_COLS, XDT_COLS_SMALL                  // ncols of k_xdt_tm_bwd
+#define XDT_WAVES 8, 9, 10, 11, 12                               // waves (of XDT_TOK_W tokens) per workgroup: xdt_waves picks one from the token count
+#define XDT_WAVES_MIN (std::min({XDT_WAVES}))
 
 namespace aumx {
+inline bool xdt_listed(int v, std::initializer_list<int> list) {
+    for (int x : list)
+        if (x == v) return true;
+    return false;
+}
 // THE shapes of the forward pass (k_xdt_tm_fwd, and k_stream_block around the same body); aum_hip.xdt_tm_supported states the same rule.
 //   ncols: a width the body is instantiated for.
 //   dim % 128: W_x passes through LDS in two K-halves walked in steps of 64 columns, so a half is a whole number of steps.  Everything
 //     else the body does with dim is implied: the conv_out prefetch ring runs over dim / 64 steps (an even count: it ends after two or
 //     after four steps of a round), a W_dt channel half is dim / 2 channels = dim / 64 pairs of 32, its bias is staged as dim / 8 float4.
 inline bool xdt_fwd_shape_ok(int ncols, int dim) {
-    return (ncols == XDT_COLS || ncols == XDT_COLS_SMALL || ncols == XDT_COLS_TINY) && dim > 0 && dim % 128 == 0 && dim <= XDT_MAX_DIM;
+    return xdt_listed(ncols, {XDT_FWD_WIDTHS}) && dim > 0 && dim % 128 == 0 && dim <= XDT_MAX_DIM;
 }
 inline int xdt_check(const AumXdtArgs* p) {
     if (!p || !p->u || !p->wx || !p->wdt || !p->x_dbl || !p->delta) return AUM_E_NULL;
@@ -47,19 +59,19 @@ inline int xdt_bwd_check(const AumXdtBwdArgs* p) {
         g.ldx < g.ncols || g.lddbc < g.ncols - g.rank)
         return AUM_E_SHAPE;
     if (g.dtype != AUM_BF16 && g.dtype != AUM_F16) return AUM_E_DTYPE;
-    if ((g.ncols != XDT_COLS && g.ncols != XDT_COLS_SMALL) || g.rank != g.ncols - 32 || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
+    if (!xdt_listed(g.ncols, {XDT_BWD_WIDTHS}) || g.rank != g.ncols - 32 || g.dim % 256 || g.dim > XDT_MAX_DIM) return AUM_E_UNSUPPORTED;
     if (g.ldd % 8 || g.ldu % 8 || g.ldwdt % 8 || g.ldwx % 8 || g.ldx % 8 || g.lddbc % 4) return AUM_E_UNSUPPORTED;
     if (((uintptr_t)g.ddelta | (uintptr_t)g.dbc | (uintptr_t)g.wdt_t | (uintptr_t)g.wx_t | (uintptr_t)g.du | (uintptr_t)g.dx_dbl) & 15u)
         return AUM_E_UNSUPPORTED;
     return AUM_OK;
 }
-// waves per workgroup for `ntok` tokens on `ncu` CUs (one workgroup per CU at a time): the count whose launch takes the fewest
+// waves per workgroup for `ntok` tokens on `ncu` CUs (one workgroup per CU at a time): the count of XDT_WAVES whose launch takes the fewest
 // wave-rounds, rounds x waves -- 2052 fragments on 256 CUs: 8 waves = 257 workgroups = 2 rounds (16), 9 waves = 228 = 1 round (9)
 inline int xdt_waves(int64_t ntok, int ncu) {
     const int64_t frags = (ntok + XDT_TOK_W - 1) / XDT_TOK_W;
-    int best = XDT_WAVES_MIN;
+    int best = 0;
     int64_t best_cost = -1;
-    for (int nw = XDT_WAVES_MIN; nw <= XDT_WAVES_MAX; ++nw) {
+    for (int nw : {XDT_WAVES}) {
         const int64_t wgs = (frags + nw - 1) / nw, cost = (wgs + ncu - 1) / ncu * nw;
         if (best_cost < 0 || cost < best_cost) {
             best = nw;

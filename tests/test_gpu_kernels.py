@@ -728,6 +728,27 @@ def test_xdt_tm_bwd(lib, case, dtype):
     KC.check_xdt_bwd(lib, "cuda", case[0], case[1], dtype, case[2])
 
 
+def xdt_ntok_for_waves(k):
+    """a token count at which both x/dt entries run k waves per workgroup (xdt_waves of csrc/xdt_args.h: the count of 8 .. 12 with the
+    fewest rounds x waves, the first of equals).  ncu * (k - 1) + 1 fragments of 16 tokens: k waves take one round (cost k), every smaller
+    count needs two (cost >= 16), every larger one costs more than k.  One fragment: 8.  The rule is restated here to hold the premise"""
+    ncu = aum_hip.cu_count()
+    ntok = 16 if k == 8 else 16 * (ncu * (k - 1) + 1)
+    ceil_div = lambda a, b: (a + b - 1) // b
+    cost = {nw: ceil_div(ceil_div(ceil_div(ntok, 16), nw), ncu) * nw for nw in range(8, 13)}
+    assert min(cost, key=lambda nw: (cost[nw], nw)) == k, (ncu, ntok, cost)
+    return ntok
+
+
+@pytest.mark.parametrize("waves", [8, 9, 10, 11, 12])
+def test_xdt_tm_every_wave_count(lib, waves):
+    """every waves-per-workgroup instantiation of aum_xdt_tm_fwd (dim 128, the smallest the check takes) and aum_xdt_tm_bwd (dim 256) is
+    reachable and right: a count missing from the dispatch is AUM_E_UNSUPPORTED at that token count alone"""
+    ntok = xdt_ntok_for_waves(waves)
+    KC.check_xdt(lib, "cuda", ntok, 128, 48, torch.bfloat16)
+    KC.check_xdt_bwd(lib, "cuda", ntok, 256, torch.bfloat16)
+
+
 def test_xdt_tm_bwd_headline_shape(lib):
     """aum_xdt_tm_bwd at the bench's own launch (64 x 513 tokens, d_inner 1536): dx_dbl and du of every token against fp32 products of
     the same operands (the three library calls it replaces: SSI:570-574, 587, 590), bitwise repeatable"""
