@@ -24,7 +24,8 @@ AUM_F32, AUM_BF16, AUM_F16 = 0, 1, 2
 SCAN_SOFTPLUS, SCAN_REVERSE, SCAN_GENERIC, SCAN_ROWPAIR, SCAN_ACCUMULATE = 1, 2, 4, 8, 16
 SCAN_DELTA_ACTIVATED = 32       # token-major scans: delta already holds softplus(raw + delta_bias) (xdt_tm_fwd(..., delta_softplus=True))
 XDT_DELTA_SOFTPLUS = 1
-CONV_SILU, CONV_REVERSE = 1, 2
+CONV_SILU, CONV_REVERSE, CONV_GENERIC = 1, 2, 4     # AUM_CONV_*: CONV_GENERIC forces the any-width kernel
+NORM_GENERIC = 2                                    # AUM_NORM_GENERIC: forces the any-cols kernel
 _DT = {torch.float32: AUM_F32, torch.bfloat16: AUM_BF16, torch.float16: AUM_F16}
 _ERR = {-1: "AUM_E_NULL", -2: "AUM_E_SHAPE", -3: "AUM_E_DTYPE", -4: "AUM_E_UNSUPPORTED", -5: "AUM_E_WORKSPACE",
         -6: "AUM_E_LAUNCH"}
@@ -457,10 +458,11 @@ def _unit(t, name):
 
 
 def _f32c(t):
-    if t is None:
-        return None
-    t = t.detach()
-    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()    # what .to().contiguous() return then
+    """a parameter as the kernels read it: fp32 contiguous.  One that already is comes back as it is -- the callers take its address and shape,
+    and a detach() is a microsecond per parameter and launch; anything else is converted off the autograd graph"""
+    if t is None or (t.dtype == torch.float32 and t.is_contiguous()):
+        return t
+    return t.detach().to(torch.float32).contiguous()
 
 
 def _bc3(t):
@@ -515,6 +517,67 @@ def scan_accumulates(u, dstate, lib=None):
     return lib.c.aum_selective_scan_ckpt_bytes(batch, dim, length, dstate) > 0
 
 
+def _scan_cm_rows(lib, u, delta, z, B, C, A, extra=()):
+    """THE operand rule of the channel-major scans (scan_fwd, scan_bwd): B / C as (batch, dstate, len) views (_bc3); every row operand on the
+    library's side with a unit time stride; u of a dtype the kernels have and delta, z, B, C of that dtype; A (dim, dstate), B / C (batch,
+    dstate, len); delta, z and every (name, tensor | None) of `extra` (scan_bwd: dout, out_pre) of u's dtype and (batch, dim, len) -- the
+    kernels are told ONE element type and ONE shape and index every one of them by it.  Returns (B, C, (batch, dim, len, dstate))."""
+    B, C = _bc3(B), _bc3(C)
+    dt, shape = u.dtype, u.shape
+    for n, t in (("u", u), ("delta", delta), ("z", z), ("B", B), ("C", C)):
+        _unit(t, n)
+        lib.check_tensor(t)
+    if dt not in _DT or delta.dtype != dt or B.dtype != dt or C.dtype != dt or (z is not None and z.dtype != dt):
+        raise RuntimeError("u, delta, z, B, C must share one dtype in {fp32, bf16, fp16}")
+    batch, dim, length = shape
+    dstate = A.shape[1]
+    if A.shape != (dim, dstate) or B.shape != (batch, dstate, length) or C.shape != B.shape:
+        raise RuntimeError("shape mismatch in selective scan arguments")
+    if delta.shape != shape or (z is not None and z.shape != shape):
+        extra = (("delta", delta), ("z", z)) + tuple(extra)            # the refusal below names the one
+    for n, t in extra:
+        if t is not None:
+            _unit(t, n)
+            lib.check_tensor(t)
+            if t.dtype != dt or t.shape != shape:
+                raise RuntimeError(f"{n}: expected u's dtype and shape ({dt}, {tuple(shape)}), got {t.dtype}, {tuple(t.shape)}")
+    return B, C, (batch, dim, length, dstate)
+
+
+def _check_scan_ck(lib, x_ck, x_lane, dims, bidir):
+    """the checkpoints as scan_ckpt / scan_lane_ckpt hand them out: on the library's side, fp32, contiguous, of exactly their shape"""
+    if x_ck is None and x_lane is None:         # the usual call: kept short
+        return
+    batch, dim, length, dstate = dims
+    for name, t, shape in (("x_ck", x_ck, (batch, dim, length // 512, dstate)), ("x_lane", x_lane, (batch, dim, 2 if bidir else 1, dstate, 64))):
+        if t is None:
+            continue
+        lib.check_tensor(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != shape:
+            raise RuntimeError(f"{name}: expected a contiguous fp32 {shape} tensor, got {tuple(t.shape)} {t.dtype}")
+
+
+def _scan_cm_flags(softplus, reverse, generic, rowpair, accumulate):
+    return ((SCAN_SOFTPLUS if softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_GENERIC if generic else 0)
+            | (SCAN_ROWPAIR if rowpair or debug.rowpair else 0) | (SCAN_ACCUMULATE if accumulate else 0)
+            | (debug.ablate << 16))   # kernel-ablation bits, set by tools/kbench.py only
+
+
+def _fill_scan_cm(a, u, delta, z, B, C, A, A_b, D, delta_bias, x_ck, x_lane, dims, flags):
+    """Writes what ScanFwdArgs and ScanBwdArgs share: the row operands' pointers and (batch, row) strides, the parameters (fp32 contiguous,
+    as the caller converted them), the checkpoints, sizes, dtype and flags."""
+    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
+    a.A, a.A_b, a.D, a.delta_bias = _ptr(A), _ptr(A_b), _ptr(D), _ptr(delta_bias)
+    a.x_ck, a.x_lane = _ptr(x_ck), _ptr(x_lane)
+    a.u_bs, a.u_ds = u.stride(0), u.stride(1)
+    a.delta_bs, a.delta_ds = delta.stride(0), delta.stride(1)
+    if z is not None:
+        a.z_bs, a.z_ds = z.stride(0), z.stride(1)
+    a.B_bs, a.B_ns, a.C_bs, a.C_ns = B.stride(0), B.stride(1), C.stride(0), C.stride(1)
+    a.batch, a.dim, a.len, a.dstate = dims
+    a.dtype, a.flags = _DT[u.dtype], flags
+
+
 def scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, reverse=False, A_b=None,
              want_out_pre=False, want_last_state=False, dmajor=False, generic=False, rowpair=False, x_ck=None,
              accumulate_into=None, x_lane=None, lib=None):
@@ -522,45 +585,20 @@ def scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
     x_ck: a scan_ckpt() tensor to fill.  accumulate_into: the `out` of the other direction's call (long rows only, see
     scan_accumulates): this call adds to it and returns it."""
     lib = lib or get()
-    B, C = _bc3(B), _bc3(C)
-    for n, t in (("u", u), ("delta", delta), ("z", z), ("B", B), ("C", C)):
-        _unit(t, n)
-        lib.check_tensor(t)
-    if u.dtype not in _DT or any(t is not None and t.dtype != u.dtype for t in (delta, z, B, C)):
-        raise RuntimeError("u, delta, z, B, C must share one dtype in {fp32, bf16, fp16}")
-    batch, dim, length = u.shape
-    dstate = A.shape[1]
-    if A.shape != (dim, dstate) or B.shape != (batch, dstate, length) or C.shape != B.shape:
-        raise RuntimeError("shape mismatch in selective scan arguments")
+    B, C, dims = _scan_cm_rows(lib, u, delta, z, B, C, A)
+    batch, dim, length, dstate = dims
+    _check_scan_ck(lib, x_ck, x_lane, dims, A_b is not None)
     A, A_b, D, delta_bias = _f32c(A), _f32c(A_b), _f32c(D), _f32c(delta_bias)
     out = accumulate_into if accumulate_into is not None else _alloc(batch, dim, length, u.dtype, u.device, dmajor)
-    assert out.shape == u.shape and out.dtype == u.dtype and out.stride(2) == 1
+    if out.shape != u.shape or out.dtype != u.dtype or out.stride(2) != 1:
+        raise RuntimeError(f"accumulate_into: expected u's dtype and shape with a unit time stride, got {out.dtype}, {tuple(out.shape)}, {out.stride()}")
     out_pre = _alloc(batch, dim, length, u.dtype, u.device, dmajor) if want_out_pre else None
     last = torch.empty((batch, dim, dstate), dtype=torch.float32, device=u.device) if want_last_state else None
     a = ScanFwdArgs()
-    a.u, a.delta, a.z, a.B, a.C = _ptr(u), _ptr(delta), _ptr(z), _ptr(B), _ptr(C)
-    a.A, a.A_b, a.D, a.delta_bias = _ptr(A), _ptr(A_b), _ptr(D), _ptr(delta_bias)
+    _fill_scan_cm(a, u, delta, z, B, C, A, A_b, D, delta_bias, x_ck, x_lane, dims,
+                  _scan_cm_flags(delta_softplus, reverse, generic, rowpair, accumulate_into is not None))
     a.out, a.out_pre, a.last_state = _ptr(out), _ptr(out_pre), _ptr(last)
-    if x_ck is not None:
-        assert x_ck.dtype == torch.float32 and x_ck.is_contiguous() and x_ck.shape == (batch, dim, length // 512, dstate)
-        lib.check_tensor(x_ck)
-        a.x_ck = _ptr(x_ck)
-    if x_lane is not None:
-        assert x_lane.dtype == torch.float32 and x_lane.is_contiguous() and x_lane.shape == (batch, dim, 2 if A_b is not None else 1, dstate, 64)
-        lib.check_tensor(x_lane)
-        a.x_lane = _ptr(x_lane)
-    a.u_bs, a.u_ds = u.stride(0), u.stride(1)
-    a.delta_bs, a.delta_ds = delta.stride(0), delta.stride(1)
-    if z is not None:
-        a.z_bs, a.z_ds = z.stride(0), z.stride(1)
-    a.B_bs, a.B_ns = B.stride(0), B.stride(1)
-    a.C_bs, a.C_ns = C.stride(0), C.stride(1)
     a.out_bs, a.out_ds = out.stride(0), out.stride(1)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = ((SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_GENERIC if generic else 0)
-               | (SCAN_ROWPAIR if rowpair or debug.rowpair else 0)
-               | (SCAN_ACCUMULATE if accumulate_into is not None else 0)
-               | (debug.ablate << 16))   # kernel-ablation bits, set by tools/kbench.py only
     _launch(lib.c.aum_selective_scan_fwd, a, u, lib, "scan_fwd_bidir" if A_b is not None else "scan_fwd",
             (batch, dim, length, dstate, u.element_size(), want_out_pre))
     return out, out_pre, last
@@ -573,15 +611,16 @@ def scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, delta_softplus=
     accumulate_into: the dict the other direction's call returned (long rows only, see scan_accumulates): this call adds its
     du, ddelta, dz, dB, dC, dD, ddelta_bias to those tensors and returns them, with its own dA."""
     lib = lib or get()
-    B, C = _bc3(B), _bc3(C)
-    for n, t in (("u", u), ("delta", delta), ("z", z), ("B", B), ("C", C), ("dout", dout), ("out_pre", out_pre)):
-        _unit(t, n)
-        lib.check_tensor(t)
-    batch, dim, length = u.shape
-    dstate = A.shape[1]
+    B, C, dims = _scan_cm_rows(lib, u, delta, z, B, C, A, (("dout", dout), ("out_pre", out_pre)))
+    batch, dim, length, dstate = dims
+    if dout is None or (z is not None and out_pre is None):
+        raise RuntimeError("dout is required, and out_pre (the forward's pre-gate sum) when z is given")
+    _check_scan_ck(lib, x_ck, x_lane, dims, A_b is not None)
     dev = u.device
     A, A_b, D, delta_bias = _f32c(A), _f32c(A_b), _f32c(D), _f32c(delta_bias)
     acc = accumulate_into
+    if acc and A_b is not None:
+        raise RuntimeError("accumulate_into: one direction per call adds to the other's tensors, not the fused pair (A_b)")
     du = acc["du"] if acc else _alloc(batch, dim, length, u.dtype, dev, dmajor)
     ddelta = acc["ddelta"] if acc else _alloc(batch, dim, length, u.dtype, dev, dmajor)
     dz = None
@@ -602,39 +641,21 @@ def scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out_pre, delta_softplus=
     dB = parts[4].view(batch, dstate, length) if not acc else None
     dC = parts[5].view(batch, dstate, length) if not acc else None
     if acc:      # the reduce stage of the call adds its partial sums to what is there
-        assert A_b is None
         dB, dC, dD, dbias = acc["dB"], acc["dC"], acc["dD"], acc["ddelta_bias"]
     ws_bytes = int(lib.c.aum_selective_scan_workspace_bytes(batch, dim, length, dstate, int(A_b is not None), 1))
     ws = torch.empty((max(ws_bytes, 4) // 4,), **f32) if ws_bytes else None
     a = ScanBwdArgs()
-    a.u, a.delta, a.z, a.B, a.C, a.dout, a.out_pre = map(_ptr, (u, delta, z, B, C, dout, out_pre))
-    a.A, a.A_b, a.D, a.delta_bias = _ptr(A), _ptr(A_b), _ptr(D), _ptr(delta_bias)
-    a.du, a.ddelta, a.dz = _ptr(du), _ptr(ddelta), _ptr(dz)
+    _fill_scan_cm(a, u, delta, z, B, C, A, A_b, D, delta_bias, x_ck, x_lane, dims, _scan_cm_flags(delta_softplus, reverse, generic, rowpair, acc))
+    a.dout, a.out_pre, a.du, a.ddelta, a.dz = map(_ptr, (dout, out_pre, du, ddelta, dz))
     a.dA, a.dA_b, a.dB, a.dC, a.dD, a.ddelta_bias = map(_ptr, (dA, dA_b, dB, dC, dD, dbias))
     a.workspace, a.workspace_bytes = _ptr(ws), ws_bytes
-    if x_ck is not None:
-        assert x_ck.dtype == torch.float32 and x_ck.is_contiguous() and x_ck.shape == (batch, dim, length // 512, dstate)
-        a.x_ck = _ptr(x_ck)
-    if x_lane is not None:
-        assert x_lane.dtype == torch.float32 and x_lane.is_contiguous() and x_lane.shape == (batch, dim, 2 if A_b is not None else 1, dstate, 64)
-        lib.check_tensor(x_lane)
-        a.x_lane = _ptr(x_lane)
-    a.u_bs, a.u_ds = u.stride(0), u.stride(1)
-    a.delta_bs, a.delta_ds = delta.stride(0), delta.stride(1)
     if z is not None:
-        a.z_bs, a.z_ds = z.stride(0), z.stride(1)
         a.out_bs, a.out_ds = out_pre.stride(0), out_pre.stride(1)
         a.dz_bs, a.dz_ds = dz.stride(0), dz.stride(1)
-    a.B_bs, a.B_ns, a.C_bs, a.C_ns = B.stride(0), B.stride(1), C.stride(0), C.stride(1)
     a.dout_bs, a.dout_ds = dout.stride(0), dout.stride(1)
     a.du_bs, a.du_ds = du.stride(0), du.stride(1)
     a.ddelta_bs, a.ddelta_ds = ddelta.stride(0), ddelta.stride(1)
     a.dB_bs, a.dB_ns, a.dC_bs, a.dC_ns = dB.stride(0), dB.stride(1), dC.stride(0), dC.stride(1)
-    a.batch, a.dim, a.len, a.dstate, a.dtype = batch, dim, length, dstate, _DT[u.dtype]
-    a.flags = ((SCAN_SOFTPLUS if delta_softplus else 0) | (SCAN_REVERSE if reverse else 0) | (SCAN_GENERIC if generic else 0)
-               | (SCAN_ROWPAIR if rowpair or debug.rowpair else 0)
-               | (SCAN_ACCUMULATE if acc else 0)
-               | (debug.ablate << 16))   # kernel-ablation bits, set by tools/kbench.py only
     _launch(lib.c.aum_selective_scan_bwd, a, u, lib, "scan_bwd_bidir" if A_b is not None else "scan_bwd",
             (batch, dim, length, dstate, u.element_size(), True))
     return dict(du=du, ddelta=ddelta, dA=dA, dA_b=dA_b, dB=dB, dC=dC, dD=dD, dz=dz, ddelta_bias=dbias)
@@ -1067,11 +1088,11 @@ def conv1d_update(x, conv_state, weight, bias=None, silu=True, lib=None):
     for t in (x, conv_state):
         lib.check_tensor(t)
     x = x.contiguous()
-    weight, bias = _f32c(weight.reshape(x.shape[1], -1)), _f32c(bias)
+    weight, bias = _conv_weights(weight, bias, x.shape[1], False)
     out = torch.empty_like(x)
     a = ConvUpdateArgs()
     a.x, a.conv_state, a.weight, a.bias, a.out = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(out)
-    a.batch, a.dim, a.width, a.dtype, a.flags = x.shape[0], x.shape[1], conv_state.shape[2], _DT[x.dtype], (CONV_SILU if silu else 0)
+    a.batch, a.dim, a.width, a.dtype, a.flags = x.shape[0], x.shape[1], conv_state.shape[2], _DT[x.dtype], _conv_flags(silu)
     _launch(lib.c.aum_causal_conv1d_update, a, x, lib, "conv1d_update")
     return out
 
@@ -1094,7 +1115,7 @@ def state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplu
     a = StateUpdateArgs()
     a.state, a.x, a.dt, a.z, a.B, a.C = _ptr(state), _ptr(x), _ptr(dt), _ptr(z), _ptr(B), _ptr(C)
     a.A, a.D, a.dt_bias, a.out = _ptr(A), _ptr(D), _ptr(dt_bias), _ptr(out)
-    a.batch, a.dim, a.dstate, a.dtype, a.flags = x.shape[0], x.shape[1], state.shape[2], _DT[dty], (SCAN_SOFTPLUS if dt_softplus else 0)
+    a.batch, a.dim, a.dstate, a.dtype, a.flags = x.shape[0], x.shape[1], state.shape[2], _DT[dty], _scan_flags(dt_softplus, False, False)
     _launch(lib.c.aum_selective_state_update, a, x, lib, "state_update")
     return out
 
@@ -1141,7 +1162,7 @@ def _conv_chunk_operands(a, name, lib, x, conv_state, weight, bias, silu, out):
     y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
     if y.dtype != x.dtype or y.shape != x.shape:
         raise RuntimeError(f"{name}: out must have x's shape and dtype")
-    held = _fill_conv(a, x, conv_state, weight, bias, y, CONV_SILU if silu else 0)
+    held = _fill_conv(a, x, conv_state, weight, bias, y, _conv_flags(silu))
     if a.width != conv_state.shape[2]:
         raise RuntimeError(f"{name}: weight (dim, width) and conv_state (rows, dim, width) disagree on the width")
     for t in held:
@@ -1153,7 +1174,7 @@ def _fill_conv(a, x, conv_state, weight, bias, y, flags):
     """The conv counterpart of _fill_scan: x / y pointers and strides (batch strides and batch / len, or total for packed rows), the cache,
     weight (dim, width) and bias as fp32 16-byte aligned tensors, dim / width / dtype / flags.  Returns the converted weight and bias."""
     dim = x.shape[-1]
-    held = weight, bias = _al16(_f32c(weight.reshape(dim, -1))), _al16(_f32c(bias))
+    held = weight, bias = _conv_weights(weight, bias, dim, True)
     a.x, a.conv_state, a.weight, a.bias, a.y = _ptr(x), _ptr(conv_state), _ptr(weight), _ptr(bias), _ptr(y)
     if x.dim() == 2:
         a.x_ts, a.y_ts, a.total = _tm2(x, "x", dim), _tm2(y, "out", dim), x.shape[0]
@@ -1518,7 +1539,7 @@ def conv1d_tm_peeks_bwd_parts(dy, x, weight, bias=None, silu=True, seq_map=None,
     a = ConvTmPeeksBwdArgs()
     a.x, a.dy, a.weight, a.bias, a.dx, a.workspace, a.cu_seqlens = _ptr(x), _ptr(dy), _ptr(weight), _ptr(bias), _ptr(dx), _ptr(ws), _ptr(seq_map.cu)
     a.workspace_bytes, a.x_ts, a.dy_ts, a.dx_ts = nbytes, _tm2(x, "x", dim), _tm2(dy, "dy", dim), dim
-    a.total, a.nseq, a.dim, a.width, a.dtype, a.flags, a.peek_every = total, nseq, dim, width, _DT[x.dtype], (CONV_SILU if silu else 0), peek_every
+    a.total, a.nseq, a.dim, a.width, a.dtype, a.flags, a.peek_every = total, nseq, dim, width, _DT[x.dtype], _conv_flags(silu), peek_every
     _launch(lib.c.aum_conv1d_tm_peeks_bwd, a, x, lib, "conv1d_tm_peeks_bwd", (nseq, dim, total, x.element_size()))
     n_w = nseq * dim * width
     return dx, (ws[:n_w].view(nseq, dim, width), ws[n_w:].view(nseq, dim))
@@ -2328,7 +2349,42 @@ def conv1d_tm_supported(x, width):
 
 def _al16(t):
     """the kernels read weights with 16-byte accesses: a parameter that is a misaligned view gets its own storage"""
-    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+    return t if t is None or t.data_ptr() % 16 == 0 else t.detach().clone()
+
+
+def _conv_weights(weight, bias, dim, align16):
+    """weight (dim, width) / (dim, 1, width) and bias (dim) | None as the conv kernels read them: fp32 contiguous, and (align16: the
+    token-major kernels) at 16-byte addresses.  The caller holds them until its launch is enqueued."""
+    weight, bias = _f32c(weight.reshape(dim, -1)), _f32c(bias)
+    return (_al16(weight), _al16(bias)) if align16 else (weight, bias)
+
+
+def _conv_flags(silu, reverse=False, generic=False):
+    return (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0) | (CONV_GENERIC if generic else 0)
+
+
+def _check_conv_dy(lib, dy, x):
+    lib.check_tensor(dy)
+    if dy.dtype != x.dtype or dy.shape != x.shape:
+        raise RuntimeError(f"dy: expected x's dtype and shape ({x.dtype}, {tuple(x.shape)}), got {dy.dtype}, {tuple(dy.shape)}")
+
+
+def _fill_conv_tm(a, x, weight, bias, silu, reverse):
+    """what the forward and backward of the token-major conv share in ConvTmArgs: x, the converted weight and bias, sizes, dtype, flags"""
+    batch, length, dim = x.shape
+    a.x, a.weight, a.bias = _ptr(x), _ptr(weight), _ptr(bias)
+    a.x_bs, a.x_ts = _tm3(x, "x", dim)
+    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
+    a.flags = _conv_flags(silu, reverse)
+
+
+def _fill_conv_cm(a, x, weight, bias, silu, reverse, generic):
+    """the same for the channel-major conv's ConvArgs"""
+    batch, dim, length = x.shape
+    a.x, a.weight, a.bias = _ptr(x), _ptr(weight), _ptr(bias)
+    a.x_bs, a.x_ds = x.stride(0), x.stride(1)
+    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
+    a.flags = _conv_flags(silu, reverse, generic)
 
 
 def conv1d_tm_fwd(x, weight, bias=None, silu=True, reverse=False, lib=None):
@@ -2337,15 +2393,12 @@ def conv1d_tm_fwd(x, weight, bias=None, silu=True, reverse=False, lib=None):
     lib = lib or get()
     lib.check_tensor(x)
     batch, length, dim = x.shape
-    weight = _al16(_f32c(weight.reshape(dim, -1)))
-    bias = _al16(_f32c(bias))
+    weight, bias = _conv_weights(weight, bias, dim, True)
     y = torch.empty((batch, length, dim), dtype=x.dtype, device=x.device)
     a = ConvTmArgs()
-    a.x, a.weight, a.bias, a.y = _ptr(x), _ptr(weight), _ptr(bias), _ptr(y)
-    a.x_bs, a.x_ts = _tm3(x, "x", dim)
+    _fill_conv_tm(a, x, weight, bias, silu, reverse)
+    a.y = _ptr(y)
     a.y_bs, a.y_ts = _tm3(y, "y", dim)
-    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
-    a.flags = (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0)
     _launch(lib.c.aum_conv1d_tm_fwd, a, x, lib, "conv_tm_fwd", (batch, dim, length, x.element_size()))
     return y
 
@@ -2387,23 +2440,20 @@ def conv1d_tm_bwd(x, weight, bias, dy, silu=True, reverse=False, dx_out=None, li
     partials=True: -> (dx, dw_part (nparts, dim, width), db_part (nparts, dim) | None) for a caller that sums them with other sets."""
     lib = lib or get()
     lib.check_tensor(x)
+    _check_conv_dy(lib, dy, x)
     batch, length, dim = x.shape
-    weight = _al16(_f32c(weight.reshape(dim, -1)))
-    bias = _al16(_f32c(bias))
-    width = weight.shape[1]
+    weight, bias = _conv_weights(weight, bias, dim, True)
     dy = dy if dy.stride(2) == 1 else dy.contiguous()
     dx = dx_out if dx_out is not None else torch.empty((batch, length, dim), dtype=x.dtype, device=x.device)
     nparts = int(lib.c.aum_conv1d_tm_nparts(batch, length))
     f32 = dict(dtype=torch.float32, device=x.device)
-    dw_part = torch.empty((nparts, dim, width), **f32)
+    dw_part = torch.empty((nparts, dim, weight.shape[1]), **f32)
     db_part = torch.empty((nparts, dim), **f32) if bias is not None else None
     a = ConvTmArgs()
-    a.x, a.dy, a.weight, a.bias, a.dx, a.dw_part, a.db_part = map(_ptr, (x, dy, weight, bias, dx, dw_part, db_part))
-    a.x_bs, a.x_ts = _tm3(x, "x", dim)
+    _fill_conv_tm(a, x, weight, bias, silu, reverse)
+    a.dy, a.dx, a.dw_part, a.db_part = _ptr(dy), _ptr(dx), _ptr(dw_part), _ptr(db_part)
     a.dy_bs, a.dy_ts = _tm3(dy, "dy", dim)
     a.dx_bs, a.dx_ts = _tm3(dx, "dx", dim)
-    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, width, _DT[x.dtype]
-    a.flags = (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0)
     _launch(lib.c.aum_conv1d_tm_bwd, a, x, lib, "conv_tm_bwd", (batch, dim, length, x.element_size()))
     if partials:
         return dx, dw_part, db_part
@@ -2419,14 +2469,11 @@ def conv1d_fwd(x, weight, bias=None, silu=True, reverse=False, dmajor=False, gen
     _unit(x, "x")
     lib.check_tensor(x)
     batch, dim, length = x.shape
-    weight = _f32c(weight.reshape(dim, -1))
-    bias = _f32c(bias)
+    weight, bias = _conv_weights(weight, bias, dim, False)
     y = _alloc(batch, dim, length, x.dtype, x.device, dmajor)
     a = ConvArgs()
-    a.x, a.weight, a.bias, a.y = _ptr(x), _ptr(weight), _ptr(bias), _ptr(y)
-    a.x_bs, a.x_ds, a.y_bs, a.y_ds = x.stride(0), x.stride(1), y.stride(0), y.stride(1)
-    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
-    a.flags = (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0) | (4 if generic else 0)
+    _fill_conv_cm(a, x, weight, bias, silu, reverse, generic)
+    a.y, a.y_bs, a.y_ds = _ptr(y), y.stride(0), y.stride(1)
     _launch(lib.c.aum_causal_conv1d_fwd, a, x, lib, "conv_fwd", (batch, dim, length, x.element_size()))
     return y
 
@@ -2438,10 +2485,9 @@ def conv1d_bwd(x, weight, bias, dy, silu=True, reverse=False, dx_out=None, gener
     _unit(x, "x")
     _unit(dy, "dy")
     lib.check_tensor(x)
-    lib.check_tensor(dy)
+    _check_conv_dy(lib, dy, x)
     batch, dim, length = x.shape
-    weight = _f32c(weight.reshape(dim, -1))
-    bias = _f32c(bias)
+    weight, bias = _conv_weights(weight, bias, dim, False)
     dx = dx_out if dx_out is not None else torch.empty((batch, dim, length), dtype=x.dtype, device=x.device)
     _unit(dx, "dx")
     # dweight / dbias accumulate (one fp32 atomic per wave and tap): one zero fill for both
@@ -2449,31 +2495,39 @@ def conv1d_bwd(x, weight, bias, dy, silu=True, reverse=False, dx_out=None, gener
     dw = zb[:weight.numel()].view_as(weight)
     db = zb[weight.numel():] if bias is not None else None
     a = ConvArgs()
-    a.x, a.dy, a.weight, a.bias, a.dx, a.dweight, a.dbias = map(_ptr, (x, dy, weight, bias, dx, dw, db))
-    a.x_bs, a.x_ds, a.dy_bs, a.dy_ds = x.stride(0), x.stride(1), dy.stride(0), dy.stride(1)
-    a.dx_bs, a.dx_ds = dx.stride(0), dx.stride(1)
-    a.batch, a.dim, a.len, a.width, a.dtype = batch, dim, length, weight.shape[1], _DT[x.dtype]
-    a.flags = (CONV_SILU if silu else 0) | (CONV_REVERSE if reverse else 0) | (4 if generic else 0)
+    _fill_conv_cm(a, x, weight, bias, silu, reverse, generic)
+    a.dy, a.dx, a.dweight, a.dbias = _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db)
+    a.dy_bs, a.dy_ds, a.dx_bs, a.dx_ds = dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1)
     _launch(lib.c.aum_causal_conv1d_bwd, a, x, lib, "conv_bwd", (batch, dim, length, x.element_size()))
     return dx, dw, db
 
 
-def rmsnorm_fwd(x, weight, residual=None, eps=1e-5, residual_dtype=None, generic=False, lib=None):
-    """_layer_norm_fwd(is_rms_norm=True) (LN:123-177).  x: (rows, cols).  Returns (y, rstd, residual_out) where
-    residual_out is x itself when no new residual tensor is needed (LN:176-177)."""
-    lib = lib or get()
-    lib.check_tensor(x)
+def _norm_refuse(name, t, rows, cols, dt=None):
+    raise RuntimeError(f"{name}: expected ({rows}, {cols}){f' {dt}' if dt else ''}, unit column stride, got {tuple(t.shape)} {t.dtype}, {t.stride()}")
+
+
+def _norm_fwd(lib, entry, name, x, weight, residual, residual_dtype, eps, generic, scale=None):
+    """The forward of the add + RMSNorm pair, plain (aum_rmsnorm_fwd, NormArgs) or with scale = (row_scale, rows_per_scale) behind stochastic
+    depth (aum_rmsnorm_drop_fwd, NormDropArgs with the same NormArgs as its base).  -> (y, rstd, res_out | None)"""
     rows, cols = x.shape
-    assert x.stride(1) == 1
+    lib.check_tensor(x)
+    if x.stride(1) != 1:
+        _norm_refuse("x", x, rows, cols)
     if residual is not None:
+        lib.check_tensor(residual)
+        if residual.shape != x.shape or residual.stride(1) != 1:
+            _norm_refuse("residual", residual, rows, cols)
         residual_dtype = residual.dtype
-        assert residual.stride(1) == 1 and residual.shape == x.shape
+    need_res_out = residual is not None or (residual_dtype is not None and residual_dtype != x.dtype)
+    d = a = NormArgs()
+    if scale is not None:               # the same NormArgs as the base of a NormDropArgs; the drop pair always has a residual
+        d = NormDropArgs()
+        a, row_scale = d.base, _row_scale(*scale, rows, x, lib)
+        d.row_scale, d.rows_per_scale = _ptr(row_scale), scale[1]
     weight = _f32c(weight)
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    need_res_out = residual is not None or (residual_dtype is not None and residual_dtype != x.dtype)
     res_out = torch.empty((rows, cols), dtype=residual_dtype, device=x.device) if need_res_out else None
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    a = NormArgs()
     a.x, a.residual, a.weight, a.y, a.residual_out, a.rstd_out = map(_ptr, (x, residual, weight, y, res_out, rstd))
     a.row_stride_x, a.row_stride_y = x.stride(0), y.stride(0)
     if residual is not None:
@@ -2483,8 +2537,59 @@ def rmsnorm_fwd(x, weight, residual=None, eps=1e-5, residual_dtype=None, generic
     a.eps, a.rows, a.cols = eps, rows, cols
     a.x_dtype = a.y_dtype = _DT[x.dtype]
     a.res_dtype = _DT[residual_dtype] if need_res_out else _DT[x.dtype]
-    a.flags = 2 if generic else 0
-    _launch(lib.c.aum_rmsnorm_fwd, a, x, lib, "rmsnorm_fwd", (rows, cols, x.element_size()))
+    a.flags = NORM_GENERIC if generic else 0
+    _launch(entry, d, x, lib, name, (rows, cols, x.element_size()))
+    return y, rstd, res_out
+
+
+def _norm_bwd(lib, entry, name, dy, x_saved, weight, rstd, dresidual, own_dres_in, x_dtype, generic, dw_out, scale=None):
+    """The backward of the pair, plain or scaled as _norm_fwd.  own_dres_in: dresidual_in is a buffer of its own.  -> (dx, dweight, dres_in | None)"""
+    rows, cols = x_saved.shape
+    x_dtype = x_dtype or x_saved.dtype
+    lib.check_tensor(dy)
+    if dy.shape != x_saved.shape or dy.stride(1) != 1 or dy.dtype != x_dtype:
+        _norm_refuse("dy", dy, rows, cols, x_dtype)
+    lib.check_tensor(x_saved)
+    if x_saved.stride(1) != 1:
+        _norm_refuse("x_saved", x_saved, rows, cols)
+    if dresidual is not None:
+        lib.check_tensor(dresidual)
+        if dresidual.shape != x_saved.shape or dresidual.stride(1) != 1 or dresidual.dtype != x_saved.dtype:
+            _norm_refuse("dresidual", dresidual, rows, cols, x_saved.dtype)
+    lib.check_tensor(rstd)
+    if rstd.shape != (rows,) or rstd.dtype != torch.float32 or not rstd.is_contiguous():
+        raise RuntimeError(f"rstd: expected the contiguous fp32 ({rows},) tensor of the forward, got {tuple(rstd.shape)} {rstd.dtype}, strides {rstd.stride()}")
+    d = a = NormArgs()
+    if scale is not None:
+        d = NormDropArgs()
+        a, row_scale = d.base, _row_scale(*scale, rows, dy, lib)
+        d.row_scale, d.rows_per_scale = _ptr(row_scale), scale[1]
+    weight = _f32c(weight)
+    dx = torch.empty((rows, cols), dtype=x_dtype, device=dy.device)
+    dres_in = torch.empty_like(x_saved, memory_format=torch.contiguous_format) if own_dres_in else None
+    flags = NORM_GENERIC if generic else 0
+    # the rows the kernel leaves sums in, and the rows to allocate (include/aum_hip.h: aum_rmsnorm_bwd_partial_rows)
+    dwp = torch.empty((int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, flags)), cols), dtype=torch.float32, device=dy.device)
+    a.x, a.dy, a.dresidual_out, a.weight, a.rstd_in = map(_ptr, (x_saved, dy, dresidual, weight, rstd))
+    a.dx, a.dresidual_in, a.dweight_partial = _ptr(dx), _ptr(dres_in), _ptr(dwp)
+    a.row_stride_x, a.row_stride_dy, a.row_stride_dx = x_saved.stride(0), dy.stride(0), dx.stride(0)
+    if dresidual is not None:
+        a.row_stride_dres_out = dresidual.stride(0)
+    if dres_in is not None:
+        a.row_stride_dres_in = dres_in.stride(0)
+    a.rows, a.cols = rows, cols
+    a.x_dtype = a.y_dtype = _DT[x_dtype]
+    a.res_dtype = _DT[x_saved.dtype]
+    a.flags = flags
+    _launch(entry, d, dy, lib, name, (rows, cols, dy.element_size()))
+    return dx, sum_rows(dwp, lib, out=dw_out), dres_in
+
+
+def rmsnorm_fwd(x, weight, residual=None, eps=1e-5, residual_dtype=None, generic=False, lib=None):
+    """_layer_norm_fwd(is_rms_norm=True) (LN:123-177).  x: (rows, cols).  Returns (y, rstd, residual_out) where
+    residual_out is x itself when no new residual tensor is needed (LN:176-177)."""
+    lib = lib or get()
+    y, rstd, res_out = _norm_fwd(lib, lib.c.aum_rmsnorm_fwd, "rmsnorm_fwd", x, weight, residual, residual_dtype, eps, generic)
     return y, rstd, (res_out if res_out is not None else x)
 
 
@@ -2492,33 +2597,9 @@ def rmsnorm_bwd(dy, x_saved, weight, rstd, dresidual=None, has_residual=False, x
     """_layer_norm_bwd(is_rms_norm=True) (LN:293-377).  x_saved = residual_out of the forward.  Returns
     (dx [x_dtype], dweight fp32, dresidual_in | None)."""
     lib = lib or get()
-    lib.check_tensor(dy)
-    rows, cols = x_saved.shape
-    x_dtype = x_dtype or x_saved.dtype
-    assert dy.stride(1) == 1 and x_saved.stride(1) == 1 and dy.dtype == x_dtype
-    weight = _f32c(weight)
-    dx = torch.empty((rows, cols), dtype=x_dtype, device=dy.device)
-    dres_in = torch.empty_like(x_saved) if (has_residual and x_dtype != x_saved.dtype) else None
-    n_part = int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, 2 if generic else 0))     # rows the kernel leaves sums in
-    dwp = torch.empty((n_part, cols), dtype=torch.float32, device=dy.device)
-    a = NormArgs()
-    a.x, a.dy, a.dresidual_out, a.weight, a.rstd_in = map(_ptr, (x_saved, dy, dresidual, weight, rstd))
-    a.dx, a.dresidual_in, a.dweight_partial = _ptr(dx), _ptr(dres_in), _ptr(dwp)
-    a.row_stride_x, a.row_stride_dy, a.row_stride_dx = x_saved.stride(0), dy.stride(0), dx.stride(0)
-    if dresidual is not None:
-        assert dresidual.dtype == x_saved.dtype and dresidual.stride(1) == 1
-        a.row_stride_dres_out = dresidual.stride(0)
-    if dres_in is not None:
-        a.row_stride_dres_in = dres_in.stride(0)
-    a.rows, a.cols = rows, cols
-    a.x_dtype = a.y_dtype = _DT[x_dtype]
-    a.res_dtype = _DT[x_saved.dtype]
-    a.flags = 2 if generic else 0
-    _launch(lib.c.aum_rmsnorm_bwd, a, dy, lib, "rmsnorm_bwd", (rows, cols, dy.element_size()))
-    dw = sum_rows(dwp, lib, out=dw_out)
-    if has_residual and dres_in is None:
-        dres_in = dx
-    return dx, dw, dres_in
+    own = has_residual and (x_dtype or x_saved.dtype) != x_saved.dtype
+    dx, dw, dres_in = _norm_bwd(lib, lib.c.aum_rmsnorm_bwd, "rmsnorm_bwd", dy, x_saved, weight, rstd, dresidual, own, x_dtype, generic, dw_out)
+    return dx, dw, (dx if has_residual and not own else dres_in)
 
 
 def _row_scale(row_scale, rows_per_scale, rows, like, lib):
@@ -2537,27 +2618,9 @@ def rmsnorm_drop_fwd(x, weight, residual, row_scale, rows_per_scale, eps=1e-5, g
     s = row_scale[row // rows_per_scale]; a sample with s == 0 has its x rows not read.  x, residual: (rows, cols); the residual is
     required.  Returns (y, rstd, residual_out), residual_out a new tensor in the residual's dtype."""
     lib = lib or get()
-    lib.check_tensor(x)
-    rows, cols = x.shape
     if residual is None:
         raise ValueError("rmsnorm_drop_fwd: the factor multiplies x on its way into the add: a residual is required")
-    assert x.stride(1) == 1 and residual.stride(1) == 1 and residual.shape == x.shape
-    row_scale = _row_scale(row_scale, rows_per_scale, rows, x, lib)
-    weight = _f32c(weight)
-    y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    res_out = torch.empty((rows, cols), dtype=residual.dtype, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    d = NormDropArgs()
-    a = d.base
-    a.x, a.residual, a.weight, a.y, a.residual_out, a.rstd_out = map(_ptr, (x, residual, weight, y, res_out, rstd))
-    a.row_stride_x, a.row_stride_y, a.row_stride_res, a.row_stride_res_out = x.stride(0), y.stride(0), residual.stride(0), res_out.stride(0)
-    a.eps, a.rows, a.cols = eps, rows, cols
-    a.x_dtype = a.y_dtype = _DT[x.dtype]
-    a.res_dtype = _DT[residual.dtype]
-    a.flags = 2 if generic else 0
-    d.row_scale, d.rows_per_scale = _ptr(row_scale), rows_per_scale
-    _launch(lib.c.aum_rmsnorm_drop_fwd, d, x, lib, "rmsnorm_drop_fwd", (rows, cols, x.element_size()))
-    return y, rstd, res_out
+    return _norm_fwd(lib, lib.c.aum_rmsnorm_drop_fwd, "rmsnorm_drop_fwd", x, weight, residual, None, eps, generic, (row_scale, rows_per_scale))
 
 
 def rmsnorm_drop_bwd(dy, x_saved, weight, rstd, row_scale, rows_per_scale, dresidual=None, x_dtype=None, generic=False, lib=None,
@@ -2565,31 +2628,8 @@ def rmsnorm_drop_bwd(dy, x_saved, weight, rstd, row_scale, rows_per_scale, dresi
     """rmsnorm_bwd of rmsnorm_drop_fwd (aum_rmsnorm_drop_bwd).  x_saved = residual_out of the forward.  Returns (dx [x_dtype] = s * g
     rounded once, +0 where s == 0; dweight fp32 (into dw_out where given); dresidual_in = g in x_saved's dtype) -- always two buffers."""
     lib = lib or get()
-    lib.check_tensor(dy)
-    rows, cols = x_saved.shape
-    x_dtype = x_dtype or x_saved.dtype
-    assert dy.stride(1) == 1 and x_saved.stride(1) == 1 and dy.dtype == x_dtype
-    row_scale = _row_scale(row_scale, rows_per_scale, rows, dy, lib)
-    weight = _f32c(weight)
-    dx = torch.empty((rows, cols), dtype=x_dtype, device=dy.device)
-    dres_in = torch.empty_like(x_saved, memory_format=torch.contiguous_format)
-    n_part = int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, 2 if generic else 0))     # rows the kernel leaves sums in
-    dwp = torch.empty((n_part, cols), dtype=torch.float32, device=dy.device)
-    d = NormDropArgs()
-    a = d.base
-    a.x, a.dy, a.dresidual_out, a.weight, a.rstd_in = map(_ptr, (x_saved, dy, dresidual, weight, rstd))
-    a.dx, a.dresidual_in, a.dweight_partial = _ptr(dx), _ptr(dres_in), _ptr(dwp)
-    a.row_stride_x, a.row_stride_dy, a.row_stride_dx, a.row_stride_dres_in = x_saved.stride(0), dy.stride(0), dx.stride(0), dres_in.stride(0)
-    if dresidual is not None:
-        assert dresidual.dtype == x_saved.dtype and dresidual.stride(1) == 1
-        a.row_stride_dres_out = dresidual.stride(0)
-    a.rows, a.cols = rows, cols
-    a.x_dtype = a.y_dtype = _DT[x_dtype]
-    a.res_dtype = _DT[x_saved.dtype]
-    a.flags = 2 if generic else 0
-    d.row_scale, d.rows_per_scale = _ptr(row_scale), rows_per_scale
-    _launch(lib.c.aum_rmsnorm_drop_bwd, d, dy, lib, "rmsnorm_drop_bwd", (rows, cols, dy.element_size()))
-    return dx, sum_rows(dwp, lib, out=dw_out), dres_in
+    return _norm_bwd(lib, lib.c.aum_rmsnorm_drop_bwd, "rmsnorm_drop_bwd", dy, x_saved, weight, rstd, dresidual, True, x_dtype, generic, dw_out,
+                     (row_scale, rows_per_scale))
 
 
 FBANK_AUG = 8     # columns of the per-clip augmentation table (include/aum_hip.h AUM_FBANK_AUG)
@@ -2856,16 +2896,23 @@ def _pad_cols8(w):
     return w.contiguous() if pad == 0 else torch.nn.functional.pad(w, (0, pad)).contiguous()
 
 
+def _proj_operands(lib, names, *tensors):
+    """the operands of the channel-major projections: on the library's side, contiguous, of the first one's 16-bit dtype"""
+    for i, t in enumerate(tensors):
+        lib.check_tensor(t)
+        if not t.is_contiguous() or t.dtype != tensors[0].dtype:
+            raise RuntimeError(f"{names[i]}: expected a contiguous {tensors[0].dtype} tensor, got {t.dtype}, {tuple(t.shape)}, strides {t.stride()}")
+
+
 def proj_fwd(conv_out2d, w_x, w_dt, dstate, lib=None):
     """conv_out2d [dim][ntok], w_x [dt_rank+2*dstate][dim], w_dt [dim][dt_rank] (all one 16-bit dtype, contiguous)
     -> x_dbl [dt_rank+2*dstate][ntok] (rows dt | B | C) and delta [dim][ntok] = w_dt @ dt   (SSI:467-468)."""
     lib = lib or get()
-    for t in (conv_out2d, w_x, w_dt):
-        lib.check_tensor(t)
-        assert t.is_contiguous() and t.dtype == conv_out2d.dtype
+    _proj_operands(lib, ("conv_out2d", "w_x", "w_dt"), conv_out2d, w_x, w_dt)
     dim, ntok = conv_out2d.shape
     rt, dt_rank = w_x.shape[0], w_dt.shape[1]
-    assert w_x.shape == (dt_rank + 2 * dstate, dim) and w_dt.shape == (dim, dt_rank)
+    if w_x.shape != (dt_rank + 2 * dstate, dim) or w_dt.shape != (dim, dt_rank):
+        raise RuntimeError(f"proj_fwd: expected w_x ({dt_rank + 2 * dstate}, {dim}) and w_dt ({dim}, {dt_rank}), got {tuple(w_x.shape)}, {tuple(w_dt.shape)}")
     w_dt = _pad_cols8(w_dt)
     x_dbl = torch.empty((rt, ntok), dtype=conv_out2d.dtype, device=conv_out2d.device)
     delta = torch.empty_like(conv_out2d)
@@ -2881,15 +2928,16 @@ def proj_bwd_data(ddelta2d, w_dt_t, w_x_t, dB, dC, dconv2d, length, lib=None):
     """ddelta2d [dim][ntok], w_dt_t = W_dt^T [dt_rank][dim], w_x_t = W_x^T [dim][rt], dB/dC fp32 (batch, dstate, len)
     -> dx_dbl [rt][ntok]; dconv2d [dim][ntok] += W_x^T dx_dbl in place   (SSI:570-574, 587, 590)."""
     lib = lib or get()
-    for t in (ddelta2d, w_dt_t, w_x_t, dconv2d):
-        lib.check_tensor(t)
-        assert t.is_contiguous() and t.dtype == ddelta2d.dtype
-    lib.check_tensor(dB), lib.check_tensor(dC)
-    assert dB.dtype == torch.float32 and dC.dtype == torch.float32 and dB.stride(2) == 1 and dC.stride(2) == 1
+    _proj_operands(lib, ("ddelta2d", "w_dt_t", "w_x_t", "dconv2d"), ddelta2d, w_dt_t, w_x_t, dconv2d)
     dim, ntok = ddelta2d.shape
     dt_rank, rt = w_dt_t.shape[0], w_x_t.shape[1]
     dstate = dB.shape[1]
-    assert rt == dt_rank + 2 * dstate and dB.shape[0] * length == ntok and dB.shape[2] == length
+    for name, t in (("dB", dB), ("dC", dC)):
+        lib.check_tensor(t)
+        if t.dtype != torch.float32 or t.stride(2) != 1:
+            raise RuntimeError(f"{name}: expected fp32 (batch, dstate, len) with a unit time stride, got {t.dtype}, strides {t.stride()}")
+    if rt != dt_rank + 2 * dstate or dB.shape[0] * length != ntok or dB.shape[2] != length:
+        raise RuntimeError(f"proj_bwd_data: w_x_t: expected {dt_rank + 2 * dstate} columns, got {rt}; dB: expected ({ntok // length}, {dstate}, {length}), got {tuple(dB.shape)}")
     w_x_t = _pad_cols8(w_x_t)
     dx_dbl = torch.empty((rt, ntok), dtype=ddelta2d.dtype, device=ddelta2d.device)
     a = ProjArgs()
@@ -2905,8 +2953,9 @@ def proj_bwd_data(ddelta2d, w_dt_t, w_x_t, dB, dC, dconv2d, length, lib=None):
 def proj_bwd_weight(x2d, y2d, transpose_out, lib=None):
     """sum_t x[e][t] * y[r][t] -> [dim][nrows] (or [nrows][dim] with transpose_out) fp32   (SSI:586, 589)."""
     lib = lib or get()
-    lib.check_tensor(x2d), lib.check_tensor(y2d)
-    assert x2d.is_contiguous() and y2d.stride(1) == 1 and y2d.stride(0) == x2d.shape[1] and x2d.dtype == y2d.dtype
+    _proj_operands(lib, ("x2d", "y2d"), x2d, y2d)
+    if y2d.shape[1] != x2d.shape[1]:
+        raise RuntimeError(f"y2d: expected (nrows, {x2d.shape[1]}) as x2d's tokens, got {tuple(y2d.shape)}")
     dim, ntok = x2d.shape
     nrows = y2d.shape[0]
     nsplit = debug.proj_splits or int(lib.c.aum_proj_bwd_weight_splits(dim, ntok))

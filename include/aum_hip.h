@@ -199,7 +199,8 @@ int aum_causal_conv1d_bwd(const AumConvArgs* args, void* stream);
  * backward: dy (rows, cols) in y_dtype; dresidual_out in res_dtype or NULL; x = the saved residual_out (or the input x
  * when no residual stream exists) in res_dtype; writes dx in x_dtype, dresidual_in (res_dtype, optional, receives the same
  * values as dx), and per-workgroup partial sums dweight_partial (n_partials, cols) fp32 that the caller reduces
- * (layernorm.py:333-372 does the same); n_partials = aum_rmsnorm_bwd_partials(rows).
+ * (layernorm.py:333-372 does the same); n_partials = aum_rmsnorm_bwd_partial_rows(rows, cols, flags): the rows the caller allocates, and
+ * every one of them holds a sum after the call.
  */
 typedef struct AumNormArgs {
     const void *x, *residual, *dy, *dresidual_out;
@@ -216,9 +217,12 @@ typedef struct AumNormArgs {
 
 int aum_rmsnorm_fwd(const AumNormArgs* args, void* stream);
 int aum_rmsnorm_bwd(const AumNormArgs* args, void* stream);
+/* the grid-side bound: the waves the backward runs, min(rows, 4096), each with its own partial sum.  NOT the size of dweight_partial. */
 int aum_rmsnorm_bwd_partials(int32_t rows);
-/* ABI 13: rows of dweight_partial that hold sums after aum_rmsnorm_bwd (<= aum_rmsnorm_bwd_partials(rows), which remains the size to
- * allocate): the vectorised kernels (cols <= 2048, no AUM_NORM_GENERIC) add eight waves' sums inside the workgroup, in wave order. */
+/* ABI 13: THE number of dweight_partial rows the caller must allocate for aum_rmsnorm_bwd / aum_rmsnorm_drop_bwd with these rows, cols and
+ * flags; the kernels write exactly these rows and nothing behind them.  Derived from the bound above: one row per wave for the any-cols
+ * kernels (cols > 2048 or AUM_NORM_GENERIC), ceil(aum_rmsnorm_bwd_partials(rows) / 8) for the vectorised kernels, which add eight waves'
+ * sums inside the workgroup, in wave order. */
 int aum_rmsnorm_bwd_partial_rows(int32_t rows, int32_t cols, uint32_t flags);
 
 /*

@@ -10,7 +10,8 @@ byte counts are in the `*_bytes` fields next to them.  What a call returns is re
 exception's type and full message.  Nothing recorded depends on the address space: host and device runs give the same record.
 
 The fixture is written by `python tests/binding_pin_checks.py --record` (lane-array library); `--record NAME ...` rewrites only the
-named cases.
+named cases.  The row families (channel-major scan, per-token updates, conv, add + RMSNorm, channel-major projections: ROW_CASES) are held
+the same way against tests/golden/binding_args_rows.json, written by `--record-rows [NAME ...]`.
 
 SEG_MIN_LEN / RANGE_MIN_LEN: the shortest rows the library takes with segments=2 / range_len=8, found on the lane-array build: 1 for
 both.  aum_scan_tm_seg_fwd / _seg_bwd / aum_scan_tm_fwd_state round a range up to the 8-step block and clamp every range to the row, so
@@ -534,6 +535,449 @@ _add_refusals()
 GROUPS = sorted({n.split("/")[0] for n in CASES})
 
 
+# ==== the row families -> tests/golden/binding_args_rows.json: channel-major scan, per-token updates, conv (token- and channel-major), ====
+# ==== add + RMSNorm, channel-major projections.  Recorded on the lane-array build, which has every one of their entry points          ====
+ROWS_FIXTURE = os.path.join(os.path.dirname(FIXTURE), "binding_args_rows.json")
+ROW_CASES = {}
+# calls whose operand is of another type, shape or device than the kernel is told: host tensors only (every such operand is LARGER than
+# what the kernel reads, so the lane-array run stays in bounds where a binding launches it); a device run could fault, so there is none
+ROW_HOST_ONLY = set()
+DT16 = dict(DT, f16=torch.float16)
+
+
+def row_case(name, host_only=False):
+    def put(fn):
+        assert name not in ROW_CASES, name
+        ROW_CASES[name] = fn
+        if host_only:
+            ROW_HOST_ONLY.add(name)
+        return fn
+    return put
+
+
+def _randn(device, dt, *shape, seed=0, scale=1.0):
+    return (torch.randn(*shape, generator=torch.Generator().manual_seed(7000 + seed)) * scale).to(DT16[dt]).to(device)
+
+
+# ---- channel-major scan: u / z the halves of one (batch, 2 dim, len) xz tensor, B / C (batch, 1, 16, len) or (batch, 16, len) ---------------
+def scan_cm_ops(device, dt, dim, length, z=True, D=True, bias=True, bc4=False, bidir=False, seed=0, batch=2):
+    xz = _randn(device, dt, batch, 2 * dim, length, seed=seed)
+    bc = _randn(device, dt, 2, batch, 1, 16, length, seed=seed + 100)
+    g = torch.Generator().manual_seed(7500 + seed)
+    A = (-torch.exp(torch.randn(dim, 16, generator=g) * 0.5)).to(device)
+    o = Ops(dt=dt, dim=dim, batch=batch, length=length, xz=xz, u=xz[:, :dim], z=xz[:, dim:] if z else None,
+            delta=_randn(device, dt, batch, dim, length, seed=seed + 200, scale=0.3).abs(), bc=bc,
+            B=bc[0] if bc4 else bc[0, :, 0], C=bc[1] if bc4 else bc[1, :, 0], A=A, A_b=(A * 1.25).contiguous() if bidir else None,
+            D=torch.randn(dim, generator=g).to(device) if D else None, bias=(torch.randn(dim, generator=g) * 0.5).to(device) if bias else None)
+    o["named"] = {"xz": xz, "delta": o.delta, "bc": bc, "A": A, "A_b": o.A_b, "D": o.D, "bias": o.bias}
+    return o
+
+
+# (tag, dtype, dim, len, z, D, delta_bias, delta_softplus, the rest): len 1 / 9 plain rows, 513 the lane checkpoint, 1025 the chunk checkpoint
+SCAN_CM_CONFIGS = (
+    ("plain_f32", "f32", 64, 1, True, True, True, True, dict(bc4=True)),
+    ("bare_bf16", "bf16", 128, 9, False, False, False, False, {}),
+    ("reverse_f32", "f32", 128, 9, True, True, False, True, dict(reverse=True)),
+    ("bidir_bf16", "bf16", 64, 9, True, True, True, True, dict(bidir=True, bc4=True)),
+    ("dmajor", "bf16", 64, 9, True, False, True, False, dict(dmajor=True)),
+    ("generic", "f32", 64, 9, True, True, True, True, dict(generic=True)),
+    ("rowpair", "bf16", 128, 9, True, True, True, True, dict(rowpair=True)),
+    ("last_state_dz_view", "f32", 64, 9, True, True, True, True, dict(want_last_state=True, dz_view=True)),
+    ("lane_bidir", "bf16", 64, 513, True, True, True, True, dict(bidir=True, lane=True)),
+    ("lane_f32", "f32", 64, 513, False, True, True, True, dict(lane=True)),
+    ("chunk_ck", "bf16", 64, 1025, True, True, True, True, dict(ck=True)),
+    ("chunk_acc", "bf16", 64, 1025, True, True, True, True, dict(ck=True, acc=True)),
+    ("chunk_f32", "f32", 128, 1025, False, False, True, False, {}),
+    ("len1_bf16", "bf16", 128, 1, True, True, True, True, {}))
+
+
+def _add_scan_cm(i, cfg):
+    tag, dt, dim, length, z, D, bias, sp, x = cfg
+    bidir, lane, ck, acc = x.get("bidir", False), x.get("lane", False), x.get("ck", False), x.get("acc", False)
+    flags = {k: x[k] for k in ("dmajor", "generic", "rowpair") if k in x}
+
+    def ops(device, lib):
+        o = scan_cm_ops(device, dt, dim, length, z, D, bias, x.get("bc4", False), bidir, seed=i)
+        o["x_ck"] = aum_hip.scan_ckpt(o.u, 16, lib=lib) if ck else None
+        o["x_lane"] = aum_hip.scan_lane_ckpt(o.u, 16, bidir, lib=lib) if lane else None
+        assert (o.x_ck is not None) == ck and (o.x_lane is not None) == lane
+        o["A_rev"] = (o.A * 1.25).contiguous() if acc else None    # the reverse direction's A of a two-launch Fo-Bi pair
+        o.named.update(x_ck=o.x_ck, x_lane=o.x_lane, A_rev=o.A_rev)
+        return o
+
+    def fwd(o, lib, reverse, A, x_ck, **kw):
+        return aum_hip.scan_fwd(o.u, o.delta, A, o.B, o.C, o.D, o.z, o.bias, sp, reverse, o.A_b, want_out_pre=z, x_ck=x_ck, x_lane=o.x_lane,
+                                lib=lib, **flags, **kw)
+
+    def bwd(o, lib, reverse, A, x_ck, dout, out_pre, **kw):
+        return aum_hip.scan_bwd(o.u, o.delta, A, o.B, o.C, o.D, o.z, o.bias, dout, out_pre, sp, reverse, o.A_b, x_ck=x_ck, x_lane=o.x_lane,
+                                lib=lib, **flags, **kw)
+
+    @row_case(f"scan_fwd/{tag}")
+    def _(lib, device):
+        o = ops(device, lib)
+        if not acc:
+            return o.named, lambda: fwd(o, lib, x.get("reverse", False), o.A, o.x_ck, want_last_state=x.get("want_last_state", False))
+        o.named["out"] = fwd(o, lib, False, o.A, None)[0]           # the other direction's output: the reverse launch adds to it
+        return o.named, lambda: fwd(o, lib, True, o.A_rev, o.x_ck, accumulate_into=o.named["out"])
+
+    @row_case(f"scan_bwd/{tag}")
+    def _(lib, device):
+        o = ops(device, lib)
+        dout = rand_like(o.delta, i)
+        o.named["dout"] = dout
+        if not acc:
+            o.named["out_pre"] = out_pre = fwd(o, lib, x.get("reverse", False), o.A, o.x_ck)[1]
+            kw = {}
+            if x.get("dz_view"):                                    # dz as the second half of a d(xz) tensor
+                o.named["dxz"] = torch.empty_like(o.xz)
+                kw["dz_out"] = o.named["dxz"][:, dim:]
+            return o.named, lambda: bwd(o, lib, x.get("reverse", False), o.A, o.x_ck, dout, out_pre, **kw)
+        g = bwd(o, lib, False, o.A, None, dout, fwd(o, lib, False, o.A, None)[1])
+        o.named["out_pre"] = out_pre = fwd(o, lib, True, o.A_rev, o.x_ck)[1]
+        o.named.update({f"acc.{k}": v for k, v in g.items()})
+        return o.named, lambda: bwd(o, lib, True, o.A_rev, o.x_ck, dout, out_pre, accumulate_into=g)
+
+
+for _i, _cfg in enumerate(SCAN_CM_CONFIGS):
+    _add_scan_cm(_i, _cfg)
+
+
+def _add_scan_ckpt_shapes():
+    """what scan_ckpt / scan_lane_ckpt / scan_accumulates hand out per length: a tensor's shape is recorded, None (or False) leaves no entry"""
+    for length in (1, 9, 513, 1025):
+        def run(lib, device, length=length):
+            u = torch.empty((2, 64, length), dtype=torch.bfloat16, device=device)
+            return {}, lambda: {"scan_ckpt": aum_hip.scan_ckpt(u, 16, lib=lib), "scan_lane_ckpt": aum_hip.scan_lane_ckpt(u, 16, False, lib=lib),
+                                "scan_lane_ckpt_bidir": aum_hip.scan_lane_ckpt(u, 16, True, lib=lib),
+                                "scan_accumulates": torch.empty((), device=device) if aum_hip.scan_accumulates(u, 16, lib=lib) else None}
+        ROW_CASES[f"scan_ckpt/len{length}"] = run
+
+
+_add_scan_ckpt_shapes()
+
+
+# ---- one token: state_update / conv1d_update ------------------------------------------------------------------------------------------------
+def _add_updates():
+    # (dtype, z, D, dt_bias, dt_softplus)
+    for i, (dt, z, D, bias, sp) in enumerate((("f32", True, True, True, True), ("bf16", False, False, False, False), ("bf16", True, True, True, True),
+                                              ("f32", False, True, False, True))):
+        @row_case(f"state_update/{_tag((dt, z, D, bias, sp))}")
+        def _(lib, device, i=i, dt=dt, z=z, D=D, bias=bias, sp=sp):
+            named = {"state": pool(device, 2, 64, 16, i), "x": _randn(device, dt, 2, 64, seed=i), "dt": _randn(device, dt, 2, 64, seed=i + 1, scale=0.3),
+                     "A": -torch.rand(64, 16).to(device), "B": _randn(device, dt, 2, 16, seed=i + 2), "C": _randn(device, dt, 2, 16, seed=i + 3),
+                     "D": torch.ones(64, device=device) if D else None, "z": _randn(device, dt, 2, 64, seed=i + 4) if z else None,
+                     "dt_bias": torch.zeros(64, device=device) if bias else None}
+            n = Ops(named)
+            return named, lambda: aum_hip.state_update(n.state, n.x, n.dt, n.A, n.B, n.C, n.D, n.z, n.dt_bias, sp, lib=lib)
+
+    for i, (dt, bias, silu) in enumerate((("f32", True, True), ("bf16", False, False), ("bf16", True, True))):
+        @row_case(f"conv1d_update/{_tag((dt, bias, silu))}")
+        def _(lib, device, i=i, dt=dt, bias=bias, silu=silu):
+            named = {"x": _randn(device, dt, 2, 64, seed=i), "conv_state": pool(device, 2, 64, 4, i), "w": _randn(device, "f32", 64, 1, 4, seed=i + 1),
+                     "b": _randn(device, "f32", 64, seed=i + 2) if bias else None}
+            n = Ops(named)
+            return named, lambda: aum_hip.conv1d_update(n.x, n.conv_state, n.w, n.b, silu, lib=lib)
+
+
+_add_updates()
+
+
+# ---- conv: token-major (batch, len, dim) and channel-major (batch, dim, len), x the first half of an xz tensor or a tensor of its own ----------
+# (dtype, dim, len, width, bias, silu, reverse, the rest)
+CONV_ROW_CONFIGS = (("f32", 64, 1, 4, True, True, False, dict(own=True)), ("bf16", 128, 3, 4, False, False, False, {}),
+                    ("bf16", 64, 9, 4, True, True, True, {}), ("f32", 128, 9, 2, True, False, False, {}),
+                    ("bf16", 128, 9, 4, True, True, False, dict(dx_view=True, partials=True, own=True)), ("f32", 64, 3, 4, False, True, True, {}),
+                    ("bf16", 64, 9, 4, True, False, False, dict(dmajor=True, generic=True, dx_view=True)))
+
+
+def _conv_row_ops(device, cfg, i, tm):
+    dt, dim, T, width, bias, silu, rev, x = cfg
+    o = conv_ops(device, dt, dim, (2, T), bias, silu, seed=50 + i, width=width)
+    if not tm:                          # the same numbers as (batch, 2 dim, len)
+        o["xz"] = o.named["xz"] = o.xz.transpose(1, 2).contiguous()
+        o["x"] = o.xz[:, :dim]
+    if x.get("own"):
+        o["x"] = o.named["x"] = o.x.contiguous()
+    o.named["dy"] = o["dy"] = rand_like(o.x.contiguous(), i)
+    o["dx_out"] = None
+    if x.get("dx_view"):                # dx as the first half of a d(xz) tensor
+        o.named["dxz"] = torch.empty_like(o.xz)
+        o["dx_out"] = o.named["dxz"][..., :dim] if tm else o.named["dxz"][:, :dim]
+    return o
+
+
+def _add_conv_rows(i, cfg):
+    dt, dim, T, width, bias, silu, rev, x = cfg
+    tag = _tag(cfg[:7]) + "".join(f"_{k}" for k in x)
+    gen = {"generic": True} if x.get("generic") else {}
+
+    if not x.get("dmajor"):
+        @row_case(f"conv1d_tm_fwd/{tag}")
+        def _(lib, device):
+            o = _conv_row_ops(device, cfg, i, True)
+            return o.named, lambda: aum_hip.conv1d_tm_fwd(o.x, o.w, o.b, silu, rev, lib=lib)
+
+        @row_case(f"conv1d_tm_bwd/{tag}")
+        def _(lib, device):
+            o = _conv_row_ops(device, cfg, i, True)
+            return o.named, lambda: aum_hip.conv1d_tm_bwd(o.x, o.w, o.b, o.dy, silu, rev, dx_out=o.dx_out, lib=lib, partials=x.get("partials", False))
+
+    @row_case(f"conv1d_fwd/{tag}")
+    def _(lib, device):
+        o = _conv_row_ops(device, cfg, i, False)
+        return o.named, lambda: aum_hip.conv1d_fwd(o.x, o.w, o.b, silu, rev, dmajor=x.get("dmajor", False), lib=lib, **gen)
+
+    @row_case(f"conv1d_bwd/{tag}")
+    def _(lib, device):
+        o = _conv_row_ops(device, cfg, i, False)
+        return o.named, lambda: aum_hip.conv1d_bwd(o.x, o.w, o.b, o.dy, silu, rev, dx_out=o.dx_out, lib=lib, **gen)
+
+
+for _i, _cfg in enumerate(CONV_ROW_CONFIGS):
+    _add_conv_rows(_i, _cfg)
+
+
+def _prefill_ops(device, dt, T, width=4, pool_width=4, seed=0):
+    o = conv_ops(device, dt, 64, (2, T), seed=60 + seed, width=width)
+    o.named["conv_state"] = o["cs"] = pool(device, 2, 64, pool_width, seed)
+    return o
+
+
+for _dt, _T in (("bf16", 1), ("f32", 3), ("bf16", 9)):          # T < width: the window shifts; T >= width: it is replaced
+    def _prefill(lib, device, dt=_dt, T=_T):
+        o = _prefill_ops(device, dt, T, seed=T)
+        return o.named, lambda: aum_hip.conv1d_tm_prefill(o.x, o.cs, o.w, o.b, o.silu, lib=lib)
+    ROW_CASES[f"conv1d_tm_prefill/{_dt}_T{_T}"] = _prefill
+
+
+# ---- add + RMSNorm --------------------------------------------------------------------------------------------------------------------------
+# (rows, cols, x dtype, residual: None | its dtype, the rest): residual_f32 = residual_dtype=torch.float32 without a residual; x_view = x the
+# first half of wider rows; bwd: dres = dresidual given, dw_out given; drop = (rows_per_scale,) -> the drop pair instead of the plain one
+NORM_CONFIGS = (
+    (1, 64, "f32", None, {}),
+    (9, 768, "bf16", "bf16", dict(dres=True)),
+    (18, 64, "bf16", "f32", dict(dw_out=True)),
+    (9, 64, "bf16", None, dict(residual_f32=True)),
+    (18, 768, "f32", "f32", dict(x_view=True, dres=True)),
+    (9, 4096, "bf16", "bf16", {}),                          # the non-vector kernels: one partial row per grid row
+    (9, 64, "bf16", "bf16", dict(generic=True)),
+    (1, 768, "bf16", "f32", {}),
+    (9, 64, "bf16", "bf16", dict(drop=1, dres=True)),
+    (18, 768, "bf16", "f32", dict(drop=9, dw_out=True)),
+    (9, 64, "f32", "f32", dict(drop=9, x_view=True)),
+    (18, 4096, "bf16", "bf16", dict(drop=1, generic=True)))
+ROW_SCALES = (0.0, 1.0, 1.0 / 0.9)
+
+
+def _add_norm(i, cfg):
+    rows, cols, dt, res, x = cfg
+    drop, generic = x.get("drop"), x.get("generic", False)
+    tag = _tag(cfg[:3]) + f"_{res}" + "".join(f"_{k}" if v is True else f"_{k}{v}" for k, v in x.items())
+
+    def ops(device):
+        wide = _randn(device, dt, rows, 2 * cols if x.get("x_view") else cols, seed=70 + i)
+        named = {"x": wide, "w": _randn(device, "f32", cols, seed=71 + i), "residual": None if res is None else _randn(device, res, rows, cols, seed=72 + i)}
+        o = Ops(x=wide[:, :cols], w=named["w"], residual=named["residual"], named=named)
+        if drop:
+            o["scale"] = named["row_scale"] = torch.tensor([ROW_SCALES[(k + i) % 3] for k in range(rows // drop)], dtype=torch.float32, device=device)
+        return o
+
+    def fwd(o, lib):
+        if drop:
+            return aum_hip.rmsnorm_drop_fwd(o.x, o.w, o.residual, o.scale, drop, 1e-5, generic=generic, lib=lib)
+        return aum_hip.rmsnorm_fwd(o.x, o.w, o.residual, 1e-5, residual_dtype=torch.float32 if x.get("residual_f32") else None, generic=generic, lib=lib)
+
+    pair = "rmsnorm_drop" if drop else "rmsnorm"
+
+    @row_case(f"{pair}_fwd/{tag}")
+    def _(lib, device):
+        o = ops(device)
+        return o.named, lambda: fwd(o, lib)
+
+    @row_case(f"{pair}_bwd/{tag}")
+    def _(lib, device):
+        o = ops(device)
+        _, rstd, saved = fwd(o, lib)
+        o.named.update(x_saved=saved, rstd=rstd, dy=rand_like(o.x.contiguous(), i))
+        dres = o.named["dresidual"] = rand_like(saved, i + 1) if x.get("dres") else None
+        dw_out = o.named["dw_out"] = torch.empty(cols, device=device) if x.get("dw_out") else None
+        kw = dict(x_dtype=DT[dt], generic=generic, lib=lib, dw_out=dw_out)
+
+        def call():                     # the partial rows handed to sum_rows are part of the record: their count is the kernel's
+            seen, orig = {}, aum_hip.sum_rows
+            aum_hip.sum_rows = lambda t, *a, **k: (seen.update(dweight_partial=t), orig(t, *a, **k))[1]
+            try:
+                if drop:
+                    ret = aum_hip.rmsnorm_drop_bwd(o.named["dy"], saved, o.w, rstd, o.scale, drop, dres, **kw)
+                else:
+                    ret = aum_hip.rmsnorm_bwd(o.named["dy"], saved, o.w, rstd, dres, res is not None, **kw)
+            finally:
+                aum_hip.sum_rows = orig
+            return dict(seen, dx=ret[0], dw=ret[1], dres_in=ret[2])
+        return o.named, call
+
+
+for _i, _cfg in enumerate(NORM_CONFIGS):
+    _add_norm(_i, _cfg)
+
+
+# ---- channel-major projections ----------------------------------------------------------------------------------------------------------------
+# (dtype, ntok, dt_rank, transpose_out): dstate 16, dim 64.  dt_rank 48 and 24 do NOT reach _pad_cols8's padding branch (48, 24, 80 and 56
+# columns are multiples of 8); dt_rank 20 does (w_dt 20 -> 24, w_x_t 52 -> 56).  aum_proj_bwd_weight_splits gives 1 split up to 128 tokens,
+# 2 at 256
+PROJ_CONFIGS = (("bf16", 64, 48, False), ("f16", 128, 24, True), ("bf16", 128, 24, False), ("f16", 64, 48, True), ("bf16", 256, 20, True))
+
+
+def _add_proj(i, cfg):
+    dt, ntok, rank, tr = cfg
+    tag, rt = _tag(cfg), rank + 32
+
+    @row_case(f"proj_fwd/{tag}")
+    def _(lib, device):
+        named = {"act": _randn(device, dt, 64, ntok, seed=80 + i), "w_x": _randn(device, dt, rt, 64, seed=81 + i), "w_dt": _randn(device, dt, 64, rank, seed=82 + i)}
+        return named, lambda: aum_hip.proj_fwd(named["act"], named["w_x"], named["w_dt"], 16, lib=lib)
+
+    @row_case(f"proj_bwd_data/{tag}")
+    def _(lib, device):
+        named = {"ddelta": _randn(device, dt, 64, ntok, seed=83 + i), "w_dt_t": _randn(device, dt, rank, 64, seed=84 + i),
+                 "w_x_t": _randn(device, dt, 64, rt, seed=85 + i), "dB": _randn(device, "f32", 2, 16, ntok // 2, seed=86 + i),
+                 "dC": _randn(device, "f32", 2, 16, ntok // 2, seed=87 + i), "dconv": _randn(device, dt, 64, ntok, seed=88 + i)}
+        n = Ops(named)
+        return named, lambda: aum_hip.proj_bwd_data(n.ddelta, n.w_dt_t, n.w_x_t, n.dB, n.dC, n.dconv, ntok // 2, lib=lib)
+
+    @row_case(f"proj_bwd_weight/{tag}")
+    def _(lib, device):
+        named = {"x": _randn(device, dt, 64, ntok, seed=89 + i), "y": _randn(device, dt, rt, ntok, seed=90 + i)}
+        return named, lambda: aum_hip.proj_bwd_weight(named["x"], named["y"], tr, lib=lib)
+
+
+for _i, _cfg in enumerate(PROJ_CONFIGS):
+    _add_proj(_i, _cfg)
+
+
+# ---- refusals the families state, and the calls they took although an operand was of another type, shape or device (ROW_HOST_ONLY) -----------
+def _add_row_refusals():
+    def scan(name, brk, bwd=False, host_only=False, length=9):
+        @row_case(f"{'scan_bwd' if bwd else 'scan_fwd'}/{name}", host_only)
+        def _(lib, device):
+            o = scan_cm_ops(device, "bf16", 64, length, seed=95)
+            o.update(dout=rand_like(o.delta, 1), out_pre=rand_like(o.delta, 2), kw={})
+            o.named.update(dout=o.dout, out_pre=o.out_pre)
+            brk(o)
+            if bwd:
+                return o.named, lambda: aum_hip.scan_bwd(o.u, o.delta, o.A, o.B, o.C, o.D, o.z, o.bias, o.dout, o.out_pre, True, lib=lib, **o.kw)
+            return o.named, lambda: aum_hip.scan_fwd(o.u, o.delta, o.A, o.B, o.C, o.D, o.z, o.bias, True, lib=lib, **o.kw)
+
+    def put(key, make, also=None):
+        def brk(o):
+            o[key] = make(o)
+            if also:
+                o.named[also] = o[key]
+        return brk
+
+    longer = lambda t: torch.cat([t, t[..., :1]], -1)           # one more step: every row the kernel reads is inside it
+    for bwd in (False, True):
+        scan("refuse_time_stride", put("delta", lambda o: o.delta.transpose(1, 2).contiguous().transpose(1, 2)), bwd)
+        scan("refuse_two_bc_groups", put("B", lambda o: torch.cat([o.bc[0], o.bc[0]], 1)), bwd)
+    scan("refuse_mixed_dtypes", put("delta", lambda o: o.delta.float(), "delta"))
+    scan("refuse_shape", put("B", lambda o: longer(o.B), "B"))
+    scan("takes_mixed_dtypes", put("delta", lambda o: o.delta.float(), "delta"), True, True)
+    scan("takes_shape", put("B", lambda o: longer(o.B), "B"), True, True)
+    scan("takes_dout_dtype", put("dout", lambda o: o.dout.float(), "dout"), True, True)
+    scan("takes_dout_shape", put("dout", lambda o: longer(o.dout), "dout"), True, True)
+    scan("takes_out_pre_dtype", put("out_pre", lambda o: o.out_pre.float(), "out_pre"), True, True)
+    scan("takes_out_pre_shape", put("out_pre", lambda o: longer(o.out_pre), "out_pre"), True, True)
+    scan("takes_delta_shape", put("delta", lambda o: longer(o.delta), "delta"), False, True)
+    scan("takes_z_shape", put("z", lambda o: longer(o.z), "z"), True, True)
+    scan("refuse_no_dout", put("dout", lambda o: None, "dout"), True)                 # the parent: the library's AUM_E_NULL
+    scan("refuse_no_out_pre", put("out_pre", lambda o: None, "out_pre"), True)
+    # a checkpoint that is not on the library's side: a `meta` tensor has a device of its own and no memory, the library is told no checkpoint
+    meta = lambda *shape: torch.empty(shape, dtype=torch.float32, device="meta")
+    scan("takes_x_ck_device", lambda o: o.kw.update(x_ck=meta(2, 64, 2, 16)), True, True, length=1025)
+    scan("refuse_x_ck_device", lambda o: o.kw.update(x_ck=meta(2, 64, 2, 16)), False, True, length=1025)      # the message names the library
+    scan("refuse_x_lane_device", lambda o: o.kw.update(x_lane=meta(2, 64, 1, 16, 64)), False, True, length=513)
+    scan("refuse_x_lane_device", lambda o: o.kw.update(x_lane=meta(2, 64, 1, 16, 64)), True, True, length=513)
+    for bwd in (False, True):           # a checkpoint of another shape than scan_ckpt() hands out
+        scan("refuse_x_ck_shape", lambda o: o.kw.update(x_ck=torch.empty((2, 64, 1, 16), device=o.u.device)), bwd, length=1025)
+
+    def norm(name, brk, drop=False, host_only=True, bwd=True):
+        @row_case(f"rmsnorm{'_drop' if drop else ''}_{'bwd' if bwd else 'fwd'}/{name}", host_only)
+        def _(lib, device):
+            o = Ops(x=_randn(device, "bf16", 9, 64, seed=96), w=_randn(device, "f32", 64, seed=97), residual=_randn(device, "bf16", 9, 64, seed=98),
+                    scale=torch.ones(9, device=device), rps=1, dres=None)
+            o["named"] = {"x": o.x, "w": o.w, "residual": o.residual, "row_scale": o.scale}
+            if bwd:
+                f = aum_hip.rmsnorm_drop_fwd(o.x, o.w, o.residual, o.scale, 1, lib=lib) if drop else aum_hip.rmsnorm_fwd(o.x, o.w, o.residual, lib=lib)
+                o.update(rstd=f[1], saved=f[2], dy=rand_like(o.x, 3))
+                o.named.update(x_saved=o.saved, dy=o.dy)
+            brk(o)
+            o.named.update(rstd=o.get("rstd"), dresidual=o.dres, row_scale=o.scale)
+            if not bwd:
+                return o.named, lambda: aum_hip.rmsnorm_drop_fwd(o.x, o.w, o.residual, o.scale, o.rps, lib=lib)
+            if drop:
+                return o.named, lambda: aum_hip.rmsnorm_drop_bwd(o.dy, o.saved, o.w, o.rstd, o.scale, o.rps, o.dres, lib=lib)
+            return o.named, lambda: aum_hip.rmsnorm_bwd(o.dy, o.saved, o.w, o.rstd, o.dres, True, lib=lib)
+
+    for drop in (False, True):
+        norm("takes_rstd_length", put("rstd", lambda o: longer(o.rstd)), drop)
+        norm("takes_rstd_dtype", put("rstd", lambda o: o.rstd.double()), drop)
+        norm("takes_rstd_strided", put("rstd", lambda o: torch.stack([o.rstd, o.rstd], 1)[:, 0]), drop)
+        norm("takes_dy_shape", put("dy", lambda o: torch.cat([o.dy, o.dy[:1]])), drop)
+        norm("takes_dresidual_shape", put("dres", lambda o: torch.zeros(10, 64, dtype=torch.bfloat16, device=o.x.device)), drop)
+    norm("refuse_no_residual", put("residual", lambda o: None), True, False, False)
+    norm("refuse_whole_samples", put("rps", lambda o: 2), True, False, False)
+    norm("refuse_row_scale", put("scale", lambda o: o.scale[:3]), True, True, False)          # host only: the message names the device
+    norm("refuse_row_scale", put("scale", lambda o: o.scale.double()), True, True)
+
+    @row_case("rmsnorm_fwd/refuse_column_stride")                   # a converted assert
+    def _(lib, device):
+        named = {"x": _randn(device, "bf16", 9, 128, seed=96), "w": _randn(device, "f32", 64, seed=97)}
+        return named, lambda: aum_hip.rmsnorm_fwd(named["x"][:, ::2], named["w"], lib=lib)
+
+    def conv(name, brk, tm, host_only=True):
+        @row_case(f"{'conv1d_tm_bwd' if tm else 'conv1d_bwd'}/{name}", host_only)
+        def _(lib, device):
+            o = _conv_row_ops(device, ("bf16", 64, 9, 4, True, True, False, {}), 9, tm)
+            brk(o)
+            o.named["dy"] = o.dy
+            return o.named, lambda: (aum_hip.conv1d_tm_bwd if tm else aum_hip.conv1d_bwd)(o.x, o.w, o.b, o.dy, lib=lib)
+
+    for tm in (True, False):
+        conv("takes_dy_dtype", put("dy", lambda o: o.dy.float()), tm)
+        conv("takes_dy_shape", put("dy", lambda o: torch.cat([o.dy, o.dy[:, :1]], 1)), tm)       # one more token (tm) / channel: still in bounds
+    conv("refuse_time_stride", put("dy", lambda o: o.dy.transpose(1, 2).contiguous().transpose(1, 2)), False, False)
+
+    @row_case("conv1d_tm_prefill/refuse_operands")
+    def _(lib, device):
+        o = _prefill_ops(device, "bf16", 9)
+        return o.named, lambda: aum_hip.conv1d_tm_prefill(o.x, o.cs[:1], o.w, o.b, lib=lib)
+
+    @row_case("conv1d_tm_prefill/refuse_width")
+    def _(lib, device):
+        o = _prefill_ops(device, "bf16", 9, pool_width=3)
+        return o.named, lambda: aum_hip.conv1d_tm_prefill(o.x, o.cs, o.w, o.b, lib=lib)
+
+    @row_case("proj_bwd_weight/refuse_shape")
+    def _(lib, device):
+        named = {"x": _randn(device, "bf16", 32, 64, seed=99), "y": _randn(device, "bf16", 80, 64, seed=99)}
+        return named, lambda: aum_hip.proj_bwd_weight(named["x"], named["y"], False, lib=lib)
+
+    @row_case("proj_bwd_weight/refuse_tokens")                      # a converted assert: y2d of another token count than x2d
+    def _(lib, device):
+        named = {"x": _randn(device, "bf16", 64, 64, seed=99), "y": _randn(device, "bf16", 80, 128, seed=99)}
+        return named, lambda: aum_hip.proj_bwd_weight(named["x"], named["y"], False, lib=lib)
+
+    @row_case("proj_fwd/refuse_dtype")                              # a converted assert: w_dt of another dtype than the activations
+    def _(lib, device):
+        named = {"act": _randn(device, "bf16", 64, 64, seed=99), "w_x": _randn(device, "bf16", 80, 64, seed=99), "w_dt": _randn(device, "f16", 64, 48, seed=99)}
+        return named, lambda: aum_hip.proj_fwd(named["act"], named["w_x"], named["w_dt"], 16, lib=lib)
+
+
+_add_row_refusals()
+ROW_GROUPS = sorted({n.split("/")[0] for n in ROW_CASES})
+
+
 # ---- compare / record ------------------------------------------------------------------------------------------------------------------------
 def _diff(path, a, b, out):
     if isinstance(a, dict) and isinstance(b, dict):
@@ -549,35 +993,36 @@ def _diff(path, a, b, out):
         out.append(f"{path}: {a!r} != {b!r}")
 
 
-def load_fixture():
-    with open(FIXTURE) as f:
+def load_fixture(path=FIXTURE):
+    with open(path) as f:
         return json.load(f)
 
 
-def check_group(group, lib, device, fixture):
+def check_group(group, lib, device, fixture, cases=CASES, skip=()):
     """every case of one entry point against the fixture, field for field"""
-    names = [n for n in CASES if n.split("/")[0] == group]
+    names = [n for n in cases if n.split("/")[0] == group and n not in skip]
     assert names
     bad = []
     for n in names:
         assert n in fixture, f"{n}: not in the fixture"
-        _diff(n, run_case(CASES[n], lib, device), fixture[n], bad)
+        _diff(n, run_case(cases[n], lib, device), fixture[n], bad)
     assert not bad, "\n".join(bad)
 
 
-def record(lib, only=()):
-    fixture = load_fixture() if only else {}
-    for n in (only or CASES):
-        fixture[n] = run_case(CASES[n], lib, "cpu")
-    with open(FIXTURE, "w") as f:
+def record(lib, only=(), path=FIXTURE, cases=CASES):
+    fixture = load_fixture(path) if only else {}
+    for n in (only or cases):
+        fixture[n] = run_case(cases[n], lib, "cpu")
+    with open(path, "w") as f:
         f.write("{\n" + ",\n".join(f"{json.dumps(n)}: {json.dumps(fixture[n], sort_keys=True)}" for n in sorted(fixture)) + "\n}\n")
     return fixture
 
 
 if __name__ == "__main__":
-    if "--record" not in sys.argv:
-        sys.exit("usage: python tests/binding_pin_checks.py --record [CASE ...]")
+    if "--record" not in sys.argv and "--record-rows" not in sys.argv:
+        sys.exit("usage: python tests/binding_pin_checks.py --record | --record-rows [CASE ...]")
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
     import build_emu
-    done = record(aum_hip.Lib(build_emu.build(), host=True), [a for a in sys.argv[1:] if a != "--record"])
-    print(f"{len(done)} cases in {FIXTURE}")
+    where = (ROWS_FIXTURE, ROW_CASES) if "--record-rows" in sys.argv else (FIXTURE, CASES)
+    done = record(aum_hip.Lib(build_emu.build(), host=True), [a for a in sys.argv[1:] if not a.startswith("--record")], *where)
+    print(f"{len(done)} cases in {where[0]}")
