@@ -24,7 +24,9 @@ position row in the middle of the sequence) as the backbone of AuM-Small (MM:348
     dropped: ImageNet's classifier is no use here) goes through load_state_dict(strict=False), so a Vim Bi-Bi checkpoint
     also initialises a Fo-Bi model (the backward-direction conv / x_proj / dt_proj / D_b are reported as unexpected).
     The returned missing and unexpected keys are those the reference prints.
-  * refused: double-cls checkpoints (a double-cls model is off the accelerated path) and another patch size.
+  * load_double_cls_token=True (a double-cls Vim checkpoint into a use_double_cls_token model): the first and the last position row
+    go to the prefix (rows 0 and 1), cls_token_head / cls_token_tail load by name; mismatched cls layouts are refused.
+  * refused: another patch size.
 """
 import math
 
@@ -87,8 +89,6 @@ def load_aum_checkpoint(model, weights, pretrain_fstride=None, pretrain_tstride=
 def load_imagenet_checkpoint(model, weights, modelkey="model", load_middle_cls_token=True, load_double_cls_token=False):
     """weights: path or the checkpoint's dict (the state dict under `modelkey`).  Returns torch's load_state_dict result with
     the missing / unexpected keys of the reference's own load (MM:393-394: the patch and position weights are not part of it)."""
-    if load_double_cls_token:
-        raise NotImplementedError("double-cls ImageNet checkpoints need a double-cls model, which is off the accelerated path")
     if weights is None:
         raise ValueError("ImageNet init needs a checkpoint: --imagenet_pretrain_path / imagenet_pretrain_path is not set")
     if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
@@ -101,6 +101,14 @@ def load_imagenet_checkpoint(model, weights, modelkey="model", load_middle_cls_t
         if k not in weights:
             raise KeyError(f"ImageNet checkpoint has no {k!r}: not a Vim state dict")
 
+    double_ckpt = "cls_token_head" in weights or "cls_token_tail" in weights
+    if load_double_cls_token and model.num_tokens != 2:
+        raise NotImplementedError("load_double_cls_token=True loads a double-cls Vim checkpoint: the model needs use_double_cls_token=True "
+                         f"(it has {model.num_tokens} cls token(s))")
+    if double_ckpt != bool(load_double_cls_token) or (model.num_tokens == 2) != bool(load_double_cls_token):
+        raise ValueError(f"cls layouts do not match: the checkpoint is {'double' if double_ckpt else 'single'}-cls, the model has "
+                         f"{model.num_tokens} cls token(s), load_double_cls_token={bool(load_double_cls_token)}")
+
     proj = model.patch_embed.proj
     proj_w = weights.pop("patch_embed.proj.weight").float()
     proj_b = weights.pop("patch_embed.proj.bias").float()
@@ -112,7 +120,10 @@ def load_imagenet_checkpoint(model, weights, modelkey="model", load_middle_cls_t
     pe = weights.pop("pos_embed").float()
     if pe.dim() != 3 or pe.shape[0] != 1:
         raise ValueError(f"ImageNet pos_embed has shape {tuple(pe.shape)}, expected (1, rows, dim)")
-    if load_middle_cls_token:                                  # FlexiPosEmbed.insert_to_prefix(pe, N // 2), TOK:411-422
+    if load_double_cls_token:                                  # FlexiPosEmbed.insert_to_prefix(pe, [0, last]): head row, tail row, patches
+        last = pe.shape[1] - 1
+        pe = torch.cat([pe[:, :1], pe[:, last:], pe[:, 1:last]], dim=1)
+    elif load_middle_cls_token:                                # FlexiPosEmbed.insert_to_prefix(pe, N // 2), TOK:411-422
         mid = (pe.shape[1] - 1) // 2
         pe = torch.cat([pe[:, mid:mid + 1], pe[:, :mid], pe[:, mid + 1:]], dim=1)
     n_prefix = model.num_tokens

@@ -7,9 +7,12 @@ forward_features MM:509-667, Block.forward MM:58-99, defaults MM:191-242) and pr
 head.*) so published checkpoints load.  Also mirrored: the cls-token placements of RUN's flags (middle / end / head,
 MM:528-535), `transpose_token_sequence` (time-major token order, MM:545-566) and `if_bidirectional` layer pairing
 (MM:623-638), and ImageNet Vim initialisation (`imagenet_pretrain`, MM:348-395; aum.checkpoint.load_imagenet_checkpoint).
-Options off that surface (rope, double cls, flexible patch sizes, token dropout) are rejected.
+The cls layouts of MM:518-537 are all here: one cls token (also at a random position per forward), `use_double_cls_token`
+(cls_token_head / cls_token_tail) and `if_cls_token=False` with `final_pool_type` none / mean / max (MM:659-685).
+Options off that surface (rope, flexible patch sizes, token dropout, final_pool_type 'all') are rejected.
 """
 import math
+import random
 
 import torch
 import torch.nn as nn
@@ -17,7 +20,7 @@ import torch.nn.functional as F
 
 from mamba_ssm.modules.mamba_simple import Mamba
 from mamba_ssm.ops.selective_scan_interface import _autocast_dtype, step_cache
-from mamba_ssm.ops.triton.layernorm import RMSNorm, rms_norm_fn
+from mamba_ssm.ops.triton.layernorm import RMSNorm, rms_norm_fn, rms_norm_pool_fn
 
 AUM_SIZES = {"base": 768, "small": 384, "tiny": 192}      # embed dims; depth 24 for all three (RUN:227-237)
 
@@ -249,15 +252,27 @@ class AudioMamba(nn.Module):
                  use_middle_cls_token=True, use_end_cls_token=False, transpose_token_sequence=False,
                  if_bidirectional=False, ssm_cfg=None, device=None, dtype=None, imagenet_pretrain=False,
                  imagenet_pretrain_path=None, imagenet_pretrain_modelkey="model", imagenet_load_middle_cls_token=True,
-                 imagenet_load_double_cls_token=False, drop_path_rate=0.0, **unsupported):
+                 imagenet_load_double_cls_token=False, drop_path_rate=0.0, if_cls_token=True, use_double_cls_token=False,
+                 final_pool_type="mean", **unsupported):
         super().__init__()
         on = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0.0, -1.0)
-              and k not in ("if_cls_token", "rms_norm", "fused_add_norm", "residual_in_fp32", "if_abs_pos_embed", "final_pool_type",
-                            "use_PI_for_patch_embed")}
-        if imagenet_load_double_cls_token:                        # needs a double-cls model
-            on["imagenet_load_double_cls_token"] = imagenet_load_double_cls_token
+              and k not in ("rms_norm", "fused_add_norm", "residual_in_fp32", "if_abs_pos_embed", "use_PI_for_patch_embed")}
         if on:
             raise NotImplementedError(f"AudioMamba options outside the accelerated path: {sorted(on)}")
+        # the cls layouts of MM:518-537: one cls token (middle / end / head), a head and a tail token, or none and a pool over the tokens
+        self.if_cls_token, self.use_double_cls_token = bool(if_cls_token), bool(use_double_cls_token)
+        if self.use_double_cls_token and not self.if_cls_token:
+            raise ValueError("use_double_cls_token needs if_cls_token=True")
+        if self.use_double_cls_token and (use_middle_cls_token or use_end_cls_token):
+            raise ValueError("use_double_cls_token puts one cls token in front of the patches and one behind them: it excludes "
+                             "use_middle_cls_token and use_end_cls_token (pass both as False)")
+        if imagenet_load_double_cls_token and not self.use_double_cls_token:
+            raise NotImplementedError("imagenet_load_double_cls_token loads a double-cls checkpoint: it needs use_double_cls_token=True")
+        if final_pool_type == "all":
+            raise NotImplementedError("final_pool_type='all' (every token's features as the model output) is off the accelerated path")
+        if final_pool_type not in ("none", "mean", "max"):
+            raise ValueError(f"final_pool_type must be 'none', 'mean' or 'max', not {final_pool_type!r}")
+        self.final_pool_type = final_pool_type                    # read only without a cls token (MM:666-675)
         if tuple(patch_size) != tuple(strides):
             raise NotImplementedError("overlapping patches are off the default path")
         self.embed_dim = self.d_model = embed_dim
@@ -277,8 +292,10 @@ class AudioMamba(nn.Module):
         tdim = (spectrogram_size[1] - patch_size[1]) // strides[1] + 1
         self.patch_grid_size = (fdim, tdim)
         self.num_patches = fdim * tdim
-        self.num_tokens = 1
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+        self.num_tokens = 0 if not self.if_cls_token else (2 if self.use_double_cls_token else 1)
+        cls_names = {0: (), 1: ("cls_token",), 2: ("cls_token_head", "cls_token_tail")}[self.num_tokens]      # MM:243-252
+        for name in cls_names:
+            setattr(self, name, nn.Parameter(torch.zeros(1, 1, embed_dim)))
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         self.layers = nn.ModuleList([
             Block(embed_dim, Mamba(embed_dim, layer_idx=i, bimamba_type=bimamba_type, if_devide_out=if_devide_out,
@@ -288,7 +305,8 @@ class AudioMamba(nn.Module):
         if isinstance(self.head, nn.Linear):                       # segm_init_weights, MM:179-184
             nn.init.trunc_normal_(self.head.weight, std=0.02)
             nn.init.zeros_(self.head.bias)
-        nn.init.trunc_normal_(self.cls_token, std=0.02)
+        for name in cls_names:
+            nn.init.trunc_normal_(getattr(self, name), std=0.02)
         self.apply(lambda m: _init_weights(m, depth))              # MM:146-176
         self.patch_embed = PatchEmbed(tuple(patch_size), tuple(strides), channels, embed_dim)
         self.pos_embed = PosEmbed(self.num_patches + self.num_tokens, embed_dim)
@@ -300,34 +318,48 @@ class AudioMamba(nn.Module):
             self.to(device=device, dtype=dtype)
 
     def no_weight_decay(self):
-        return {"pos_embed", "cls_token"}
+        return {"pos_embed", "cls_token", "cls_token_head", "cls_token_tail"}
 
-    def tokens(self, x):
-        """(B, T, F) spectrogram -> (B, N+1, Dm) token sequence with the cls token in the middle (MM:509-541)."""
+    def _cls_pos(self, cls_pos=None):
+        """where the single cls token goes (MM:526-533): cls_pos where given (a random position of this forward), else by the flags"""
+        Np = self.num_patches
+        return cls_pos if cls_pos is not None else (Np // 2 if self.use_middle_cls_token else (Np if self.use_end_cls_token else 0))
+
+    def tokens(self, x, cls_pos=None):
+        """(B, T, F) spectrogram -> ((B, N + num_tokens, Dm) token sequence, where the cls rows are) (MM:509-562).  One cls token: in
+        the middle / at the end / in front, or at cls_pos; position row 0 is its.  Two: [head | patches | tail], position rows 0 and 1
+        are the head's and the tail's and rows 2.. the patches' (FlexiPosEmbed.insert_to_prefix, TOK:389-399), the place is
+        (0, N + 1).  None: the patches alone, place None.  transpose_token_sequence reorders the patches only."""
         x = x.unsqueeze(1).transpose(2, 3)                         # B x 1 x F x T
         x = self.patch_embed(x)                                    # token index = f * n_t + t
         Bsz, Np, _ = x.shape
         pe = self.pos_embed.pos_embed
-        pos = Np // 2 if self.use_middle_cls_token else (Np if self.use_end_cls_token else 0)      # MM:528-535
-        cls = (self.cls_token + pe[:, :1]).expand(Bsz, -1, -1)
-        x = x + pe[:, 1:]                                          # position embedding belongs to the (f, t) cell
+        x = x + pe[:, self.num_tokens:]                            # position embedding belongs to the (f, t) cell
         if self.transpose_token_sequence:                          # MM:545-566: patches in time-major order, cls stays put
             nf, nt = self.patch_grid_size
             x = x.reshape(Bsz, nf, nt, -1).transpose(1, 2).reshape(Bsz, nt * nf, -1)
+        if self.num_tokens == 0:
+            return x, None
+        if self.num_tokens == 2:
+            head = (self.cls_token_head + pe[:, :1]).expand(Bsz, -1, -1)
+            tail = (self.cls_token_tail + pe[:, 1:2]).expand(Bsz, -1, -1)
+            return torch.cat((head.to(x.dtype), x, tail.to(x.dtype)), dim=1), (0, Np + 1)
+        pos = self._cls_pos(cls_pos)                               # MM:526-535
+        cls = (self.cls_token + pe[:, :1]).expand(Bsz, -1, -1)
         return torch.cat((x[:, :pos], cls.to(x.dtype), x[:, pos:]), dim=1), pos
 
-    def tokens_from_wave(self, wave, fe):
+    def tokens_from_wave(self, wave, fe, cls_pos=None):
         """(B, n_samples) mean-removed waveform + aum.frontend.WaveInput -> the same token sequence as tokens(spectrogram), in one
         launch when the configuration is the 16 kHz / 128-mel / 16 x 16 autocast one; otherwise log-mel kernel + tokens()."""
         import aum_hip
         dtype = torch.get_autocast_dtype(wave.device.type) if torch.is_autocast_enabled(wave.device.type) else None
         ps = self.patch_embed.proj
-        if (dtype is None or tuple(ps.kernel_size) != (16, 16) or ps.in_channels != 1 or self.patch_grid_size[0] != 8
+        # (the one-launch kernel writes the single-cls layout, at any position; double-cls and cls-free models take the log-mel kernel)
+        if (dtype is None or self.num_tokens != 1 or tuple(ps.kernel_size) != (16, 16) or ps.in_channels != 1 or self.patch_grid_size[0] != 8
                 or self.patch_grid_size[1] * 16 != fe.target_length
                 or not aum_hip.frontend_tokens_supported(fe.tables.tables, fe.target_length, self.embed_dim, dtype)):
-            return self.tokens(fe.spectrogram(wave))
-        Np = self.num_patches
-        pos = Np // 2 if self.use_middle_cls_token else (Np if self.use_end_cls_token else 0)
+            return self.tokens(fe.spectrogram(wave), cls_pos)
+        pos = self._cls_pos(cls_pos)
         tok = FrontendTokensFn.apply(wave, ps.weight, ps.bias, self.pos_embed.pos_embed, self.cls_token, fe, dtype, pos,
                                      self.transpose_token_sequence)
         return tok, pos
@@ -347,16 +379,38 @@ class AudioMamba(nn.Module):
         """this forward's drop_scales, or None (eval, rate 0): then no factor exists and the unscaled add + norm kernels run"""
         return self.drop_scales(hidden.shape[0], hidden.device) if self.training and self.drop_path_rate > 0 else None
 
-    def forward_features(self, x, frontend=None):
-        hidden, pos = self.tokens(x) if frontend is None else self.tokens_from_wave(x, frontend)
+    def forward_features(self, x, frontend=None, if_random_cls_token_position=False):
+        """if_random_cls_token_position (MM:526-527, the training loop's argument): the single cls token at one random.randint(0, N)
+        position for this forward"""
+        cls_pos = None
+        if if_random_cls_token_position:
+            if self.num_tokens != 1:
+                raise ValueError("if_random_cls_token_position moves the single cls token: not with use_double_cls_token or if_cls_token=False")
+            cls_pos = random.randint(0, self.num_patches)
+        hidden, pos = self.tokens(x, cls_pos) if frontend is None else self.tokens_from_wave(x, frontend, cls_pos)
         scales = self._drop(hidden)
         with step_cache([layer.mixer for layer in self.layers], _autocast_dtype()):     # all blocks' 16-bit weights and A in a few launches
             hidden, residual = self._run_layers(hidden, scales)
         # MM:646-657, then the cls row (MM:660-680).  add + RMSNorm is row-wise and only the cls row is read: the final norm runs on
         # those `batch` rows instead of on all 513 per clip (same values, same gradients; 0.1 ms per step at the bench shape)
-        return rms_norm_fn(hidden[:, pos], self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps,
-                           residual=None if residual is None else residual[:, pos], prenorm=False, residual_in_fp32=True,
-                           row_scale=None if scales is None or residual is None else scales[-1])
+        last = None if scales is None or residual is None else scales[-1]
+        norm = lambda h, r: rms_norm_fn(h, self.norm_f.weight, self.norm_f.bias, eps=self.norm_f.eps, residual=r, prenorm=False,
+                                        residual_in_fp32=True, row_scale=last)
+        rows = lambda t, idx: None if t is None else t[:, idx]
+        if self.num_tokens == 2:                                   # MM:661-662: the mean of the two cls rows; the norm runs on those two
+            f = norm(rows(hidden, list(pos)), rows(residual, list(pos)))
+            return (f[:, 0] + f[:, 1]) / 2
+        if self.num_tokens == 0 and self.final_pool_type != "none":        # MM:668-671
+            if self.final_pool_type == "max":                      # every token's features: forward() takes the max of their logits
+                return norm(hidden, residual)
+            if last is None and residual is not None and hidden.dtype in (torch.bfloat16, torch.float16):
+                # add + norm + mean in one pass (aum_rmsnorm_pool_fwd / _bwd): the normalised (B, L, D) rows and their gradient never exist
+                return rms_norm_pool_fn(hidden, self.norm_f.weight, residual, self.norm_f.eps)
+            # fp32 activations, or stochastic depth on the add in training: the norm kernels on all rows, then the mean
+            return norm(hidden, residual).mean(dim=1)
+        if self.num_tokens == 0:
+            pos = hidden.shape[1] - 1                              # MM:667: 'none' reads the last token
+        return norm(hidden[:, pos], rows(residual, pos))
 
     def _run_layers(self, hidden, scales=None):
         """scales: drop_scales() of this forward or None; block i takes row i (each layer of an `if_bidirectional` pair its own)"""
@@ -378,6 +432,9 @@ class AudioMamba(nn.Module):
     def _check_streamable(self):
         """Streaming needs every token to depend on earlier tokens only and the cls token to come last: causal blocks, one direction,
         time-major token order, cls at the end."""
+        if self.num_tokens != 1:
+            raise ValueError("streaming inference needs the single end cls token (if_cls_token=True, use_double_cls_token=False, "
+                             "use_end_cls_token=True): it is the row that reads the state behind the tokens pushed so far")
         bt = self.layers[0].mixer.bimamba_type if len(self.layers) else "none"
         if bt != "none":
             raise ValueError(f"streaming inference needs bimamba_type='none' (causal blocks), not {bt!r}")
@@ -1102,13 +1159,16 @@ class AudioMamba(nn.Module):
             hidden, residual = self._stream_layers(cls, copies)
         return self._head_rows(hidden[:, 0], residual[:, 0], return_features)
 
-    def forward(self, x, return_features=False, frontend=None, timeline=False):
+    def forward(self, x, return_features=False, frontend=None, timeline=False, if_random_cls_token_position=False):
         """x: (B, T, F) normalised log-mel spectrogram, or -- with frontend=aum.frontend.WaveInput -- (B, n_samples) waveform.
         timeline=True: forward_timeline on the same arguments, (B, K, classes) (so that a DistributedDataParallel wrapper reaches it)"""
         if timeline:
             return self.forward_timeline(x, return_features, frontend)
-        f = self.forward_features(x, frontend)
-        return f if return_features else self.head(f)
+        f = self.forward_features(x, frontend, if_random_cls_token_position)
+        if return_features:
+            return f
+        out = self.head(f)
+        return out.max(dim=1)[0] if f.dim() == 3 else out          # MM:683-684: final_pool_type 'max' over the tokens' logits
 
 
 def _init_weights(module, n_layer):

@@ -16,7 +16,7 @@ GPU; bf16 autocast (no GradScaler needed) around the HIP mixer; DDP with a stati
 ImageNet init (--imagenet_pretrain, a Vim checkpoint as the backbone) is aum.checkpoint.load_imagenet_checkpoint.
 EPIC-Sounds (--dataset epic_sounds, run.py:139-158) reads the reference's annotation pickles and audio; its log-mel and SpecAugment run on
 the GPU (aum.epic).
-Out of scope here (rejected with an error): --model ast, flexible patch training, drop path, double-cls ImageNet init.
+Out of scope here (rejected with an error): --model ast, flexible patch training, --if_random_token_rank.
 """
 import argparse
 import ast as _ast
@@ -83,6 +83,7 @@ def build_parser():
     a("--use_double_cls_token", type=_lit, default="False")
     a("--use_end_cls_token", type=_lit, default="False")
     a("--transpose_token_sequence", type=_lit, default="False")
+    a("--final_pool_type", type=str, default="mean", help="cls-free models (--if_cls_token False): none (last token) / mean / max")
     a("--if_random_cls_token_position", type=_lit, default="False")
     a("--if_random_token_rank", type=_lit, default="False")
     a("--aum_type", type=str, default="Fo-Bi")
@@ -136,13 +137,19 @@ def check_scope(args):
         # implicit configuration is not implemented here: the data source is always given
         raise NotImplementedError("--dataset epic_sounds needs its data source: --epic_config (the reference's yaml), or "
                                   "--epic_annotations_dir and --epic_audio; the reference's built-in default config is not implemented")
-    if args.imagenet_pretrain and args.imagenet_load_double_cls_token:
-        raise NotImplementedError("--imagenet_load_double_cls_token: a double-cls ImageNet checkpoint needs a double-cls model, "
-                                  "which is off the accelerated path")
+    if args.imagenet_pretrain and bool(args.imagenet_load_double_cls_token) != bool(args.use_double_cls_token):
+        raise NotImplementedError("--imagenet_load_double_cls_token loads a double-cls Vim checkpoint into a --use_double_cls_token model: "
+                         "set both or neither")
     if args.imagenet_pretrain and not args.imagenet_pretrain_path:
         raise ValueError("--imagenet_pretrain True needs --imagenet_pretrain_path")
-    if not args.if_cls_token or args.use_double_cls_token or args.if_random_cls_token_position or args.if_random_token_rank:
-        raise NotImplementedError("no / double / randomly placed cls tokens are off the accelerated path")
+    if args.if_random_token_rank:
+        raise NotImplementedError("--if_random_token_rank (a random order of all tokens; debug code in the reference) is off the accelerated path")
+    if args.if_random_cls_token_position and (not args.if_cls_token or args.use_double_cls_token):
+        raise ValueError("--if_random_cls_token_position moves the single cls token: not with --use_double_cls_token True or --if_cls_token False")
+    if args.use_double_cls_token and (not args.if_cls_token or args.use_middle_cls_token or args.use_end_cls_token):
+        raise ValueError("--use_double_cls_token True needs --if_cls_token True --use_middle_cls_token False --use_end_cls_token False")
+    if args.final_pool_type not in ("none", "mean", "max"):
+        raise NotImplementedError("--final_pool_type is one of none / mean / max ('all' is off the accelerated path)")
     if args.timeline_loss and not (args.aum_type == "Fo-Fo" and not args.use_middle_cls_token and args.use_end_cls_token
                                    and args.transpose_token_sequence):
         raise ValueError("--timeline_loss True trains a streaming model: it needs --aum_type Fo-Fo --use_middle_cls_token False "
@@ -216,7 +223,8 @@ def build_model(args):
                        strides=(args.fstride, args.tstride), depth=args.depth, embed_dim=AUM_SIZES[size], num_classes=args.n_class,
                        bimamba_type=bimamba, use_middle_cls_token=args.use_middle_cls_token,
                        use_end_cls_token=args.use_end_cls_token, transpose_token_sequence=args.transpose_token_sequence,
-                       drop_path_rate=args.aum_drop_path)
+                       drop_path_rate=args.aum_drop_path, if_cls_token=args.if_cls_token, use_double_cls_token=args.use_double_cls_token,
+                       final_pool_type=args.final_pool_type)
     if args.imagenet_pretrain:                   # ImageNet first, AuM second: the AuM checkpoint's values win (MM:348-446)
         from .checkpoint import load_imagenet_checkpoint
         print(load_imagenet_checkpoint(model, args.imagenet_pretrain_path, args.imagenet_pretrain_modelkey,
@@ -518,7 +526,12 @@ def train(model, train_loader, val_loader, args, D):
             with torch.no_grad():
                 x, fe = fe_train(wave, n_valid.to(D.device))
             with _autocast(args, D):
-                out = net(x, frontend=fe, timeline=True) if args.timeline_loss else net(x, frontend=fe)
+                if args.timeline_loss:
+                    out = net(x, frontend=fe, timeline=True)
+                elif args.if_random_cls_token_position:      # the training forward only, as the reference's loop (one position per step)
+                    out = net(x, frontend=fe, if_random_cls_token_position=True)
+                else:
+                    out = net(x, frontend=fe)
             loss = _timeline_loss(loss_fn, out.float(), labels) if args.timeline_loss else _loss(loss_fn, out.float(), labels)
             if args.if_nan2num:
                 loss = torch.nan_to_num(loss)

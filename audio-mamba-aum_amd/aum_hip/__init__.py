@@ -9,6 +9,7 @@ The functions mirror the reference's extension modules:
   conv1d_fwd / conv1d_bwd      <- causal_conv1d_cuda.causal_conv1d_fwd / _bwd (SSI:463, 594-596)
   rmsnorm_fwd / rmsnorm_bwd    <- _layer_norm_fwd / _layer_norm_bwd (LN:123-177, 293-377)
   rmsnorm_drop_fwd / _bwd      <- the same behind timm's DropPath on x (MM:90, MM:650): the per-sample factor inside the kernels
+  rmsnorm_pool_fwd / _bwd      <- the final add + norm and hidden_states.mean(dim=1) of a cls-free model (MM:649-669) in one pass
 """
 import ctypes as C
 import math
@@ -132,6 +133,11 @@ class NormArgs(C.Structure):
 
 class NormDropArgs(C.Structure):
     _fields_ = [("base", NormArgs), ("row_scale", _vp), ("rows_per_scale", _i32), ("reserved", _i32)]
+
+
+class NormPoolArgs(C.Structure):
+    _fields_ = ([("base", NormArgs), ("pooled", _vp), ("dpooled", _vp), ("pool_partial", _vp), ("row_stride_pooled", _i64),
+                 ("row_stride_dpooled", _i64), ("rows_per_sample", _i32), ("reserved", _i32)])
 
 
 class FbankArgs(C.Structure):
@@ -326,7 +332,7 @@ _SIGNATURES = {name: ([_vp, _vp], C.c_int) for name in (
     "aum_selective_state_update", "aum_conv1d_tm_chunk", "aum_scan_tm_chunk", "aum_conv1d_tm_chunk_var", "aum_scan_tm_chunk_var", "aum_stream_block_tm", "aum_scan_tm_fwd_state",
     "aum_conv1d_tm_prefill_var", "aum_scan_tm_fwd_state_var", "aum_conv1d_tm_chunk_peeks", "aum_scan_tm_chunk_peeks", "aum_fbank_stream_fwd",
     "aum_scan_tm_peeks_fwd_ckpt", "aum_scan_tm_peeks_bwd", "aum_conv1d_tm_peeks_bwd", "aum_stream_park", "aum_stream_in_tm", "aum_stream_out_tm",
-    "aum_stream_layers", "aum_rmsnorm_drop_fwd", "aum_rmsnorm_drop_bwd")}
+    "aum_stream_layers", "aum_rmsnorm_drop_fwd", "aum_rmsnorm_drop_bwd", "aum_rmsnorm_pool_fwd", "aum_rmsnorm_pool_bwd")}
 _SIGNATURES.update({
     "aum_abi_version": ([], C.c_int), "aum_scan_max_single_pass_len": ([], C.c_int),
     "aum_selective_scan_workspace_bytes": ([_i32] * 6, _i64), "aum_selective_scan_ckpt_bytes": ([_i32] * 4, _i64),
@@ -343,6 +349,7 @@ _SIGNATURES.update({
     "aum_scan_tm_peeks_ckpt_bytes": ([_i32] * 4, _i64), "aum_scan_tm_peeks_bwd_workspace_bytes": ([_i32] * 4, _i64),
     "aum_conv1d_tm_peeks_bwd_workspace_bytes": ([_i32] * 3, _i64),
     "aum_stream_layers_scratch_bytes": ([_i32] * 4, _i64),
+    "aum_rmsnorm_pool_partial_rows": ([_i32], C.c_int),
 })
 EXPORTS = list(_SIGNATURES)
 
@@ -2630,6 +2637,87 @@ def rmsnorm_drop_bwd(dy, x_saved, weight, rstd, row_scale, rows_per_scale, dresi
     lib = lib or get()
     return _norm_bwd(lib, lib.c.aum_rmsnorm_drop_bwd, "rmsnorm_drop_bwd", dy, x_saved, weight, rstd, dresidual, True, x_dtype, generic, dw_out,
                      (row_scale, rows_per_scale))
+
+
+def _norm_pool_operands(lib, name, lead, weight, rows_per_sample, others):
+    """THE operand rule of the add + RMSNorm + mean pair: `lead` (the forward's x, the backward's saved residual_out) is (rows, cols) with
+    unit column stride, rows whole samples of rows_per_sample, cols what the vectorised norm kernels take; others = [(name, tensor, shape,
+    dtype)] are on the library's side with that shape and dtype and unit last stride.  -> (rows, cols, samples, the weight as fp32)"""
+    rows, cols = lead.shape
+    if rows_per_sample < 1 or rows < 1 or rows % rows_per_sample:
+        raise ValueError(f"{name}: {rows} rows are not whole samples of {rows_per_sample} rows")
+    if cols % 8 or cols > 2048:
+        raise RuntimeError(f"{name}: {cols} columns: the pooled norm takes cols % 8 == 0 and cols <= 2048")
+    samples = rows // rows_per_sample
+    for what, t, shape, dt in others:
+        lib.check_tensor(t)
+        want = tuple(samples if s == "samples" else s for s in shape)
+        if tuple(t.shape) != want or t.dtype != dt or (t.dim() and t.stride(-1) != 1 and t.shape[-1] != 1) or (t.dim() == 1 and not t.is_contiguous()):
+            raise RuntimeError(f"{name}: {what} must be {want} {dt} with unit last stride, got {tuple(t.shape)} {t.dtype}, strides {t.stride()}")
+    if weight.shape != (cols,):
+        raise RuntimeError(f"{name}: weight must be ({cols},), got {tuple(weight.shape)}")
+    return rows, cols, samples, _f32c(weight)
+
+
+def _fill_norm_pool(q, lead_dtype, weight, rows, cols, rows_per_sample, eps=0.0):
+    """THE filler of NormPoolArgs: what both directions share"""
+    a = q.base
+    a.weight, a.eps, a.rows, a.cols = _ptr(weight), eps, rows, cols
+    a.x_dtype = a.y_dtype = _DT[lead_dtype]
+    a.res_dtype, a.flags = _DT[torch.float32], 0
+    q.rows_per_sample, q.reserved = rows_per_sample, 0
+    return a
+
+
+def rmsnorm_pool_fwd(x, weight, residual, rows_per_sample, eps=1e-5, save=True, lib=None):
+    """add + RMSNorm + mean over a sample's rows (aum_rmsnorm_pool_fwd).  x (rows, cols) bf16 / fp16, residual (rows, cols) fp32, rows =
+    samples x rows_per_sample -> (pooled (samples, cols) in x's dtype, rstd (rows,) | None, residual_out (rows, cols) fp32 | None); the
+    last two are aum_rmsnorm_fwd's (what the backward needs) and exist with save=True.  The normalised rows are not stored."""
+    lib = lib or get()
+    lib.check_tensor(x)
+    if x.dim() != 2 or x.dtype not in (torch.bfloat16, torch.float16) or x.stride(1) != 1:
+        raise RuntimeError(f"rmsnorm_pool_fwd: x must be (rows, cols) bf16 / fp16 with unit column stride, got {tuple(x.shape)} {x.dtype}, {x.stride()}")
+    if residual is None:
+        raise ValueError("rmsnorm_pool_fwd: the residual stream is required")
+    rows, cols, samples, weight = _norm_pool_operands(lib, "rmsnorm_pool_fwd", x, weight, rows_per_sample,
+                                                      [("residual", residual, x.shape, torch.float32)])
+    pooled = torch.empty((samples, cols), dtype=x.dtype, device=x.device)
+    res_out = torch.empty((rows, cols), dtype=torch.float32, device=x.device) if save else None
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if save else None
+    nchunk = int(lib.c.aum_rmsnorm_pool_partial_rows(rows_per_sample))
+    part = torch.empty((samples * nchunk, cols), dtype=torch.float32, device=x.device) if nchunk > 1 else None
+    q = NormPoolArgs()
+    a = _fill_norm_pool(q, x.dtype, weight, rows, cols, rows_per_sample, eps)
+    a.x, a.residual, a.residual_out, a.rstd_out = map(_ptr, (x, residual, res_out, rstd))
+    a.row_stride_x, a.row_stride_res, a.row_stride_res_out = x.stride(0), residual.stride(0), cols
+    q.pooled, q.pool_partial, q.row_stride_pooled = _ptr(pooled), _ptr(part), cols
+    _launch(lib.c.aum_rmsnorm_pool_fwd, q, x, lib, "rmsnorm_pool_fwd", (rows, cols, x.element_size()))
+    return pooled, rstd, res_out
+
+
+def rmsnorm_pool_bwd(dpooled, x_saved, weight, rstd, rows_per_sample, lib=None, dw_out=None):
+    """The backward of rmsnorm_pool_fwd (aum_rmsnorm_pool_bwd).  dpooled (samples, cols) bf16 / fp16; x_saved, rstd: the forward's
+    residual_out and rstd.  Every row of sample s gets what rmsnorm_bwd writes for dy = (dpooled[s] / rows_per_sample) rounded to dpooled's
+    dtype.  -> (dx (rows, cols) in dpooled's dtype, dweight fp32 (into dw_out where given), dresidual_in (rows, cols) fp32)"""
+    lib = lib or get()
+    lib.check_tensor(x_saved)
+    if x_saved.dim() != 2 or x_saved.dtype != torch.float32 or x_saved.stride(1) != 1:
+        raise RuntimeError(f"rmsnorm_pool_bwd: x_saved must be the forward's (rows, cols) fp32 residual_out, got {tuple(x_saved.shape)} {x_saved.dtype}")
+    if dpooled.dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError(f"rmsnorm_pool_bwd: dpooled must be bf16 / fp16, got {dpooled.dtype}")
+    rows, cols, samples, weight = _norm_pool_operands(lib, "rmsnorm_pool_bwd", x_saved, weight, rows_per_sample,
+                                                      [("dpooled", dpooled, ("samples", x_saved.shape[1]), dpooled.dtype),
+                                                       ("rstd", rstd, (x_saved.shape[0],), torch.float32)])
+    dx = torch.empty((rows, cols), dtype=dpooled.dtype, device=dpooled.device)
+    dres_in = torch.empty((rows, cols), dtype=torch.float32, device=dpooled.device)
+    dwp = torch.empty((int(lib.c.aum_rmsnorm_bwd_partial_rows(rows, cols, 0)), cols), dtype=torch.float32, device=dpooled.device)
+    q = NormPoolArgs()
+    a = _fill_norm_pool(q, dpooled.dtype, weight, rows, cols, rows_per_sample)
+    a.x, a.rstd_in, a.dx, a.dresidual_in, a.dweight_partial = map(_ptr, (x_saved, rstd, dx, dres_in, dwp))
+    a.row_stride_x, a.row_stride_dx, a.row_stride_dres_in = x_saved.stride(0), cols, cols
+    q.dpooled, q.row_stride_dpooled = _ptr(dpooled), dpooled.stride(0)
+    _launch(lib.c.aum_rmsnorm_pool_bwd, q, dpooled, lib, "rmsnorm_pool_bwd", (rows, cols, dpooled.element_size()))
+    return dx, sum_rows(dwp, lib, out=dw_out), dres_in
 
 
 FBANK_AUG = 8     # columns of the per-clip augmentation table (include/aum_hip.h AUM_FBANK_AUG)

@@ -112,6 +112,16 @@ template <class TX, class TR> AUM_GLOBAL void k_norm_drop_bwd(AumNormArgs a, int
     extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
     rmsnorm_bwd_wave<TX, TR>(a, (int)blockIdx.x, n_partials, dyn_lds, sc);
 }
+// add + RMSNorm + mean over a sample's rows (aum_rmsnorm_pool_fwd / _bwd)
+template <class TX, int NCH> __global__ __launch_bounds__(NORM_BWD_NW * 64) void k_norm_pool_fwd_vec(AumNormPoolArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[NormBwdVecLds<NCH>::n];
+    rmsnorm_pool_fwd_vec<TX, float, NCH>(a, (int)blockIdx.x, lds);
+}
+template <class TX> AUM_GLOBAL void k_norm_pool_finish(AumNormPoolArgs a) { rmsnorm_pool_finish<TX>(a, (int)blockIdx.x); }
+template <class TX, int NCH> __global__ __launch_bounds__(NORM_BWD_NW * 64) void k_norm_pool_bwd_vec(AumNormArgs a, int n_waves, DyPooled g) {
+    __shared__ __attribute__((aligned(16))) float lds[NormBwdVecLds<NCH>::n];
+    rmsnorm_bwd_vec<TX, float, NCH, NoRowScale, DyPooled>(a, (int)blockIdx.x, n_waves, lds, NoRowScale{}, g);
+}
 #if AUM_API_PART == 3 || AUM_API_PART == 0
 AUM_GLOBAL void k_selftest_sum32(const float* in, float* out) {
     vf v[32], w[16];
@@ -716,6 +726,53 @@ static int norm_drop_dispatch(const AumNormDropArgs* d, bool bwd, void* stream) 
 }
 AUM_API int aum_rmsnorm_drop_fwd(const AumNormDropArgs* a, void* stream) { return norm_drop_dispatch(a, false, stream); }
 AUM_API int aum_rmsnorm_drop_bwd(const AumNormDropArgs* a, void* stream) { return norm_drop_dispatch(a, true, stream); }
+
+// add + RMSNorm + mean over a sample's rows: the vectorised row routines of the pair above on 16-bit x and an fp32 residual stream.
+// Forward: one workgroup per 32-row chunk of a sample, and where a sample has several chunks one more launch that adds them (fixed orders
+// throughout, conv_norm_kernels.h).  Backward: rmsnorm_bwd_vec with its dy formed from dpooled: the grid and partial rows of aum_rmsnorm_bwd.
+static_assert(NORM_POOL_CHUNK == NORM_POOL_ROWS * NORM_BWD_NW, "a chunk is the rows of one workgroup");
+AUM_API int aum_rmsnorm_pool_partial_rows(int32_t rows_per_sample) { return rows_per_sample < 1 ? 0 : norm_pool_chunks(rows_per_sample); }
+template <class TX> static int norm_pool_launch(const AumNormPoolArgs& q, bool bwd, aum_stream_t s) {
+    const AumNormArgs& a = q.base;
+    const int nch = (a.cols + 511) / 512;
+    if (bwd) {
+        const int np = aum_rmsnorm_bwd_partials(a.rows);
+        const DyPooled g = {q.dpooled, q.row_stride_dpooled, q.rows_per_sample};
+        return with_int<1, 2, 3, 4>(nch, [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return AUM_LAUNCH((np + NORM_BWD_NW - 1) / NORM_BWD_NW, NORM_BWD_NW * 64, s, (NormBwdVecLds<N>{}), (k_norm_pool_bwd_vec<TX, N>),
+                              (rmsnorm_bwd_vec<TX, float, N, NoRowScale, DyPooled>(a, wg, np, lds, NoRowScale{}, g)), a, np, g);
+        });
+    }
+    const int samples = a.rows / q.rows_per_sample, nchunk = norm_pool_chunks(q.rows_per_sample);
+    const int rc = with_int<1, 2, 3, 4>(nch, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return AUM_LAUNCH((int64_t)samples * nchunk, NORM_BWD_NW * 64, s, (NormBwdVecLds<N>{}), (k_norm_pool_fwd_vec<TX, N>),
+                          (rmsnorm_pool_fwd_vec<TX, float, N>(q, wg, lds)), q);
+    });
+    if (rc || nchunk == 1) return rc;
+    return AUM_LAUNCH((int64_t)samples * nch, 64, s, (NoLds{}), (k_norm_pool_finish<TX>), (rmsnorm_pool_finish<TX>(q, wg)), q);
+}
+static int norm_pool_dispatch(const AumNormPoolArgs* q, bool bwd, void* stream) {
+    if (!q) return AUM_E_NULL;
+    const AumNormArgs* a = &q->base;
+    if (!a->x || !a->weight) return AUM_E_NULL;
+    if (bwd ? (!q->dpooled || !a->rstd_in || !a->dx || !a->dresidual_in || !a->dweight_partial) : (!a->residual || !q->pooled)) return AUM_E_NULL;
+    if (a->rows <= 0 || a->cols <= 0 || q->rows_per_sample < 1 || a->rows % q->rows_per_sample != 0) return AUM_E_SHAPE;
+    if (a->x_dtype < 0 || a->x_dtype > 2 || a->res_dtype < 0 || a->res_dtype > 2 || a->y_dtype != a->x_dtype) return AUM_E_DTYPE;
+    if (a->x_dtype == AUM_F32 || a->res_dtype != AUM_F32 || a->flags != 0 || q->reserved != 0) return AUM_E_UNSUPPORTED;
+    if (a->cols % 8 != 0 || a->cols > 2048) return AUM_E_UNSUPPORTED;
+    if (a->y || a->dy || a->dresidual_out) return AUM_E_UNSUPPORTED;
+    if (!bwd) {
+        if ((a->residual_out == nullptr) != (a->rstd_out == nullptr)) return AUM_E_UNSUPPORTED;
+        if (norm_pool_chunks(q->rows_per_sample) > 1 && !q->pool_partial) return AUM_E_NULL;
+        if ((int64_t)(a->rows / q->rows_per_sample) * norm_pool_chunks(q->rows_per_sample) > 0x7fffffff) return AUM_E_SHAPE;
+    }
+    aum_stream_t s = (aum_stream_t)stream;
+    return a->x_dtype == AUM_BF16 ? norm_pool_launch<bf16_t>(*q, bwd, s) : norm_pool_launch<f16_t>(*q, bwd, s);
+}
+AUM_API int aum_rmsnorm_pool_fwd(const AumNormPoolArgs* a, void* stream) { return norm_pool_dispatch(a, false, stream); }
+AUM_API int aum_rmsnorm_pool_bwd(const AumNormPoolArgs* a, void* stream) { return norm_pool_dispatch(a, true, stream); }
 
 // ---- fbank frontend ----------------------------------------------------------------------------
 typedef Lds<float, FBANK_LDS_FLOATS> FbankLds;

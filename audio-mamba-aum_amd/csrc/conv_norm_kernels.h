@@ -385,8 +385,10 @@ template <class TX, class TR> AUM_DEV void norm_pre8_scaled(const TX* xp, const 
         for (int j = 0; j < 8; ++j) v[j] = vfma(splat(s), v[j], r[j]);
     }
 }
-template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnorm_fwd_vec(const AumNormArgs& p, int wg, const S sc = S{}) {
-    const int row = wg;
+// One row of the forward.  KEEP_Y: the row's y, rounded to TX as the store would round it, stays in ykeep[NCH][8] and is not stored (the
+// pooling kernel adds it up); otherwise y is stored and ykeep is not touched -- the statements aum_rmsnorm_fwd has always run.
+template <class TX, class TR, int NCH, class S = NoRowScale, bool KEEP_Y = false>
+AUM_DEV void rmsnorm_fwd_vec_row(const AumNormArgs& p, int row, const S sc, vf (*ykeep)[8]) {
     const float s = sc.at(row);
     const TX* xp = (const TX*)p.x + (int64_t)row * p.row_stride_x;
     const TR* rp = p.residual ? (const TR*)p.residual + (int64_t)row * p.row_stride_res : nullptr;
@@ -423,15 +425,121 @@ template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnor
         row_load8(p.weight, c0, p.cols, wv);
         AUM_UNROLL
         for (int j = 0; j < 8; ++j) y[j] = v[c][j] * rstd * wv[j];
-        row_store8(yp, c0, p.cols, y);
+        if constexpr (KEEP_Y) {
+            AUM_UNROLL
+            for (int j = 0; j < 8; ++j) ykeep[c][j] = vround_elem<TX>(y[j]);
+        } else {
+            row_store8(yp, c0, p.cols, y);
+        }
     }
 }
+template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnorm_fwd_vec(const AumNormArgs& p, int wg, const S sc = S{}) {
+    rmsnorm_fwd_vec_row<TX, TR, NCH, S>(p, wg, sc, nullptr);
+}
+
+// ---- add + RMSNorm + mean over a sample's rows (aum_rmsnorm_pool_fwd) ---------------------------------------------------------------
+// A workgroup of NORM_BWD_NW waves owns one 32-row chunk of one sample: wave w normalises rows 4 w .. 4 w + 3 of the chunk one after the other
+// (rmsnorm_fwd_vec_row: the row in registers, x and residual read once) and adds their rounded y in row order; the waves meet in LDS in wave
+// order, as the backward's weight-gradient sums do.  A sample of one chunk leaves as pooled at once; otherwise the chunk's fp32 sums go to
+// pool_partial[sample][chunk] and rmsnorm_pool_finish adds a sample's chunks in chunk order: no atomics, every order fixed by
+// rows_per_sample alone.
+constexpr int NORM_POOL_ROWS = 4;                                   // rows per wave
+constexpr int NORM_POOL_CHUNK = NORM_POOL_ROWS * 8;                 // rows per workgroup (8 = NORM_BWD_NW, declared below)
+constexpr int norm_pool_chunks(int per) { return (per + NORM_POOL_CHUNK - 1) / NORM_POOL_CHUNK; }
+// sum / rows_per_sample (fp32 division), rounded once to TX by the store
+template <class TX> AUM_DEV void norm_pool_store(const AumNormPoolArgs& q, int sample, vi c0, vf (&sum)[8]) {
+    AUM_UNROLL
+    for (int j = 0; j < 8; ++j) sum[j] = vdiv(sum[j], splat((float)q.rows_per_sample));
+    row_store8((TX*)q.pooled + (int64_t)sample * q.row_stride_pooled, c0, q.base.cols, sum);
+}
+template <class TX, class TR, int NCH> AUM_DEV void rmsnorm_pool_fwd_vec(const AumNormPoolArgs& q, int wg, float* lds) {
+    constexpr int NW = 8;
+    const AumNormArgs& p = q.base;
+    const int per = q.rows_per_sample, nchunk = norm_pool_chunks(per);
+    const int sample = wg / nchunk, chunk = wg - sample * nchunk;
+    const vi lane = lane_id();
+    vf acc[AUM_PER_WAVE(NW)][NCH][8];
+    AUM_FOR_EACH_WAVE(w, NW) {
+        AUM_UNROLL
+        for (int c = 0; c < NCH; ++c)
+            AUM_UNROLL
+            for (int j = 0; j < 8; ++j) acc[AUM_W(w)][c][j] = splat(0.f);
+        const int r0 = chunk * NORM_POOL_CHUNK + w * NORM_POOL_ROWS;
+        const int r1 = r0 + NORM_POOL_ROWS < per ? r0 + NORM_POOL_ROWS : per;
+        for (int r = r0; r < r1; ++r) {
+            vf y[NCH][8];
+            rmsnorm_fwd_vec_row<TX, TR, NCH, NoRowScale, true>(p, sample * per + r, NoRowScale{}, y);
+            AUM_UNROLL
+            for (int c = 0; c < NCH; ++c)
+                AUM_UNROLL
+                for (int j = 0; j < 8; ++j) acc[AUM_W(w)][c][j] = acc[AUM_W(w)][c][j] + y[c][j];
+        }
+        if (w > 0) {            // [wave - 1][chunk][j][lane], the layout of rmsnorm_bwd_vec's hand-over
+            float* mine = lds + (w - 1) * (NCH * 512);
+            AUM_UNROLL
+            for (int c = 0; c < NCH; ++c)
+                AUM_UNROLL
+                for (int j = 0; j < 8; ++j) lds_write(mine, lane + (c * 8 + j) * WAVE, acc[AUM_W(w)][c][j]);
+        }
+    }
+    AUM_WG_BARRIER();
+    AUM_FOR_EACH_WAVE(w, NW) {
+        if (w == 0) {
+            AUM_UNROLL
+            for (int c = 0; c < NCH; ++c) {
+                AUM_UNROLL
+                for (int j = 0; j < 8; ++j) {
+                    vf a = acc[AUM_W(0)][c][j];
+                    for (int o = 0; o < NW - 1; ++o) a = a + lds_read(lds + o * (NCH * 512), lane + (c * 8 + j) * WAVE);
+                    acc[AUM_W(0)][c][j] = a;
+                }
+                const vi c0 = lane * 8 + c * 512;
+                if (nchunk == 1) norm_pool_store<TX>(q, sample, c0, acc[AUM_W(0)][c]);
+                else row_store8(q.pool_partial + (int64_t)wg * p.cols, c0, p.cols, acc[AUM_W(0)][c]);
+            }
+        }
+    }
+}
+// one wave per (sample, 512-column chunk): the sample's chunk sums in chunk order, then norm_pool_store
+template <class TX> AUM_DEV void rmsnorm_pool_finish(const AumNormPoolArgs& q, int wg) {
+    const int cols = q.base.cols, nch = (cols + 511) / 512, nchunk = norm_pool_chunks(q.rows_per_sample);
+    const int sample = wg / nch;
+    const vi c0 = lane_id() * 8 + (wg - sample * nch) * 512;
+    vf sum[8];
+    AUM_UNROLL
+    for (int j = 0; j < 8; ++j) sum[j] = splat(0.f);
+    for (int k = 0; k < nchunk; ++k) {
+        vf t[8];
+        row_load8(q.pool_partial + ((int64_t)sample * nchunk + k) * cols, c0, cols, t);
+        AUM_UNROLL
+        for (int j = 0; j < 8; ++j) sum[j] = sum[j] + t[j];
+    }
+    norm_pool_store<TX>(q, sample, c0, sum);
+}
+
+// The backward's dy.  DyRows: the (rows, cols) tensor of aum_rmsnorm_bwd.  DyPooled (aum_rmsnorm_pool_bwd): every row of sample s has
+// dy = dpooled[s] / rows_per_sample rounded to TX -- the gradient of the mean, formed from the sample's one row where a row needs it.
+struct DyRows {
+    static constexpr bool pooled = false;
+};
+struct DyPooled {
+    static constexpr bool pooled = true;
+    const void* dpooled;
+    int64_t stride;
+    int32_t per;
+    template <class TX> AUM_DEV void load(int row, vi c0, int cols, vf (&dyv)[8]) const {
+        row_load8((const TX*)dpooled + (int64_t)(row / per) * stride, c0, cols, dyv);
+        AUM_UNROLL
+        for (int j = 0; j < 8; ++j) dyv[j] = vround_elem<TX>(vdiv(dyv[j], splat((float)per)));
+    }
+};
 
 // The backward's waves: one per ~9 rows (aum_rmsnorm_bwd_partials(rows) of them), the weight-gradient terms of a wave's rows in registers.
 // Round 6: NORM_BWD_NW waves form a workgroup and add their sums through LDS in wave order before one row of partials leaves -- 512 partial
 // rows instead of 4 096 for the caller to add (one launch of aum_sum_rows instead of two: 12 -> 4 us per layer).
 constexpr int NORM_BWD_NW = 8;
-template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnorm_bwd_vec(const AumNormArgs& p, int wg, int n_waves, float* lds, const S sc = S{}) {
+template <class TX, class TR, int NCH, class S = NoRowScale, class G = DyRows>
+AUM_DEV void rmsnorm_bwd_vec(const AumNormArgs& p, int wg, int n_waves, float* lds, const S sc = S{}, const G dg = G{}) {
     // rows dealt evenly: 64 x 513 rows on 4 096 waves are 8 rows each and a ninth for the first 64 (ceil(rows / waves) = 9 rows each left
     // 448 of the 4 096 waves without any)
     const int base = p.rows / n_waves, rem = p.rows - base * n_waves;
@@ -463,7 +571,8 @@ template <class TX, class TR, int NCH, class S = NoRowScale> AUM_DEV void rmsnor
             const vi c0 = lane * 8 + c * 512;
             vf dyv[8];
             row_load8(xp, c0, p.cols, xh[c]);
-            row_load8(gp, c0, p.cols, dyv);
+            if constexpr (G::pooled) dg.template load<TX>(row, c0, p.cols, dyv);
+            else row_load8(gp, c0, p.cols, dyv);
             AUM_UNROLL
             for (int j = 0; j < 8; ++j) {
                 xh[c][j] = xh[c][j] * rstd;

@@ -146,6 +146,8 @@ template <class T> AUM_DEV vf gload(const T* p, vi idx, vm m) { return m ? elem_
 template <class T> AUM_DEV void gstore(T* p, vi idx, vf v, vm m) { if (m) f32_to_elem(v, p[(uint32_t)idx]); }
 // unconditional load (caller clamps idx into range): no exec-mask branch, so several can be in flight
 template <class T> AUM_DEV vf gload_u(const T* p, vi idx) { return elem_to_f32(p[(uint32_t)idx]); }
+// v as a store to T and a load back would leave it: one round-to-nearest-even to T's precision (fp32: v itself)
+template <class T> AUM_DEV vf vround_elem(vf v) { T e; f32_to_elem(v, e); return elem_to_f32(e); }
 AUM_DEV void gatomic_add(float* p, vi idx, vf v, vm m) { if (m) atomicAdd(p + idx, v); }
 // 8 consecutive elements per lane as ONE (2-byte types) or TWO (fp32) 16-byte vector accesses.  Rows of the
 // (batch, dim, len) tensors start at arbitrary element offsets (len = 513), so the address is only element-aligned:
@@ -629,6 +631,7 @@ template <class T> inline vf gload(const T* p, const vi& idx, const vm& m) {
     vf r; AUM_LANES { if (m.v[l]) aum_emu_idx_ok(idx.v[l], "gload"); r.v[l] = m.v[l] ? elem_to_f32(p[idx.v[l]]) : 0.f; } return r;
 }
 template <class T> inline vf gload_u(const T* p, const vi& idx) { vf r; AUM_LANES { aum_emu_idx_ok(idx.v[l], "gload_u"); r.v[l] = elem_to_f32(p[idx.v[l]]); } return r; }
+template <class T> inline vf vround_elem(const vf& v) { vf r; AUM_LANES { T e; f32_to_elem(v.v[l], e); r.v[l] = elem_to_f32(e); } return r; }
 template <class T> inline void gstore(T* p, const vi& idx, const vf& v, const vm& m) {
     AUM_LANES if (m.v[l]) { aum_emu_idx_ok(idx.v[l], "gstore"); f32_to_elem(v.v[l], p[idx.v[l]]); }
 }

@@ -129,6 +129,67 @@ def rms_norm_fn(x, weight, bias, residual=None, prenorm=False, residual_in_fp32=
     return layer_norm_fn(x, weight, bias, residual, eps, prenorm, residual_in_fp32, True, row_scale)
 
 
+def rms_norm_pool_ref(x, weight, residual, eps=1e-6, rows_per_sample=None):
+    """Pure-PyTorch add + RMSNorm + mean over a sample's tokens, the statement of rms_norm_pool_fn: the norm in fp32 on x + residual, its rows
+    rounded to x's dtype (the hidden_states the reference's final norm returns, MM:649-657), their mean (MM:669) added in fp32 and rounded
+    once.  x (B, L, D), or (B L, D) with rows_per_sample = L -> (B, D)."""
+    if x.dim() == 2:
+        x, residual = (t.reshape(-1, rows_per_sample, t.shape[-1]) for t in (x, residual))
+    z = x.float() + residual.float()
+    y = (z * torch.rsqrt(z.square().mean(dim=-1, keepdim=True) + eps) * weight.float()).to(x.dtype)
+    return (y.float().sum(dim=1) / x.shape[1]).to(x.dtype)
+
+
+class RMSNormPoolFn(torch.autograd.Function):
+    """aum_rmsnorm_pool_fwd / _bwd under autograd: x (B, L, D) bf16 / fp16 and the fp32 residual stream -> (B, D); gradients to x, the
+    weight (into its gradient home where it has one) and the residual.  Without grad mode nothing is saved and the kernel only reads."""
+
+    @staticmethod
+    def forward(ctx, x, weight, residual, eps, rows_per_sample):
+        cols = x.shape[-1]
+        x2, r2 = x.reshape(-1, cols), residual.reshape(-1, cols)
+        x2 = x2 if x2.stride(-1) == 1 else x2.contiguous()
+        r2 = r2 if r2.stride(-1) == 1 else r2.contiguous()
+        need = any(ctx.needs_input_grad)
+        pooled, rstd, res_out = aum_hip.rmsnorm_pool_fwd(x2, weight, r2, rows_per_sample, eps, save=need)
+        if need:
+            ctx.save_for_backward(res_out, weight, rstd)
+        ctx.shape, ctx.per, ctx.wparam = x.shape, rows_per_sample, weight
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        res_out, weight, rstd = ctx.saved_tensors
+        from mamba_ssm.ops.selective_scan_interface import _homed, grad_home
+        home = grad_home(ctx.wparam)
+        dpooled = dpooled if dpooled.stride(-1) == 1 else dpooled.contiguous()
+        dx, dw, dres = aum_hip.rmsnorm_pool_bwd(dpooled, res_out, weight, rstd, ctx.per, dw_out=home)
+        return dx.reshape(ctx.shape), _homed(dw.to(weight.dtype), home), dres.reshape(ctx.shape), None, None
+
+
+def rms_norm_pool_fn(x, weight, residual, eps=1e-6, rows_per_sample=None):
+    """Fused final add + RMSNorm + mean over the tokens of each sample: what rms_norm_fn(x, weight, None, residual=residual).mean(dim=1)
+    computes, without the (B, L, D) normalised tensor or its gradient ever existing.  x (B, L, D) -> (B, D); a (B L, D) x takes
+    rows_per_sample = L.  x is bf16 / fp16 and the residual fp32 (the autocast residual stream); CPU tensors without a library that takes
+    them run rms_norm_pool_ref."""
+    if x.dim() == 3:
+        if rows_per_sample not in (None, x.shape[1]):
+            raise ValueError(f"rms_norm_pool_fn: rows_per_sample {rows_per_sample} against x {tuple(x.shape)}")
+        rows_per_sample = x.shape[1]
+    elif x.dim() != 2 or rows_per_sample is None or rows_per_sample < 1 or x.shape[0] % rows_per_sample:
+        raise ValueError(f"rms_norm_pool_fn: x must be (B, L, D), or (B L, D) with rows_per_sample = L; got {tuple(x.shape)}, {rows_per_sample}")
+    if residual is None or residual.shape != x.shape:
+        raise ValueError("rms_norm_pool_fn: the residual stream is required, in x's shape")
+    if x.device.type == "cpu" and not _host_library():
+        return rms_norm_pool_ref(x, weight, residual, eps, rows_per_sample)
+    return RMSNormPoolFn.apply(x, weight, residual, eps, rows_per_sample)
+
+
+def _host_library():
+    """whether aum_hip's library in use takes host tensors (the tests' lane-array build where libaum_hip.so would be)"""
+    return aum_hip._product is not None and aum_hip._product.host
+
+
 class RMSNorm(torch.nn.Module):
     """LN:481-502: .weight (ones), .bias = None, .eps; forward(x, residual=None, prenorm=False, residual_in_fp32=False)."""
 

@@ -49,7 +49,9 @@ extern "C" {
                                    flags (AUM_XDT_DELTA_SOFTPLUS) -- zero / NULL keeps the previous behaviour; aum_xdt_tm_bwd also takes
                                    (ncols, rank) = (56, 24) and aum_gemm_wgrad k in {24, 56} (AuM-Small: shapes that were AUM_E_UNSUPPORTED);
                                    aum_stream_park / AumParkArgs (streaming sessions to a blob and back in one launch);
-                                   aum_rmsnorm_drop_fwd / _bwd / AumNormDropArgs (stochastic depth inside the add + RMSNorm) */
+                                   aum_rmsnorm_drop_fwd / _bwd / AumNormDropArgs (stochastic depth inside the add + RMSNorm);
+                                   aum_rmsnorm_pool_fwd / _bwd / AumNormPoolArgs, aum_rmsnorm_pool_partial_rows (add + RMSNorm + mean over a
+                                   sample's tokens: the head of a cls-free model) */
 
 enum { AUM_F32 = 0, AUM_BF16 = 1, AUM_F16 = 2 };
 
@@ -247,6 +249,40 @@ typedef struct AumNormDropArgs {
 
 int aum_rmsnorm_drop_fwd(const AumNormDropArgs* args, void* stream);
 int aum_rmsnorm_drop_bwd(const AumNormDropArgs* args, void* stream);
+
+/*
+ * Fused add + RMSNorm + mean over a sample's tokens (the head of a cls-free model, final_pool_type 'mean': MM:649-669).  Row r belongs to
+ * sample r / rows_per_sample.  The normalised rows are never stored: forward moves x and residual once, backward has no (rows, cols) dy.
+ *   base      the arguments of aum_rmsnorm_fwd / _bwd with these differences: x_dtype is AUM_BF16 or AUM_F16, res_dtype AUM_F32, flags 0,
+ *             cols % 8 == 0 and cols <= 2048 (anything else: AUM_E_UNSUPPORTED); y, dy and dresidual_out are not used and must be NULL
+ *   forward   per row z = x + residual, rstd and y = z * rstd * weight rounded to x_dtype exactly as aum_rmsnorm_fwd computes them;
+ *             pooled[s][c] = (sum over the sample's rows of the ROUNDED y) / rows_per_sample, added in fp32 in a fixed order (a wave's 4
+ *             consecutive rows in row order, the 8 waves of a 32-row chunk in wave order, the chunks in chunk order) and rounded once to
+ *             x_dtype: a sample's result depends on neither the batch size, its neighbours nor the run.  residual (required), weight;
+ *             residual_out and rstd_out are optional, BOTH or NEITHER (aum_rmsnorm_fwd's bits; the backward needs them)
+ *   pooled    (rows / rows_per_sample, cols) x_dtype, row stride row_stride_pooled elements
+ *   pool_partial   fp32 workspace of rows / rows_per_sample * aum_rmsnorm_pool_partial_rows(rows_per_sample) contiguous rows of cols, every
+ *             one written; needed only where that count is above 1 (a sample of more than 32 rows: a second launch adds its chunks)
+ *   backward  dpooled (rows / rows_per_sample, cols) x_dtype; g[s] = dpooled[s] / rows_per_sample (fp32 division) rounded to x_dtype; every
+ *             row of sample s gets the dx (x_dtype) and dresidual_in (fp32, required) that aum_rmsnorm_bwd writes for dy = g[s], bit for
+ *             bit; x = the saved residual_out, rstd_in.  dweight_partial: aum_rmsnorm_bwd_partial_rows(rows, cols, 0) rows, as there
+ * AUM_E_NULL: a required pointer is NULL;  AUM_E_SHAPE: rows_per_sample < 1 or rows % rows_per_sample != 0;  reserved: 0 (else
+ * AUM_E_UNSUPPORTED).  A refused call writes nothing.
+ */
+typedef struct AumNormPoolArgs {
+    AumNormArgs base;
+    void* pooled;
+    const void* dpooled;
+    float* pool_partial;
+    int64_t row_stride_pooled, row_stride_dpooled;
+    int32_t rows_per_sample;
+    int32_t reserved;
+} AumNormPoolArgs;
+
+int aum_rmsnorm_pool_fwd(const AumNormPoolArgs* args, void* stream);
+int aum_rmsnorm_pool_bwd(const AumNormPoolArgs* args, void* stream);
+/* the 32-row chunks of a sample: ceil(rows_per_sample / 32) (0 for rows_per_sample < 1); pool_partial holds that many rows per sample */
+int aum_rmsnorm_pool_partial_rows(int32_t rows_per_sample);
 
 /*
  * Log-mel filterbank frontend (replaces torchaudio.compliance.kaldi.fbank + pad + normalise on the CPU DataLoader

@@ -178,6 +178,22 @@ def main():
         y, rstd, ro = aum_hip.rmsnorm_fwd(x, wn, r, 1e-5)
         dy = torch.randn(M, C, device=dev).to(dt)
         rec("rmsnorm_bwd", timeit(lambda: aum_hip.rmsnorm_bwd(dy, ro, wn, rstd, r, True, x_dtype=dt)), M * C * (2 * s + 12))
+    if want("norm_pool") and dt != torch.float32:      # add + RMSNorm + mean over a sample's tokens against its composition (--only norm_pool --len 512)
+        M, C = Bsz * L, a.dmodel
+        x = torch.randn(M, C, device=dev).to(dt)
+        r = torch.randn(M, C, device=dev)
+        wn = torch.ones(C, device=dev)
+        dp = torch.randn(Bsz, C, device=dev).to(dt)
+        rec("rmsnorm_pool_fwd", timeit(lambda: aum_hip.rmsnorm_pool_fwd(x, wn, r, L, 1e-5)), M * C * (s + 8))
+        rec("rmsnorm_pool_fwd_eval", timeit(lambda: aum_hip.rmsnorm_pool_fwd(x, wn, r, L, 1e-5, save=False)), M * C * (s + 4))
+        rec("composed_fwd", timeit(lambda: aum_hip.rmsnorm_fwd(x, wn, r, 1e-5)[0].view(Bsz, L, C).mean(dim=1)), M * C * (s + 8))
+        _, rstd, ro = aum_hip.rmsnorm_pool_fwd(x, wn, r, L, 1e-5)
+        rec("rmsnorm_pool_bwd", timeit(lambda: aum_hip.rmsnorm_pool_bwd(dp, ro, wn, rstd, L)), M * C * (s + 8))
+
+        def composed_bwd():      # what autograd runs behind .mean(dim=1): the broadcast of dpooled / L, then the norm's backward
+            dy = (dp / L)[:, None, :].expand(Bsz, L, C).reshape(M, C)
+            return aum_hip.rmsnorm_bwd(dy, ro, wn, rstd, None, True, x_dtype=dt)
+        rec("composed_bwd", timeit(composed_bwd), M * C * (s + 8))
     if want("proj") and dt != torch.float32:
         R, rt, ntok = a.dmodel // 16, a.dmodel // 16 + 2 * N, Bsz * L
         conv2 = torch.randn(E, ntok, device=dev).to(dt)
